@@ -1,9 +1,20 @@
 #!/usr/bin/env python3
 """Headline benchmark: spectrogram frames/s of the U-Net forward on 513x256 fp32 batches (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: it sets up, runs W untimed steps, times exactly K steps, writes what
+the last timed step computed if --dump-outputs is given, and prints the line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step`, `config`, `ranks`).  --full adds everything else, as the sections below describe: the per-launch
+event timing of the timed steps (`roofline`, `forward`), the all-gather probe and `per_gpu_reference` on more than one rank,
+the sub-benchmarks and `cpu_baseline`.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what its last timed step handed the caller, float32: DIR/y.npy = the
+network output of its clips, DIR/loss_per_clip.npy = the gathered (clips, 4) per-clip losses (total, stft, mel, l1).  Inputs
+and weights are seeded, so the same arguments give the same inputs in every run.  Past 64 MB the output is replaced by a fixed
+sample of whole clips (seed 0): DIR/y_sample.npy and their indices DIR/y_sample_clips.npy (float64).
 
 A step = one forward of the hot path over one resident batch per GPU (BASELINE configs[1]: batch 64 of synthetic
 513x256 fp32 spectrograms) + the per-clip CombinedPerceptualLoss kernels, and for N > 1 the one RCCL all-gather of
@@ -11,7 +22,7 @@ the per-clip values (4 floats per clip).  Clips shard over ranks, weights are re
 collective; weak scaling: the batch per GPU is fixed.  Rank 0 prints ONE JSON line; `value` = all ranks' frames /
 max-over-ranks time between barrier + synchronize pairs.
 
-roofline (dominant kernel = wino4_conv_f32, Winograd F(4x4,3x3) on the exact-fp32 matrix cores: all 17 3x3 convolutions
+roofline (--full; dominant kernel = wino4_conv_f32, Winograd F(4x4,3x3) on the exact-fp32 matrix cores: all 17 3x3 convolutions
 at 513x256, 87 % of the forward's time; layers whose image its 32x32 tiles do not fit -- none at this size -- run
 wino_conv_dma_f32, F(2x2,3x3), and would be summarised under `other_3x3_kernel`; ADN_WINO_TILE=2 pins F(2x2,3x3)
 everywhere, ADN_CONV_ALGO=direct selects the direct implicit-GEMM kernel conv_mfma<float>):
@@ -27,11 +38,11 @@ everywhere, ADN_CONV_ALGO=direct selects the direct implicit-GEMM kernel conv_mf
 
 Batch per GPU: 64 at N = 1 (BASELINE configs[1], the config `metric` is quoted on); 256 when launched on more than one
 rank (BASELINE configs[3]: batch 2048 sharded over 8 GPUs = 256 clips per GPU; weak scaling, so 2 and 4 ranks also run 256
-per GPU).  The N = 1 line carries `fp32_b256` -- the same step at 256 clips on one GPU -- which is the per-GPU figure the
-N > 1 values are to be compared with.  Every line carries `ranks`: how many ranks the gathered tensor held, each rank's own
-time for the K steps (min / max) and the all-gather's own time.
+per GPU).  The N = 1 line of --full carries `fp32_b256` -- the same step at 256 clips on one GPU -- which is the per-GPU
+figure the N > 1 values are to be compared with.  Every line carries `ranks`: how many ranks the gathered tensor held, each
+rank's own time for the K steps (min / max) and, with --full, the all-gather's own time.
 
-Sub-benchmarks in the same JSON line (rank 0, N = 1 only; --no-extras skips them):
+Sub-benchmarks in the same JSON line (--full, rank 0, N = 1 only; --no-extras skips them):
   `fp32_b256`  the main step at batch 256 (north_star's batch, one rank's shard of configs[3]).
   `exact_f32`  the headline step with exact-fp32 matrix instructions everywhere (ADN_CONVT_SPLIT=0).
   `b1`    single-clip latency at 513x256 and the reference's own shapes (257x188 whole test set of 5 clips as test.py:112-113
@@ -47,7 +58,7 @@ Sub-benchmarks in the same JSON line (rank 0, N = 1 only; --no-extras skips them
   `f16`   BASELINE configs[4]: the same forward at batch 256 with fp16 storage + fp16 MFMA; MFMA roofline of
           conv16_f16 against the dense fp16 peak.
 
-cpu_baseline: the oracle's torch.nn.functional restatement of the reference forward (same ATen/oneDNN kernels
+cpu_baseline (--full): the oracle's torch.nn.functional restatement of the reference forward (same ATen/oneDNN kernels
 the reference's model.py dispatches to; kind "port") timed on this host's cores on a bounded sample.
 """
 from __future__ import annotations
@@ -838,6 +849,34 @@ def per_gpu_reference():
     return {"value": None, "note": "no recorded N = 1 line of this build with fp32_b256 under profiles/ (rNN_bench.json)"}
 
 
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir: str, y: torch.Tensor, per_clip: torch.Tensor) -> None:
+    """--dump-outputs (module docstring): the last timed step's network output and per-clip losses as float32 .npy files.  An
+    output past the budget is replaced by a fixed sample of whole clips (seed 0, in index order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    loss = per_clip.detach().float().reshape(-1, 4).cpu().numpy()
+    y = y.detach().float()
+    n = y.shape[0]
+    room = (DUMP_BUDGET_BYTES - loss.nbytes - 8 * n) // (y[0].numel() * 4)
+    files = {"loss_per_clip": loss}
+    if n <= room:
+        files["y"] = y.cpu().numpy()
+        stale = ("y_sample", "y_sample_clips")
+    else:
+        clips = np.sort(np.random.default_rng(0).choice(n, size=int(room), replace=False))
+        files["y_sample"] = y[torch.from_numpy(clips).to(y.device)].cpu().numpy()
+        files["y_sample_clips"] = clips.astype(np.float64)
+        stale = ("y",)
+    for name in stale:                                  # a file of an earlier run with another batch must not be compared
+        path = os.path.join(out_dir, name + ".npy")
+        if os.path.exists(path):
+            os.remove(path)
+    for name, arr in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -845,9 +884,14 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch-per-gpu", type=int, default=None,
                     help="default: 64 on one GPU (BASELINE configs[1]), 256 on more than one rank (configs[3] = 2048 / 8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (module docstring)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: per-launch timing of the timed steps (roofline, forward), the all-gather "
+                         "probe (N > 1), the sub-benchmarks and the CPU baseline (off: a plain run times the steps and prints)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the sub-benchmarks (stft = configs[2], f16 = configs[4], fp32_b256, b1)")
+                    help="with --full: skip the sub-benchmarks (stft = configs[2], f16 = configs[4], fp32_b256, b1)")
     ap.add_argument("--extras", default="stft,f16,fp32_b256,b1,exact_f32,e2e_config0,host_boundary",
                     help="which sub-benchmarks to run (comma list; tools/profile_bench.sh profiles with stft,f16 only, so that the "
                          "kernel statistics of the headline kernel are not mixed with other batch sizes)")
@@ -889,24 +933,34 @@ def main() -> None:
     x = torch.rand((b, 1, F_BINS, T_FRAMES), generator=g, device=dev) * 4.0      # resident in HBM
     target = torch.rand((b, 1, F_BINS, T_FRAMES), generator=g, device=dev) * 4.0
 
+    last = {}
+
     def step():
         y = net(x)
+        last["y"] = y                                         # what the caller receives: kept for --dump-outputs
         loss = perceptual_loss_per_clip(y, target)            # (b, 4): total, stft, mel, l1 per clip
         return D.gather_per_clip(loss.reshape(-1))
 
     L = _lib.load()
+
+    def start_launch_timing():                                # --full: events around every launch of the timed steps
+        _lib.check(L.adn_unet_set_timing(net._handle, args.steps), "adn_unet_set_timing")
+
     payload = torch.zeros(4 * b, dtype=torch.float32, device=dev)
     with torch.no_grad():
         tr = timed_region(step, args.steps, args.warmup, lambda: torch.cuda.synchronize(dev), dev,
-                          on_timed_start=lambda: _lib.check(L.adn_unet_set_timing(net._handle, args.steps), "adn_unet_set_timing"),
-                          gather_probe=(lambda: D.gather_per_clip(payload)) if world > 1 else None)
+                          on_timed_start=start_launch_timing if args.full else None,
+                          gather_probe=(lambda: D.gather_per_clip(payload)) if world > 1 and args.full else None)
     elapsed, allv = tr["elapsed_s"], tr["last"]
     tr["ranks"]["allgather_payload_floats_per_rank"] = 4 * b
     assert allv.numel() == 4 * b * world and (args.no_finite_check or bool(torch.isfinite(allv).all()))
     assert tr["ranks"]["ranks_seen"] == world, tr["ranks"]
-    ms_mean = launch_timings(net, args.steps)      # per-launch durations of the timed steps (events inside libadn)
+    ms_mean = launch_timings(net, args.steps) if args.full else None      # per-launch durations of the timed steps
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last["y"], allv)
+        last.clear()
         algo, peak, kname, tkey, wmode = kernel_names(f16)
         arith = ("fp16 storage + fp16 MFMA, fp32 accumulate" if f16 else
                  "fp32 storage; 3x3 layers on exact-fp32 MFMA (Winograd F(4x4,3x3)); transposed convolutions "
@@ -915,16 +969,17 @@ def main() -> None:
                     if convt_uses_split_bf16(False) else "on exact-fp32 MFMA (ADN_CONVT_SPLIT=0)"))
         out = assemble_line(elapsed, args.steps, args.warmup, world, b, args.dtype, tr["ranks"],
                             {"lib_digest": lib_digest()[:12], "arithmetic": arith})
-        out["roofline"] = conv_roofline(ms_mean, b, algo, peak, kname, tkey, wmode)
-        out["forward"] = forward_summary(ms_mean, b, algo, peak, wmode)
+        if args.full:
+            out["roofline"] = conv_roofline(ms_mean, b, algo, peak, kname, tkey, wmode)
+            out["forward"] = forward_summary(ms_mean, b, algo, peak, wmode)
         if rehearsal:
             out["data"] = "synthetic; REHEARSAL of the N > 1 path on one GPU (gloo, every rank on device 0): not a measurement"
-        if world > 1:
+        if world > 1 and args.full:
             out["config"]["per_gpu_reference"] = per_gpu_reference()
             out["config"]["compare_with"] = ("the N = 1 line's fp32_b256.value (the same 256 clips per GPU on one GPU); the N = 1 "
                                              "headline value is BASELINE configs[1] at 64 clips")
         del allv
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             net._workspace = None
             del x, target
             torch.cuda.empty_cache()
@@ -944,7 +999,7 @@ def main() -> None:
                     out["e2e_config0"] = bench_e2e_config0(sd_np, dev, with_cpu=not args.no_cpu_baseline)
                 if "host_boundary" in extras:
                     out["host_boundary"] = bench_host_boundary(sd_np, dev)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(sd_np)
         print(json.dumps(out), flush=True)
     D.barrier()

@@ -266,6 +266,32 @@ def test_bench_timed_region_and_line_world8_gloo():
     assert "configs[1]" in one["config"]["workload"] and one["value"] == 64 * 256 * 10
 
 
+def test_bench_dump_outputs_whole_then_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 files; the whole output while everything fits 64 MB, past that the same seeded sample of
+    whole clips in every run (indices alongside), and no file of an earlier run with another batch left behind."""
+    import bench
+    loss = torch.arange(64 * 4, dtype=torch.float32)
+    y = torch.arange(64, dtype=torch.float32).reshape(64, 1, 1, 1).expand(64, 1, 513, 256)
+    bench.dump_outputs(str(tmp_path), y, loss)
+    assert sorted(os.listdir(tmp_path)) == ["loss_per_clip.npy", "y.npy"]
+    got = np.load(tmp_path / "y.npy")
+    assert got.dtype == np.float32 and got.shape == (64, 1, 513, 256) and np.array_equal(got, y.numpy())
+    assert np.array_equal(np.load(tmp_path / "loss_per_clip.npy"), loss.numpy().reshape(64, 4))
+    n = 160                                                  # 84 MB of output: a sample of whole clips
+    y = torch.arange(n, dtype=torch.float32).reshape(n, 1, 1, 1).expand(n, 1, 513, 256)
+    loss = torch.zeros(n * 4)
+    runs = []
+    for _ in range(2):
+        bench.dump_outputs(str(tmp_path), y, loss)
+        assert sorted(os.listdir(tmp_path)) == ["loss_per_clip.npy", "y_sample.npy", "y_sample_clips.npy"]
+        assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64e6
+        clips, sample = np.load(tmp_path / "y_sample_clips.npy"), np.load(tmp_path / "y_sample.npy")
+        assert clips.dtype == np.float64 and sample.dtype == np.float32 and len(clips) > n // 2
+        assert np.all(np.diff(clips) > 0) and np.array_equal(sample[:, 0, 0, 0], clips.astype(np.float32))
+        runs.append(clips)
+    assert np.array_equal(runs[0], runs[1])
+
+
 def test_wav_reader_formats(tmp_path):
     """PCM16 (checked against the stdlib reader), float32, stereo mix-down, extensible header, odd chunk padding."""
     import struct

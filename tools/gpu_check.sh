@@ -1,16 +1,17 @@
 #!/bin/bash
-# GPU-box check of the current tree: all -m gpu tests, smoke(), default bench line.  Outputs under gpurun_out/<tag>_*.
-#     gpurun --timeout 1200 -- 'bash tools/gpu_check.sh r03a'
+# GPU-box check of the current tree: all -m gpu tests, smoke(), the --full bench line.  Outputs under $OUT_DIR/<tag>_*
+# (default results/).      bash tools/gpu_check.sh r03a
 TAG=${1:-check}
-mkdir -p gpurun_out
-timeout -k 10 1000 python -m pytest tests -x -q -m gpu > gpurun_out/${TAG}_pytest_gpu.log 2>&1; rc=$?
-tail -3 gpurun_out/${TAG}_pytest_gpu.log
+OUT_DIR=${OUT_DIR:-results}
+mkdir -p $OUT_DIR
+timeout -k 10 1000 python -m pytest tests -x -q -m gpu > $OUT_DIR/${TAG}_pytest_gpu.log 2>&1; rc=$?
+tail -3 $OUT_DIR/${TAG}_pytest_gpu.log
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" || exit 1
-timeout -k 10 500 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || { tail -5 gpurun_out/${TAG}_bench.err; exit 1; }
+timeout -k 10 500 python bench.py --full > $OUT_DIR/${TAG}_bench.json 2> $OUT_DIR/${TAG}_bench.err || { tail -5 $OUT_DIR/${TAG}_bench.err; exit 1; }
 python - <<PY
 import json
-d = json.load(open("gpurun_out/${TAG}_bench.json"))
+d = json.load(open("$OUT_DIR/${TAG}_bench.json"))
 print("value", d["value"], "ms/step", d["ms_per_step"], "frac", d["roofline"]["frac"], "ranks", d["ranks"])
 print("stft", d["stft"]["ms_per_launch"], d["stft"]["roofline"]["frac"], "fit", d["stft"]["fused_to_network_input"]["ms_per_launch"])
 print("f16", d["f16"]["ms_per_step"], d["f16"]["roofline"]["frac"])

@@ -99,7 +99,7 @@ def main():
     ap.add_argument("--write")
     ap.add_argument("--tag", default="r02")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
-    ap.add_argument("--cmd", default="python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline")
+    ap.add_argument("--cmd", default="python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline")
     ap.add_argument("--traffic-json", action="store_true", help="(re)write profiles/pmc_traffic.json")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
