@@ -1153,6 +1153,32 @@ int adn_perceptual_loss(const float *pred, const float *target, int n_clips, int
     return ADN_OK;
 }
 
+int adn_perceptual_loss_backward_workspace_bytes(int n_clips, int F, int T, size_t *bytes)
+{
+    if (!bytes || n_clips < 1 || F < 1 || T < adn::ADN_LOSS_MIN_T || T > adn::ADN_LOSS_MAX_T)
+        return fail(ADN_ERR_INVALID, "adn_perceptual_loss_backward_workspace_bytes: need n_clips,F >= 1 and 32 <= T < 2^24");
+    *bytes = adn::perceptual_loss_backward_workspace_floats(n_clips, F, T) * sizeof(float);
+    return ADN_OK;
+}
+
+int adn_perceptual_loss_backward(const float *pred, const float *target, int n_clips, int F, int T, const float *grad_out,
+                                 void *workspace, size_t workspace_bytes, float *grad_pred, float *grad_target, void *stream)
+{
+    if (!pred || !target || !grad_out) return fail(ADN_ERR_INVALID, "adn_perceptual_loss_backward: null pointer");
+    if (!grad_pred && !grad_target)
+        return fail(ADN_ERR_INVALID, "adn_perceptual_loss_backward: grad_pred and grad_target are both null");
+    if (n_clips < 1 || F < 1 || T < adn::ADN_LOSS_MIN_T || T > adn::ADN_LOSS_MAX_T)
+        return fail(ADN_ERR_INVALID, "adn_perceptual_loss_backward: need n_clips,F >= 1 and 32 <= T < 2^24 (reflect padding of "
+                                     "the mel term needs T > 31)");
+    const size_t need = adn::perceptual_loss_backward_workspace_floats(n_clips, F, T) * sizeof(float);
+    if (!workspace || workspace_bytes < need) return fail(ADN_ERR_WORKSPACE, "adn_perceptual_loss_backward: workspace too small");
+    if (!aligned_to(workspace, 16)) return fail(ADN_ERR_INVALID, "adn_perceptual_loss_backward: workspace must be 16-byte aligned");
+    ADN_LAUNCH(adn::launch_perceptual_loss_backward(pred, target, n_clips, F, T, grad_out, static_cast<float *>(workspace),
+                                                    grad_pred, grad_target, static_cast<hipStream_t>(stream)),
+               "adn_perceptual_loss_backward");
+    return ADN_OK;
+}
+
 /* ---- inverse STFT / Griffin-Lim (test.py:29-48) -------------------------------------------------------------- */
 static bool gl_size_ok(int n_fft) { return n_fft >= 64 && n_fft <= 4096 && (n_fft & (n_fft - 1)) == 0; }
 

@@ -281,5 +281,9 @@ constexpr int ADN_LOSS_MAX_T = 1 << 24;     // (partial sums and frame indices a
 constexpr int ADN_LOSS_MIN_T = 32;          // loss.py:39-41: the mel transform's reflect padding (31 samples) needs T > 31
 hipError_t launch_perceptual_loss(const float *pred, const float *tgt, int n_clips, int F, int T, float *workspace,
                                   float *out, hipStream_t st);
+// Backward of launch_perceptual_loss: grad_out (n_clips, 4) -> grad_pred / grad_tgt (either may be null), written.
+size_t perceptual_loss_backward_workspace_floats(int n_clips, int F, int T);
+hipError_t launch_perceptual_loss_backward(const float *pred, const float *tgt, int n_clips, int F, int T, const float *grad_out,
+                                           float *workspace, float *grad_pred, float *grad_tgt, hipStream_t st);
 
 }  // namespace adn

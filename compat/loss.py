@@ -1,3 +1,3 @@
 """`from loss import CombinedPerceptualLoss` (reference code/loss.py) resolved to the device implementation
-(evaluation only: per-clip kernels, no autograd)."""
+(per-clip kernels; `loss.backward()` runs the HIP backward, as in train.py:67-68)."""
 from audiodenoiser_amd.loss import CombinedPerceptualLoss  # noqa: F401

@@ -14,7 +14,7 @@
  *     message.  Nothing throws or aborts across the ABI.
  *   - work is enqueued on the caller's stream.  The only calls that block or allocate: adn_unet_create / adn_unet_destroy
  *     (one-time weight upload / free), adn_prepare, and the FIRST call per (device, n_fft) of an STFT-family entry point
- *     (adn_stft_mag, adn_stft_mag_fit, adn_stft_complex, adn_istft, adn_griffin_lim) or per device of adn_perceptual_loss, which
+ *     (adn_stft_mag, adn_stft_mag_fit, adn_stft_complex, adn_istft, adn_griffin_lim) or per device of adn_perceptual_loss / adn_perceptual_loss_backward, which
  *     builds a few KB of constant tables (window, twiddles, mel filters) with a blocking upload -- unless adn_prepare did so
  *     before.  Such a cold call on a stream that is being captured enqueues nothing and returns ADN_ERR_INVALID (never a HIP
  *     error): call adn_prepare(device, n_fft) before capturing.  adn_unet_forward never blocks or allocates.
@@ -32,7 +32,7 @@
 
 #include <stddef.h>
 
-/* The 28 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 30 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -166,6 +166,18 @@ ADN_API int adn_per_clip_l1(const float *a, const float *b, int n_clips, long el
 ADN_API int adn_perceptual_loss_workspace_bytes(int n_clips, int F, int T, size_t *bytes);
 ADN_API int adn_perceptual_loss(const float *pred, const float *target, int n_clips, int F, int T, void *workspace,
                         size_t workspace_bytes, float *out, void *stream);
+/* Backward of adn_perceptual_loss (what loss.backward() needs in the reference's train.py:67-68): the exact chain rule of
+ * the four per-clip outputs with respect to both inputs, as torch autograd differentiates the reference's loss (abs'(0) = 0,
+ * sign(0) = 0; zero-padded STFT samples drop out, reflected mel samples fold back onto the series).
+ * grad_out: device (n_clips, 4) fp32, d(objective)/d{total, stft, mel, l1} per clip.
+ * grad_pred, grad_target: device (n_clips, 1, F, T) fp32, written (not accumulated); either may be NULL, not both.
+ * Same shape limits as adn_perceptual_loss (T >= 32); adn_perceptual_loss_backward_workspace_bytes of device scratch (16-byte
+ * aligned).  The mel filterbank is the one adn_perceptual_loss / adn_prepare builds.  Deterministic: no float atomics, two calls
+ * give bit-identical gradients. */
+ADN_API int adn_perceptual_loss_backward_workspace_bytes(int n_clips, int F, int T, size_t *bytes);
+ADN_API int adn_perceptual_loss_backward(const float *pred, const float *target, int n_clips, int F, int T,
+                                         const float *grad_out, void *workspace, size_t workspace_bytes,
+                                         float *grad_pred, float *grad_target, void *stream);
 
 /* ---- inverse STFT and Griffin-Lim ----------------------------------------------------------------------------
  * Replaces griffin_lim_reconstruction (/root/reference/code/test.py:29-48): librosa.istft + librosa.stft iterated
