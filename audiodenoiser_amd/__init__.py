@@ -6,19 +6,23 @@ and every entry point raises if it is unavailable — there is no CPU or eager-P
 __version__ = "0.1.0"
 
 __all__ = ["UNet", "SpectrogramDataset", "WavToSpecDataset", "audio_to_magnitude_spectrogram",
-           "audio_to_spectrogram", "stft_magnitude", "per_clip_l1", "CombinedPerceptualLoss"]
+           "audio_to_spectrogram", "stft_magnitude", "per_clip_l1", "CombinedPerceptualLoss", "NoiseMixDataset",
+           "resample_length", "mix_snr", "load_audio"]      # (resample itself: audiodenoiser_amd.resample.resample -- the module owns the name)
 
 
 def __getattr__(name):
     if name == "UNet":
         from .model import UNet
         return UNet
-    if name in ("SpectrogramDataset", "WavToSpecDataset"):
+    if name in ("SpectrogramDataset", "WavToSpecDataset", "NoiseMixDataset"):
         from . import data_loader
         return getattr(data_loader, name)
     if name in ("audio_to_magnitude_spectrogram", "audio_to_spectrogram", "stft_magnitude"):
         from . import stft
         return getattr(stft, name)
+    if name in ("resample_length", "mix_snr", "load_audio"):
+        import importlib
+        return getattr(importlib.import_module(".resample", __name__), name)
     if name in ("per_clip_l1", "CombinedPerceptualLoss"):
         from . import loss
         return getattr(loss, name)

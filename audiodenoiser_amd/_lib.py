@@ -63,6 +63,11 @@ def load() -> ctypes.CDLL:
         L.adn_perceptual_loss.argtypes = [vp, vp, ci, ci, ci, vp, sz, vp, vp]
         L.adn_perceptual_loss_backward_workspace_bytes.argtypes = [ci, ci, ci, ctypes.POINTER(sz)]
         L.adn_perceptual_loss_backward.argtypes = [vp, vp, ci, ci, ci, vp, vp, sz, vp, vp, vp]
+        L.adn_resample_length.argtypes = [cl, ci, ci, ctypes.POINTER(cl)]
+        L.adn_resample_prepare.argtypes = [ci, ci, ci]
+        L.adn_resample.argtypes = [vp, ci, cl, ci, ci, vp, vp]
+        L.adn_mix_snr_workspace_bytes.argtypes = [ci, cl, ctypes.POINTER(sz)]
+        L.adn_mix_snr.argtypes = [vp, vp, ci, cl, ctypes.c_float, vp, sz, vp, vp]
         L.adn_istft_length.argtypes = [ci, ci, ctypes.POINTER(cl)]
         L.adn_griffin_lim_workspace_bytes.argtypes = [ci, ci, ci, ctypes.POINTER(sz)]
         L.adn_griffin_lim.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, sz, vp, vp]
@@ -73,7 +78,8 @@ def load() -> ctypes.CDLL:
                      "adn_unet_set_batch_invariant", "adn_unet_destroy", "adn_unet_workspace_bytes", "adn_unet_forward", "adn_unet_forward_taps", "adn_unet_set_timing", "adn_unet_get_timing",
                      "adn_stft_n_frames", "adn_stft_mag", "adn_stft_mag_fit", "adn_quantize_pad", "adn_per_clip_l1",
                      "adn_perceptual_loss_workspace_bytes", "adn_perceptual_loss", "adn_perceptual_loss_backward_workspace_bytes",
-                     "adn_perceptual_loss_backward", "adn_istft_length",
+                     "adn_perceptual_loss_backward", "adn_resample_length", "adn_resample_prepare", "adn_resample",
+                     "adn_mix_snr_workspace_bytes", "adn_mix_snr", "adn_istft_length",
                      "adn_griffin_lim_workspace_bytes", "adn_griffin_lim", "adn_stft_complex",
                      "adn_istft_workspace_bytes", "adn_istft"):
             getattr(L, name).restype = ci
@@ -105,4 +111,5 @@ EXPORTED_SYMBOLS = (
     "adn_quantize_pad", "adn_per_clip_l1", "adn_perceptual_loss_workspace_bytes", "adn_perceptual_loss",
     "adn_perceptual_loss_backward_workspace_bytes", "adn_perceptual_loss_backward", "adn_istft_length", "adn_griffin_lim_workspace_bytes", "adn_griffin_lim", "adn_stft_complex",
     "adn_istft_workspace_bytes", "adn_istft",
+    "adn_resample_length", "adn_resample_prepare", "adn_resample", "adn_mix_snr_workspace_bytes", "adn_mix_snr",
 )

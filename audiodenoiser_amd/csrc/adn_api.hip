@@ -1128,6 +1128,84 @@ int adn_per_clip_l1(const float *a, const float *b, int n_clips, long elems_per_
     return ADN_OK;
 }
 
+int adn_resample_length(long length, int src_rate, int dst_rate, long *out_length)
+{
+    int up = 0, down = 0;
+    if (!out_length) return fail(ADN_ERR_INVALID, "adn_resample_length: null pointer");
+    if (!adn::resample_ratio(src_rate, dst_rate, &up, &down))
+        return fail(ADN_ERR_INVALID, "adn_resample_length: rates must be >= 1 with max(up, down) <= 4096 after dividing by their gcd");
+    if (length < 1) return fail(ADN_ERR_INVALID, "adn_resample_length: length must be >= 1");
+    if (length > (0x7fffffffL * down) / up) return fail(ADN_ERR_INVALID, "adn_resample_length: output length must be < 2^31");
+    const long m = (length * up + down - 1) / down;
+    if (m >= (1L << 31)) return fail(ADN_ERR_INVALID, "adn_resample_length: output length must be < 2^31");
+    *out_length = m;
+    return ADN_OK;
+}
+
+int adn_resample_prepare(int device, int src_rate, int dst_rate)
+{
+    int up = 0, down = 0;
+    if (!adn::resample_ratio(src_rate, dst_rate, &up, &down))
+        return fail(ADN_ERR_INVALID, "adn_resample_prepare: rates must be >= 1 with max(up, down) <= 4096 after dividing by their gcd");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(ADN_ERR_NO_DEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return fail(ADN_ERR_INVALID, "adn_resample_prepare: bad device index");
+    if (up == down) return ADN_OK;                        // equal rates: a copy, no table
+    DeviceGuard guard(device);
+    if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
+    ADN_HIP(adn::resample_prepare(up, down, nullptr));
+    return ADN_OK;
+}
+
+int adn_resample(const float *audio, int n_clips, long length, int src_rate, int dst_rate, float *out, void *stream)
+{
+    if (!audio || !out) return fail(ADN_ERR_INVALID, "adn_resample: null pointer");
+    if (audio == out) return fail(ADN_ERR_INVALID, "adn_resample: out may not alias audio");
+    if (n_clips < 1) return fail(ADN_ERR_INVALID, "adn_resample: n_clips must be >= 1");
+    long m = 0;
+    if (adn_resample_length(length, src_rate, dst_rate, &m) != ADN_OK) return ADN_ERR_INVALID;
+    int up = 0, down = 0;
+    adn::resample_ratio(src_rate, dst_rate, &up, &down);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (up == down) {
+        ADN_HIP(hipMemcpyAsync(out, audio, (size_t)n_clips * length * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return ADN_OK;
+    }
+    hipError_t e = adn::launch_resample(audio, n_clips, length, m, up, down, out, st);
+    if (e == adn::ADN_COLD_IN_CAPTURE)
+        return fail(ADN_ERR_INVALID, "adn_resample: first use of this (device, rate pair) on a stream that is being captured -- the "
+                    "coefficient table is built with a blocking upload; call adn_resample_prepare(device, src_rate, dst_rate) before "
+                    "the capture");
+    if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_resample: grid too large (n_clips x output blocks >= 2^31)");
+    if (e != hipSuccess) return fail_hip(e, "adn_resample");
+    return ADN_OK;
+}
+
+int adn_mix_snr_workspace_bytes(int n_clips, long length, size_t *bytes)
+{
+    if (!bytes || n_clips < 1 || length < 1 || length >= (1L << 40))
+        return fail(ADN_ERR_INVALID, "adn_mix_snr_workspace_bytes: need n_clips >= 1 and 1 <= length < 2^40");
+    *bytes = adn::mix_snr_workspace_floats(n_clips, length) * sizeof(float);
+    return ADN_OK;
+}
+
+int adn_mix_snr(const float *clean, const float *noise, int n_clips, long length, float snr_db, void *workspace,
+                size_t workspace_bytes, float *out, void *stream)
+{
+    if (!clean || !noise || !out) return fail(ADN_ERR_INVALID, "adn_mix_snr: null pointer");
+    if (out == clean) return fail(ADN_ERR_INVALID, "adn_mix_snr: out may alias noise but not clean");
+    size_t need = 0;
+    if (adn_mix_snr_workspace_bytes(n_clips, length, &need) != ADN_OK) return ADN_ERR_INVALID;
+    if (!(snr_db >= -200.f && snr_db <= 200.f)) return fail(ADN_ERR_INVALID, "adn_mix_snr: snr_db must be in [-200, 200]");
+    if (!workspace || workspace_bytes < need) return fail(ADN_ERR_WORKSPACE, "adn_mix_snr: workspace too small");
+    const float inv_lin = (float)std::pow(10.0, -(double)snr_db / 20.0);
+    hipError_t e = adn::launch_mix_snr(clean, noise, n_clips, length, inv_lin, static_cast<float *>(workspace), out,
+                                       static_cast<hipStream_t>(stream));
+    if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_mix_snr: grid too large (n_clips x length / 8192 >= 2^31)");
+    if (e != hipSuccess) return fail_hip(e, "adn_mix_snr");
+    return ADN_OK;
+}
+
 int adn_perceptual_loss_workspace_bytes(int n_clips, int F, int T, size_t *bytes)
 {
     if (!bytes || n_clips < 1 || F < 1 || T < adn::ADN_LOSS_MIN_T || T > adn::ADN_LOSS_MAX_T)

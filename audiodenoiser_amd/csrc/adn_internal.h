@@ -271,6 +271,14 @@ hipError_t launch_stft_complex(const float *audio, int n_clips, long L, int n_ff
                                hipStream_t st);
 hipError_t launch_quantize_pad(const float *in, int n, int h, int w, float *out, int H, int W, hipStream_t st);
 hipError_t launch_per_clip_l1(const float *a, const float *b, int n_clips, long elems, float *out, hipStream_t st);
+// Polyphase resampler and SNR mixer (resample_kernels.hip).  resample_ratio: up / down of a rate pair, false outside the limits
+// of adn.h.  The coefficient table is built on first use per (device, up, down) like stft_tables (ADN_COLD_IN_CAPTURE applies).
+bool resample_ratio(int src_rate, int dst_rate, int *up, int *down);
+hipError_t resample_prepare(int up, int down, hipStream_t st);
+hipError_t launch_resample(const float *audio, int n_clips, long L, long M, int up, int down, float *out, hipStream_t st);
+size_t mix_snr_workspace_floats(int n_clips, long L);
+hipError_t launch_mix_snr(const float *clean, const float *noise, int n_clips, long L, float inv_snr_linear, float *workspace,
+                          float *out, hipStream_t st);
 size_t perceptual_loss_workspace_floats(int n_clips, int F, int T);
 // LDS the finishing kernel needs for T frames (ADN_LOSS_MAX_LDS: 160 KiB per CU minus the kernel's static reduction scratch):
 // up to ADN_LOSS_LDS_T frames a clip's series and mel spectra are held on chip, longer clips keep the series in the workspace

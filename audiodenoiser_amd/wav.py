@@ -4,8 +4,10 @@ The reference reads audio with ``librosa.load(path, sr=SAMPLE_RATE)`` (``create_
 ``create_test_dataset.py:144``): float32 in [-1, 1), channels averaged to mono.  librosa and soundfile are not
 in this image, so the container format is parsed here: PCM 8/16/24/32-bit, IEEE float 32/64, plain and
 WAVE_FORMAT_EXTENSIBLE headers.  Integer PCM is scaled by 2^-(bits-1) (8-bit: (x-128)/128), which is what
-libsndfile does.  Resampling (librosa's ``sr=`` argument uses soxr) is NOT provided: files must already be at
-the rate the caller expects, and ``read_wav`` returns the file's rate so callers can check.
+libsndfile does.  ``read_wav`` returns the audio at the FILE's rate together with that rate; the rate conversion of
+librosa's ``sr=`` argument lives in :mod:`audiodenoiser_amd.resample` (``load_audio(path, sr=8000)``: a device-side Kaiser
+polyphase resampler of this project's own definition -- librosa uses soxr, whose output it does not reproduce bit for bit).
+``wav_info`` reads the header only (rate, channels, frames): dataset lengths are known without decoding audio.
 """
 from __future__ import annotations
 
@@ -13,7 +15,7 @@ import struct
 
 import numpy as np
 
-__all__ = ["read_wav", "write_wav"]
+__all__ = ["read_wav", "write_wav", "wav_info"]
 
 
 def read_wav(path, mono: bool = True):
@@ -70,6 +72,36 @@ def read_wav(path, mono: bool = True):
     if mono:
         x = x[:, 0] if channels == 1 else x.mean(axis=1, dtype=np.float32)
     return np.ascontiguousarray(x, dtype=np.float32), int(rate)
+
+
+def wav_info(path):
+    """-> (sample_rate, channels, frames) from the RIFF chunks' headers; the sample data is not read."""
+    with open(path, "rb") as fh:
+        head = fh.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
+            raise ValueError(f"{path}: not a RIFF/WAVE file")
+        fmt = None
+        while True:
+            hdr = fh.read(8)
+            if len(hdr) < 8:
+                break
+            tag, size = hdr[:4], struct.unpack("<I", hdr[4:])[0]
+            if tag == b"fmt ":
+                fmt = fh.read(size)
+                fh.seek(size & 1, 1)
+            elif tag == b"data" and fmt is not None:
+                if len(fmt) < 16:
+                    break
+                _, channels, rate, _, _, bits = struct.unpack_from("<HHIIHH", fmt, 0)
+                if channels < 1 or bits < 8:
+                    raise ValueError(f"{path}: bad fmt chunk")
+                here = fh.tell()
+                fh.seek(0, 2)
+                size = min(size, fh.tell() - here)             # a truncated file decodes what is there (read_wav does)
+                return int(rate), int(channels), size // ((bits // 8) * channels)
+            else:
+                fh.seek(size + (size & 1), 1)
+    raise ValueError(f"{path}: missing fmt or data chunk")
 
 
 def write_wav(path, audio, sample_rate: int, subtype: str = "PCM_16"):

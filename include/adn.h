@@ -16,7 +16,7 @@
  *     (one-time weight upload / free), adn_prepare, and the FIRST call per (device, n_fft) of an STFT-family entry point
  *     (adn_stft_mag, adn_stft_mag_fit, adn_stft_complex, adn_istft, adn_griffin_lim) or per device of adn_perceptual_loss / adn_perceptual_loss_backward, which
  *     builds a few KB of constant tables (window, twiddles, mel filters) with a blocking upload -- unless adn_prepare did so
- *     before.  Such a cold call on a stream that is being captured enqueues nothing and returns ADN_ERR_INVALID (never a HIP
+ *     before; and the FIRST adn_resample per (device, rate pair), which builds its coefficient table (adn_resample_prepare).  Such a cold call on a stream that is being captured enqueues nothing and returns ADN_ERR_INVALID (never a HIP
  *     error): call adn_prepare(device, n_fft) before capturing.  adn_unet_forward never blocks or allocates.
  *   - ownership: the caller owns every buffer it passes (x, y, audio, out, workspace); a handle owns only
  *     its packed (BatchNorm-folded, re-laid-out) weights.
@@ -32,7 +32,7 @@
 
 #include <stddef.h>
 
-/* The 30 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 35 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -178,6 +178,40 @@ ADN_API int adn_perceptual_loss_backward_workspace_bytes(int n_clips, int F, int
 ADN_API int adn_perceptual_loss_backward(const float *pred, const float *target, int n_clips, int F, int T,
                                          const float *grad_out, void *workspace, size_t workspace_bytes,
                                          float *grad_pred, float *grad_target, void *stream);
+
+/* ---- resampling and SNR noise mixing: the ingest of the training path --------------------------------------------------------
+ * adn_resample replaces the rate conversion of librosa.load(path, sr=SAMPLE_RATE) (code/create_train_dataset.py:204,217,
+ * code/create_test_dataset.py:144).  librosa resamples with soxr; this library DEFINES its own filter instead (soxr's taps are
+ * not reproduced: parity with librosa.load is unpinned, like the STFT's parity with librosa), chosen so that an independent
+ * implementation exists -- with the taps h below, scipy.signal.resample_poly(x, up, down, window=h / up) is the same operator.
+ *   g = gcd(src_rate, dst_rate), up = dst_rate / g, down = src_rate / g, q = max(up, down)
+ *   prototype low-pass on the up-times oversampled grid, length 2*half + 1, half = ZEROS * q:
+ *     h[j] = up * fc * sinc(fc * j) * kaiser(2*half + 1, BETA)[j + half],  j = -half .. half,  fc = ROLLOFF / q,
+ *     sinc(t) = sin(pi t) / (pi t), kaiser = numpy.kaiser;  ZEROS = 32, BETA = 12.0, ROLLOFF = 0.88
+ *   output length M = ceil(L * up / down) (adn_resample_length; librosa's and scipy's rule)
+ *   y[m] = sum_i x[i] * h[m*down - i*up] over the i with |m*down - i*up| <= half and 0 <= i < L
+ *     (zero extension at both ends, zero phase: sample 0 maps to sample 0)
+ *   src_rate == dst_rate: a plain copy (the filter is not applied).
+ * The taps are computed on the host in float64, rounded once to fp32 and cached per (device, up, down); sums are accumulated in
+ * fp32, one output per lane in a fixed order: no atomics, two calls are bit-identical and a clip's result does not depend on the
+ * batch it is in.  Pass band (44.1 / 48 kHz -> 8 kHz): |gain - 1| < 1e-5 up to 3 kHz; at and above the new Nyquist < -110 dB.
+ * Limits: rates >= 1, max(up, down) <= 4096, length >= 1, M < 2^31 (ADN_ERR_INVALID otherwise).
+ * audio: device (n_clips, length) fp32; out: device (n_clips, M) fp32, may not alias audio.  adn_resample_prepare builds the table
+ * of a rate pair on `device` ahead of time (synchronous, idempotent, thread-safe); a cold adn_resample on a stream that is being
+ * captured enqueues nothing and returns ADN_ERR_INVALID. */
+ADN_API int adn_resample_length(long length, int src_rate, int dst_rate, long *out_length);
+ADN_API int adn_resample_prepare(int device, int src_rate, int dst_rate);
+ADN_API int adn_resample(const float *audio, int n_clips, long length, int src_rate, int dst_rate, float *out, void *stream);
+/* add_noise for "white" / "urban" (code/create_train_dataset.py:147-157), clip by clip:
+ *   c = sqrt(mean(clean^2) + 1e-12), n = sqrt(mean(noise^2) + 1e-12), s = c / 10^(snr_db / 20) / n,
+ *   out = clip(clean + s * noise, -1, 1)
+ * (the reference's `noise_rms > 1e-9` branch is always taken because of the 1e-12; silent noise gives s * 0 = 0).
+ * clean, noise, out: device (n_clips, length) fp32; out may be `noise` (written in place) but not `clean`.  The two mean
+ * squares are blocked fp32 sums in a fixed order (8192-sample blocks spread over the chip, then a tree): no float atomics,
+ * two calls are bit-identical.  adn_mix_snr_workspace_bytes of device scratch; snr_db in [-200, 200]. */
+ADN_API int adn_mix_snr_workspace_bytes(int n_clips, long length, size_t *bytes);
+ADN_API int adn_mix_snr(const float *clean, const float *noise, int n_clips, long length, float snr_db,
+                        void *workspace, size_t workspace_bytes, float *out, void *stream);
 
 /* ---- inverse STFT and Griffin-Lim ----------------------------------------------------------------------------
  * Replaces griffin_lim_reconstruction (/root/reference/code/test.py:29-48): librosa.istft + librosa.stft iterated
