@@ -7,7 +7,7 @@ __version__ = "0.1.0"
 
 __all__ = ["UNet", "SpectrogramDataset", "WavToSpecDataset", "audio_to_magnitude_spectrogram",
            "audio_to_spectrogram", "stft_magnitude", "per_clip_l1", "CombinedPerceptualLoss", "NoiseMixDataset",
-           "resample_length", "mix_snr", "load_audio"]      # (resample itself: audiodenoiser_amd.resample.resample -- the module owns the name)
+           "resample_length", "mix_snr", "load_audio", "Denoiser"]      # (resample itself: audiodenoiser_amd.resample.resample -- the module owns the name)
 
 
 def __getattr__(name):
@@ -23,6 +23,9 @@ def __getattr__(name):
     if name in ("resample_length", "mix_snr", "load_audio"):
         import importlib
         return getattr(importlib.import_module(".resample", __name__), name)
+    if name == "Denoiser":
+        import importlib
+        return importlib.import_module(".denoise", __name__).Denoiser
     if name in ("per_clip_l1", "CombinedPerceptualLoss"):
         from . import loss
         return getattr(loss, name)

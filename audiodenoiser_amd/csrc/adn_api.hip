@@ -1340,4 +1340,69 @@ int adn_griffin_lim(const float *magnitude, const float *rnd, int n_clips, int n
     return ADN_OK;
 }
 
+/* ---- long-form denoising: windows, stitch, resynthesis (adn.h, "denoise") --------------------------------------- */
+// element counts are indexed with `long` in the kernels; what is refused is what would not fit the 32-bit frame / grid arithmetic
+static const char *denoise_plan_text = ": need n_frames >= 1, window >= 16 and 0 <= overlap <= window / 2";
+
+int adn_denoise_plan(int n_frames, int window, int overlap, int *n_windows, int *window_width)
+{
+    if (!n_windows || !window_width) return fail(ADN_ERR_INVALID, "adn_denoise_plan: null pointer");
+    adn::DenoiseGeom g;
+    if (!adn::denoise_geom(n_frames, window, overlap, &g)) return fail(ADN_ERR_INVALID, std::string("adn_denoise_plan") + denoise_plan_text);
+    *n_windows = g.K;
+    *window_width = g.Wd;
+    return ADN_OK;
+}
+
+int adn_denoise_windows(const float *spec, int n_clips, int n_frames, int n_bins, int window, int overlap, float *out, void *stream)
+{
+    if (!spec || !out) return fail(ADN_ERR_INVALID, "adn_denoise_windows: null pointer");
+    if (n_clips < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, "adn_denoise_windows: n_clips and n_bins must be >= 1");
+    adn::DenoiseGeom g;
+    if (!adn::denoise_geom(n_frames, window, overlap, &g)) return fail(ADN_ERR_INVALID, std::string("adn_denoise_windows") + denoise_plan_text);
+    if ((long)g.K * g.Wd >= (1L << 31)) return fail(ADN_ERR_INVALID, "adn_denoise_windows: windows x width must be < 2^31 frames");
+    if (!aligned_to(spec, 8) || !aligned_to(out, 4)) return fail(ADN_ERR_INVALID, "adn_denoise_windows: spec must be 8-byte aligned, out 4-byte aligned");
+    hipError_t e = adn::launch_denoise_windows(spec, n_clips, n_bins, g, out, static_cast<hipStream_t>(stream));
+    if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_denoise_windows: grid too large (n_clips x windows x 32x32 tiles >= 2^31)");
+    ADN_HIP(e);
+    return ADN_OK;
+}
+
+int adn_denoise_stitch(const float *y, int n_clips, int n_frames, int n_bins, int window, int overlap, int clamp, float *out, void *stream)
+{
+    if (!y || !out) return fail(ADN_ERR_INVALID, "adn_denoise_stitch: null pointer");
+    if (y == out) return fail(ADN_ERR_INVALID, "adn_denoise_stitch: out may not alias y");
+    if (n_clips < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, "adn_denoise_stitch: n_clips and n_bins must be >= 1");
+    if (clamp != 0 && clamp != 1) return fail(ADN_ERR_INVALID, "adn_denoise_stitch: clamp must be 0 or 1");
+    adn::DenoiseGeom g;
+    if (!adn::denoise_geom(n_frames, window, overlap, &g)) return fail(ADN_ERR_INVALID, std::string("adn_denoise_stitch") + denoise_plan_text);
+    if ((long)g.K * g.Wd >= (1L << 31)) return fail(ADN_ERR_INVALID, "adn_denoise_stitch: windows x width must be < 2^31 frames");
+    const bool vec = ((g.T | g.Wd | g.S | g.V) & 3) == 0;          // the 16-byte path (launch_denoise_stitch takes it by the same rule)
+    if (!aligned_to(y, vec ? 16 : 4) || !aligned_to(out, vec ? 16 : 4))
+        return fail(ADN_ERR_INVALID, "adn_denoise_stitch: y and out must be 4-byte aligned (16-byte when n_frames, the window width, stride and overlap are all multiples of 4)");
+    hipError_t e = adn::launch_denoise_stitch(y, n_clips, n_bins, g, clamp, out, static_cast<hipStream_t>(stream));
+    if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_denoise_stitch: grid too large (n_clips x n_bins x n_frames / 1024 >= 2^31)");
+    ADN_HIP(e);
+    return ADN_OK;
+}
+
+int adn_denoise_resynth(const float *y, const float *spec, int n_clips, long length, int n_fft, int hop, int window, int overlap,
+                        float *audio_out, void *stream)
+{
+    if (!y || !spec || !audio_out) return fail(ADN_ERR_INVALID, "adn_denoise_resynth: null pointer");
+    if (!gl_size_ok(n_fft)) return fail(ADN_ERR_INVALID, "adn_denoise_resynth: n_fft must be a power of two in [64, 4096]");
+    if (hop < 1 || hop > n_fft / 4)
+        return fail(ADN_ERR_INVALID, "adn_denoise_resynth: need 1 <= hop <= n_fft / 4 (at n_fft / 2 the window sum-of-squares of the tail samples falls to 2e-8)");
+    if (n_clips < 1 || length < 1 || length >= (1L << 30)) return fail(ADN_ERR_INVALID, "adn_denoise_resynth: need n_clips >= 1 and 1 <= length < 2^30");
+    adn::DenoiseGeom g;
+    if (!adn::denoise_geom((int)(1 + length / hop), window, overlap, &g)) return fail(ADN_ERR_INVALID, std::string("adn_denoise_resynth") + denoise_plan_text);
+    if ((long)g.K * g.Wd >= (1L << 31)) return fail(ADN_ERR_INVALID, "adn_denoise_resynth: windows x width must be < 2^31 frames");
+    if (!aligned_to(spec, 8) || !aligned_to(y, 4) || !aligned_to(audio_out, 4))
+        return fail(ADN_ERR_INVALID, "adn_denoise_resynth: spec must be 8-byte aligned, y and audio_out 4-byte aligned");
+    hipError_t e = adn::launch_denoise_resynth(y, spec, n_clips, length, n_fft, hop, g, audio_out, static_cast<hipStream_t>(stream));
+    if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_denoise_resynth: grid too large (n_clips x length / 2048 >= 2^31)");
+    ADN_LAUNCH(e, "adn_denoise_resynth");
+    return ADN_OK;
+}
+
 }  // extern "C"

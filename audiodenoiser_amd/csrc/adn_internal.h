@@ -269,6 +269,18 @@ hipError_t launch_istft_frames(const void *spec, int n_clips, int T, int n_fft, 
 hipError_t launch_istft_ola(const float *buf, int n_clips, int T, int n_fft, int hop, float *audio, hipStream_t st);
 hipError_t launch_stft_complex(const float *audio, int n_clips, long L, int n_fft, int hop, int T, void *spec,
                                hipStream_t st);
+// Long-form denoising (denoise_kernels.hip).  DenoiseGeom: the window plan of adn.h ("denoise", rule 2) for T frames --
+// K windows of Wd frames, S = window - overlap frames apart, V = overlap shared frames; denoise_geom is false outside
+// n_frames >= 1, window >= 16, 0 <= overlap <= window / 2.  Windows are bin-major [clip * K + k][F][Wd], X frame-major float2.
+struct DenoiseGeom {
+    int T, K, Wd, S, V;
+};
+bool denoise_geom(int n_frames, int window, int overlap, DenoiseGeom *g);
+hipError_t launch_denoise_windows(const void *spec, int n_clips, int F, const DenoiseGeom &g, float *out, hipStream_t st);
+hipError_t launch_denoise_stitch(const float *y, int n_clips, int F, const DenoiseGeom &g, int clamp, float *out,
+                                 hipStream_t st);
+hipError_t launch_denoise_resynth(const float *y, const void *spec, int n_clips, long L, int n_fft, int hop,
+                                  const DenoiseGeom &g, float *audio, hipStream_t st);
 hipError_t launch_quantize_pad(const float *in, int n, int h, int w, float *out, int H, int W, hipStream_t st);
 hipError_t launch_per_clip_l1(const float *a, const float *b, int n_clips, long elems, float *out, hipStream_t st);
 // Polyphase resampler and SNR mixer (resample_kernels.hip).  resample_ratio: up / down of a rate pair, false outside the limits

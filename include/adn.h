@@ -32,7 +32,7 @@
 
 #include <stddef.h>
 
-/* The 35 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 39 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -231,6 +231,51 @@ ADN_API int adn_stft_complex(const float *audio, int n_clips, long length, int n
 ADN_API int adn_istft_workspace_bytes(int n_clips, int n_frames, int n_fft, size_t *bytes);
 ADN_API int adn_istft(const float *spec, int n_clips, int n_frames, int n_fft, int hop, void *workspace, size_t workspace_bytes,
               float *audio_out, void *stream);
+
+/* ---- denoise: audio of any length through the network and back ---------------------------------------------------------------
+ * The reference feeds one fixed 257 x 188 spectrogram per clip to the network (test.py:100-114) and goes back to audio through
+ * Griffin-Lim from a random phase (test.py:29-48).  These entry points DEFINE the long form (no reference counterpart; float64
+ * restatement in tests/denoise_ref.py): the spectrogram is cut into overlapping windows of the width the network was trained
+ * for, the outputs are cross-faded, and the audio comes back with the noisy input's own phase.
+ * Not pinned / not validated: parity of the STFT with librosa stays unpinned as for adn_stft_complex; the defaults
+ * window = 256, overlap = 32 are design defaults whose audible quality has not been judged (no trained checkpoint exists
+ * here); the result of overlapping windows DIFFERS from a forward over the whole spectrogram by design (the network's receptive
+ * field is wider than the overlap) -- the single-window case is exact, the multi-window case is what is defined below.
+ *
+ *   n_fft power of two in [64, 4096], 1 <= hop <= n_fft / 4, F = n_fft / 2 + 1, window W >= 16, overlap 0 <= V <= W / 2, S = W - V.
+ *   1. X = adn_stft_complex(x): T = 1 + floor(L / hop) frames, centred, zero padded.
+ *   2. Plan (adn_denoise_plan): T <= W: one window of width max(T, 16).  Otherwise K = 1 + ceil((T - W) / S) windows of width W,
+ *      window k holds frames [k S, k S + W), frames >= T are zero.  in[k, 0, f, j] = |X[k S + j, f]| with
+ *      |X| = sqrtf(fmaf(re, re, im * im))   (one rounded product, one fma, one correctly rounded square root; no fp16 step).
+ *   3. y = UNet(in), (K, 1, F, W).
+ *   4. Stitch: weight of window k at local frame j: (j + 1) / (V + 1) for j < V and k > 0; (W - j) / (V + 1) for j >= W - V
+ *      and k < K - 1; 1 otherwise.  At most two windows cover a frame and their weights sum to 1.
+ *      Y[f, t] = sum_k a_k y[k, 0, f, t - k S] in ascending k: fp32 weights (one division), two rounded products, one rounded
+ *      sum, never contracted; a frame covered by one window is y itself, bit for bit.  M = max(Y, 0) with clamp (NaN stays NaN,
+ *      as in the network's ReLU), Y without.
+ *   5. Noisy phase (adn_denoise_resynth, clamp on): S^[t, f] = M[f, t] X[t, f] / |X[t, f]|, S^ = M (real) where the |X| of
+ *      rule 2 is 0; x^ = inverse STFT as adn_istft defines it (periodic Hann, overlap-added frames divided by the window
+ *      sum-of-squares of the frames that cover a sample, summed in ascending frame order) but of length L like
+ *      librosa.istft(..., length=L): the L - hop (T - 1) < hop tail samples are still covered by the last centred frames.
+ *      hop <= n_fft / 4 keeps that divisor >= 0.25 over [0, L); at hop = n_fft / 2 it falls to 2e-8 at the last tail sample,
+ *      hence the limit.  T = 1 (L < hop) is legal.
+ * Layouts: spec is frame-major (n_clips, n_frames, n_bins, 2) fp32 as adn_stft_complex writes it (8-byte aligned); windows /
+ * y are (n_clips * K, 1, n_bins, width) fp32, the window's frame index fastest, a clip's K windows consecutive; stitched
+ * spectrograms are (n_clips, n_bins, n_frames).  adn_denoise_windows and adn_denoise_stitch take any n_bins >= 1.
+ * All three kernels are deterministic (no atomics, fixed summation order): two calls are bit-identical and a clip's result does
+ * not depend on the batch it is in.  adn_denoise_resynth needs no workspace: a workgroup owns up to 4096 output samples, recomputes the
+ * n_fft / hop - 1 frames it shares with its neighbours, and keeps frames and the stitched magnitudes in LDS; it uses the tables
+ * of (device, n_fft) like the STFT family (adn_prepare before a capture).
+ * Limits (ADN_ERR_INVALID otherwise): length < 2^30 samples; K * width < 2^31; launch grids < 2^31 workgroups (n_clips x windows
+ * x 32x32 tiles; n_clips x n_bins x ceil(n_frames / 1024); n_clips x ceil(length / 2048)).  Element offsets are 64-bit.
+ * adn_denoise_plan is host-only (no device needed). */
+ADN_API int adn_denoise_plan(int n_frames, int window, int overlap, int *n_windows, int *window_width);
+ADN_API int adn_denoise_windows(const float *spec, int n_clips, int n_frames, int n_bins, int window, int overlap, float *out,
+                                void *stream);
+ADN_API int adn_denoise_stitch(const float *y, int n_clips, int n_frames, int n_bins, int window, int overlap, int clamp,
+                               float *out, void *stream);
+ADN_API int adn_denoise_resynth(const float *y, const float *spec, int n_clips, long length, int n_fft, int hop, int window,
+                                int overlap, float *audio_out, void *stream);
 
 /* ---- environment switches -------------------------------------------------------------------------------------------------
  * Read ONCE, when a U-Net handle is created (never per call).  None is needed in production: the defaults are the measured best

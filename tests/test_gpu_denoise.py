@@ -1,0 +1,371 @@
+"""Long-form denoiser on the device (csrc/denoise_kernels.hip, audiodenoiser_amd/denoise.py) against the float64 restatement
+in tests/denoise_ref.py.
+
+Bounds (derived, not tuned; eps = 2^-24):
+* adn_denoise_windows, per element: |X| = sqrtf(fmaf(re, re, im * im)) is one rounded product (relative e1 on im^2), one fma
+  (e2 on the sum) and one correctly rounded square root (e3): sqrt((re^2 + im^2 (1 + e1)) (1 + e2)) (1 + e3) differs from
+  |X| by at most (e1 / 2 + e2 / 2 + e3) |X| <= 2 eps |X|; 2.01 eps |X| + 2^-62 (the square root of the smallest normal,
+  for squares that underflow).  The restatement is applied to the DOWNLOADED device spectrogram, so the STFT's own error
+  does not enter.  Padding is exactly zero.
+* adn_denoise_stitch, per element: the fp32 weight is one correctly rounded division of two exact integers (eps), each
+  product rounds once (eps), the sum of the two products rounds once (eps): (1 + eps)^3 - 1 <= 3.01 eps relative to
+  sum_k a_k |y_k|; 4 eps sum_k a_k |y_k| leaves one eps for a division that is not correctly rounded.  A frame that one
+  window covers is y itself.
+* adn_denoise_resynth: the tree's inverse-STFT tolerance TOL = 1e-4 of max |ref| (test_istft_and_complex_stft_match_oracle);
+  the round trip with y = windows(X) within the tree's round-trip figure 1e-5 absolute on uniform [-1, 1] audio, and over the
+  last `hop` samples, where the window sum-of-squares falls from 1.5 to as little as 0.26, that figure times 1.5 / 0.26: 6e-5.
+* U-Net: the tree's TOL = 1e-4 of max |ref| in fp32, 1e-2 in fp16 (test_gpu_parity.py).
+Measured on the MI355X: the windows use up to 0.94 of their bound, the stitch 0.67.
+"""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import denoise_ref as ref  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EPS = 2.0 ** -24
+TOL = 1e-4
+PARAMS = ((512, 128, 256, 32), (512, 128, 64, 0), (256, 64, 48, 24), (1024, 256, 32, 16))     # n_fft, hop, W, V
+N_CLIPS = 3
+
+
+def lengths(hop):
+    return (24000, 24001, 100000, 37, 1, hop - 1, 2 * hop - 1)
+
+
+CASES = [p + (length,) for p in PARAMS for length in lengths(p[1])]
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
+    return torch.device("cuda", 0)
+
+
+def _net(weights_np, dev):
+    from audiodenoiser_amd.model import UNet
+    m = UNet(1, 1)
+    m.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in weights_np.items()}, strict=True)
+    return m.to(dev).eval()
+
+
+@pytest.fixture(scope="module")
+def net(weights_np, dev):
+    return _net(weights_np, dev)
+
+
+def _dn(net, n_fft=512, hop=128, window=256, overlap=32, **kw):
+    from audiodenoiser_amd import Denoiser
+    return Denoiser(net, n_fft=n_fft, hop_length=hop, window_frames=window, overlap_frames=overlap, **kw)
+
+
+def _audio(dev, n_fft, window, length, n_clips=N_CLIPS):
+    x = np.random.default_rng([n_fft, window, length]).uniform(-1.0, 1.0, (n_clips, length)).astype(np.float32)
+    return x, torch.from_numpy(x).to(dev)
+
+
+def _spec(xd, n_fft, hop):
+    from audiodenoiser_amd.griffin_lim import stft_complex
+    spec = stft_complex(xd, n_fft, hop)
+    return spec, spec.cpu().numpy().astype(np.complex128)
+
+
+@pytest.mark.parametrize("n_fft,hop,window,overlap,length", CASES)
+def test_windows_against_restatement(dev, net, n_fft, hop, window, overlap, length):
+    dn = _dn(net, n_fft, hop, window, overlap)
+    _, xd = _audio(dev, n_fft, window, length)
+    spec, spec_h = _spec(xd, n_fft, hop)
+    n_frames = 1 + length // hop
+    assert spec.shape == (N_CLIPS, n_frames, n_fft // 2 + 1)
+    k, width = ref.plan(n_frames, window, overlap)
+    got = dn.windows(spec)
+    assert got.shape == (N_CLIPS * k, 1, n_fft // 2 + 1, width) and got.dtype == torch.float32
+    got = got.cpu().numpy().astype(np.float64).reshape(N_CLIPS, k, n_fft // 2 + 1, width)
+    worst = 0.0
+    for c in range(N_CLIPS):
+        want = ref.windows(np.abs(spec_h[c]), window, overlap)
+        err = np.abs(got[c] - want)
+        bound = 2.01 * EPS * want + 2.0 ** -62
+        worst = max(worst, float((err / bound).max()))
+        assert np.all(err <= bound), (c, float(err.max()))
+        for i in range(k):                                     # frames past the end of the clip: exactly zero
+            n = min(width, n_frames - i * (window - overlap))
+            assert np.all(got[c, i, :, n:] == 0.0)
+    print(f"windows n_fft {n_fft} W {window} V {overlap} L {length}: K {k} width {width}, largest share of the bound {worst:.3f}")
+
+
+@pytest.mark.parametrize("clamp", (False, True))
+@pytest.mark.parametrize("n_bins,n_frames,window,overlap", ((257, 188, 256, 32), (257, 782, 256, 32), (257, 781, 256, 32), (129, 1, 48, 24),
+                                                           (129, 1563, 48, 24), (513, 391, 32, 16), (257, 300, 64, 0), (33, 1024, 64, 8)))
+def test_stitch_against_restatement(dev, net, clamp, n_bins, n_frames, window, overlap):
+    dn = _dn(net, 512, 128, window, overlap)
+    k, width = ref.plan(n_frames, window, overlap)
+    rng = np.random.default_rng([n_bins, n_frames, window])
+    y = rng.standard_normal((N_CLIPS * k, 1, n_bins, width)).astype(np.float32)
+    yd = torch.from_numpy(y).to(dev)
+    got = dn.stitch(yd, N_CLIPS, n_frames, clamp)
+    assert got.shape == (N_CLIPS, n_bins, n_frames)
+    assert torch.equal(got, dn.stitch(yd, N_CLIPS, n_frames, clamp))
+    got = got.cpu().numpy().astype(np.float64)
+    y64 = y.astype(np.float64).reshape(N_CLIPS, k, n_bins, width)
+    worst = 0.0
+    for c in range(N_CLIPS):
+        want, sum_abs = ref.stitch(y64[c], n_frames, window, overlap, clamp=clamp, with_sum_abs=True)
+        err = np.abs(got[c] - want)
+        bound = 4.0 * EPS * sum_abs
+        worst = max(worst, float((err / np.maximum(bound, 1e-300)).max()))
+        assert np.all(err <= bound), (c, float(err.max()))
+    print(f"stitch F {n_bins} T {n_frames} W {window} V {overlap} clamp {clamp}: K {k}, largest share of the bound {worst:.3f}")
+    if k == 1 and not clamp:
+        assert np.array_equal(got, y64[:, 0, :, :n_frames])      # one window: y itself, bit for bit
+
+
+@pytest.mark.parametrize("clamp", (False, True))
+def test_stitch_passes_nan_and_inf(dev, net, clamp):
+    dn = _dn(net, 512, 128, 64, 16)
+    n_frames, n_bins = 200, 40
+    k, width = ref.plan(n_frames, 64, 16)
+    y = np.random.default_rng(9).standard_normal((k, 1, n_bins, width)).astype(np.float32)
+    y[1, 0, 2, 3] = np.nan            # inside the cross-fade of windows 0 and 1 (frame 51)
+    y[1, 0, 5, 30] = np.nan           # covered by window 1 alone (frame 78)
+    y[2, 0, 0, 60] = np.inf           # cross-fade of windows 2 and 3 (frame 156)
+    y[0, 0, 7, 10] = -np.inf          # window 0 alone
+    got = dn.stitch(torch.from_numpy(y).to(dev), 1, n_frames, clamp).cpu().numpy()[0]
+    want, sum_abs = ref.stitch(y[:, 0].astype(np.float64), n_frames, 64, 16, clamp=clamp, with_sum_abs=True)
+    assert np.array_equal(np.isnan(got), np.isnan(want)) and np.isnan(got).sum() == 2
+    assert np.array_equal(np.isposinf(got), np.isposinf(want)) and np.isposinf(got).sum() == 1
+    assert np.array_equal(np.isneginf(got), np.isneginf(want)) and np.isneginf(got).sum() == (0 if clamp else 1)
+    ok = np.isfinite(want)
+    assert np.all(np.abs(got[ok] - want[ok]) <= 4.0 * EPS * sum_abs[ok])
+
+
+@pytest.mark.parametrize("n_fft,hop,window,overlap,length", CASES)
+def test_resynth(dev, net, n_fft, hop, window, overlap, length):
+    """Measured on the MI355X, worst over all cases: identity round trip 4.2e-7 absolute in the body and 3.0e-7 over the last
+    hop samples (allowances 1e-5 / 6e-5); random y against the restatement 2.3e-7 and against the composed device form 3.3e-7
+    of the maximum (TOL 1e-4)."""
+    from audiodenoiser_amd.griffin_lim import istft
+    dn = _dn(net, n_fft, hop, window, overlap)
+    x, xd = _audio(dev, n_fft, window, length)
+    spec, spec_h = _spec(xd, n_fft, hop)
+    n_frames = 1 + length // hop
+    k, width = ref.plan(n_frames, window, overlap)
+    n_bins = n_fft // 2 + 1
+    # (a) identity in place of the network: the input comes back
+    back = dn.resynth(dn.windows(spec), spec, length)
+    assert back.shape == (N_CLIPS, length) and back.dtype == torch.float32
+    err = np.abs(back.cpu().numpy().astype(np.float64) - x)
+    body, tail = err[:, :max(length - hop, 0)], err[:, max(length - hop, 0):]
+    e_body, e_tail = float(body.max()) if body.size else 0.0, float(tail.max())
+    print(f"resynth n_fft {n_fft} W {window} V {overlap} L {length}: identity body {e_body:.3g} tail {e_tail:.3g}")
+    assert e_body <= 1e-5 and e_tail <= 6e-5
+    rng = np.random.default_rng([n_fft, window, length, 1])
+    for kind in ("non-negative", "signed"):
+        y = rng.standard_normal((N_CLIPS * k, 1, n_bins, width)).astype(np.float32)
+        y = np.abs(y) if kind == "non-negative" else y
+        yd = torch.from_numpy(y).to(dev)
+        got_d = dn.resynth(yd, spec, length)
+        got = got_d.cpu().numpy().astype(np.float64)
+        y64 = y.astype(np.float64).reshape(N_CLIPS, k, n_bins, width)
+        # (b) against the restatement
+        for c in range(N_CLIPS):
+            want = ref.resynth(y64[c], spec_h[c], length, hop, window, overlap)
+            e = float(np.abs(got[c] - want).max() / np.abs(want).max())
+            assert e <= TOL, (kind, c, e)
+        # (c) against the composed form on the device: stitch + clamp, rescale, adn_istft
+        if n_frames >= 2:
+            m = dn.stitch(yd, N_CLIPS, n_frames, clamp=True).transpose(1, 2)          # (N, T, F)
+            mag = spec.abs()
+            s_hat = torch.where(mag > 0, m * spec / torch.where(mag > 0, mag, torch.ones_like(mag)), m.to(torch.complex64))
+            composed = istft(s_hat.contiguous(), hop).cpu().numpy().astype(np.float64)
+            n = hop * (n_frames - 1)
+            e = float(np.abs(got[:, :n] - composed).max() / np.abs(composed).max())
+            print(f"  {kind}: restatement {float(np.abs(got[c] - want).max() / np.abs(want).max()):.3g}, composed form {e:.3g}")
+            assert e <= TOL, (kind, e)
+        # (d) deterministic, and a clip does not depend on its batch
+        assert torch.equal(got_d, dn.resynth(yd, spec, length))
+        alone = dn.resynth(yd[k:2 * k].clone(), spec[1:2].clone(), length)
+        assert torch.equal(alone[0], got_d[1])
+
+
+def test_resynth_silence_is_finite(dev, net):
+    """|X| = 0 (digital silence, whole clip and a stretch inside a clip): S^ = M, finite output."""
+    dn = _dn(net)
+    length = 40000
+    x = np.random.default_rng(2).uniform(-1, 1, (2, length)).astype(np.float32)
+    x[0] = 0.0
+    x[1, 10000:30000] = 0.0
+    spec, spec_h = _spec(torch.from_numpy(x).to(dev), 512, 128)
+    assert (spec_h[1] == 0).all(axis=1).sum() > 100
+    k, width = ref.plan(1 + length // 128, 256, 32)
+    y = np.abs(np.random.default_rng(3).standard_normal((2 * k, 1, 257, width))).astype(np.float32)
+    got = dn.resynth(torch.from_numpy(y).to(dev), spec, length).cpu().numpy().astype(np.float64)
+    assert np.isfinite(got).all()
+    for c in range(2):
+        want = ref.resynth(y.astype(np.float64).reshape(2, k, 257, width)[c], spec_h[c], length, 128, 256, 32)
+        assert np.abs(got[c] - want).max() <= TOL * np.abs(want).max()
+
+
+@pytest.mark.parametrize("dtype,n_fft,hop,window,overlap,length,n_clips",
+                         (("f32", 512, 128, 256, 32, 100000, 1), ("f32", 256, 64, 48, 24, 24001, 3), ("f32", 512, 128, 256, 32, 24000, 2),
+                          ("f16", 512, 128, 256, 32, 60000, 1)))
+def test_end_to_end_in_two_links(dev, weights_np, dtype, n_fft, hop, window, overlap, length, n_clips):
+    """Device y against oracle/unet_torch.py on the device's own windows; device audio against the restatement fed the
+    device's y: no tolerance of its own."""
+    from oracle import unet_torch
+    net = _net(weights_np, dev).set_compute_dtype(dtype)
+    dn = _dn(net, n_fft, hop, window, overlap, batch_windows=3)
+    x, xd = _audio(dev, n_fft, window, length, n_clips)
+    spec, spec_h = _spec(xd, n_fft, hop)
+    win = dn.windows(spec)
+    y = dn.network(win)
+    sd = unet_torch.to_torch_state(weights_np)
+    win_h, y_h = win.cpu(), y.cpu().numpy()
+    tol = TOL if dtype == "f32" else 1e-2
+    for i in range(win_h.shape[0]):
+        want = unet_torch.unet_forward(sd, win_h[i:i + 1]).numpy()
+        e = float(np.abs(y_h[i:i + 1] - want).max() / np.abs(want).max())
+        assert e <= tol, (i, e)
+    out = dn.denoise(xd)
+    assert out.shape == xd.shape and out.is_cuda and torch.isfinite(out).all()
+    assert torch.equal(out, dn.resynth(y, spec, length))
+    k = win_h.shape[0] // n_clips
+    got = out.cpu().numpy().astype(np.float64)
+    for c in range(n_clips):
+        want = ref.resynth(y_h.astype(np.float64).reshape(n_clips, k, *y_h.shape[2:])[c], spec_h[c], length, hop, window, overlap)
+        e = float(np.abs(got[c] - want).max() / np.abs(want).max())
+        print(f"end to end {dtype} n_fft {n_fft} L {length} clip {c}: audio {e:.3g}")
+        assert e <= TOL, (c, e)
+    # numpy in -> numpy out, (L,) in -> (L,) out
+    one = dn.denoise(x[0])
+    assert isinstance(one, np.ndarray) and one.shape == (length,) and one.dtype == np.float32
+    net._workspace = None
+
+
+def test_denoise_spectrogram(dev, weights_np):
+    net = _net(weights_np, dev)
+    dn = _dn(net)
+    g = torch.Generator(device=dev).manual_seed(5)
+    for shape in ((2, 257, 188), (1, 257, 256), (3, 64, 16)):
+        mag = torch.rand(shape, generator=g, device=dev) * 3.0
+        with torch.no_grad():
+            want = net(mag[:, None])[:, 0]
+        assert torch.equal(dn.denoise_spectrogram(mag), want), shape
+    with torch.no_grad():
+        want_one = net(mag[:1, None])[0, 0]                    # (F, T) in = a batch of one (the default handle is not batch invariant)
+    single = dn.denoise_spectrogram(mag[0].cpu().numpy())
+    assert isinstance(single, np.ndarray) and np.array_equal(single, want_one.cpu().numpy())
+    short = dn.denoise_spectrogram(torch.rand((1, 257, 5), generator=g, device=dev))       # padded to 16 frames inside
+    assert short.shape == (1, 257, 5) and torch.isfinite(short).all()
+    net.set_batch_invariant(True)
+    mag = torch.rand((2, 257, 1000), generator=g, device=dev) * 3.0                        # 5 windows per clip
+    outs = [_dn(net, batch_windows=b).denoise_spectrogram(mag) for b in (1, 7, 64)]
+    assert outs[0].shape == mag.shape and torch.isfinite(outs[0]).all()
+    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+    # the restatement's stitch of the same windows
+    k, width = ref.plan(1000, 256, 32)
+    x = torch.zeros((2, k, 257, width), device=dev)
+    for i in range(k):
+        part = mag[:, :, i * 224:i * 224 + width]
+        x[:, i, :, :part.shape[2]] = part
+    y = _dn(net).network(x.view(2 * k, 1, 257, width)).cpu().numpy().astype(np.float64).reshape(2, k, 257, width)
+    for c in range(2):
+        want, sum_abs = ref.stitch(y[c], 1000, 256, 32, with_sum_abs=True)
+        assert np.all(np.abs(outs[0][c].cpu().numpy() - want) <= 4.0 * EPS * sum_abs)
+    net._workspace = None
+
+
+@pytest.mark.parametrize("rate", (44100, 48000))
+def test_other_rates_come_back_at_their_rate_and_length(dev, net, rate):
+    from audiodenoiser_amd.resample import resample
+    dn = _dn(net)
+    for length in (66150, 66151, 1000):
+        x = torch.from_numpy(np.random.default_rng([rate, length]).uniform(-0.5, 0.5, (2, length)).astype(np.float32)).to(dev)
+        out = dn.denoise(x, sr=rate)
+        assert out.shape == x.shape and out.is_cuda and torch.isfinite(out).all()
+        up = resample(dn.denoise(resample(x, rate, 8000)), 8000, rate)
+        by_hand = torch.zeros_like(x)
+        n = min(length, up.shape[1])
+        by_hand[:, :n] = up[:, :n]
+        assert torch.equal(out, by_hand), (rate, length)
+    assert torch.equal(dn.denoise(x, sr=8000), dn.denoise(x))
+
+
+def test_griffin_lim_phase(dev, net):
+    from audiodenoiser_amd.griffin_lim import griffin_lim_reconstruction
+    dn = _dn(net, phase="griffin_lim", gl_iterations=4)
+    x, xd = _audio(dev, 512, 256, 24000, 1)
+    rand = np.random.default_rng(6).random((1, 257, 188))
+    out = dn.denoise(xd, rand=rand)
+    assert out.shape == (1, 24000) and torch.isfinite(out).all()
+    assert torch.equal(out, dn.denoise(xd, rand=rand))
+    spec, _ = _spec(xd, 512, 128)
+    mag = dn.windows(spec)                                       # (1, 1, 257, 188): the reference's network input
+    with torch.no_grad():
+        want = griffin_lim_reconstruction(net(mag)[:, 0], 512, 128, 4, rand=rand)
+    assert want.shape == (1, 23936)
+    assert torch.equal(out[:, :23936], want) and torch.all(out[:, 23936:] == 0)
+    long_x, long_xd = _audio(dev, 512, 256, 100000, 2)          # stitched, unclamped, then Griffin-Lim
+    long_out = dn.denoise(long_xd, rand=np.random.default_rng(7).random((2, 257, 782)))
+    assert long_out.shape == (2, 100000) and torch.isfinite(long_out).all() and torch.all(long_out[:, 128 * 781:] == 0)
+    with pytest.raises(ValueError, match="hop_length samples"):
+        dn.denoise(xd[:, :100])
+
+
+def test_ten_minute_signal(dev, net):
+    dn = _dn(net)
+    length = 4_800_000
+    x = torch.from_numpy(np.random.default_rng(8).uniform(-0.5, 0.5, length).astype(np.float32)).to(dev)
+    torch.cuda.synchronize(dev)
+    torch.cuda.reset_peak_memory_stats(dev)
+    out = dn.denoise(x)
+    torch.cuda.synchronize(dev)
+    peak = torch.cuda.max_memory_allocated(dev)
+    print(f"10-minute signal: {dn.plan(1 + length // 128)[0]} windows, peak device memory {peak / 2 ** 20:.0f} MiB")
+    assert out.shape == (length,) and torch.isfinite(out).all()
+    net._workspace = None
+
+
+def test_denoise_file_and_command_line(dev, net, weights_np, tmp_path):
+    from audiodenoiser_amd.wav import read_wav, write_wav
+    dn = _dn(net)
+    rng = np.random.default_rng(10)
+    t = np.arange(50000) / 44100.0
+    tone = (0.4 * np.sin(2 * np.pi * 440.0 * t) + 0.05 * rng.standard_normal(t.size)).astype(np.float32)
+    src, dst, dst_cli = str(tmp_path / "in.wav"), str(tmp_path / "out.wav"), str(tmp_path / "out_cli.wav")
+    write_wav(src, tone, 44100, "PCM_16")
+    assert dn.denoise_file(src, dst) == (50000, 44100)
+    samples, rate = read_wav(src)
+    want = dn.denoise(samples, sr=44100)
+    want = (np.clip(np.rint(want * 32768.0), -32768, 32767) / 32768.0).astype(np.float32)     # write_wav's PCM_16 rounding
+    got, got_rate = read_wav(dst)
+    assert got_rate == 44100 and got.shape == (50000,) and np.array_equal(got, want)
+    stereo = str(tmp_path / "stereo.wav")
+    write_wav(stereo, np.stack([tone, 0.5 * tone[::-1]], axis=1), 44100, "PCM_16")
+    assert dn.denoise_file(stereo, str(tmp_path / "stereo_out.wav"), subtype="FLOAT") == (50000, 44100)
+    both, _ = read_wav(str(tmp_path / "stereo_out.wav"), mono=False)
+    # every channel is a clip: the file equals denoise() of the (channels, L) array
+    assert both.shape == (50000, 2) and np.array_equal(both.T, dn.denoise(np.ascontiguousarray(read_wav(stereo, mono=False)[0].T), sr=44100))
+    ckpt = str(tmp_path / "ckpt.pth")
+    torch.save({k: torch.from_numpy(np.array(v)) for k, v in weights_np.items()}, ckpt)
+    run = subprocess.run([sys.executable, "-m", "audiodenoiser_amd.denoise", "--model", ckpt, src, dst_cli], cwd=ROOT,
+                         capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stderr[-2000:]
+    got_cli, rate_cli = read_wav(dst_cli)
+    assert rate_cli == 44100 and np.array_equal(got_cli, want)
+    folder_in, folder_out = tmp_path / "in_dir", tmp_path / "out_dir"
+    folder_in.mkdir()
+    write_wav(str(folder_in / "a.wav"), tone[:20000], 44100, "PCM_16")
+    write_wav(str(folder_in / "b.wav"), tone[:9000], 8000, "PCM_16")
+    run = subprocess.run([sys.executable, "-m", "audiodenoiser_amd.denoise", "--model", ckpt, "--dtype", "f16", "--window", "64",
+                          "--overlap", "8", str(folder_in), str(folder_out)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stderr[-2000:]
+    assert read_wav(str(folder_out / "a.wav"))[0].shape == (20000,) and read_wav(str(folder_out / "b.wav"))[1] == 8000
