@@ -7,7 +7,8 @@ __version__ = "0.1.0"
 
 __all__ = ["UNet", "SpectrogramDataset", "WavToSpecDataset", "audio_to_magnitude_spectrogram",
            "audio_to_spectrogram", "stft_magnitude", "per_clip_l1", "CombinedPerceptualLoss", "NoiseMixDataset",
-           "resample_length", "mix_snr", "load_audio", "Denoiser"]      # (resample itself: audiodenoiser_amd.resample.resample -- the module owns the name)
+           "resample_length", "mix_snr", "load_audio", "Denoiser", "ReverbSettings"]
+# (resample / reverb themselves: audiodenoiser_amd.resample.resample, audiodenoiser_amd.reverb.reverb -- the modules own the names)
 
 
 def __getattr__(name):
@@ -23,6 +24,9 @@ def __getattr__(name):
     if name in ("resample_length", "mix_snr", "load_audio"):
         import importlib
         return getattr(importlib.import_module(".resample", __name__), name)
+    if name == "ReverbSettings":
+        import importlib
+        return importlib.import_module(".reverb", __name__).ReverbSettings
     if name == "Denoiser":
         import importlib
         return importlib.import_module(".denoise", __name__).Denoiser

@@ -68,6 +68,8 @@ def load() -> ctypes.CDLL:
         L.adn_resample.argtypes = [vp, ci, cl, ci, ci, vp, vp]
         L.adn_mix_snr_workspace_bytes.argtypes = [ci, cl, ctypes.POINTER(sz)]
         L.adn_mix_snr.argtypes = [vp, vp, ci, cl, ctypes.c_float, vp, sz, vp, vp]
+        cf = ctypes.c_float
+        L.adn_reverb.argtypes = [vp, ci, cl, ci, cf, cf, cf, cf, cf, ci, vp, vp]
         L.adn_istft_length.argtypes = [ci, ci, ctypes.POINTER(cl)]
         L.adn_griffin_lim_workspace_bytes.argtypes = [ci, ci, ci, ctypes.POINTER(sz)]
         L.adn_griffin_lim.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, sz, vp, vp]
@@ -83,7 +85,7 @@ def load() -> ctypes.CDLL:
                      "adn_stft_n_frames", "adn_stft_mag", "adn_stft_mag_fit", "adn_quantize_pad", "adn_per_clip_l1",
                      "adn_perceptual_loss_workspace_bytes", "adn_perceptual_loss", "adn_perceptual_loss_backward_workspace_bytes",
                      "adn_perceptual_loss_backward", "adn_resample_length", "adn_resample_prepare", "adn_resample",
-                     "adn_mix_snr_workspace_bytes", "adn_mix_snr", "adn_istft_length",
+                     "adn_mix_snr_workspace_bytes", "adn_mix_snr", "adn_reverb", "adn_istft_length",
                      "adn_griffin_lim_workspace_bytes", "adn_griffin_lim", "adn_stft_complex",
                      "adn_istft_workspace_bytes", "adn_istft",
                      "adn_denoise_plan", "adn_denoise_windows", "adn_denoise_stitch", "adn_denoise_resynth"):
@@ -116,6 +118,6 @@ EXPORTED_SYMBOLS = (
     "adn_quantize_pad", "adn_per_clip_l1", "adn_perceptual_loss_workspace_bytes", "adn_perceptual_loss",
     "adn_perceptual_loss_backward_workspace_bytes", "adn_perceptual_loss_backward", "adn_istft_length", "adn_griffin_lim_workspace_bytes", "adn_griffin_lim", "adn_stft_complex",
     "adn_istft_workspace_bytes", "adn_istft",
-    "adn_resample_length", "adn_resample_prepare", "adn_resample", "adn_mix_snr_workspace_bytes", "adn_mix_snr",
+    "adn_resample_length", "adn_resample_prepare", "adn_resample", "adn_mix_snr_workspace_bytes", "adn_mix_snr", "adn_reverb",
     "adn_denoise_plan", "adn_denoise_windows", "adn_denoise_stitch", "adn_denoise_resynth",
 )

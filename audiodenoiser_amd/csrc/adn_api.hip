@@ -1206,6 +1206,34 @@ int adn_mix_snr(const float *clean, const float *noise, int n_clips, long length
     return ADN_OK;
 }
 
+int adn_reverb(const float *audio, int n_clips, long length, int sample_rate, float room_size, float damping, float wet_level,
+               float dry_level, float width, int clip, float *out, void *stream)
+{
+    if (!audio || !out) return fail(ADN_ERR_INVALID, "adn_reverb: null pointer");
+    if (n_clips < 1) return fail(ADN_ERR_INVALID, "adn_reverb: n_clips must be >= 1");
+    if (length < 1 || length >= (1L << 30)) return fail(ADN_ERR_INVALID, "adn_reverb: need 1 <= length < 2^30");
+    if (!adn::reverb_rate_ok(sample_rate))
+        return fail(ADN_ERR_INVALID, "adn_reverb: sample_rate must be in [2000, 128000] (the delay lines of a clip are held in LDS)");
+    const float par[5] = {room_size, damping, wet_level, dry_level, width};
+    for (float v : par)
+        if (!(v >= 0.f && v <= 1.f))
+            return fail(ADN_ERR_INVALID, "adn_reverb: room_size, damping, wet_level, dry_level and width must be in [0, 1]");
+    // the scalars of adn.h, each operation rounded to fp32 (volatile: no contraction into an fma)
+    volatile float t = room_size * 0.28f;
+    const float feedback = t + 0.7f;
+    const float damp = damping * 0.4f;
+    t = wet_level * 3.f;
+    t = 0.5f * t;
+    volatile float w1 = 1.f + width;
+    const float wet1 = t * w1;
+    const float dry = dry_level * 2.f;
+    hipError_t e = adn::launch_reverb(audio, n_clips, (int)length, sample_rate, feedback, damp, wet1, dry, clip != 0, out,
+                                      static_cast<hipStream_t>(stream));
+    if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_reverb: unsupported sample_rate");
+    if (e != hipSuccess) return fail_hip(e, "adn_reverb");
+    return ADN_OK;
+}
+
 int adn_perceptual_loss_workspace_bytes(int n_clips, int F, int T, size_t *bytes)
 {
     if (!bytes || n_clips < 1 || F < 1 || T < adn::ADN_LOSS_MIN_T || T > adn::ADN_LOSS_MAX_T)

@@ -291,6 +291,12 @@ hipError_t launch_resample(const float *audio, int n_clips, long L, long M, int 
 size_t mix_snr_workspace_floats(int n_clips, long L);
 hipError_t launch_mix_snr(const float *clean, const float *noise, int n_clips, long L, float inv_snr_linear, float *workspace,
                           float *out, hipStream_t st);
+// Freeverb over a batch of clips (reverb_kernels.hip; definition in adn.h).  The scalars arrive as adn.h derives them; the
+// delay lines of a clip live in the LDS of its workgroup, which bounds the rate from above, the shortest delay from below.
+constexpr int ADN_REVERB_MIN_RATE = 2000, ADN_REVERB_MAX_RATE = 128000;
+bool reverb_rate_ok(int sample_rate);
+hipError_t launch_reverb(const float *audio, int n_clips, int L, int sample_rate, float feedback, float damp, float wet1, float dry,
+                         int clip, float *out, hipStream_t st);
 size_t perceptual_loss_workspace_floats(int n_clips, int F, int T);
 // LDS the finishing kernel needs for T frames (ADN_LOSS_MAX_LDS: 160 KiB per CU minus the kernel's static reduction scratch):
 // up to ADN_LOSS_LDS_T frames a clip's series and mel spectra are held on chip, longer clips keep the series in the workspace

@@ -342,13 +342,20 @@ class NoiseMixDataset(Dataset):
       ``"noise_cancellation"`` (one per 16000-sample block, ``:124-135``) and the seed of the white noise, which is
       ``torch.randn`` of a ``torch.Generator`` on the device.  :meth:`item_plan` returns them; :meth:`set_epoch` changes the draw.
     * Noise types: ``"white"`` and ``"urban"`` are mixed at ``snr_db`` by ``adn_mix_snr``; ``"noise_cancellation"`` is
-      elementwise on the device; ``"reverb"`` needs the third-party Pedalboard ``Reverb`` effect and raises ``ValueError``.
+      elementwise on the device.  ``"reverb"`` is refused with ``ValueError`` by default: the reference renders it with the
+      third-party Pedalboard ``Reverb`` effect, which is not reproduced.  ``reverb=True`` (default settings) or
+      ``reverb=ReverbSettings(...)`` opts in to this project's own Freeverb (:mod:`audiodenoiser_amd.reverb`, ``adn_reverb``;
+      defined in ``include/adn.h``, parity with Pedalboard unpinned): the item is ``reverb(clean_chunk, sample_rate, clip=True)``
+      with zero state at the chunk's first sample (``pedalboard_reverb`` + ``np.clip``, ``:87-102,116-121``), one launch per
+      batch.  It uses none of the item's random draws, and opting in changes no draw of any item.
     * ``ds[i]`` -> ``(noisy, clean)`` each ``(1, H, W)`` float32 host tensors (the reference's item format);
       ``ds.audio_batch(indices)`` -> ``(noisy_audio, clean_audio)`` each ``(B, chunk)`` on the device;
       ``ds.load_batch_to_device(indices)`` -> ``(noisy, clean)`` each ``(B, 1, H, W)`` on the device, the
       ``stft_magnitude_fit`` of exactly those audio batches (``center=False`` as in ``audio_to_magnitude_spectrogram``,
       ``:162-174``).  Per batch: one resample launch per (rate, length) group of files not yet cached, one mix launch per
       noise type, two STFT launches.
+
+    ``NOISE_TYPES`` lists the types that need no opt-in.
     """
 
     NOISE_TYPES = ("white", "urban", "noise_cancellation")
@@ -356,14 +363,26 @@ class NoiseMixDataset(Dataset):
 
     def __init__(self, clean_dir, noise_dir, noise_types=("white", "urban"), sample_rate: int = 8000, chunk_seconds: float = 2.0,
                  snr_db: float = 8.0, target_size=(256, 64), n_fft: int = 512, hop_length: int = 128, center: bool = False,
-                 seed: int = 0, device="cuda"):
+                 seed: int = 0, device="cuda", reverb=None):
         noise_types = tuple(noise_types)
-        if "reverb" in noise_types:
+        if reverb is None or reverb is False:
+            self.reverb = None
+        else:
+            from .reverb import MAX_SAMPLE_RATE, MIN_SAMPLE_RATE, ReverbSettings
+            if reverb is not True and not isinstance(reverb, ReverbSettings):
+                raise TypeError("reverb must be None, True (default settings) or a ReverbSettings")
+            if not MIN_SAMPLE_RATE <= int(sample_rate) <= MAX_SAMPLE_RATE:
+                raise ValueError(f"reverb needs a sample_rate in [{MIN_SAMPLE_RATE}, {MAX_SAMPLE_RATE}], got {sample_rate}")
+            self.reverb = ReverbSettings() if reverb is True else reverb
+        if "reverb" in noise_types and self.reverb is None:
             raise ValueError('noise type "reverb" is not available: the reference renders it with the third-party Pedalboard '
-                             "Reverb effect (create_train_dataset.py:87-102), which this project does not reimplement")
-        bad = [t for t in noise_types if t not in self.NOISE_TYPES]
+                             "Reverb effect (create_train_dataset.py:87-102), which this project does not reimplement; pass "
+                             "reverb=True or reverb=ReverbSettings(...) to opt in to this project's own Freeverb "
+                             "(audiodenoiser_amd.reverb), whose parity with Pedalboard is unpinned")
+        legal = self.NOISE_TYPES + (("reverb",) if self.reverb is not None else ())
+        bad = [t for t in noise_types if t not in legal]
         if bad or not noise_types:
-            raise ValueError(f"noise_types must be a non-empty selection of {self.NOISE_TYPES}, got {noise_types}")
+            raise ValueError(f"noise_types must be a non-empty selection of {legal}, got {noise_types}")
         self.noise_types, self.sample_rate, self.snr_db = noise_types, int(sample_rate), float(snr_db)
         self.chunk_samples = int(self.sample_rate * chunk_seconds)
         if self.chunk_samples < 1:
@@ -437,6 +456,7 @@ class NoiseMixDataset(Dataset):
     def audio_batch(self, indices):
         """``(noisy_audio, clean_audio)`` each ``(B, chunk)`` float32 on the device for the items ``indices``."""
         from .resample import mix_snr
+        from .reverb import reverb
         plans = [self.item_plan(i) for i in indices]
         if not plans:
             raise ValueError("audio_batch: no indices")
@@ -449,6 +469,10 @@ class NoiseMixDataset(Dataset):
             if not rows:
                 continue
             sel = torch.as_tensor(rows, device=clean.device)
+            if kind == "reverb":
+                r = self.reverb
+                noisy[sel] = reverb(clean[sel], self.sample_rate, r.room_size, r.damping, r.wet_level, r.dry_level, r.width, clip=True)
+                continue
             if kind == "noise_cancellation":
                 out = clean[sel]
                 for j, k in enumerate(rows):

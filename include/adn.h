@@ -32,7 +32,7 @@
 
 #include <stddef.h>
 
-/* The 39 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 40 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -212,6 +212,37 @@ ADN_API int adn_resample(const float *audio, int n_clips, long length, int src_r
 ADN_API int adn_mix_snr_workspace_bytes(int n_clips, long length, size_t *bytes);
 ADN_API int adn_mix_snr(const float *clean, const float *noise, int n_clips, long length, float snr_db,
                         void *workspace, size_t workspace_bytes, float *out, void *stream);
+
+/* add_noise for "reverb" (code/create_train_dataset.py:87-102,116-121), clip by clip.  The reference renders it with Pedalboard's
+ * Reverb, which wraps JUCE's Reverb, which is Freeverb (public domain).  This library DEFINES the effect below; the constants
+ * were written down without the JUCE source at hand and have NOT been checked against it: they are this project's effect, and
+ * parity with Pedalboard is unpinned (float64 restatement: tests/reverb_ref.py).
+ * Mono, every clip on its own, all state zero at the clip's first sample (the reference applies a fresh board to each chunk).
+ *   delay lengths D = (sample_rate * tuning) / 44100 in integer arithmetic (rounded down);
+ *     comb tunings 1116, 1188, 1277, 1356, 1422, 1491, 1557, 1617; all-pass tunings 556, 441, 341, 225
+ *     (8 kHz: combs 202, 215, 231, 245, 257, 270, 282, 293; all-pass 100, 80, 61, 40)
+ *   scalars, every operation rounded to fp32, in this order:
+ *     feedback = room_size * 0.28 + 0.7;  damp = damping * 0.4;  gain = 0.015;
+ *     wet1 = 0.5 * (wet_level * 3) * (1 + width);  dry = dry_level * 2
+ *   per sample n, with in = x[n] * gain and acc = 0:
+ *     comb j = 0..7 in index order, each with a circular buffer buf_j of D_j zeros and last_j = 0:
+ *       o = buf_j[n mod D_j];  last_j = o * (1 - damp) + last_j * damp;  buf_j[n mod D_j] = in + last_j * feedback;  acc += o
+ *     all-pass j = 0..3 in series:  b = buf[n mod D];  buf[n mod D] = acc + b * 0.5;  acc = b - acc
+ *     y[n] = acc * wet1 + x[n] * dry, then clipped to [-1, 1] when `clip` is nonzero (add_noise clips).
+ *   This function has no defaults; the Python mirror's are the reference's call (create_train_dataset.py:94: room_size 0.9,
+ *   damping 0.9, wet_level 0.33) plus dry_level 0.4 and width 1.0 for the two it leaves to Pedalboard.
+ * Not reproduced: JUCE's parameter smoothing ramps (the parameters are constant over a clip), its denormal nudge, freeze mode
+ * and the stereo pair (width only enters wet1).
+ * The kernel walks a clip in chunks of min(D) samples: inside a chunk no delay line meets itself, the comb sum and the all-pass
+ * chain are element-wise and each comb's low-pass is a wave-level scan v[i] = damp v[i-1] + b[i] with the previous chunk's
+ * carry.  That re-associates the low-pass sums only (fp32 throughout; within a few fp32 roundings of the sample-by-sample fp32
+ * loop).  No atomics, one fixed order: two calls are bit-identical and a clip's result does not depend on the batch it is in.
+ * audio, out: device (n_clips, length) fp32; out may be `audio` (each sample is read before it is written).  No workspace: the
+ * twelve delay lines of a clip live in the LDS of its workgroup (9 KB at 8 kHz, 50 KB at 44.1 kHz, 110 KB at 96 kHz).
+ * Limits (ADN_ERR_INVALID otherwise, nothing is launched): 2000 <= sample_rate <= 128000 (shortest delay >= 10 samples; state
+ * + staging <= 160 KiB); the five parameters in [0, 1] (NaN refused); n_clips >= 1; 1 <= length < 2^30 (sample indices inside a clip are 32-bit; offsets between clips 64-bit). */
+ADN_API int adn_reverb(const float *audio, int n_clips, long length, int sample_rate, float room_size, float damping,
+                       float wet_level, float dry_level, float width, int clip, float *out, void *stream);
 
 /* ---- inverse STFT and Griffin-Lim ----------------------------------------------------------------------------
  * Replaces griffin_lim_reconstruction (/root/reference/code/test.py:29-48): librosa.istft + librosa.stft iterated
