@@ -1,0 +1,66 @@
+// Helpers shared by the translation units that implement the C ABI of include/adn.h (adn_api.hip, unet.hip): the last-error
+// string, the status-returning wrappers around HIP calls, and the device guard.  Not part of the public ABI.
+#pragma once
+#include "../../include/adn.h"
+#include "adn_internal.h"
+
+#include <string>
+
+namespace adn {
+
+extern thread_local std::string g_err;          // what adn_last_error() returns; defined in adn_api.hip
+
+inline int fail(int code, const std::string &msg)
+{
+    g_err = msg;
+    return code;
+}
+inline int fail_hip(hipError_t e, const char *what)
+{
+    g_err = std::string(what) + ": " + hipGetErrorString(e);
+    return ADN_ERR_HIP;
+}
+#define ADN_HIP(call)                                   \
+    do {                                                \
+        hipError_t e_ = (call);                         \
+        if (e_ != hipSuccess) return adn::fail_hip(e_, #call); \
+    } while (0)
+// launches that may need a constant table: a cold lookup on a capturing stream is the CALLER's error (adn.h, Conventions)
+inline int fail_launch(hipError_t e, const char *what)
+{
+    if (e == ADN_COLD_IN_CAPTURE)
+        return fail(ADN_ERR_INVALID, std::string(what) + ": first use of this (device, n_fft) on a stream that is being captured -- the "
+                    "constant tables are built with a blocking upload; call adn_prepare(device, n_fft) before the capture");
+    return fail_hip(e, what);
+}
+#define ADN_LAUNCH(call, what)                          \
+    do {                                                \
+        hipError_t e_ = (call);                         \
+        if (e_ != hipSuccess) return adn::fail_launch(e_, what); \
+    } while (0)
+
+// Switches the calling thread to `device` for the lifetime of the guard and restores the caller's device on every
+// exit path: no entry point leaves a hidden side effect on the caller's HIP state (adn.h, Conventions).
+struct DeviceGuard {
+    int prev = -1;
+    bool switched = false;
+    hipError_t err = hipSuccess;
+    explicit DeviceGuard(int device)
+    {
+        err = hipGetDevice(&prev);
+        if (err == hipSuccess && prev != device) {
+            err = hipSetDevice(device);
+            switched = err == hipSuccess;
+        }
+    }
+    ~DeviceGuard()
+    {
+        if (switched) (void)hipSetDevice(prev);
+    }
+    DeviceGuard(const DeviceGuard &) = delete;
+    DeviceGuard &operator=(const DeviceGuard &) = delete;
+};
+
+inline bool aligned_to(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+}  // namespace adn

@@ -99,7 +99,7 @@ __device__ __forceinline__ int fastdiv(int n, unsigned d, unsigned m) { return d
 struct ConvArgs {
     ConvSrc s0, s1;        // channels [0, s0.C) come from s0, [s0.C, s0.C + s1.C) from s1 (virtual concat)
     int nchunk0, nchunk;   // K-chunks served by s0 / in total
-    const void *wpk;       // packed weights, see pack_* in adn_api.hip
+    const void *wpk;       // packed weights, see pack_* in unet.hip
     const void *wpk4;      // fp32 3x3 layers: the same weights packed for the F(4x4,3x3) kernel (pack_wino4_3x3), or nullptr
     const float *bias;     // per GEMM column (BatchNorm folded), always fp32
     void *out;             // output in the blocked layout (above)
@@ -143,6 +143,10 @@ inline bool wino4_pair_mode(const ConvArgs &a)
 // Largest number of K splits any launcher asks for (wino_ksplit, convt_ksplit, conv16_ksplit); the reduce kernels read all the
 // copies of an element before adding them (one memory latency per element instead of one per copy)
 constexpr int ADN_MAX_KSPLIT = 8;
+
+// Workgroups of one K split of a launch whose tile grid is written into its arguments (conv_mfma_tiles / wino_tiles below): what the
+// launchers size their grid by, and what the *_ksplit rules are asked about.
+inline long conv_workgroups(const ConvArgs &a) { return (long)a.N * a.tilesY * a.tilesX * a.nct; }
 
 // Number of K splits for a 3x3 layer launched as `nwg` Winograd workgroups of `nchunk` chunks: only when the grid
 // cannot fill the 512 workgroup slots of the chip (2 per CU) and the K loop is long enough to be worth cutting.
@@ -210,6 +214,9 @@ struct ConvGeom {
     int KC;      // channels per K-chunk
 };
 ConvGeom conv_geom(ConvKind kind, int Cout, bool f16);
+// The direct kernels' tile grid of a layer (conv_geom's tiles over a.N / H / W / Cout) written into a.tilesY / tilesX / nct; returns
+// conv_workgroups(a).  The one place the workspace plan, the kernel choice and the launch arguments get that grid from.
+long conv_mfma_tiles(ConvKind kind, bool f16, ConvArgs &a);
 
 // Direct implicit-GEMM kernels (conv_kernels.hip), fp32 or fp16 storage.
 hipError_t launch_conv_mfma(ConvKind kind, const ConvArgs &a, bool f16, hipStream_t st);
@@ -219,16 +226,21 @@ hipError_t launch_conv_reduce_f16(ConvKind kind, const float *partial, const flo
 // second launch of a K-split transposed convolution (ConvArgs::ksplit > 1, fp32 split-bf16 form): out = sum of the copies + bias
 hipError_t launch_convt_reduce(const float *partial, const float *bias, float *out, int ksplit, int N, int Ho, int Wo, int Cout,
                                hipStream_t st);
-// Winograd F(2x2,3x3) variant of the 3x3 kinds, fp32 only (wino_kernels.hip): tile 16x16 px x 32 couts, 8-ch chunks.
+// Winograd F(2x2,3x3) variant of the 3x3 kinds, fp32 only (wino_kernels.hip): tile 16x16 px x WINO_BN couts, 8-ch chunks.
+constexpr int WINO_BN = 32;
 hipError_t launch_wino_conv(ConvKind kind, const ConvArgs &a, hipStream_t st);
+// its tile grid of a layer written into a.tilesY / tilesX / nct (the launcher does the same); returns conv_workgroups(a): the
+// workgroups of one K split that have a tile to compute (what wino_ksplit() is asked about)
+long wino_tiles(ConvArgs &a);
 // second launch of a split-K 3x3 layer of either Winograd kernel (wino_kernels.hip): ConvArgs::partial -> out (+ pool)
 hipError_t launch_wino_reduce(ConvKind kind, const ConvArgs &a, hipStream_t st);
-// workgroups of one K split of a Winograd launch that have a tile to compute (what wino_ksplit() is asked about)
-long wino_workgroups(const ConvArgs &a);
 // Winograd F(4x4,3x3) variant (wino4_kernels.hip): tile 32x32 px x 32 couts, 8-ch chunks, weights from ConvArgs::wpk
 // in pack_wino4_3x3 layout.  wino4_applicable: plain / pooled 3x3 layers whose image the 32x32 tiles cover with little
 // waste; everything else (fused first / last layer, split-K, small images) stays on F(2x2,3x3).
 bool wino4_applicable(ConvKind kind, const ConvArgs &a, bool force);
+// workgroups of one K split of its launch of a layer, without the supertile padding (what wino4_ksplit() is asked about): 32x32-pixel
+// tiles x 32 couts over a.N / H / W / Cout, two clips per tile in pair mode
+long wino4_workgroups(const ConvArgs &a);
 hipError_t launch_wino4_conv(ConvKind kind, const ConvArgs &a, hipStream_t st);
 
 // fp16 3x3 layers on v_mfma_f32_16x16x32_f16 (conv16_kernels.hip): 32 x 16-pixel tiles x 64 couts, 32-channel chunks (ConvArgs::

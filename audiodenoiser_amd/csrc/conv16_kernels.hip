@@ -563,15 +563,21 @@ __global__ __launch_bounds__(C16_NT, 2) void conv16_f16(const ConvArgs p)
     }
 }
 
+// item grid of a layer written into a.tilesY / tilesX / nct: C16_TH x C16_TW pixels x 64 couts per item; returns the item count
+long c16_tiles(ConvArgs &a)
+{
+    a.tilesY = (a.H + C16_TH - 1) / C16_TH;
+    a.tilesX = (a.W + C16_TW - 1) / C16_TW;
+    a.nct = a.Cout / 64;
+    return conv_workgroups(a);
+}
+
 template <int EPI, bool WRES, bool FIRST = false>
 hipError_t launch_c16(const ConvArgs &a, hipStream_t st)
 {
     using L = C16Lds<WRES, FIRST>;
     ConvArgs a2 = a;
-    a2.tilesY = (a.H + C16_TH - 1) / C16_TH;
-    a2.tilesX = (a.W + C16_TW - 1) / C16_TW;
-    a2.nct = a.Cout / 64;
-    const long nitems = (long)a.N * a2.tilesY * a2.tilesX * a2.nct;
+    const long nitems = c16_tiles(a2);
     long maxd = a2.nct > a2.tilesX ? (a2.nct > a2.tilesY ? a2.nct : a2.tilesY) : (a2.tilesX > a2.tilesY ? a2.tilesX : a2.tilesY);
     a2.pair = 0;
     if (nitems <= 0 || nitems > 0x7fffffffL || (unsigned long long)nitems * (unsigned long long)maxd >= 0x100000000ull) return hipErrorInvalidValue;
@@ -615,8 +621,8 @@ bool conv16_applicable(ConvKind kind, const ConvArgs &a)
         (size_t)a.s1.H * a.s1.W * 64 >= (size_t)0xfffffff0u)
         return false;
     {   // the item decode divides by multiply-high with launch constants: exact while item count x divisor < 2^32 (c16_decode)
-        const long ty = (a.H + C16_TH - 1) / C16_TH, tx = (a.W + C16_TW - 1) / C16_TW, nct = a.Cout / 64;
-        const long nitems = (long)a.N * ty * tx * nct, maxd = std::max(nct, std::max(tx, ty));
+        ConvArgs t = a;
+        const long nitems = c16_tiles(t), maxd = std::max(t.nct, std::max(t.tilesX, t.tilesY));
         if (nitems <= 0 || nitems > 0x7fffffffL || (unsigned long long)nitems * (unsigned long long)maxd >= 0x100000000ull) return false;
     }
     if (a.firstw) return kind == CONV3X3_RELU_POOL && a.firstb && a.s0.C == 1 && a.s1.C == 0 && a.Cout == 64;   // fused first layer

@@ -63,7 +63,7 @@ __device__ __forceinline__ int xcd_remap(int b, int nwg)
 // GEMM column of the transposed convolution -> sub-pixel ij = 2*di + dj and output channel:
 //   column = ((di*(Cout/64) + cg)*2 + dj)*64 + c64, co = 64*cg + c64: the 128 columns of a workgroup are both dj of one di and
 //   64 channels, so that its stores cover whole runs of output pixels (2*gx + dj) per channel block.  pack_convt
-//   (adn_api.hip) and the bias vector follow the same order.
+//   (unet.hip) and the bias vector follow the same order.
 __host__ __device__ __forceinline__ void convt_column(int col, int Cout, int &ij, int &co)
 {
     const int c64 = col & 63, dj = (col >> 6) & 1, g = col >> 7, ncg = Cout >> 6;
@@ -523,7 +523,7 @@ struct DmaCfg {
 // bits; bf16 has fp32's exponent range, so nothing needs scaling), and the six products of total order
 // <= 2 -- hi*hi, hi*mid, mid*hi, hi*lo, lo*hi, mid*mid -- are accumulated in fp32 (the dropped terms are <= 2^-24 relative): the
 // result differs from an exact-fp32 MFMA sum by rounding noise (measured through the network: tools/report_parity.py).  Weights
-// are split on the host (pack_convt_split, adn_api.hip: three planes per 16-channel chunk), activations in registers after the LDS
+// are split on the host (pack_convt_split, unet.hip: three planes per 16-channel chunk), activations in registers after the LDS
 // read (v_cvt_pk_bf16_f32 + a subtraction per term).  6 x v_mfma_f32_32x32x16_bf16 (192 cycles) replace 8 x v_mfma_f32_32x32x2_f32
 // (512 cycles) per 32x32 tile and 16 channels.
 // Range: round-to-nearest turns |x| >= 3.3961e38 (the top 0.2 % of fp32's range) into a bf16 infinity, whose residual would be
@@ -907,7 +907,7 @@ hipError_t launch_cfg(const ConvArgs &a, hipStream_t st)
     constexpr int HALO = (TAPS == 9) ? 1 : 0;
     constexpr int PH = TH + 2 * HALO, PW = TW + 2 * HALO;
     constexpr size_t lds = (size_t)(PH * PW * (8 * KG + 4) + TAPS * KG * 2 * BN * 4) * sizeof(float);
-    const long nwg = (long)a.N * a.tilesY * a.tilesX * a.nct;
+    const long nwg = conv_workgroups(a);
     if (nwg <= 0 || nwg > 0x7fffffffL) return hipErrorInvalidValue;
     hipLaunchKernelGGL((conv_mfma<T, TH, BN, WM, WN, TAPS, KG, EPI>), dim3((unsigned)nwg), dim3(64 * WM * WN), lds, st, a);
     return hipGetLastError();
@@ -917,7 +917,7 @@ template <typename T, int TH, int BN, int WM, int WN, int TAPS, int KG, int EPI,
 hipError_t launch_dma_cfg(const ConvArgs &a, hipStream_t st)
 {
     using C = DmaCfg<T, TH, BN, WM, WN, TAPS, KG, SPLIT>;
-    const long nwg = (long)a.N * a.tilesY * a.tilesX * a.nct;
+    const long nwg = conv_workgroups(a);
     const int ks = KSPLIT ? a.ksplit : 1;
     if (nwg <= 0 || ks < 1 || nwg * ks > 0x7fffffffL || a.nchunk % ks) return hipErrorInvalidValue;
     ConvArgs a2 = a;                                    // reciprocals of the tile decode's divisors (fdGc = nct; fdGc.d = 0: plain division)
@@ -1067,6 +1067,15 @@ ConvGeom conv_geom(ConvKind kind, int Cout, bool f16)
     if (f16) return ConvGeom{32, 64, cpg};       // fp16 3x3: 32x16-pixel tiles x 64 couts for every layer
     if (Cout == 64) return ConvGeom{16, 64, cpg};
     return ConvGeom{8, 128, cpg};
+}
+
+long conv_mfma_tiles(ConvKind kind, bool f16, ConvArgs &a)
+{
+    const ConvGeom g = conv_geom(kind, a.Cout, f16);
+    a.tilesY = (a.H + g.TH - 1) / g.TH;
+    a.tilesX = (a.W + TW - 1) / TW;
+    a.nct = (kind == CONVT2X2 ? 4 * a.Cout : a.Cout) / g.BN;
+    return conv_workgroups(a);
 }
 
 hipError_t launch_conv_mfma(ConvKind kind, const ConvArgs &a, bool f16, hipStream_t st)

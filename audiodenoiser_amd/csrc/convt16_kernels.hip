@@ -253,6 +253,16 @@ __global__ __launch_bounds__(T16_NT, 2) void convt16_f16(const ConvArgs p)
     }
 }
 
+// item grid of a layer written into a.tilesY / tilesX / nct: T16_ROWS x T16_PX input pixels x 256 GEMM columns (4 sub-pixels x 64
+// couts) per item; returns the item count
+long t16_tiles(ConvArgs &a)
+{
+    a.tilesY = (a.H + T16_ROWS - 1) / T16_ROWS;
+    a.tilesX = (a.W + T16_PX - 1) / T16_PX;
+    a.nct = a.Cout / 64;
+    return conv_workgroups(a);
+}
+
 }  // namespace
 
 // Layers the kernel serves: Cin a multiple of 128 (items of a multiple of four 32-channel chunks: the LDS image of a step is a
@@ -262,8 +272,8 @@ bool convt16_applicable(const ConvArgs &a)
 {
     if ((a.s0.C & 127) || a.s0.C < 128 || (a.Cout & 63) || a.Cout > T16_MAX_COUT) return false;
     if ((size_t)a.H * a.W * 128 >= (size_t)0xfffffff0u) return false;                 // output block: 4 H W pixels x 32 bytes
-    const long ty = (a.H + T16_ROWS - 1) / T16_ROWS, tx = (a.W + T16_PX - 1) / T16_PX;
-    const long nitems = (long)a.N * ty * tx * (a.Cout / 64);
+    ConvArgs t = a;
+    const long nitems = t16_tiles(t);
     return nitems > 0 && nitems <= 0x7fffffffL && (size_t)(a.Cout / 64) * (a.s0.C / 32) * T16_W_BYTES < (size_t)0xfffffff0u;
 }
 
@@ -271,11 +281,8 @@ hipError_t launch_convt16(const ConvArgs &a, hipStream_t st)
 {
     if (!convt16_applicable(a)) return hipErrorInvalidValue;
     ConvArgs a2 = a;
-    a2.tilesY = (a.H + T16_ROWS - 1) / T16_ROWS;
-    a2.tilesX = (a.W + T16_PX - 1) / T16_PX;
-    a2.nct = a.Cout / 64;                              // 4 Cout columns / 256 per item
+    const long nitems = t16_tiles(a2);
     a2.nchunk = a.s0.C / 32;
-    const long nitems = (long)a.N * a2.tilesY * a2.tilesX * a2.nct;
     a2.nwg_total = (int)nitems;
     static std::atomic<int> cus{0};                    // (one device model per process: gfx950 only, checked at handle creation)
     int c = cus.load(std::memory_order_relaxed);

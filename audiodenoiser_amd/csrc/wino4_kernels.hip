@@ -72,7 +72,7 @@ constexpr int HPX = HP + 2;                  // pixel columns of a halo row in L
 constexpr int RSL = 2 * HPX;
 constexpr int HR = 5;                        // DMA rounds (512 slots each) covering the 34*72 + 8 = 2456 halo slots
 constexpr int HSLOTS = HR * NT;
-constexpr int USLOTS = 36 * KC * 32 / 4;     // 2304 slots: U slab, see pack_wino4_3x3 (adn_api.hip)
+constexpr int USLOTS = 36 * KC * 32 / 4;     // 2304 slots: U slab, see pack_wino4_3x3 (unet.hip)
 constexpr int UR = (USLOTS + NT - 1) / NT;   // 5 rounds, the last one half full (waves 0-3)
 constexpr int IMG = (HSLOTS + USLOTS) * 4;   // floats per LDS image (77 824 bytes)
 constexpr int SUP = 32;                      // workgroups resident on one XCD (one per CU)
@@ -858,7 +858,24 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     }   // !SWP
 }
 
+// tile grid of a layer written into a.tilesY / tilesX / pair / nct: REG x REG pixels x 32 couts per workgroup; images at most 16
+// pixels wide run in pair mode, where a tile covers 32 rows x 16 columns of each of two clips.  Returns wino4_workgroups(a).
+long wino4_tiles(ConvArgs &a)
+{
+    a.tilesY = (a.H + REG - 1) / REG;
+    a.tilesX = (a.W + REG - 1) / REG;
+    a.pair = wino4_pair_mode(a) ? 1 : 0;
+    a.nct = a.Cout / 32;
+    return (long)((a.N + a.pair) >> a.pair) * a.tilesY * a.tilesX * a.nct;
+}
+
 }  // namespace
+
+long wino4_workgroups(const ConvArgs &a)
+{
+    ConvArgs t = a;
+    return wino4_tiles(t);
+}
 
 // F(4x4,3x3) serves a layer when its 32x32-pixel workgroup tiles waste little of the image: at most a quarter of the
 // tiled area outside it (small images stay on F(2x2,3x3), whose tiles are 16x16).  The choice
@@ -871,9 +888,10 @@ bool wino4_applicable(ConvKind kind, const ConvArgs &a, bool force)
     if (kind == CONV3X3_RELU_DOT && (!a.dotw || !a.dot_out)) return false;
     if (a.firstw || (a.Cout & 31) || a.nchunk < 1) return false;
     if (a.ksplit > 1 && (kind == CONV3X3_RELU_DOT || !a.partial || a.nchunk % a.ksplit || a.ksplit > ADN_MAX_KSPLIT)) return false;
-    // images at most 16 pixels wide run in pair mode: a tile covers 32 rows x 16 columns of each of two clips
-    const long th = (a.H + REG - 1) / REG, tw = (a.W + REG - 1) / REG;
-    const long tiled = wino4_pair_mode(a) ? th * REG * 16 : th * tw * REG * REG;
+    ConvArgs t = a;
+    wino4_tiles(t);
+    const long th = t.tilesY, tw = t.tilesX;
+    const long tiled = t.pair ? th * REG * 16 : th * tw * REG * REG;
     return force || tiled * 3 <= (long)a.H * a.W * 4;
 }
 
@@ -881,10 +899,7 @@ hipError_t launch_wino4_conv(ConvKind kind, const ConvArgs &a, hipStream_t st)
 {
     if (!wino4_applicable(kind, a, true)) return hipErrorInvalidValue;
     ConvArgs a2 = a;
-    a2.tilesY = (a.H + REG - 1) / REG;
-    a2.tilesX = (a.W + REG - 1) / REG;
-    a2.pair = wino4_pair_mode(a) ? 1 : 0;
-    a2.nct = a.Cout / 32;
+    wino4_tiles(a2);
     const long gc = a2.nct < SUP ? a2.nct : SUP, gp = SUP / gc;
     const long ptiles = (long)((a2.N + a2.pair) >> a2.pair) * a2.tilesY * a2.tilesX;
     const long nwg = ((ptiles + gp - 1) / gp) * gp * a2.nct;

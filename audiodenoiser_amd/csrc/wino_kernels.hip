@@ -545,13 +545,23 @@ __global__ __launch_bounds__(256) void wino_reduce_kernel(const float *__restric
     }
 }
 
+// tile grid of the NW-wave kernel: WT x TPW pixels x WINO_BN couts per workgroup
+template <int NW>
+long wino_tiles_n(ConvArgs &a)
+{
+    a.tilesY = (a.H + WT - 1) / WT;
+    a.tilesX = (a.W + DmaGeom<NW>::TPW - 1) / DmaGeom<NW>::TPW;
+    a.nct = a.Cout / WINO_BN;
+    return conv_workgroups(a);                          // without the padding of the last supertile: those exit at once
+}
+
 template <int NW>
 hipError_t launch_wino_dma_n(ConvKind kind, const ConvArgs &a, hipStream_t st)
 {
     using G = DmaGeom<NW>;
     constexpr size_t lds = (size_t)2 * G::DBUF * sizeof(float);
     ConvArgs a2 = a;
-    a2.tilesX = (a.W + G::TPW - 1) / G::TPW;
+    wino_tiles_n<NW>(a2);
     // grid padded to whole supertiles (see the kernel): gp pixel tiles x gc cout tiles, gc*gp = SUP
     const long ptiles = (long)a2.N * a2.tilesY * a2.tilesX;
     int gc, gp;
@@ -646,12 +656,7 @@ hipError_t launch_wino_reduce(ConvKind kind, const ConvArgs &a, hipStream_t st)
     return hipGetLastError();
 }
 
-long wino_workgroups(const ConvArgs &a)
-{
-    using G = DmaGeom<4>;
-    const long tilesX = (a.W + G::TPW - 1) / G::TPW;
-    return (long)a.N * a.tilesY * tilesX * a.nct;       // without the padding of the last supertile: those exit at once
-}
+long wino_tiles(ConvArgs &a) { return wino_tiles_n<4>(a); }      // (the kernel launch_wino_conv runs)
 
 hipError_t launch_wino_conv(ConvKind kind, const ConvArgs &a, hipStream_t st)
 {

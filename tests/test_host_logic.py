@@ -652,5 +652,49 @@ def test_library_sources_carry_no_experiment_switches():
         assert "ADN_EXPERIMENTS" not in text, path
         for name in re.findall(r'getenv\("([A-Z0-9_]+)"\)', text):
             read.setdefault(name, set()).add(os.path.basename(path))
-    assert set().union(*read.values()) == {"adn_api.hip"}, read
+    assert set().union(*read.values()) == {"unet.hip"}, read
     assert set(read) == documented, sorted(set(read) ^ documented)
+
+
+# adn_unet_workspace_bytes(NULL, N, F, T) as recorded from a build of commit d46d057, before the workspace plan, the kernel choice
+# and the launchers came to share one tile-grid helper per kernel family: (N, F, T, bytes)
+WORKSPACE_BYTES_D46D057 = (
+    (1, 513, 256, 179503104), (2, 513, 256, 325451776), (3, 513, 256, 488177664), (4, 513, 256, 617349120),
+    (8, 513, 256, 1201143808), (16, 513, 256, 2469396480), (32, 513, 256, 4670357504), (64, 513, 256, 9340715008),
+    (1, 257, 188, 78326784), (2, 257, 188, 131819520), (3, 257, 188, 196942848), (4, 257, 188, 238997504),
+    (8, 257, 188, 520986624), (16, 257, 188, 949698560), (32, 257, 188, 1807122432), (64, 257, 188, 3429695488),
+    (1, 16, 16, 546816), (2, 16, 16, 1093632), (3, 16, 16, 1640448), (4, 16, 16, 2187264),
+    (8, 16, 16, 4374528), (16, 16, 16, 8749056), (32, 16, 16, 17498112), (64, 16, 16, 34996224),
+    (1, 40, 33, 2803712), (2, 40, 33, 5607424), (3, 40, 33, 8411136), (4, 40, 33, 11214848),
+    (8, 40, 33, 22102016), (16, 40, 33, 34045952), (32, 40, 33, 67436544), (64, 40, 33, 113901568),
+    (1, 64, 4094, 358170624), (2, 64, 4094, 649494528), (3, 64, 4094, 873971712), (4, 64, 4094, 1232142336),
+    (8, 64, 4094, 2330591232), (16, 64, 4094, 4661182464), (32, 64, 4094, 9322364928), (64, 64, 4094, 18644729856),
+    (1, 33, 47, 3266816), (2, 33, 47, 6533632), (3, 33, 47, 9800448), (4, 33, 47, 13067264),
+    (8, 33, 47, 25487360), (16, 33, 47, 39563264), (32, 33, 47, 65773568), (64, 33, 47, 130498560),
+    (1, 129, 517, 90820352), (2, 129, 517, 181378560), (3, 129, 517, 272067840), (4, 129, 517, 329202688),
+    (8, 129, 517, 624850944), (16, 129, 517, 1182593024), (32, 129, 517, 2499403776), (64, 129, 517, 4730372096),
+    (1, 1025, 65, 107266816), (2, 1025, 65, 180979200), (3, 1025, 65, 246302976), (4, 1025, 65, 328403968),
+    (8, 1025, 65, 656807936), (16, 1025, 65, 1179398144), (32, 1025, 65, 2493014016), (64, 1025, 65, 4717592576),
+    (1, 1100, 48, 72216576), (2, 1100, 48, 144433152), (3, 1100, 48, 216207360), (4, 1100, 48, 261537792),
+    (8, 1100, 48, 523468800), (16, 1100, 48, 939196416), (32, 1100, 48, 1878392832), (64, 1100, 48, 3756785664),
+    (1, 513, 261000, 148799199232), (2, 8191, 16383, 298399580160),
+)
+
+
+def test_workspace_bytes_are_pinned():
+    """The partial-sum buffer behind the activations is sized from the same tile grids and K-split rules the launchers use; a
+    drift between the two is a K-split launch writing past the workspace.  The sizes below were recorded before the plan was
+    rebuilt on the shared helpers and must not move by a byte: batch sizes on both sides of every split threshold, deepest levels
+    at most 16 pixels wide (pair mode of the F(4x4,3x3) kernel: T < 272) and wider, odd F and T, F*T near 2^27."""
+    from audiodenoiser_amd import _lib
+    L = _lib.load()
+    assert len(WORKSPACE_BYTES_D46D057) >= 40
+    assert {n for n, _, _, _ in WORKSPACE_BYTES_D46D057} >= {1, 2, 3, 4, 8, 16, 32, 64}
+    assert any(t // 16 <= 16 for _, _, t, _ in WORKSPACE_BYTES_D46D057) and any(t // 16 > 16 for _, _, t, _ in WORKSPACE_BYTES_D46D057)
+    assert any(f % 2 and t % 2 for _, f, t, _ in WORKSPACE_BYTES_D46D057) and any(f * t > 0.99 * 2 ** 27 for _, f, t, _ in WORKSPACE_BYTES_D46D057)
+    need = ctypes.c_size_t()
+    got = []
+    for n, f, t, _ in WORKSPACE_BYTES_D46D057:
+        assert L.adn_unet_workspace_bytes(None, n, f, t, ctypes.byref(need)) == 0, (n, f, t)
+        got.append((n, f, t, need.value))
+    assert tuple(got) == WORKSPACE_BYTES_D46D057, [(g, w[3]) for g, w in zip(got, WORKSPACE_BYTES_D46D057) if g != w]

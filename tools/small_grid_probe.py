@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-launch times of the forward at small batches under the three kernel-choice modes (GPU box):
 default (automatic small-grid rule, ADN_AUTO_GRID workgroups), ADN_BATCH_INVARIANT=1, ADN_WINO_TILE=2 + ADN_WINO_SPLITK=1.
-Calibrates the threshold of choose_algo (csrc/adn_api.hip).  -> stdout
+Calibrates the threshold of choose_conv3 (csrc/unet.hip).  -> stdout
     python tools/small_grid_probe.py [auto_grid ...]
 """
 import os
