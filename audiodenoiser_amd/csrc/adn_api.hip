@@ -1,5 +1,5 @@
 // C ABI of libadn.so (include/adn.h) outside the U-Net (unet.hip): version, last error, device queries and the argument checks in
-// front of the STFT, loader, loss, Griffin-Lim, resampler, mixer, reverb and long-form denoising launchers.
+// front of the STFT, loader, loss, Griffin-Lim, resampler, mixer, reverb, long-form and streaming denoising launchers.
 #include "adn_host.h"
 
 #include <cmath>
@@ -419,6 +419,153 @@ int adn_denoise_resynth(const float *y, const float *spec, int n_clips, long len
     hipError_t e = adn::launch_denoise_resynth(y, spec, n_clips, length, n_fft, hop, g, audio_out, static_cast<hipStream_t>(stream));
     if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_denoise_resynth: grid too large (n_clips x length / 2048 >= 2^31)");
     ADN_LAUNCH(e, "adn_denoise_resynth");
+    return ADN_OK;
+}
+
+/* ---- streaming denoiser: plan, state, analysis, emit (adn.h, "stream") ------------------------------------------- */
+static const char *stream_plan_text = ": need a power-of-two n_fft in [64, 4096], 1 <= hop <= n_fft / 4, window >= 16, block >= 1, "
+                                      "lookahead >= 0, block + lookahead <= window, n_streams >= 1 and 1 <= max_steps <= 65536";
+
+// What a call of n_steps steps from `first` covers (adn_internal.h, StreamCall); every quantity follows from the step index.
+static int stream_call(const char *who, const adn::StreamGeom &g, long first, int n_steps, long final_length, adn::StreamCall *c)
+{
+    const std::string w(who);
+    if (first < 0 || n_steps < 1) return fail(ADN_ERR_INVALID, w + ": need first_step >= 0 and n_steps >= 1");
+    if (n_steps > g.S - 1) return fail(ADN_ERR_INVALID, w + ": n_steps exceeds the max_steps the state was sized for");
+    if (final_length < -1 || final_length == 0 || final_length >= (1L << 30))
+        return fail(ADN_ERR_INVALID, w + ": final_length must be -1 (the stream runs) or the stream's length, 1 <= length < 2^30");
+    const long B = g.B, D = g.B + g.A, hop = g.hop, M = g.n_fft / 2, keep = g.n_fft - g.hop;
+    if (first >= (1L << 30)) return fail(ADN_ERR_INVALID, w + ": step index too large");
+    const long last = first + n_steps - 1;
+    // sample positions are 32-bit inside the kernels: the last position a call touches stays below 2^30 (flush before that)
+    if ((last * B + D) * hop + 2L * g.n_fft >= (1L << 30))
+        return fail(ADN_ERR_INVALID, w + ": the steps reach past sample 2^30 of the stream (32-bit positions inside the kernels); flush the stream before");
+    c->first = (int)first;
+    c->n_steps = n_steps;
+    c->T = -1;
+    c->L = -1;
+    bool closes = false;
+    if (final_length > 0) {
+        const long T = 1 + final_length / hop, K = (T + B - 1) / B;
+        if (last >= K) return fail(ADN_ERR_INVALID, w + ": steps past the last step ceil((1 + final_length / hop) / block) of the stream");
+        c->T = (int)T;
+        c->L = (int)final_length;
+        closes = last == K - 1;
+    }
+    c->base = first == 0 ? 0 : (int)((first * B + g.A - 1) * hop + M);
+    c->end = (int)((last * B + D - 1) * hop + M);
+    c->f_new0 = first == 0 ? 0 : (int)(first * B + g.A);
+    c->f_new1 = (int)(last * B + D);
+    c->slot_in = first == 0 ? 0 : (int)((first - 1) % g.S);
+    c->slot_out = (int)(last % g.S);
+    c->f_first = (int)(first * B);
+    c->f_last = (int)((last + 1) * B - 1);
+    c->p_begin = (int)(first * B * hop);
+    c->p_first = c->p_begin > M ? c->p_begin : (int)M;
+    if (closes) {
+        if (c->f_last > c->T - 1) c->f_last = c->T - 1;
+        c->p_out = (int)(final_length + M);
+        c->p_tail = 0x7fffffff;
+        c->p_end = c->p_out;
+    } else {
+        c->p_out = (int)((last + 1) * B * hop);
+        c->p_tail = c->p_out;
+        c->p_end = (int)(c->p_out + keep);
+    }
+    return ADN_OK;
+}
+
+int adn_stream_plan(int n_fft, int hop, int window, int block, int lookahead, long received, long *steps_done, long *emitted,
+                    long *latency)
+{
+    adn::StreamGeom g;
+    if (!adn::stream_geom(1, n_fft, hop, window, block, lookahead, 1, &g)) return fail(ADN_ERR_INVALID, std::string("adn_stream_plan") + stream_plan_text);
+    if (received < 0 || received >= (1L << 40)) return fail(ADN_ERR_INVALID, "adn_stream_plan: need 0 <= received < 2^40");
+    const long r = received - n_fft / 2 - (long)(block + lookahead - 1) * hop;
+    const long steps = r < 0 ? 0 : r / ((long)block * hop) + 1;
+    const long out = steps * block * hop - n_fft / 2;
+    if (steps_done) *steps_done = steps;
+    if (emitted) *emitted = out > 0 ? out : 0;
+    if (latency) *latency = (long)(block + lookahead - 1) * hop + n_fft;
+    return ADN_OK;
+}
+
+int adn_stream_state_bytes(int n_streams, int n_fft, int hop, int window, int block, int lookahead, int max_steps, size_t *bytes)
+{
+    adn::StreamGeom g;
+    if (!bytes) return fail(ADN_ERR_INVALID, "adn_stream_state_bytes: null pointer");
+    if (!adn::stream_geom(n_streams, n_fft, hop, window, block, lookahead, max_steps, &g))
+        return fail(ADN_ERR_INVALID, std::string("adn_stream_state_bytes") + stream_plan_text);
+    *bytes = (size_t)g.total * sizeof(float);
+    return ADN_OK;
+}
+
+static int stream_state(const char *who, void *state, size_t state_bytes, int n_streams, int n_fft, int hop, int window, int block,
+                        int lookahead, int max_steps, adn::StreamGeom *g)
+{
+    const std::string w(who);
+    if (!state) return fail(ADN_ERR_INVALID, w + ": null pointer");
+    if (!adn::stream_geom(n_streams, n_fft, hop, window, block, lookahead, max_steps, g)) return fail(ADN_ERR_INVALID, w + stream_plan_text);
+    if (state_bytes < (size_t)g->total * sizeof(float)) return fail(ADN_ERR_WORKSPACE, w + ": state smaller than adn_stream_state_bytes");
+    if (!aligned_to(state, 8)) return fail(ADN_ERR_INVALID, w + ": state must be 8-byte aligned");
+    return ADN_OK;
+}
+
+int adn_stream_reset(void *state, size_t state_bytes, int n_streams, int n_fft, int hop, int window, int block, int lookahead,
+                     int max_steps, void *stream)
+{
+    adn::StreamGeom g;
+    const int rc = stream_state("adn_stream_reset", state, state_bytes, n_streams, n_fft, hop, window, block, lookahead, max_steps, &g);
+    if (rc != ADN_OK) return rc;
+    ADN_HIP(hipMemsetAsync(state, 0, (size_t)g.total * sizeof(float), static_cast<hipStream_t>(stream)));
+    return ADN_OK;
+}
+
+int adn_stream_analyze(void *state, size_t state_bytes, const float *audio, long audio_stride, int n_streams, long first_step,
+                       int n_steps, long final_length, int n_fft, int hop, int window, int block, int lookahead, int max_steps,
+                       float *windows_out, void *stream)
+{
+    adn::StreamGeom g;
+    adn::StreamCall c;
+    int rc = stream_state("adn_stream_analyze", state, state_bytes, n_streams, n_fft, hop, window, block, lookahead, max_steps, &g);
+    if (rc != ADN_OK) return rc;
+    if (!audio || !windows_out) return fail(ADN_ERR_INVALID, "adn_stream_analyze: null pointer");
+    if (!aligned_to(audio, 4) || !aligned_to(windows_out, 4)) return fail(ADN_ERR_INVALID, "adn_stream_analyze: audio and windows_out must be 4-byte aligned");
+    rc = stream_call("adn_stream_analyze", g, first_step, n_steps, final_length, &c);
+    if (rc != ADN_OK) return rc;
+    const long n_new = (c.L >= 0 && c.L < c.end ? c.L : c.end) - (long)c.base;
+    if (audio_stride < 0 || (n_streams > 1 && audio_stride < n_new))
+        return fail(ADN_ERR_INVALID, "adn_stream_analyze: audio_stride is smaller than the samples the steps bring");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipError_t e = adn::launch_stream_frames(audio, audio_stride, n_streams, g, c, static_cast<float *>(state), st);
+    if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_stream_analyze: grid too large");
+    ADN_LAUNCH(e, "adn_stream_analyze");
+    e = adn::launch_stream_windows(static_cast<const float *>(state), n_streams, g, c, windows_out, st);
+    if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_stream_analyze: grid too large (n_streams x n_steps x 32x32 tiles >= 2^31)");
+    ADN_HIP(e);
+    return ADN_OK;
+}
+
+int adn_stream_emit(void *state, size_t state_bytes, const float *y, int n_streams, long first_step, int n_steps, long final_length,
+                    int n_fft, int hop, int window, int block, int lookahead, int max_steps, float *audio_out, long out_stride,
+                    void *stream)
+{
+    adn::StreamGeom g;
+    adn::StreamCall c;
+    int rc = stream_state("adn_stream_emit", state, state_bytes, n_streams, n_fft, hop, window, block, lookahead, max_steps, &g);
+    if (rc != ADN_OK) return rc;
+    if (!y) return fail(ADN_ERR_INVALID, "adn_stream_emit: null pointer");
+    rc = stream_call("adn_stream_emit", g, first_step, n_steps, final_length, &c);
+    if (rc != ADN_OK) return rc;
+    const long n_out = c.p_out > c.p_first ? (long)c.p_out - c.p_first : 0;
+    if (n_out > 0 && !audio_out) return fail(ADN_ERR_INVALID, "adn_stream_emit: null pointer");
+    if (out_stride < 0 || (n_streams > 1 && out_stride < n_out))
+        return fail(ADN_ERR_INVALID, "adn_stream_emit: out_stride is smaller than the samples the steps emit");
+    if (!aligned_to(y, 4) || !aligned_to(audio_out, 4)) return fail(ADN_ERR_INVALID, "adn_stream_emit: y and audio_out must be 4-byte aligned");
+    hipError_t e = adn::launch_stream_emit(y, n_streams, g, c, static_cast<float *>(state), audio_out, out_stride,
+                                           static_cast<hipStream_t>(stream));
+    if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_stream_emit: grid too large");
+    ADN_LAUNCH(e, "adn_stream_emit");
     return ADN_OK;
 }
 

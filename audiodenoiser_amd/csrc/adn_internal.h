@@ -293,6 +293,29 @@ hipError_t launch_denoise_stitch(const float *y, int n_clips, int F, const Denoi
                                  hipStream_t st);
 hipError_t launch_denoise_resynth(const float *y, const void *spec, int n_clips, long L, int n_fft, int hop,
                                   const DenoiseGeom &g, float *audio, hipStream_t st);
+// Streaming denoiser (stream_kernels.hip; adn.h, "stream").  StreamGeom: the plan and the layout of the state buffer of one batch
+// of streams, in floats (sections X, mag, hist, tail; `total` floats in all); stream_geom is false outside the limits of adn.h.
+// StreamCall: what one call of n_steps steps from step `first` covers, derived from the step index alone (stream_call):
+// samples [base, end) arrive, frames [f_new0, f_new1) are transformed, frames [f_first, f_last] go back to audio over the
+// untrimmed positions [p_begin, p_end), of which [p_first, p_out) are written out and [p_tail, p_tail + n_fft - hop) carried.
+struct StreamGeom {
+    int n_fft, hop, W, B, A;
+    int S, RX, RM;                       // history / tail slots, ring lengths in frames
+    long x_off, mag_off, hist_off, tail_off, total;
+};
+struct StreamCall {
+    int first, n_steps, T, L;            // T, L: frames and samples of the finished stream, -1 while it runs
+    int base, end, f_new0, f_new1;
+    int slot_in, slot_out;
+    int f_first, f_last, p_begin, p_first, p_out, p_tail, p_end;
+};
+bool stream_geom(int n_streams, int n_fft, int hop, int window, int block, int lookahead, int max_steps, StreamGeom *g);
+hipError_t launch_stream_frames(const float *audio, long audio_stride, int n_streams, const StreamGeom &g, const StreamCall &c,
+                                float *state, hipStream_t st);
+hipError_t launch_stream_windows(const float *state, int n_streams, const StreamGeom &g, const StreamCall &c, float *out,
+                                 hipStream_t st);
+hipError_t launch_stream_emit(const float *y, int n_streams, const StreamGeom &g, const StreamCall &c, float *state, float *audio,
+                              long out_stride, hipStream_t st);
 hipError_t launch_quantize_pad(const float *in, int n, int h, int w, float *out, int H, int W, hipStream_t st);
 hipError_t launch_per_clip_l1(const float *a, const float *b, int n_clips, long elems, float *out, hipStream_t st);
 // Polyphase resampler and SNR mixer (resample_kernels.hip).  resample_ratio: up / down of a rate pair, false outside the limits

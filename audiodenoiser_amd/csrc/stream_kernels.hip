@@ -1,0 +1,437 @@
+// Streaming denoiser for gfx950: the stateful ends of the pipeline.  Definition: include/adn.h, "stream"; float64 restatement:
+// tests/stream_ref.py.  Audio arrives in pieces; step k feeds the network the last W frames of |X| and takes B frames of its
+// output back to audio.  Everything that has to survive between two calls lives in a caller-owned state buffer.
+//
+// State of one batch of n_streams streams (StreamGeom::*_off, floats; S = max_steps + 1 slots):
+//   X     [stream][RX][F] float2   complex frames that are still to be emitted, ring over the FRAME index, RX = max_steps B + A
+//   mag   [stream][RM][F]          |X| of the last frames, ring over the frame index, RM = W + (max_steps - 1) B
+//   hist  [stream][S][n_fft - hop] the samples the first new frame of the next call shares with this one, slot = last step mod S
+//   tail  [stream][S][n_fft - hop] overlap-add partial sums past the last emitted sample, slot = last step mod S
+// Frames, and with them every ring position, follow from the step index the caller passes: nothing is ever shifted in place.
+//
+// Who writes what (no state word is written by one workgroup and read by another in the same launch):
+//   stream_frames   (analysis, launch 1) reads hist slot (first_step - 1) mod S and the new samples; workgroup (x, stream) WRITES
+//                   the X and mag ring rows of its own FB frames; the workgroups with x = 0 also WRITE hist slot last_step mod S.
+//                   n_steps <= max_steps < S: the slot read and the slot written differ.  It reads neither ring.
+//   stream_windows  (analysis, launch 2) READS the mag ring rows of frames [first B + B + A - W, last B + B + A) -- at most RM
+//                   consecutive frames, so no two share a row -- and writes only the network input.  The frames of one call come
+//                   from several workgroups of launch 1; the launch boundary is the only synchronisation.
+//   stream_emit     READS X ring rows of frames [first B, last B + B) (at most RX consecutive frames together with the A frames
+//                   beyond them that launch 1 has already written), READS tail slot (first_step - 1) mod S, WRITES tail slot
+//                   last_step mod S (a different slot) and the audio.  A workgroup owns a span of samples; a sample of the
+//                   output or of the new tail is written by exactly one thread.
+// Order of the sums: a sample is the carried partial sum plus its frames in ascending frame order, all fp32 adds of one thread
+// -- the same chain whether the frames arrive in one call or in many, so the same audio gives the same bits however it was
+// split, and a stream never reads another stream's rows.  No atomics, no workspace.
+#include "adn_internal.h"
+#include "fft_core.h"
+
+#include <cfloat>
+
+namespace adn {
+namespace {
+
+using namespace fftcore;
+
+template <int M>
+struct StCfg {
+    static constexpr int N = 2 * M, TPF = M / 8, FB = STFT_THREADS / TPF;   // FB frames per FFT pass (GlCfg<M>'s split)
+    static constexpr int TBL = N + 2 * M + (M + 2);                         // window, twiddles, half-step twiddles
+    static constexpr size_t LDS_FRAMES = (size_t)(TBL + 2 * FB * M) * sizeof(float);
+    // emit: DnCfg<M>'s budget (denoise_kernels.hip) -- stages of SB frames of y parked in LDS [frame][bin] with an odd pitch
+    static constexpr int SB0 = 16384 / M < 32 ? 16384 / M : 32;
+    static constexpr int SB = FB > SB0 ? FB : SB0;
+    static constexpr int PITCH = M + 1;
+    static constexpr int SPT = 8, SPAN = STFT_THREADS * SPT;                // samples per thread / per workgroup
+    static constexpr size_t LDS_EMIT = (size_t)(TBL + 2 * FB * M + SB * PITCH) * sizeof(float);
+    static_assert(SB % FB == 0 && STFT_THREADS % SB == 0 && (SB & (SB - 1)) == 0, "bad stage size");
+    static_assert(LDS_EMIT <= 160 * 1024, "stage does not fit the LDS of a CU");
+};
+
+// |X| as adn.h fixes it ("denoise", rule 2): one product, one fma, one square root
+__device__ __forceinline__ float mag_of(float2 x) { return sqrtf(fmaf(x.x, x.x, __fmul_rn(x.y, x.y))); }
+
+// S^[k] = M[k] * X[k] / |X[k]|, M real where |X| = 0 ("denoise", rule 5)
+__device__ __forceinline__ float2 rephase(float2 x, float m)
+{
+    const float mag = mag_of(x);
+    if (mag == 0.f) return make_float2(m, 0.f);
+    const float s = m / mag;
+    return make_float2(x.x * s, x.y * s);
+}
+
+// Sample s of the stream: zero before the start and, once the length is known, from the end on; the call's new samples start at
+// `base`, the n_fft - hop before them are the carried history.
+struct Samples {
+    const float *audio, *hist;
+    int base, keep, L;               // L < 0 while the stream runs
+    __device__ __forceinline__ float at(int s) const
+    {
+        if (s < 0 || (L >= 0 && s >= L)) return 0.f;
+        return s >= base ? audio[s - base] : hist[s - (base - keep)];
+    }
+};
+
+// ---------------------------------------------------------------------------------------------- analysis 1: new frames
+template <int M>
+__global__ __launch_bounds__(STFT_THREADS) void stream_frames_kernel(const float *__restrict__ audio, long audio_stride,
+                                                                    StreamGeom g, StreamCall c,
+                                                                    const float *__restrict__ tables, float *__restrict__ state)
+{
+    using C = StCfg<M>;
+    constexpr int N = C::N, TPF = C::TPF, FB = C::FB, F = M + 1;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float *s_win = smem;
+    float2 *s_tw = reinterpret_cast<float2 *>(smem + N);
+    float2 *s_tw2 = s_tw + M;
+    float2 *s_sc = reinterpret_cast<float2 *>(smem + C::TBL);
+    const int tid = threadIdx.x;
+    for (int i = tid; i < C::TBL; i += STFT_THREADS) smem[i] = tables[i];
+    __syncthreads();
+
+    const long strm = blockIdx.y;
+    const int keep = N - g.hop;
+    Samples in;
+    in.audio = audio + strm * audio_stride;
+    in.hist = state + g.hist_off + (strm * g.S + c.slot_in) * (long)keep;
+    in.base = c.base;
+    in.keep = keep;
+    in.L = c.L;
+
+    if (blockIdx.x == 0) {           // the samples the next call's first frame shares with this one
+        float *h = state + g.hist_off + (strm * g.S + c.slot_out) * (long)keep;
+        for (int i = tid; i < keep; i += STFT_THREADS) h[i] = in.at(c.end - keep + i);
+    }
+
+    const int fl = tid / TPF, t = tid - fl * TPF;
+    const int f = c.f_new0 + blockIdx.x * FB + fl;
+    const bool live = f < c.f_new1;
+    const int s0 = (live ? f : c.f_new0) * g.hop - M;
+    float2 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int n2 = 2 * (t + u * TPF);
+        const float x0 = live ? in.at(s0 + n2) : 0.f;
+        const float x1 = live ? in.at(s0 + n2 + 1) : 0.f;
+        v[u] = make_float2(s_win[n2] * x0, s_win[n2 + 1] * x1);
+    }
+    float2 *sc = s_sc + fl * M;
+    fft_frame<M>(sc, s_tw, t, v);
+    if (live) {
+        // frames from T on (after the end of the stream) are zero in the windows and never emitted
+        const bool past = c.T >= 0 && f >= c.T;
+        float2 *o = reinterpret_cast<float2 *>(state + g.x_off) + (strm * g.RX + f % g.RX) * (long)F;
+        float *m = state + g.mag_off + (strm * g.RM + f % g.RM) * (long)F;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {                                 // the real-input split of stft_complex_kernel
+            const int k = t + b * TPF;                                // 0 .. M/2-1
+            if (k == 0) {
+                const float2 z0 = sc[0];
+                const float2 a0 = make_float2(z0.x + z0.y, 0.f), aM = make_float2(z0.x - z0.y, 0.f);
+                const float2 zh = sc[M / 2];
+                const float2 ah = make_float2(zh.x, -zh.y);
+                o[0] = a0;
+                o[M] = aM;
+                o[M / 2] = ah;
+                m[0] = past ? 0.f : mag_of(a0);
+                m[M] = past ? 0.f : mag_of(aM);
+                m[M / 2] = past ? 0.f : mag_of(ah);
+            } else {
+                const float2 A = sc[k], Bc = sc[M - k];
+                const float2 ev = make_float2(0.5f * (A.x + Bc.x), 0.5f * (A.y - Bc.y));
+                const float2 d = make_float2(0.5f * (A.x - Bc.x), 0.5f * (A.y + Bc.y));
+                const float2 wo = cmul(s_tw2[k], make_float2(d.y, -d.x));     // w^k * (d / i)
+                const float2 xa = cadd(ev, wo);
+                const float2 xb0 = csub(ev, wo);
+                const float2 xb = make_float2(xb0.x, -xb0.y);
+                o[k] = xa;
+                o[M - k] = xb;
+                m[k] = past ? 0.f : mag_of(xa);
+                m[M - k] = past ? 0.f : mag_of(xb);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- analysis 2: network input
+// mag ring rows are frame-major [frame][F], the network's windows bin-major [window][F][W] with the frame index fastest: a
+// 32 x 32 tile through LDS (pitch 33) keeps both sides contiguous along their fastest index, as dn_windows_kernel.
+__global__ __launch_bounds__(256) void stream_windows_kernel(const float *__restrict__ state, int F, StreamGeom g, StreamCall c,
+                                                             int tilesJ, int tilesF, float *__restrict__ out)
+{
+    __shared__ float tile[32][33];
+    unsigned b = blockIdx.x;
+    const int tj = (int)(b % (unsigned)tilesJ);
+    b /= (unsigned)tilesJ;
+    const int tf = (int)(b % (unsigned)tilesF);
+    const long win = b / (unsigned)tilesF;                       // stream * n_steps + i
+    const long strm = win / c.n_steps;
+    const int i = (int)(win - strm * c.n_steps);
+    const int fw0 = (c.first + i) * g.B + g.B + g.A - g.W;       // first frame of the step's window
+    const int j0 = tj * 32, f0 = tf * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const float *mg = state + g.mag_off + strm * g.RM * (long)F;
+    for (int r = ty; r < 32; r += 8) {
+        const int j = j0 + r, fr = fw0 + j, bin = f0 + tx;
+        float v = 0.f;
+        if (j < g.W && fr >= 0 && (c.T < 0 || fr < c.T) && bin < F) v = mg[(long)(fr % g.RM) * F + bin];
+        tile[r][tx] = v;
+    }
+    __syncthreads();
+    for (int r = ty; r < 32; r += 8) {
+        const int bin = f0 + r, j = j0 + tx;
+        if (bin < F && j < g.W) out[(win * F + bin) * (long)g.W + j] = tile[tx][r];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- emit
+// Positions are those of the untrimmed signal, p = n + n_fft/2: frame f covers [f hop, f hop + n_fft).  The calls before this one
+// have emitted p < p_begin = first B hop and left the partial sums of [p_begin, p_begin + n_fft - hop) in the tail; this call adds
+// frames [f_first, f_last], emits [p_begin, p_out) and leaves [p_tail, p_tail + n_fft - hop) in the new tail (p_tail = p_out
+// while the stream runs; nothing once the stream's last sample is out).  A workgroup owns `span` positions of
+// [p_begin, p_end); the frames that cover its span and belong to this call are rebuilt in LDS as dn_resynth_kernel does.
+template <int M>
+__global__ __launch_bounds__(STFT_THREADS, (M == 256 ? 4 : 2)) void stream_emit_kernel(
+    const float *__restrict__ y, StreamGeom g, StreamCall c, int nblk, const float *__restrict__ tables,
+    float *__restrict__ state, float *__restrict__ audio, long out_stride)
+{
+    using C = StCfg<M>;
+    constexpr int N = C::N, TPF = C::TPF, FB = C::FB, SB = C::SB, F = M + 1, P = C::PITCH, SPT = C::SPT, span = C::SPAN;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float *s_win = smem;
+    float2 *s_tw = reinterpret_cast<float2 *>(smem + N);
+    float2 *s_tw2 = s_tw + M;                                   // exp(-2 pi i k / N), k = 0 .. M/2
+    float2 *s_sc = reinterpret_cast<float2 *>(smem + C::TBL);
+    float *s_fr = smem + C::TBL;                                // the same storage once a pass's frames are windowed: [FB][N]
+    float *s_tile = smem + C::TBL + 2 * FB * M;                 // [SB][P] clamped magnitudes of the stage
+    const int tid = threadIdx.x;
+    for (int i = tid; i < C::TBL; i += STFT_THREADS) smem[i] = tables[i];
+    __syncthreads();                                            // (a workgroup past the call's last frame runs no FFT pass)
+
+    const long strm = blockIdx.x / (unsigned)nblk;
+    const int bx = (int)(blockIdx.x - strm * nblk);
+    const int hop = g.hop, keep = N - hop;
+    const int pa = c.p_begin + bx * span;
+    const int pb = pa + span < c.p_end ? pa + span : c.p_end;
+    // frames of this call that cover [pa, pb): ceil((pa - n_fft + 1) / hop) .. floor((pb - 1) / hop), clipped to the call's frames
+    int f_begin = pa < N ? 0 : (pa - N + hop) / hop;
+    if (f_begin < c.f_first) f_begin = c.f_first;
+    int f_end = (pb - 1) / hop;
+    if (f_end > c.f_last) f_end = c.f_last;
+
+    // the thread's positions pa + tid + u * 512 start from the carried partial sums (zero before the first step and past them)
+    const int p0 = pa + tid;
+    const float *tail_in = state + g.tail_off + (strm * g.S + c.slot_in) * (long)keep;
+    float acc[SPT];
+#pragma unroll
+    for (int u = 0; u < SPT; ++u) {
+        const int q = p0 + u * STFT_THREADS - c.p_begin;
+        acc[u] = (c.first > 0 && q < keep && p0 + u * STFT_THREADS < pb) ? tail_in[q] : 0.f;
+    }
+
+    const float *ys = y + strm * c.n_steps * (long)F * g.W;
+    const float2 *Xs = reinterpret_cast<const float2 *>(state + g.x_off) + strm * g.RX * (long)F;
+    const int fl = tid / TPF, t = tid - fl * TPF;               // FFT role: frame slot, lane inside the frame
+    const int jf = tid & (SB - 1), kb = tid / SB;               // staging role: frame of the stage, first bin
+    const float inv = 1.0f / (float)M;
+    const int j_keep = g.W - g.B - g.A;                         // local frame of the first frame a step keeps
+
+    for (int fs = f_begin; fs <= f_end; fs += SB) {
+        {
+            const int f = fs + jf;
+            const bool lv = f <= f_end;
+            const int fc = lv ? f : f_begin;
+            const int step = fc / g.B;                          // frame f is local frame W - B - A + f mod B of step f / B
+            constexpr int KS = STFT_THREADS / SB;               // bins between a thread's loads; 8 loads in flight per thread
+            const float *yf = ys + (long)(step - c.first) * F * g.W + j_keep + (fc - step * g.B);
+            for (int k0 = kb; k0 < F; k0 += 8 * KS) {
+                float hi[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const int k = k0 + e * KS < F ? k0 + e * KS : F - 1;
+                    hi[e] = yf[(long)k * g.W];
+                }
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    if (k0 + e * KS < F) s_tile[jf * P + k0 + e * KS] = lv ? relu_nan(hi[e]) : 0.f;
+            }
+        }
+        __syncthreads();
+        for (int fp = fs; fp < fs + SB && fp <= f_end; fp += FB) {
+            const int f = fp + fl;
+            const bool live = f <= f_end;
+            const float2 *Xf = Xs + (long)((live ? f : f_begin) % g.RX) * F;
+            const float *mt = s_tile + (fp - fs + fl) * P;
+            float2 v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int k = t + u * TPF;                       // 0 .. M-1
+                float2 xk = rephase(Xf[k], mt[k]), xm = rephase(Xf[M - k], mt[M - k]);
+                if (k == 0) { xk.y = 0.f; xm.y = 0.f; }          // irfft ignores Im X[0], Im X[M]
+                const float2 ev = make_float2(0.5f * (xk.x + xm.x), 0.5f * (xk.y - xm.y));
+                const float2 d = make_float2(0.5f * (xk.x - xm.x), 0.5f * (xk.y + xm.y));
+                float2 wi;
+                if (k <= M / 2) { const float2 w = s_tw2[k]; wi = make_float2(w.x, -w.y); }
+                else { const float2 w = s_tw2[M - k]; wi = make_float2(-w.x, -w.y); }
+                const float2 od = cmul(wi, d);
+                const float2 z = make_float2(ev.x - od.y, ev.y + od.x);
+                v[u] = live ? make_float2(z.x, -z.y) : make_float2(0.f, 0.f);
+            }
+            float2 *sc = s_sc + fl * M;
+            fft_frame<M>(sc, s_tw, t, v);
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {                        // window in place: slot n holds samples 2n, 2n + 1
+                const int n = t + u * TPF;
+                const float2 z = sc[n];
+                sc[n] = make_float2(s_win[2 * n] * (z.x * inv), s_win[2 * n + 1] * (-z.y * inv));
+            }
+            __syncthreads();
+            // gather: frame fr holds position p at j = p - fr * hop when 0 <= j < n_fft; frames ascend
+            const int fr_last = fp + FB - 1 < f_end ? fp + FB - 1 : f_end;
+            for (int fr = fp; fr <= fr_last; ++fr) {
+                const float *frame = s_fr + (fr - fp) * N;
+                const int j0 = p0 - fr * hop;
+#pragma unroll
+                for (int u = 0; u < SPT; ++u) {
+                    const int j = j0 + u * STFT_THREADS;
+                    const bool in = (unsigned)j < (unsigned)N;
+                    const float s = frame[in ? j : 0];
+                    if (in) acc[u] += s;
+                }
+            }
+            // no barrier here: the next pass overwrites the frames behind fft_frame's first barrier, and a new stage only
+            // touches the tile, which every thread has finished reading before that same barrier
+        }
+    }
+    float *tail_out = state + g.tail_off + (strm * g.S + c.slot_out) * (long)keep;
+#pragma unroll
+    for (int u = 0; u < SPT; ++u) {
+        const int p = p0 + u * STFT_THREADS;
+        if (p >= pb) continue;
+        if (p >= c.p_tail) tail_out[p - c.p_tail] = acc[u];     // partial sums the next call goes on from (p_tail >= p_out)
+        if (p >= c.p_out || p < M) continue;                    // positions before n_fft/2 are the trimmed front
+        // window sum-of-squares of the frames that cover the sample: dn_resynth_kernel's range, order and arithmetic
+        int f_hi = p / hop;
+        if (c.T >= 0 && f_hi > c.T - 1) f_hi = c.T - 1;
+        const int f_lo = p < N ? 0 : (p - N + hop) / hop;
+        float wss = 0.f;
+        for (int fr = f_lo; fr <= f_hi; ++fr) {
+            const float w = s_win[p - fr * hop];
+            wss += w * w;
+        }
+        audio[strm * out_stride + (p - c.p_first)] = wss > FLT_MIN ? acc[u] / wss : acc[u];
+    }
+}
+
+template <int M>
+hipError_t launch_frames_m(const float *audio, long audio_stride, int n_streams, const StreamGeom &g, const StreamCall &c,
+                           const float *tables, float *state, hipStream_t st)
+{
+    using C = StCfg<M>;
+    auto kern = stream_frames_kernel<M>;
+    if (C::LDS_FRAMES > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)C::LDS_FRAMES);
+        if (e != hipSuccess) return e;
+    }
+    const int nf = c.f_new1 - c.f_new0;
+    dim3 grid((unsigned)((nf + C::FB - 1) / C::FB), (unsigned)n_streams);
+    hipLaunchKernelGGL(kern, grid, dim3(STFT_THREADS), C::LDS_FRAMES, st, audio, audio_stride, g, c, tables, state);
+    return hipGetLastError();
+}
+
+template <int M>
+hipError_t launch_emit_m(const float *y, int n_streams, const StreamGeom &g, const StreamCall &c, const float *tables,
+                         float *state, float *audio, long out_stride, hipStream_t st)
+{
+    using C = StCfg<M>;
+    auto kern = stream_emit_kernel<M>;
+    if (C::LDS_EMIT > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)C::LDS_EMIT);
+        if (e != hipSuccess) return e;
+    }
+    const long total = (long)c.p_end - c.p_begin;
+    if (total <= 0) return hipSuccess;
+    const long nblk = (total + C::SPAN - 1) / C::SPAN;
+    if (nblk * n_streams > 0x7fffffffL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nblk * n_streams)), dim3(STFT_THREADS), C::LDS_EMIT, st, y, g, c, (int)nblk,
+                       tables, state, audio, out_stride);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+bool stream_geom(int n_streams, int n_fft, int hop, int window, int block, int lookahead, int max_steps, StreamGeom *g)
+{
+    if (n_streams < 1 || n_fft < 64 || n_fft > 4096 || (n_fft & (n_fft - 1))) return false;
+    if (hop < 1 || hop > n_fft / 4 || window < 16 || block < 1 || lookahead < 0) return false;
+    if ((long)block + lookahead > window || max_steps < 1) return false;
+    // ring lengths in frames stay far below 2^31 (the state of a larger plan could not be allocated anyway)
+    if (window > (1 << 20) || max_steps > (1 << 16) || (long)max_steps * block > (1L << 24) || n_streams > (1 << 20)) return false;
+    g->n_fft = n_fft;
+    g->hop = hop;
+    g->W = window;
+    g->B = block;
+    g->A = lookahead;
+    g->S = max_steps + 1;
+    g->RX = max_steps * block + lookahead;
+    g->RM = window + (max_steps - 1) * block;
+    const long F = n_fft / 2 + 1, keep = n_fft - hop, n = n_streams;
+    g->x_off = 0;                                    // the float2 rows first: 8-byte aligned whatever follows
+    g->mag_off = n * 2 * F * g->RX;
+    g->hist_off = g->mag_off + n * F * g->RM;
+    g->tail_off = g->hist_off + n * keep * g->S;
+    g->total = g->tail_off + n * keep * g->S;
+    return true;
+}
+
+hipError_t launch_stream_frames(const float *audio, long audio_stride, int n_streams, const StreamGeom &g, const StreamCall &c,
+                                float *state, hipStream_t st)
+{
+    const float *tables = nullptr;
+    hipError_t e = stft_tables(g.n_fft, &tables, st);
+    if (e != hipSuccess) return e;
+    switch (g.n_fft) {
+        case 64: return launch_frames_m<32>(audio, audio_stride, n_streams, g, c, tables, state, st);
+        case 128: return launch_frames_m<64>(audio, audio_stride, n_streams, g, c, tables, state, st);
+        case 256: return launch_frames_m<128>(audio, audio_stride, n_streams, g, c, tables, state, st);
+        case 512: return launch_frames_m<256>(audio, audio_stride, n_streams, g, c, tables, state, st);
+        case 1024: return launch_frames_m<512>(audio, audio_stride, n_streams, g, c, tables, state, st);
+        case 2048: return launch_frames_m<1024>(audio, audio_stride, n_streams, g, c, tables, state, st);
+        case 4096: return launch_frames_m<2048>(audio, audio_stride, n_streams, g, c, tables, state, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_stream_windows(const float *state, int n_streams, const StreamGeom &g, const StreamCall &c, float *out,
+                                 hipStream_t st)
+{
+    const int F = g.n_fft / 2 + 1;
+    const long tilesJ = (g.W + 31) / 32, tilesF = (F + 31) / 32;
+    const long grid = tilesJ * tilesF * c.n_steps * (long)n_streams;
+    if (grid > 0x7fffffffL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(stream_windows_kernel, dim3((unsigned)grid), dim3(256), 0, st, state, F, g, c, (int)tilesJ, (int)tilesF,
+                       out);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_emit(const float *y, int n_streams, const StreamGeom &g, const StreamCall &c, float *state, float *audio,
+                              long out_stride, hipStream_t st)
+{
+    const float *tables = nullptr;
+    hipError_t e = stft_tables(g.n_fft, &tables, st);
+    if (e != hipSuccess) return e;
+    switch (g.n_fft) {
+        case 64: return launch_emit_m<32>(y, n_streams, g, c, tables, state, audio, out_stride, st);
+        case 128: return launch_emit_m<64>(y, n_streams, g, c, tables, state, audio, out_stride, st);
+        case 256: return launch_emit_m<128>(y, n_streams, g, c, tables, state, audio, out_stride, st);
+        case 512: return launch_emit_m<256>(y, n_streams, g, c, tables, state, audio, out_stride, st);
+        case 1024: return launch_emit_m<512>(y, n_streams, g, c, tables, state, audio, out_stride, st);
+        case 2048: return launch_emit_m<1024>(y, n_streams, g, c, tables, state, audio, out_stride, st);
+        case 4096: return launch_emit_m<2048>(y, n_streams, g, c, tables, state, audio, out_stride, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace adn

@@ -14,7 +14,7 @@
  *     message.  Nothing throws or aborts across the ABI.
  *   - work is enqueued on the caller's stream.  The only calls that block or allocate: adn_unet_create / adn_unet_destroy
  *     (one-time weight upload / free), adn_prepare, and the FIRST call per (device, n_fft) of an STFT-family entry point
- *     (adn_stft_mag, adn_stft_mag_fit, adn_stft_complex, adn_istft, adn_griffin_lim) or per device of adn_perceptual_loss / adn_perceptual_loss_backward, which
+ *     (adn_stft_mag, adn_stft_mag_fit, adn_stft_complex, adn_istft, adn_griffin_lim, adn_denoise_resynth, adn_stream_analyze, adn_stream_emit) or per device of adn_perceptual_loss / adn_perceptual_loss_backward, which
  *     builds a few KB of constant tables (window, twiddles, mel filters) with a blocking upload -- unless adn_prepare did so
  *     before; and the FIRST adn_resample per (device, rate pair), which builds its coefficient table (adn_resample_prepare).  Such a cold call on a stream that is being captured enqueues nothing and returns ADN_ERR_INVALID (never a HIP
  *     error): call adn_prepare(device, n_fft) before capturing.  adn_unet_forward never blocks or allocates.
@@ -32,7 +32,7 @@
 
 #include <stddef.h>
 
-/* The 40 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 45 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -307,6 +307,63 @@ ADN_API int adn_denoise_stitch(const float *y, int n_clips, int n_frames, int n_
                                float *out, void *stream);
 ADN_API int adn_denoise_resynth(const float *y, const float *spec, int n_clips, long length, int n_fft, int hop, int window,
                                 int overlap, float *audio_out, void *stream);
+
+/* ---- stream: audio that is still arriving, in blocks, with the state carried on the device ------------------------------------
+ * adn_denoise_* handle a finished recording.  These entry points DEFINE the streaming form (no reference counterpart; float64
+ * restatement in tests/stream_ref.py): the "denoise" definition above with rules 2-4 replaced.  Rule 1 (the centred STFT) and
+ * rule 5 (clamp, the noisy input's phase, the inverse STFT of the input's full length L) stay as they are.
+ * Not pinned / not validated: parity of the STFT with librosa, as everywhere; the quality of the proposed defaults window 192,
+ * block 16, look-ahead 0 (design values); equality with the offline form -- the windows differ by design.
+ *
+ *   n_fft power of two in [64, 4096], 1 <= hop <= n_fft / 4, F = n_fft / 2 + 1, window W >= 16 frames, block B >= 1 frames,
+ *   look-ahead A >= 0 frames, B + A <= W.
+ *   Frames: frame t is the centred frame of rule 1: samples [t hop - n_fft/2, t hop + n_fft/2), samples before 0 are zero; it is
+ *     complete once t hop + n_fft/2 samples have arrived.
+ *   Steps: step k = 0, 1, ... feeds the network one window per stream, in[k, 0, f, j] = |X[k B + B + A - W + j, f]| for j < W;
+ *     frames < 0 are zero and, after the end, frames >= T are zero; |X| exactly as in rule 2.  Step k can run when frame
+ *     k B + B + A - 1 is complete: after m samples steps_done(m) = 0 if r = m - n_fft/2 - (B + A - 1) hop < 0, else r / (B hop) + 1.
+ *   Join: Y[f, k B + i] = y[k, 0, f, W - B - A + i] for i < B: every frame comes from exactly one window, bit for bit -- no
+ *     cross-fade; the past context provides continuity.  M = max(Y, 0), NaN stays NaN.
+ *   Output: after step k the samples n < (k + 1) B hop - n_fft/2 are final: emitted(m) = max(0, steps_done(m) B hop - n_fft/2).
+ *   Latency: at worst (B + A - 1) hop + n_fft samples between a sample's arrival and its emission.
+ *   End of stream: after L samples in all the remaining steps up to K = ceil(T / B), T = 1 + L / hop, run with the frames that
+ *     reach past L zero padded and the frames >= T zero in the windows; the stream has then produced exactly L samples, and they
+ *     are rule 5's inverse STFT of M with the phase of X.
+ *
+ * The library keeps no per-stream host state: the step index is an argument and everything carried between calls lives in a
+ * caller-owned device buffer (`state`, adn_stream_state_bytes, 8-byte aligned, opaque; adn_stream_reset before the first step of a
+ * stream).  All n_streams streams of a state advance in lockstep.  A call covers the n_steps <= max_steps consecutive steps
+ * first_step .. first_step + n_steps - 1; calls go in step order, and the steps a call analyses are emitted before later steps
+ * are analysed.  final_length is -1 while the stream runs and L for the steps that run after its end (at most up to step K - 1).
+ *   adn_stream_analyze: `audio` holds, per stream (audio_stride floats apart), the samples the steps bring: samples
+ *     [e(first_step - 1), e(last_step)) with e(k) = (k B + B + A - 1) hop + n_fft/2 and e(-1) = 0, cut at L when final_length is
+ *     given (the pointer must be valid even when that leaves none).  windows_out: (n_streams * n_steps, 1, F, W) fp32, the frame
+ *     index fastest, a stream's steps consecutive: the input of adn_unet_forward.
+ *   adn_stream_emit: y, the network's output for those windows, same layout.  audio_out, per stream (out_stride floats apart),
+ *     receives samples [max(0, first_step B hop - n_fft/2), (last_step + 1) B hop - n_fft/2), or up to L when last_step = K - 1
+ *     with final_length given; it may be NULL when that range is empty (B hop < n_fft/2 in the first steps).
+ * Two launches analyse (new frames into the state, then the windows out of it), one emits.  No atomics, no workspace; a sample
+ * is the carried partial sum plus its frames in ascending frame order, so the same audio gives the same bits however it was
+ * split into calls and a stream's result does not depend on its neighbours in the batch.  At the start of a stream and after its
+ * end the divisor is adn_denoise_resynth's.  The kernels use the tables of (device, n_fft) like the STFT family: adn_prepare
+ * before a capture (a cold call on a capturing stream enqueues nothing and returns ADN_ERR_INVALID).
+ * Limits (ADN_ERR_INVALID otherwise, nothing is launched): the parameter ranges above; n_streams >= 1; 1 <= max_steps <= 65536;
+ * n_steps <= max_steps; the steps of a call end before sample 2^30 of the stream (positions are 32-bit inside the kernels: flush
+ * before that, 37 hours at 8 kHz).  ADN_ERR_WORKSPACE: state_bytes below adn_stream_state_bytes.
+ * adn_stream_plan (steps_done, emitted and latency for `received` samples; any output pointer may be NULL) and
+ * adn_stream_state_bytes are host-only (no device needed). */
+ADN_API int adn_stream_plan(int n_fft, int hop, int window, int block, int lookahead, long received, long *steps_done,
+                            long *emitted, long *latency);
+ADN_API int adn_stream_state_bytes(int n_streams, int n_fft, int hop, int window, int block, int lookahead, int max_steps,
+                                   size_t *bytes);
+ADN_API int adn_stream_reset(void *state, size_t state_bytes, int n_streams, int n_fft, int hop, int window, int block,
+                             int lookahead, int max_steps, void *stream);
+ADN_API int adn_stream_analyze(void *state, size_t state_bytes, const float *audio, long audio_stride, int n_streams,
+                               long first_step, int n_steps, long final_length, int n_fft, int hop, int window, int block,
+                               int lookahead, int max_steps, float *windows_out, void *stream);
+ADN_API int adn_stream_emit(void *state, size_t state_bytes, const float *y, int n_streams, long first_step, int n_steps,
+                            long final_length, int n_fft, int hop, int window, int block, int lookahead, int max_steps,
+                            float *audio_out, long out_stride, void *stream);
 
 /* ---- environment switches -------------------------------------------------------------------------------------------------
  * Read ONCE, when a U-Net handle is created (never per call).  None is needed in production: the defaults are the measured best
