@@ -7,7 +7,7 @@ __version__ = "0.1.0"
 
 __all__ = ["UNet", "SpectrogramDataset", "WavToSpecDataset", "audio_to_magnitude_spectrogram",
            "audio_to_spectrogram", "stft_magnitude", "per_clip_l1", "CombinedPerceptualLoss", "NoiseMixDataset",
-           "resample_length", "mix_snr", "load_audio", "Denoiser", "StreamDenoiser", "ReverbSettings"]
+           "resample_length", "mix_snr", "load_audio", "StreamResampler", "Denoiser", "StreamDenoiser", "ReverbSettings"]
 # (resample / reverb themselves: audiodenoiser_amd.resample.resample, audiodenoiser_amd.reverb.reverb -- the modules own the names)
 
 
@@ -21,7 +21,7 @@ def __getattr__(name):
     if name in ("audio_to_magnitude_spectrogram", "audio_to_spectrogram", "stft_magnitude"):
         from . import stft
         return getattr(stft, name)
-    if name in ("resample_length", "mix_snr", "load_audio"):
+    if name in ("resample_length", "mix_snr", "load_audio", "StreamResampler"):
         import importlib
         return getattr(importlib.import_module(".resample", __name__), name)
     if name == "ReverbSettings":

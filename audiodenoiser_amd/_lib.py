@@ -85,6 +85,9 @@ def load() -> ctypes.CDLL:
         L.adn_stream_reset.argtypes = [vp, sz, ci, ci, ci, ci, ci, ci, ci, vp]
         L.adn_stream_analyze.argtypes = [vp, sz, vp, cl, ci, cl, ci, cl, ci, ci, ci, ci, ci, ci, vp, vp]
         L.adn_stream_emit.argtypes = [vp, sz, vp, ci, cl, ci, cl, ci, ci, ci, ci, ci, ci, vp, cl, vp]
+        L.adn_resample_stream_plan.argtypes = [ci, ci, cl, ci, ctypes.POINTER(cl), ctypes.POINTER(cl), ctypes.POINTER(cl)]
+        L.adn_resample_stream_state_bytes.argtypes = [ci, ci, ci, ctypes.POINTER(sz)]
+        L.adn_resample_stream.argtypes = [vp, sz, vp, cl, ci, cl, cl, cl, ci, ci, ci, vp, cl, vp]
         for name in ("adn_device_count", "adn_prepare", "adn_unet_create", "adn_unet_create_ex", "adn_unet_create_general", "adn_unet_channels",
                      "adn_unet_set_batch_invariant", "adn_unet_destroy", "adn_unet_workspace_bytes", "adn_unet_forward", "adn_unet_forward_taps", "adn_unet_set_timing", "adn_unet_get_timing",
                      "adn_stft_n_frames", "adn_stft_mag", "adn_stft_mag_fit", "adn_quantize_pad", "adn_per_clip_l1",
@@ -94,7 +97,8 @@ def load() -> ctypes.CDLL:
                      "adn_griffin_lim_workspace_bytes", "adn_griffin_lim", "adn_stft_complex",
                      "adn_istft_workspace_bytes", "adn_istft",
                      "adn_denoise_plan", "adn_denoise_windows", "adn_denoise_stitch", "adn_denoise_resynth",
-                     "adn_stream_plan", "adn_stream_state_bytes", "adn_stream_reset", "adn_stream_analyze", "adn_stream_emit"):
+                     "adn_stream_plan", "adn_stream_state_bytes", "adn_stream_reset", "adn_stream_analyze", "adn_stream_emit",
+                     "adn_resample_stream_plan", "adn_resample_stream_state_bytes", "adn_resample_stream"):
             getattr(L, name).restype = ci
         _lib = L
         return L
@@ -127,4 +131,5 @@ EXPORTED_SYMBOLS = (
     "adn_resample_length", "adn_resample_prepare", "adn_resample", "adn_mix_snr_workspace_bytes", "adn_mix_snr", "adn_reverb",
     "adn_denoise_plan", "adn_denoise_windows", "adn_denoise_stitch", "adn_denoise_resynth",
     "adn_stream_plan", "adn_stream_state_bytes", "adn_stream_reset", "adn_stream_analyze", "adn_stream_emit",
+    "adn_resample_stream_plan", "adn_resample_stream_state_bytes", "adn_resample_stream",
 )

@@ -143,6 +143,9 @@ int adn_resample_prepare(int device, int src_rate, int dst_rate)
     DeviceGuard guard(device);
     if (guard.err != hipSuccess) return fail_hip(guard.err, "hipSetDevice");
     ADN_HIP(adn::resample_prepare(up, down, nullptr));
+    adn::ResampleStreamGeom g;                            // ... and adn_resample_stream's, where the pair can be streamed
+    if (adn::resample_stream_geom(src_rate, dst_rate, &g) && g.H <= adn::ADN_RESAMPLE_STREAM_MAX_H)
+        ADN_HIP(adn::resample_stream_prepare(g, nullptr));
     return ADN_OK;
 }
 
@@ -566,6 +569,82 @@ int adn_stream_emit(void *state, size_t state_bytes, const float *y, int n_strea
                                            static_cast<hipStream_t>(stream));
     if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_stream_emit: grid too large");
     ADN_LAUNCH(e, "adn_stream_emit");
+    return ADN_OK;
+}
+
+static const char *resample_stream_text = ": rates must be >= 1 with max(up, down) <= 4096 after dividing by their gcd, and at most "
+                                          "16384 carried samples (2 floor(half / up) + ceil(down / up) + 1)";
+
+static bool resample_stream_plan_ok(int src_rate, int dst_rate, adn::ResampleStreamGeom *g)
+{
+    return adn::resample_stream_geom(src_rate, dst_rate, g) && g->H <= adn::ADN_RESAMPLE_STREAM_MAX_H;
+}
+
+int adn_resample_stream_plan(int src_rate, int dst_rate, long received, int final, long *emitted, long *history, long *latency)
+{
+    adn::ResampleStreamGeom g;
+    if (!resample_stream_plan_ok(src_rate, dst_rate, &g)) return fail(ADN_ERR_INVALID, std::string("adn_resample_stream_plan") + resample_stream_text);
+    if (received < 0 || received >= (1L << 40)) return fail(ADN_ERR_INVALID, "adn_resample_stream_plan: need 0 <= received < 2^40");
+    if (final != 0 && final != 1) return fail(ADN_ERR_INVALID, "adn_resample_stream_plan: final must be 0 or 1");
+    if (emitted) *emitted = adn::resample_stream_emitted(g, received, final != 0);
+    if (history) *history = g.H;
+    if (latency) *latency = g.latency;
+    return ADN_OK;
+}
+
+int adn_resample_stream_state_bytes(int n_streams, int src_rate, int dst_rate, size_t *bytes)
+{
+    adn::ResampleStreamGeom g;
+    if (!bytes) return fail(ADN_ERR_INVALID, "adn_resample_stream_state_bytes: null pointer");
+    if (n_streams < 1) return fail(ADN_ERR_INVALID, "adn_resample_stream_state_bytes: n_streams must be >= 1");
+    if (!resample_stream_plan_ok(src_rate, dst_rate, &g)) return fail(ADN_ERR_INVALID, std::string("adn_resample_stream_state_bytes") + resample_stream_text);
+    *bytes = (size_t)n_streams * 2 * (size_t)g.H * sizeof(float);
+    return ADN_OK;
+}
+
+int adn_resample_stream(void *state, size_t state_bytes, const float *audio, long audio_stride, int n_streams, long call_index,
+                        long received_before, long n_new, int final, int src_rate, int dst_rate, float *out, long out_stride,
+                        void *stream)
+{
+    adn::ResampleStreamGeom g;
+    if (!resample_stream_plan_ok(src_rate, dst_rate, &g)) return fail(ADN_ERR_INVALID, std::string("adn_resample_stream") + resample_stream_text);
+    if (n_streams < 1) return fail(ADN_ERR_INVALID, "adn_resample_stream: n_streams must be >= 1");
+    if (final != 0 && final != 1) return fail(ADN_ERR_INVALID, "adn_resample_stream: final must be 0 or 1");
+    if (n_new < (final ? 0 : 1)) return fail(ADN_ERR_INVALID, "adn_resample_stream: need n_new >= 1 (>= 0 in the final call)");
+    if (call_index < 0 || received_before < 0 || (call_index == 0) != (received_before == 0))
+        return fail(ADN_ERR_INVALID, "adn_resample_stream: need call_index >= 0 and received_before >= 0, both 0 in the first call of a stream and only there");
+    if (received_before >= (1L << 31) || n_new >= (1L << 31) || received_before + n_new >= (1L << 31))
+        return fail(ADN_ERR_INVALID, "adn_resample_stream: input positions must be < 2^31; end the stream before");
+    const long m0 = adn::resample_stream_emitted(g, received_before, false);
+    const long m1 = adn::resample_stream_emitted(g, received_before + n_new, final != 0);
+    if (m1 >= (1L << 31)) return fail(ADN_ERR_INVALID, "adn_resample_stream: output positions must be < 2^31; end the stream before");
+    const long n_out = m1 - m0;
+    const bool copy = g.up == g.down;
+    if ((!state && !copy) || (!audio && n_new > 0) || (!out && n_out > 0)) return fail(ADN_ERR_INVALID, "adn_resample_stream: null pointer");
+    if (audio_stride < 0 || (n_streams > 1 && audio_stride < n_new))
+        return fail(ADN_ERR_INVALID, "adn_resample_stream: audio_stride is smaller than n_new");
+    if (out_stride < 0 || (n_streams > 1 && out_stride < n_out))
+        return fail(ADN_ERR_INVALID, "adn_resample_stream: out_stride is smaller than the samples the call emits");
+    if (!aligned_to(state, 8) || !aligned_to(audio, 4) || !aligned_to(out, 4))
+        return fail(ADN_ERR_INVALID, "adn_resample_stream: state must be 8-byte aligned, audio and out 4-byte aligned");
+    if (state_bytes < (size_t)n_streams * 2 * (size_t)g.H * sizeof(float))
+        return fail(ADN_ERR_WORKSPACE, "adn_resample_stream: state smaller than adn_resample_stream_state_bytes");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (copy) {                                           // equal rates: no filter, no state
+        if (n_new > 0)
+            ADN_HIP(hipMemcpy2DAsync(out, (size_t)(n_streams > 1 ? out_stride : n_new) * sizeof(float), audio,
+                                     (size_t)(n_streams > 1 ? audio_stride : n_new) * sizeof(float), (size_t)n_new * sizeof(float),
+                                     (size_t)n_streams, hipMemcpyDeviceToDevice, st));
+        return ADN_OK;
+    }
+    hipError_t e = adn::launch_resample_stream(static_cast<float *>(state), audio, audio_stride, n_streams, g, call_index,
+                                               received_before, n_new, final != 0, out, out_stride, st);
+    if (e == adn::ADN_COLD_IN_CAPTURE)
+        return fail(ADN_ERR_INVALID, "adn_resample_stream: first use of this (device, rate pair) on a stream that is being captured -- the "
+                    "coefficient table is built with a blocking upload; call adn_resample_prepare(device, src_rate, dst_rate) before "
+                    "the capture");
+    if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_resample_stream: grid too large (n_streams x output blocks >= 2^31)");
+    if (e != hipSuccess) return fail_hip(e, "adn_resample_stream");
     return ADN_OK;
 }
 

@@ -323,6 +323,25 @@ hipError_t launch_per_clip_l1(const float *a, const float *b, int n_clips, long 
 bool resample_ratio(int src_rate, int dst_rate, int *up, int *down);
 hipError_t resample_prepare(int up, int down, hipStream_t st);
 hipError_t launch_resample(const float *audio, int n_clips, long L, long M, int up, int down, float *out, hipStream_t st);
+// The prototype low-pass of adn.h for a reduced rate pair: half = ZEROS max(up, down), and tap h[j], |j| <= half, computed in
+// float64 and rounded once to fp32 -- the one function both resampler tables take their coefficients from.
+long resample_half(int up, int down);
+float resample_tap(long j, int up, int down);
+// Resampler inside a stream (stream_resample_kernels.hip; adn.h, "resample stream").  ResampleStreamGeom: the plan of a rate pair
+// -- K = floor(half / up), H carried samples per slot, latency in input samples (H = latency = 0 for equal rates, a copy);
+// resample_stream_geom is false outside the rate limits of adn_resample.  The state is [stream][2][H] floats.  The coefficient table
+// is built on first use per (device, up, down) or by resample_stream_prepare (ADN_COLD_IN_CAPTURE applies).
+constexpr long ADN_RESAMPLE_STREAM_MAX_H = 16384;
+struct ResampleStreamGeom {
+    int up, down, K;
+    long half, H, latency;
+};
+bool resample_stream_geom(int src_rate, int dst_rate, ResampleStreamGeom *g);
+long resample_stream_emitted(const ResampleStreamGeom &g, long received, bool final);
+hipError_t resample_stream_prepare(const ResampleStreamGeom &g, hipStream_t st);
+hipError_t launch_resample_stream(float *state, const float *audio, long audio_stride, int n_streams, const ResampleStreamGeom &g,
+                                  long call_index, long received_before, long n_new, bool final, float *out, long out_stride,
+                                  hipStream_t st);
 size_t mix_snr_workspace_floats(int n_clips, long L);
 hipError_t launch_mix_snr(const float *clean, const float *noise, int n_clips, long L, float inv_snr_linear, float *workspace,
                           float *out, hipStream_t st);

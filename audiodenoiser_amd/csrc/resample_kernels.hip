@@ -371,6 +371,15 @@ long mix_blocks(long L) { return (L + MIX_BLK - 1) / MIX_BLK; }
 
 }  // namespace
 
+long resample_half(int up, int down) { return (long)RS_ZEROS * (up > down ? up : down); }
+
+float resample_tap(long j, int up, int down)
+{
+    static const double i0_beta = bessel_i0(RS_BETA);
+    const int q = up > down ? up : down;
+    return (float)prototype_tap(j, resample_half(up, down), up, RS_ROLLOFF / (double)q, i0_beta);
+}
+
 bool resample_ratio(int src_rate, int dst_rate, int *up, int *down)
 {
     if (src_rate < 1 || dst_rate < 1) return false;

@@ -9,6 +9,10 @@ are not reproduced here: results are NOT bit-compatible with ``librosa.load`` an
 
 ``mix_snr`` is ``add_noise`` for the "white" / "urban" types (``create_train_dataset.py:147-157``) over a batch.
 
+``StreamResampler`` is ``resample`` for audio that is still arriving (``adn_resample_stream``; definition: ``include/adn.h``,
+"resample stream"): ``push`` returns the samples that have become final, ``flush`` the rest, and their concatenation is, bit for
+bit, ``resample`` of the finished signal however it was cut into pushes.  The filter's history lives on the device between calls.
+
 numpy in -> numpy out (staged on the device); a tensor on a ROCm device stays there; a CPU tensor raises.  There is no
 CPU arithmetic path.
 """
@@ -22,7 +26,7 @@ import torch
 from . import _lib
 from .wav import read_wav
 
-__all__ = ["resample_length", "resample", "prepare_resample", "mix_snr", "load_audio"]
+__all__ = ["resample_length", "resample", "prepare_resample", "mix_snr", "load_audio", "StreamResampler", "resample_stream_plan"]
 
 
 def resample_length(length: int, orig_sr: int, target_sr: int) -> int:
@@ -68,6 +72,119 @@ def resample(audio, orig_sr: int, target_sr: int, device=None):
         return _resample_device(audio, orig_sr, target_sr)
     a = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(device or _lib.staging_device())
     return _resample_device(a, orig_sr, target_sr).cpu().numpy()
+
+
+def resample_stream_plan(received: int, orig_sr: int, target_sr: int, final: bool = False):
+    """``(emitted, history, latency)`` of a stream that has received ``received`` samples at ``orig_sr`` (``adn_resample_stream_plan``,
+    host only): outputs that are final (all of them with ``final``), input samples carried between calls, and the latency in input
+    samples."""
+    e, h, lat = ctypes.c_long(), ctypes.c_long(), ctypes.c_long()
+    _lib.check(_lib.load().adn_resample_stream_plan(int(orig_sr), int(target_sr), int(received), 1 if final else 0, ctypes.byref(e),
+                                                    ctypes.byref(h), ctypes.byref(lat)), "adn_resample_stream_plan")
+    return int(e.value), int(h.value), int(lat.value)
+
+
+class StreamResampler:
+    """``n_streams`` streams at ``orig_sr`` -> the same streams at ``target_sr``, block by block; all streams advance in lockstep."""
+
+    def __init__(self, orig_sr: int, target_sr: int, n_streams: int = 1, device=None):
+        if not (isinstance(orig_sr, int) and isinstance(target_sr, int) and orig_sr >= 1 and target_sr >= 1):
+            raise ValueError("StreamResampler: rates must be integers >= 1")
+        if not (isinstance(n_streams, int) and n_streams >= 1):
+            raise ValueError("StreamResampler: n_streams must be >= 1")
+        self.orig_sr, self.target_sr, self.n_streams = orig_sr, target_sr, n_streams
+        need = ctypes.c_size_t()
+        _lib.check(_lib.load().adn_resample_stream_state_bytes(n_streams, orig_sr, target_sr, ctypes.byref(need)),
+                   "adn_resample_stream_state_bytes")
+        self._state_bytes = need.value
+        self._device = torch.device(device) if device is not None else None
+        self._state = None                 # allocated with the first block: on its device, or the staging device for numpy
+        self._numpy = True
+        self.reset()
+
+    @property
+    def latency_samples(self) -> int:
+        """Input samples that at worst lie between a sample's arrival and the output it feeds: ``ceil(half / up)``."""
+        return resample_stream_plan(0, self.orig_sr, self.target_sr)[2]
+
+    @property
+    def received(self) -> int:
+        return self._received
+
+    @property
+    def emitted(self) -> int:
+        return self._emitted
+
+    def reset(self):
+        """Forget the running stream.  Call 0 of a stream reads no state, so nothing is enqueued."""
+        self._received = self._emitted = self._calls = 0
+
+    def _to_device(self, block) -> torch.Tensor:
+        self._numpy = not isinstance(block, torch.Tensor)
+        if self._numpy:
+            if self._device is None:
+                self._device = _lib.staging_device()
+            x = torch.from_numpy(np.ascontiguousarray(block, dtype=np.float32)).to(self._device)
+        else:
+            x = block
+            if not x.is_cuda:
+                raise RuntimeError("StreamResampler.push: a tensor must live on a ROCm device (no CPU path); pass numpy to have it staged")
+            if x.dtype != torch.float32:
+                raise TypeError("StreamResampler.push: expected float32 audio")
+            if self._device is None:
+                self._device = x.device
+            x = x.to(self._device)
+        if x.dim() == 1:
+            x = x[None]
+        if x.dim() != 2 or x.shape[0] != self.n_streams:
+            raise ValueError(f"StreamResampler.push: audio must be (m,) for one stream or (n_streams, m) = ({self.n_streams}, m)")
+        return x if x.stride(1) == 1 or x.shape[1] == 0 else x.contiguous()
+
+    def _call(self, x, final: bool) -> torch.Tensor:
+        """One ``adn_resample_stream`` call on the device tensor ``x`` (n_streams, n_new), or the last one with ``x`` None."""
+        dev = self._device
+        n_new = 0 if x is None else x.shape[1]
+        total = resample_stream_plan(self._received + n_new, self.orig_sr, self.target_sr, final)[0]
+        out = torch.empty((self.n_streams, total - self._emitted), dtype=torch.float32, device=dev)
+        if self._state is None:
+            self._state = torch.empty(max(self._state_bytes, 8), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().adn_resample_stream(self._state.data_ptr(), self._state_bytes, x.data_ptr() if n_new else None,
+                                                       x.stride(0) if n_new else 0, self.n_streams, self._calls, self._received, n_new,
+                                                       1 if final else 0, self.orig_sr, self.target_sr,
+                                                       out.data_ptr() if out.shape[1] else None, out.shape[1],
+                                                       torch.cuda.current_stream(dev).cuda_stream), "adn_resample_stream")
+        self._received += n_new
+        self._emitted = total
+        self._calls += 1
+        return out
+
+    def _empty(self):
+        out = torch.empty((self.n_streams, 0), dtype=torch.float32, device=self._device)
+        return out.cpu().numpy() if self._numpy else out
+
+    def push(self, block):
+        """``block``: the next ``m >= 0`` samples of every stream at ``orig_sr``, ``(m,)`` for one stream or ``(n_streams, m)``, float32.
+        Returns ``(n_streams, emitted(received) - emitted(before))`` samples at ``target_sr``: those no later input can change.  One
+        kernel launch on the current stream; a push of nothing returns nothing and launches nothing."""
+        x = self._to_device(block)
+        if x.shape[1] == 0:
+            return self._empty()
+        if self._received + x.shape[1] >= 1 << 31:
+            raise ValueError("StreamResampler.push: a stream holds fewer than 2^31 samples; flush() it before")
+        out = self._call(x, False)
+        return out.cpu().numpy() if self._numpy else out
+
+    def flush(self):
+        """The stream has ended: returns the rest, so that it has produced ``resample_length(received)`` samples in all, in the kind
+        (numpy / tensor) of the last ``push``.  The object is then ready for a new stream."""
+        if self._received == 0:
+            out = self._empty() if self._device is not None else np.empty((self.n_streams, 0), dtype=np.float32)
+        else:
+            out = self._call(None, True)
+            out = out.cpu().numpy() if self._numpy else out
+        self.reset()
+        return out
 
 
 def _mix_device(clean: torch.Tensor, noise: torch.Tensor, snr_db: float) -> torch.Tensor:

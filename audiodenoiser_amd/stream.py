@@ -5,9 +5,10 @@
     for block in feed:                                # (m,) or (n_streams, m) float32 at sample_rate, any m >= 0
         out = sd.push(block)                          # (n_streams, newly final samples), possibly zero columns
     out = sd.flush()                                  # the rest: exactly as many samples out as went in
+    sd = StreamDenoiser(model, input_rate=48000)      # the same for a feed at 48 kHz: samples at 48 kHz in, samples at 48 kHz out
 
     python -m audiodenoiser_amd.stream --model CKPT.pth IN.wav OUT.wav [--chunk 1024] [--window 192] [--block 16]
-                                       [--lookahead 0] [--dtype f32|f16]
+                                       [--lookahead 0] [--dtype f32|f16] [--live]
 
 ``Denoiser`` handles a finished recording.  This class handles a call, a capture device, a long file read block by block, or many
 concurrent feeds served from one card (definition: ``include/adn.h``, "stream"; float64 restatement: ``tests/stream_ref.py``;
@@ -20,9 +21,16 @@ returned.  The result does not depend on how the audio was cut into ``push`` cal
 ``(B + A - 1) hop + n_fft`` samples lie between a sample's arrival and its return.
 
 All streams of one object advance in lockstep (one ``push`` brings the same number of samples for each); feeds with independent
-timing use separate objects.  ``push`` takes audio at ``sample_rate`` only: converting the rate inside a stream would need a
-resampler that carries its own state, which this package does not have (the command line converts the whole file before and
-after).  A ``push`` that completes several steps sends them through the network as one batch, ``batch_windows`` windows at a time.
+timing use separate objects.  A ``push`` that completes several steps sends them through the network as one batch,
+``batch_windows`` windows at a time.
+
+``sample_rate`` is the network's working rate.  A feed at another rate names it as ``input_rate``: ``push`` then takes and returns
+samples at ``input_rate``, and inside a ``StreamResampler`` (``adn_resample_stream``, the filter's history carried on the device)
+brings them to the working rate, the steps above run, and a second one takes the result back -- all on the current stream.  The
+result is, bit for bit with ``set_batch_invariant(True)``, ``resample`` of the whole input -> this class at the working rate ->
+``resample`` back, cut to the input's length, whatever the pushes were; ``latency_input_samples`` bounds the delay at the input
+rate (14 976 samples, 0.312 s, at 48 kHz with the default plan).  The command line's ``--live`` feeds the file that way, ``--chunk``
+samples at its own rate at a time; without it the file is converted as a whole before and after the stream, as before.
 
 What is NOT claimed: parity of the STFT with librosa stays unpinned, as everywhere in this package; ``window_frames=192``,
 ``block_frames=16`` and ``lookahead_frames=0`` are design values whose audible quality has not been judged; the result differs
@@ -31,13 +39,14 @@ from ``Denoiser``'s by design (other windows).  There is no CPU path.
 from __future__ import annotations
 
 import ctypes
+import math
 
 import numpy as np
 import torch
 
 from . import _lib
 
-__all__ = ["StreamDenoiser", "stream_plan"]
+__all__ = ["StreamDenoiser", "stream_plan", "stream_rate_plan"]
 
 
 def stream_plan(received: int, n_fft: int = 512, hop_length: int = 128, window_frames: int = 192, block_frames: int = 16,
@@ -49,13 +58,33 @@ def stream_plan(received: int, n_fft: int = 512, hop_length: int = 128, window_f
     return int(s.value), int(e.value), int(lat.value)
 
 
+def _rate_latency(input_rate: int, sample_rate: int, latency_samples: int) -> int:
+    """``ceil((2 half + latency_samples down) / up)`` with up / down of input -> working rate: both filters' reach plus the steps'."""
+    g = math.gcd(input_rate, sample_rate)
+    up, down = sample_rate // g, input_rate // g
+    half = 0 if up == down else 32 * max(up, down)
+    return -(-(2 * half + latency_samples * down) // up)
+
+
+def stream_rate_plan(received: int, input_rate: int, n_fft: int = 512, hop_length: int = 128, window_frames: int = 192,
+                     block_frames: int = 16, lookahead_frames: int = 0, sample_rate: int = 8000):
+    """``(emitted, latency_input_samples)``, both at ``input_rate``, of a ``StreamDenoiser(..., input_rate=input_rate)`` that has
+    received ``received`` samples: the three plans composed (resampler in, steps, resampler out; host only)."""
+    from .resample import resample_stream_plan
+    plan = (n_fft, hop_length, window_frames, block_frames, lookahead_frames)
+    at_work = resample_stream_plan(received, input_rate, sample_rate)[0]
+    _, at_work_out, lat = stream_plan(at_work, *plan)
+    return resample_stream_plan(at_work_out, sample_rate, input_rate)[0], _rate_latency(int(input_rate), int(sample_rate), lat)
+
+
 def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
 
 
 class StreamDenoiser:
     def __init__(self, model, n_streams: int = 1, sample_rate: int = 8000, n_fft: int = 512, hop_length: int = 128,
-                 window_frames: int = 192, block_frames: int = 16, lookahead_frames: int = 0, batch_windows: int = 64):
+                 window_frames: int = 192, block_frames: int = 16, lookahead_frames: int = 0, batch_windows: int = 64,
+                 input_rate=None):
         if not (isinstance(n_streams, int) and n_streams >= 1):
             raise ValueError("StreamDenoiser: n_streams must be >= 1")
         if not (isinstance(n_fft, int) and 64 <= n_fft <= 4096 and n_fft & (n_fft - 1) == 0):
@@ -75,6 +104,8 @@ class StreamDenoiser:
             raise ValueError("StreamDenoiser: batch_windows must be >= 1")
         if not (isinstance(sample_rate, int) and sample_rate >= 1):
             raise ValueError("StreamDenoiser: sample_rate must be >= 1")
+        if input_rate is not None and not (isinstance(input_rate, int) and input_rate >= 1):
+            raise ValueError("StreamDenoiser: input_rate must be None (the feed is at sample_rate) or an integer >= 1")
         from .model import UNet
         if not isinstance(model, UNet) or model.in_channels != 1 or model.num_classes != 1:
             raise ValueError("StreamDenoiser: model must be an audiodenoiser_amd.model.UNet(1, 1)")
@@ -99,6 +130,13 @@ class StreamDenoiser:
         self._cap = self._end_of(0) + self.max_steps * block_frames * hop_length
         self._pend = torch.zeros((n_streams, self._cap), dtype=torch.float32, device=dev)
         self._numpy = True
+        # a feed at another rate: one resampler into the working rate, one back (none otherwise)
+        self.input_rate = sample_rate if input_rate is None else input_rate
+        self._rs_in = self._rs_out = None
+        if self.input_rate != sample_rate:
+            from .resample import StreamResampler
+            self._rs_in = StreamResampler(self.input_rate, sample_rate, n_streams, dev)
+            self._rs_out = StreamResampler(sample_rate, self.input_rate, n_streams, dev)
         self.reset()
 
     # ------------------------------------------------------------------ the plan
@@ -114,15 +152,25 @@ class StreamDenoiser:
         return stream_plan(0, *self._plan)[2]
 
     @property
+    def latency_input_samples(self) -> int:
+        """``latency_samples`` at ``input_rate``, the reach of the two resampling filters included."""
+        return _rate_latency(self.input_rate, self.sample_rate, self.latency_samples)
+
+    @property
     def received(self) -> int:
-        return self._received
+        """Samples pushed so far, at ``input_rate``."""
+        return self._received if self._rs_in is None else self._rs_in.received
 
     @property
     def emitted(self) -> int:
-        return self._emitted
+        """Samples returned so far, at ``input_rate``."""
+        return self._emitted if self._rs_out is None else self._rs_out.emitted
 
     def reset(self):
         """Forget the running stream: the object is ready for a new one."""
+        if self._rs_in is not None:
+            self._rs_in.reset()
+            self._rs_out.reset()
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().adn_stream_reset(self._state.data_ptr(), self._state.numel(), self.n_streams, *self._plan,
                                                     self.max_steps, _stream(self.device)), "adn_stream_reset")
@@ -213,16 +261,25 @@ class StreamDenoiser:
             raise ValueError(f"StreamDenoiser.push: audio must be (m,) for one stream or (n_streams, m) = ({self.n_streams}, m)")
         return x
 
+    def _cat(self, outs) -> torch.Tensor:
+        return torch.cat(outs, dim=1) if outs else torch.empty((self.n_streams, 0), dtype=torch.float32, device=self.device)
+
     def _result(self, outs):
-        out = torch.cat(outs, dim=1) if outs else torch.empty((self.n_streams, 0), dtype=torch.float32, device=self.device)
+        out = self._cat(outs)
         return out.cpu().numpy() if self._numpy else out
 
     def push(self, block):
-        """``block``: the next ``m >= 0`` samples of every stream at ``sample_rate`` (no rate conversion inside a stream), ``(m,)`` for
-        one stream or ``(n_streams, m)``, float32.  Returns the samples that have become final, ``(n_streams, emitted(received) -
-        emitted(before))`` -- zero columns while no step completes; numpy in -> numpy out, a tensor on the ROCm device in -> a
-        tensor there out.  Everything between the input copy and the output copy runs on the device on the current stream."""
+        """``block``: the next ``m >= 0`` samples of every stream at ``input_rate`` (``sample_rate`` unless given), ``(m,)`` for
+        one stream or ``(n_streams, m)``, float32.  Returns the samples that have become final, at the same rate, ``(n_streams,
+        emitted(received) - emitted(before))`` (``stream_plan``; ``stream_rate_plan`` with an ``input_rate``) -- zero columns while no
+        step completes; numpy in -> numpy out, a tensor on the ROCm device in -> a tensor there out.  Everything between the input copy and the output copy runs on the device on the current stream."""
         x = self._to_device(block)
+        if self._rs_in is None:
+            return self._result(self._push_steps(x))
+        return self._result([self._rs_out.push(self._cat(self._push_steps(self._rs_in.push(x))))])
+
+    def _push_steps(self, x: torch.Tensor):
+        """``x`` (n_streams, m) at the working rate on the device -> the list of tensors the completed steps returned."""
         m, pos, outs = x.shape[1], 0, []
         if self._received + m >= 1 << 30:
             raise ValueError("StreamDenoiser.push: a stream holds fewer than 2^30 samples; flush() it before")
@@ -239,22 +296,35 @@ class StreamDenoiser:
                 break
         self._received += m
         self._emitted = stream_plan(self._received, *self._plan)[1]
-        return self._result(outs)
+        return outs
 
     def flush(self):
         """The stream has ended: runs the remaining steps (frames that reach past the end zero padded) and returns the rest, so that
         the stream has produced exactly ``received`` samples, in the kind (numpy / tensor) of the last ``push``.  The object is then
-        ready for a new stream."""
+        ready for a new stream.  With an ``input_rate`` the three stages end in order -- the resampler in, the steps, the resampler
+        out -- and the result is cut to the input's length (``ceil(ceil(L up / down) down / up) >= L``)."""
+        if self._rs_in is None or self._rs_in.received == 0:
+            out = self._result(self._flush_steps())
+            self.reset()
+            return out
+        length, before = self._rs_in.received, self._rs_out.emitted
+        outs = self._push_steps(self._rs_in.flush())
+        out = self._cat([self._rs_out.push(self._cat(outs + self._flush_steps())), self._rs_out.flush()])
+        assert before <= length <= before + out.shape[1], (before, out.shape, length)
+        out = self._result([out[:, :length - before]])
+        self.reset()
+        return out
+
+    def _flush_steps(self):
+        """The remaining steps of the stream at the working rate -> the list of tensors they returned."""
         length, outs = self._received, []
         if length:
             n_frames = 1 + length // self.hop_length
             k = -(-n_frames // self.block_frames)
             while self._done < k:
                 outs.append(self._run(min(self.max_steps, k - self._done), length))
-        out = self._result(outs)
-        assert self._emitted + out.shape[1] == length, (self._emitted, out.shape, length)
-        self.reset()
-        return out
+        assert self._emitted + sum(o.shape[1] for o in outs) == length, (self._emitted, length)
+        return outs
 
 
 def main(argv=None) -> int:
@@ -268,7 +338,9 @@ def main(argv=None) -> int:
     ap.add_argument("--model", required=True, help="checkpoint: the state_dict of UNet(1, 1) (reference train.py:142)")
     ap.add_argument("src", metavar="IN", help="the wav file to read")
     ap.add_argument("dst", metavar="OUT", help="the wav file to write")
-    ap.add_argument("--chunk", type=int, default=1024, help="samples per push at the working rate")
+    ap.add_argument("--chunk", type=int, default=1024, help="samples per push at the working rate (with --live: at the file's rate)")
+    ap.add_argument("--live", action="store_true",
+                    help="push the file at its own rate, as a live feed arrives: the rate is converted inside the stream")
     ap.add_argument("--window", type=int, default=192)
     ap.add_argument("--block", type=int, default=16)
     ap.add_argument("--lookahead", type=int, default=0)
@@ -280,20 +352,21 @@ def main(argv=None) -> int:
     audio, rate = read_wav(args.src, mono=False)             # (L, channels): every channel is a stream
     x = torch.from_numpy(np.ascontiguousarray(audio.T, dtype=np.float32)).to(dev)
     sd = StreamDenoiser(_load_model(args.model, args.dtype, dev), n_streams=x.shape[0], window_frames=args.window,
-                        block_frames=args.block, lookahead_frames=args.lookahead)
+                        block_frames=args.block, lookahead_frames=args.lookahead, input_rate=rate if args.live else None)
     length = x.shape[1]
-    if rate != sd.sample_rate:                               # the stream itself has no resampler: the file is converted as a whole
+    if rate != sd.input_rate:                                # not --live: the file is converted as a whole, before and after
         x = _resample_device(x, rate, sd.sample_rate)
     outs = [sd.push(x[:, i:i + args.chunk]) for i in range(0, x.shape[1], args.chunk)]
     outs.append(sd.flush())
     out = torch.cat(outs, dim=1)
-    if rate != sd.sample_rate:
+    if rate != sd.input_rate:
         up = _resample_device(out, sd.sample_rate, rate)
         out = torch.zeros((x.shape[0], length), dtype=torch.float32, device=dev)
         n = min(length, up.shape[1])
         out[:, :n] = up[:, :n]
     write_wav(args.dst, np.ascontiguousarray(out.cpu().numpy().T), rate)
-    print(f"{args.src} -> {args.dst}: {length} samples at {rate} Hz in pushes of {args.chunk}, latency {sd.latency_samples} samples")
+    print(f"{args.src} -> {args.dst}: {length} samples at {rate} Hz in pushes of {args.chunk}"
+          f"{' at its own rate' if args.live else ''}, latency {sd.latency_input_samples if args.live else sd.latency_samples} samples")
     return 0
 
 

@@ -16,7 +16,8 @@
  *     (one-time weight upload / free), adn_prepare, and the FIRST call per (device, n_fft) of an STFT-family entry point
  *     (adn_stft_mag, adn_stft_mag_fit, adn_stft_complex, adn_istft, adn_griffin_lim, adn_denoise_resynth, adn_stream_analyze, adn_stream_emit) or per device of adn_perceptual_loss / adn_perceptual_loss_backward, which
  *     builds a few KB of constant tables (window, twiddles, mel filters) with a blocking upload -- unless adn_prepare did so
- *     before; and the FIRST adn_resample per (device, rate pair), which builds its coefficient table (adn_resample_prepare).  Such a cold call on a stream that is being captured enqueues nothing and returns ADN_ERR_INVALID (never a HIP
+ *     before; and the FIRST adn_resample or adn_resample_stream per (device, rate pair), which builds its coefficient table
+ *     (adn_resample_prepare builds both).  Such a cold call on a stream that is being captured enqueues nothing and returns ADN_ERR_INVALID (never a HIP
  *     error): call adn_prepare(device, n_fft) before capturing.  adn_unet_forward never blocks or allocates.
  *   - ownership: the caller owns every buffer it passes (x, y, audio, out, workspace); a handle owns only
  *     its packed (BatchNorm-folded, re-laid-out) weights.
@@ -32,7 +33,7 @@
 
 #include <stddef.h>
 
-/* The 45 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 48 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -196,8 +197,8 @@ ADN_API int adn_perceptual_loss_backward(const float *pred, const float *target,
  * fp32, one output per lane in a fixed order: no atomics, two calls are bit-identical and a clip's result does not depend on the
  * batch it is in.  Pass band (44.1 / 48 kHz -> 8 kHz): |gain - 1| < 1e-5 up to 3 kHz; at and above the new Nyquist < -110 dB.
  * Limits: rates >= 1, max(up, down) <= 4096, length >= 1, M < 2^31 (ADN_ERR_INVALID otherwise).
- * audio: device (n_clips, length) fp32; out: device (n_clips, M) fp32, may not alias audio.  adn_resample_prepare builds the table
- * of a rate pair on `device` ahead of time (synchronous, idempotent, thread-safe); a cold adn_resample on a stream that is being
+ * audio: device (n_clips, length) fp32; out: device (n_clips, M) fp32, may not alias audio.  adn_resample_prepare builds the tables
+ * of a rate pair (adn_resample's and adn_resample_stream's) on `device` ahead of time (synchronous, idempotent, thread-safe); a cold adn_resample on a stream that is being
  * captured enqueues nothing and returns ADN_ERR_INVALID. */
 ADN_API int adn_resample_length(long length, int src_rate, int dst_rate, long *out_length);
 ADN_API int adn_resample_prepare(int device, int src_rate, int dst_rate);
@@ -364,6 +365,40 @@ ADN_API int adn_stream_analyze(void *state, size_t state_bytes, const float *aud
 ADN_API int adn_stream_emit(void *state, size_t state_bytes, const float *y, int n_streams, long first_step, int n_steps,
                             long final_length, int n_fft, int hop, int window, int block, int lookahead, int max_steps,
                             float *audio_out, long out_stride, void *stream);
+
+/* ---- resample stream: adn_resample for audio that is still arriving ----------------------------------------------------------------
+ * The resampler definition above (up, down, q, half = 32 q, the taps h, y[m] = sum_i x[i] h[m down - i up] with zero extension)
+ * with a finality rule added (float64 restatement: tests/stream_resample_ref.py).  For a stream that has received n input samples:
+ *   Running: output m is final once every input it reads has arrived, m down + half < n up:
+ *     emitted(n) = 0 if n up <= half, else floor((n up - half - 1) / down) + 1.
+ *   Ended at length L: emitted = ceil(L up / down); inputs from L on are zero, exactly as in adn_resample.
+ *   Carried samples: at most H = 2 floor(half / up) + ceil(down / up) + 1 input samples have to survive a call.
+ *   Latency: n - emitted(n) down / up <= half / up for every n: latency = ceil(half / up) input samples, 4 ms at every audio rate pair.
+ *   Equal rates: a copy, no state read or written (its size is 0, the pointer may be NULL), emitted(n) = n, H = latency = 0.
+ * Arithmetic: one output per lane, acc = 0, then acc = fmaf(x[i], h32, acc) over the output's own window in ascending i, with the
+ * fp32 taps adn_resample uses.  That is the chain adn_resample runs (its further steps carry zero coefficients or zero samples
+ * and leave a finite accumulator unchanged): the outputs of a stream are, bit for bit, adn_resample's of the finished signal,
+ * however it was cut into calls; a stream's result does not depend on its neighbours in the batch.  No atomics, no workspace.
+ *
+ * The library keeps no per-stream host state: everything a call needs follows from its arguments and the caller-owned, opaque,
+ * 8-byte-aligned `state` (adn_resample_stream_state_bytes: two slots of H samples per stream).  One call = the next n_new samples of
+ * every one of the n_streams streams (`audio`, audio_stride floats apart), one kernel launch.  call_index is the number of earlier
+ * calls of this stream and received_before the samples they brought; call 0 reads no state, so a new stream needs no reset.
+ * final = 1 marks the last call (n_new may then be 0, and audio NULL).  The call writes, per stream (out_stride floats apart), the
+ * outputs [emitted(received_before), emitted(received_before + n_new, final)); `out` may be NULL when that range is empty.
+ * Limits (ADN_ERR_INVALID before any HIP call): the rate limits of adn_resample; H <= 16384 (192 kHz -> 8 kHz: 1561; excluded are
+ * ratios such as 4096:1, whose single output reads 262 145 inputs); n_streams >= 1; n_new >= 1 unless final; call_index >= 0 and
+ * call_index == 0 exactly when received_before == 0; input and output positions < 2^31; null pointers; strides below the samples
+ * of a call when n_streams > 1.  ADN_ERR_WORKSPACE: state_bytes below adn_resample_stream_state_bytes.
+ * adn_resample_prepare builds this entry point's coefficient table too; a cold call on a capturing stream enqueues nothing and
+ * returns ADN_ERR_INVALID, a warm call only enqueues.  adn_resample_stream_plan (emitted for `received` samples, H and the latency;
+ * any output pointer may be NULL) and adn_resample_stream_state_bytes are host-only (no device needed). */
+ADN_API int adn_resample_stream_plan(int src_rate, int dst_rate, long received, int final, long *emitted, long *history,
+                                     long *latency);
+ADN_API int adn_resample_stream_state_bytes(int n_streams, int src_rate, int dst_rate, size_t *bytes);
+ADN_API int adn_resample_stream(void *state, size_t state_bytes, const float *audio, long audio_stride, int n_streams,
+                                long call_index, long received_before, long n_new, int final, int src_rate, int dst_rate,
+                                float *out, long out_stride, void *stream);
 
 /* ---- environment switches -------------------------------------------------------------------------------------------------
  * Read ONCE, when a U-Net handle is created (never per call).  None is needed in production: the defaults are the measured best
