@@ -127,6 +127,9 @@ struct ConvArgs {
     // 64-channel tensor Conv2d(1->64)+BN+ReLU (model.py:11-13 via :56) is computed on the fly from firstw [9 taps][64] and
     // firstb [64] (BatchNorm folded) instead of being copied; nullptr = ordinary activation source
     const float *firstw, *firstb;
+    // WINO_GEMM only (the matrix stage of the three-stage F(4x4,3x3) form, below): the GEMM's rows = 4x4 output tiles of the
+    // whole batch; 0 for every other kind
+    long rows;
 };
 
 // wino4_conv_f32's pair mode: a workgroup tile holds the same 32 rows of TWO neighbouring clips side by side (images at most 16
@@ -205,7 +208,9 @@ inline int conv16_ksplit(long nwg, int nchunk, size_t out_floats)
 // the network's last layer) and stores one float per pixel into plane `ct` of ConvArgs::dot_out; launch_dot_finish adds
 // the planes and the bias.  Saves the 64-channel tensor's HBM round trip (write + read of N*H*W*64 floats).
 // fp16 kernel (conv_dma, 64 couts per workgroup): the dot is complete inside the workgroup, dot_out is the final output.
-enum ConvKind { CONV3X3_RELU = 0, CONV3X3_RELU_POOL = 1, CONVT2X2 = 2, CONV3X3_RELU_DOT = 3 };
+// WINO_GEMM (conv_dma, fp32 split-bf16 form only): one of the 36 transform-domain GEMMs of the three-stage F(4x4,3x3) form --
+// "clip" = position, the "image" = the rows of V 16 to a line, raw sums stored in the same layout (launch_wino_gemm).
+enum ConvKind { CONV3X3_RELU = 0, CONV3X3_RELU_POOL = 1, CONVT2X2 = 2, CONV3X3_RELU_DOT = 3, WINO_GEMM = 4 };
 
 // Tile geometry chosen per layer (must match the weight packing).
 struct ConvGeom {
@@ -242,6 +247,25 @@ bool wino4_applicable(ConvKind kind, const ConvArgs &a, bool force);
 // tiles x 32 couts over a.N / H / W / Cout, two clips per tile in pair mode
 long wino4_workgroups(const ConvArgs &a);
 hipError_t launch_wino4_conv(ConvKind kind, const ConvArgs &a, hipStream_t st);
+
+// Three-stage F(4x4,3x3) for the deep fp32 3x3 layers (wino3s_kernels.hip + conv_dma<..., WINO_GEMM> in conv_kernels.hip): the
+// products of wino4_conv_f32 on the bf16 matrix cores.  Stage 1 writes V = B^T d B of every 4x4 output tile (tiles numbered over the
+// whole batch = GEMM rows) as V[pos 0..35][Cin/8][row][8]; stage 2 is 36 GEMMs M_pos = V_pos U_pos in the three-term bf16 split of
+// the transposed convolutions (128 x 128 tiles, six products per term pair, fp32 sums) -> M[pos][Cout/8][row][8]; stage 3 applies
+// A^T M A + bias + ReLU (+ 2x2 max-pool) and writes the C8 output.  V and M are 2.25x the layer's input / output: the form pays only
+// where images are small and channels many (levels 3 and 4).  U: pack_wino4_split (unet.hip).
+struct Wino3sGeom {
+    int tilesY, tilesX;        // 4x4 output tiles of one image
+    long rows;                 // N * tilesY * tilesX
+    size_t v_bytes, m_bytes;   // of V and M
+    long gemm_grid;            // workgroups of stage 2
+};
+bool wino3s_applicable(ConvKind kind, const ConvArgs &a);
+Wino3sGeom wino3s_geom(const ConvArgs &a);
+// a.wpk = the U planes; V, M: wino3s_geom's bytes, 16-byte aligned, disjoint from the layer's tensors
+hipError_t launch_wino3s_conv(ConvKind kind, const ConvArgs &a, float *V, float *M, hipStream_t st);
+// stage 2 alone (conv_kernels.hip)
+hipError_t launch_wino_gemm(const float *V, const void *U, float *M, long rows, int Cin, int Cout, hipStream_t st);
 
 // fp16 3x3 layers on v_mfma_f32_16x16x32_f16 (conv16_kernels.hip): 32 x 16-pixel tiles x 64 couts, 32-channel chunks (ConvArgs::
 // nchunk0 / nchunk count those), persistent workgroups, weights from ConvArgs::wpk in pack_conv16 layout; `resident`: the whole

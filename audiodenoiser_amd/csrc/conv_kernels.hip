@@ -357,7 +357,8 @@ __device__ __forceinline__ void conv_epilogue_staged(const ConvArgs &p, f32x16 (
     const int wm = wave / WN, wn = wave % WN;
     const int hh = lane >> 5, l31 = lane & 31;
     T *stage = reinterpret_cast<T *>(smem);
-    static_assert(HALVES == 1 || (EPI == CONVT2X2 && HALVES == 2 && WM == 2 && TH % 2 == 0), "two-half staging: convT, WM = 2");
+    static_assert(HALVES == 1 || ((EPI == CONVT2X2 || EPI == WINO_GEMM) && HALVES == 2 && WM == 2 && TH % 2 == 0),
+                  "two-half staging: convT / Winograd GEMM, WM = 2");
 
 #pragma unroll
     for (int hf = 0; hf < HALVES; ++hf) {
@@ -375,7 +376,7 @@ __device__ __forceinline__ void conv_epilogue_staged(const ConvArgs &p, f32x16 (
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 v[r] = acc[i][j][r] + bv;
-                if (EPI != CONVT2X2) v[r] = relu_nan(v[r]);
+                if (EPI != CONVT2X2 && EPI != WINO_GEMM) v[r] = relu_nan(v[r]);
             }
             if constexpr (sizeof(T) == 4) {
 #pragma unroll
@@ -422,6 +423,22 @@ __device__ __forceinline__ void conv_epilogue_staged(const ConvArgs &p, f32x16 (
             const piece_t val = *reinterpret_cast<const piece_t *>(stage + (py * TW + gxl) * RS + dj * 64 + b8 * BE + half * EPP);
             if (gy < p.H && gx < p.W)
                 *reinterpret_cast<piece_t *>(ob + b8 * bstr + ((size_t)(2 * gy + di) * Wo + 2 * gx + dj) * BE + half * EPP) = val;
+        }
+        if (HALVES > 1 && hf + 1 < HALVES) __syncthreads();                      // the stores of this half have read the tile
+    } else if constexpr (EPI == WINO_GEMM) {
+        // Raw sums M[position n][cout block][row][8]: lane = (row, half block), so a wave stores 32 rows x 32 bytes = one 1 KB run
+        // of a cout block.  (tilesX = 1: the tile's pixels are the GEMM rows ty * TH * TW ...)
+        static_assert(sizeof(T) == 4 && BN % 8 == 0, "Winograd GEMM: fp32");
+        constexpr int HPIX = NPIX / HALVES;
+        T *ob = outp + (size_t)n * p.rows * p.Cout + (size_t)ct * (BN / 8) * p.rows * 8;
+#pragma unroll
+        for (int it = 0; it < HPIX * PPR / NT; ++it) {
+            const int id = it * NT + tid;
+            const int b8 = id / (2 * HPIX), rem = id - b8 * (2 * HPIX), pix = rem >> 1, half = rem & 1;
+            const long row = (long)ty * NPIX + hf * HPIX + pix;
+            if (row < p.rows)
+                *reinterpret_cast<piece_t *>(ob + ((size_t)b8 * p.rows + row) * 8 + half * 4) =
+                    *reinterpret_cast<const piece_t *>(stage + pix * RS + b8 * 8 + half * 4);
         }
         if (HALVES > 1 && hf + 1 < HALVES) __syncthreads();                      // the stores of this half have read the tile
     } else if constexpr (EPI == CONV3X3_RELU_DOT) {
@@ -543,6 +560,10 @@ __global__ __launch_bounds__(64 * WM * WN, WPE) void conv_dma(const ConvArgs p)
     using C = DmaCfg<T, TH, BN, WM, WN, TAPS, KG, SPLIT>;
     static_assert(!KSPLIT || EPI == CONVT2X2 || (sizeof(T) == 2 && EPI == CONV3X3_RELU), "K split: transposed convolutions, fp16 3x3 layers");
     static_assert(!SPLIT || (sizeof(T) == 4 && KG == 2 && TAPS == 1), "SPLIT: fp32 storage, one 16-channel chunk (two fp32 k-groups), 1 tap");
+    // WINO_GEMM: "clip" n = transform-domain position, the image = p.rows GEMM rows (16 to a line, the last line partial), the
+    // weights of position n and column tile ct are slab n * nct + ct, no bias
+    constexpr bool GEMM = EPI == WINO_GEMM;
+    static_assert(!GEMM || (SPLIT && !KSPLIT && TW == 16), "Winograd GEMM stage: split-bf16 form");
     constexpr int NT = C::NT, EPV = Elem<T>::EPV, HALO = C::HALO, PW = C::PW;
     static_assert(2 * EPV == ACT_BLOCK<T>, "one k-group = one channel block of the activation layout");   // KG blocks per chunk
     constexpr int PSLOT = C::PSLOT, RSLOT = C::RSLOT, A_SLOTS = C::A_SLOTS, SLOTS = C::SLOTS, NPIECE = C::NPIECE;
@@ -588,11 +609,12 @@ __global__ __launch_bounds__(64 * WM * WN, WPE) void conv_dma(const ConvArgs p)
     // descriptors: ONE K-chunk (KG channel blocks, `cstr` bytes: < 4 GB for every image the launcher admits) of the current source
     // image of clip n -- its 64-bit base walks the image chunk by chunk, so an image may exceed the 4 GB one descriptor spans --
     // and the weight slabs of this column tile
-    auto src_base = [&](const ConvSrc &s) { return reinterpret_cast<const char *>(static_cast<const T *>(s.ptr) + (size_t)n * s.H * s.W * s.C); };
+    auto src_hw = [&](const ConvSrc &s) { return GEMM ? (size_t)p.rows : (size_t)s.H * s.W; };     // pixels of one source image
+    auto src_base = [&](const ConvSrc &s) { return reinterpret_cast<const char *>(static_cast<const T *>(s.ptr) + (size_t)n * src_hw(s) * s.C); };
     const char *hptr = src_base(p.s0);                  // the next chunk's channel blocks
-    const __amdgpu_buffer_rsrc_t wrs = dma_rsrc(static_cast<const float *>(p.wpk) + (size_t)ct * p.nchunk * B_DW,
+    const __amdgpu_buffer_rsrc_t wrs = dma_rsrc(static_cast<const float *>(p.wpk) + (size_t)(GEMM ? n * p.nct + ct : ct) * p.nchunk * B_DW,
                                                 (unsigned)((size_t)p.nchunk * B_DW * 4));
-    unsigned cstr = (unsigned)((size_t)KG * p.s0.H * p.s0.W * ACT_BLOCK<T> * sizeof(T));
+    unsigned cstr = (unsigned)((size_t)KG * src_hw(p.s0) * ACT_BLOCK<T> * sizeof(T));
     unsigned wsoff = 0;                                 // byte offset of the next chunk's slab
     const int c0 = KSPLIT ? ksp * nloc : 0;            // first chunk of this workgroup's slice
     bool in2 = false;                                   // the slice starts inside the second source (virtual concat)
@@ -634,8 +656,8 @@ __global__ __launch_bounds__(64 * WM * WN, WPE) void conv_dma(const ConvArgs p)
             const int pix = k / PSLOT, q = k - pix * PSLOT;
             const bool data = s < C::A_USED && pix < PW && q < C::KQ;
             const int y0 = gy0 + row - src.offY, x0 = gx0 + pix - src.offX;
-            hcur[r] = (data && y0 >= 0 && y0 < src.H && x0 >= 0 && x0 < src.W)
-                          ? (unsigned)act_off<T>(src.C, (long)src.H * src.W, y0 * src.W + x0, q * EPV) * (unsigned)sizeof(T) : ADN_DMA_OOB;
+            hcur[r] = (data && y0 >= 0 && y0 < src.H && x0 >= 0 && x0 < src.W && (!GEMM || (long)y0 * src.W + x0 < p.rows))
+                          ? (unsigned)act_off<T>(src.C, (long)src_hw(src), y0 * src.W + x0, q * EPV) * (unsigned)sizeof(T) : ADN_DMA_OOB;
         }
     };
     if (in2) plan(p.s1);
@@ -656,7 +678,7 @@ __global__ __launch_bounds__(64 * WM * WN, WPE) void conv_dma(const ConvArgs p)
 
     float bias_r[NB];
 #pragma unroll
-    for (int j = 0; j < NB; ++j) bias_r[j] = p.bias[ct * BN + (wn * NB + j) * 32 + l31];
+    for (int j = 0; j < NB; ++j) bias_r[j] = GEMM ? 0.f : p.bias[ct * BN + (wn * NB + j) * 32 + l31];
 
     f32x16 acc[MB][NB];
 #pragma unroll
@@ -741,7 +763,7 @@ __global__ __launch_bounds__(64 * WM * WN, WPE) void conv_dma(const ConvArgs p)
     // too -- a lane's direct stores would be 4 bytes into 32-byte segments, the staged form writes 1 KB runs.
     if constexpr (KSPLIT && EPI != CONVT2X2) {
         conv_epilogue_raw<TH, BN, WM, WN>(p, acc, lane, wave, ct, n + ksp * p.N, ty, tx);
-    } else if constexpr (sizeof(T) == 2 || EPI == CONVT2X2) {
+    } else if constexpr (sizeof(T) == 2 || EPI == CONVT2X2 || GEMM) {
         constexpr size_t tile = (size_t)TH * TW * (BN + 16 / sizeof(T)) * sizeof(T);
         constexpr int HALVES = tile <= C::LDS_BYTES ? 1 : 2;
         static_assert(tile / HALVES <= C::LDS_BYTES, "staging tile (or half of it) must fit the two images");
@@ -1081,6 +1103,32 @@ long conv_mfma_tiles(ConvKind kind, bool f16, ConvArgs &a)
 hipError_t launch_conv_mfma(ConvKind kind, const ConvArgs &a, bool f16, hipStream_t st)
 {
     return f16 ? launch_conv_mfma_t<_Float16>(kind, a, st) : launch_conv_mfma_t<float>(kind, a, st);
+}
+
+// Stage 2 of the three-stage F(4x4,3x3) form: M[pos][Cout/8][row][8] = sum over cin of V[pos][Cin/8][row][8] * U_pos, 36 positions
+// as the "clips" of one conv_dma<..., SPLIT> launch with 128-row x 128-column tiles.  Workgroup ids run column tile first, then
+// row tile, then position: the workgroups that share an XCD (xcd_remap) work on neighbouring row tiles of one position.
+hipError_t launch_wino_gemm(const float *V, const void *U, float *M, long rows, int Cin, int Cout, hipStream_t st)
+{
+    // (a chunk of V -- two channel blocks of all rows -- must stay inside the 4 GB of a buffer descriptor)
+    if (!V || !U || !M || rows < 1 || rows >= (1L << 25) || Cin < 16 || (Cin & 15) || Cout < 128 || (Cout & 127)) return hipErrorInvalidValue;
+    ConvArgs a{};
+    a.N = 36;
+    a.W = TW;
+    a.H = (int)((rows + TW - 1) / TW);
+    a.rows = rows;
+    a.s0 = ConvSrc{V, a.H, a.W, Cin, 0, 0};
+    a.s1 = ConvSrc{V, 0, 0, 0, 0, 0};
+    a.nchunk0 = a.nchunk = Cin / 16;
+    a.wpk = U;
+    a.out = M;
+    a.Cout = Cout;
+    a.ksplit = 1;
+    a.split = 1;
+    a.tilesY = (a.H + 7) / 8;
+    a.tilesX = 1;
+    a.nct = Cout / 128;
+    return launch_dma_cfg<float, 8, 128, 2, 2, 1, CONVT_KG, WINO_GEMM, 3, 1>(a, st);
 }
 
 hipError_t launch_conv_reduce_f16(ConvKind kind, const float *partial, const float *bias, void *out, void *pool, int ksplit, int N,

@@ -59,6 +59,7 @@ static_assert(1 + N_LAYERS + 1 == ADN_N_LAUNCHES, "layer table does not match th
 struct LayerWeights {
     size_t w_off, b_off;   // the form the path's own kernel reads, and the bias per GEMM column
     size_t w4_off;         // 3x3, fp32 Winograd path: F(4x4,3x3) pack of the same weights
+    size_t w3_off;         // 3x3 at levels 3 and 4 from 512 input channels on, fp32 Winograd path: U as three bf16 planes (pack_wino4_split)
     size_t w16_off;        // fp16 path: pack_conv16 / pack_convt16 form (16x16x32 MFMA kernels)
     size_t braw_off;       // transposed convolution: the Cout biases as they are (convt16_f16; the K-split reduce launch)
 };
@@ -109,6 +110,13 @@ struct adn_unet {
     // workgroups, is level at 160 and loses by 25-50 % from 240 on; the 64-channel full-resolution layers (8-chunk K loops,
     // where the prologue and epilogue of the 32x32-tile kernel weigh most, and down1 can take the first convolution in) switch at 512
     long auto_grid = 192, auto_grid64 = 512;
+    // Deep fp32 3x3 layers (levels 3 and 4) as three launches -- input transform, 36 split-bf16 GEMMs, output transform
+    // (wino3s_kernels.hip): 0 = never, 1 = where its V and M fit the workspace and the GEMM launch is at least `gemm_grid`
+    // workgroups, or the handle is pinned (choose_conv3), 2 = wherever they fit (tests).  ADN_WINO_GEMM when the handle is created.
+    // gemm_grid: two rounds of three workgroups per CU (batch 11 of 513x256 at level 3, 21 at level 4).  Measured per layer at batch
+    // 4 ... 32 (profiles/wino_gemm_ab.md) the form also wins from 576 workgroups on; the whole suite has only been run with 1536.
+    int wino_gemm = 1;
+    long gemm_grid = 1536;
 };
 
 namespace {
@@ -296,6 +304,48 @@ inline float bf16_to_float(uint16_t b)
     std::memcpy(&f, &u, 4);
     return f;
 }
+// x = hi + mid + lo in bf16, round-to-nearest each; a finite x in the top 0.2 % of fp32's range rounds to a bf16 infinity: largest
+// finite bf16 instead (split3_bf16 in adn_internal.h clamps the activations the same way); the residuals stay finite
+inline void split3_host(float v, uint16_t (&t)[3])
+{
+    uint16_t hi = bf16_rne(v);
+    if ((hi & 0x7fffu) == 0x7f80u && std::isfinite(v)) hi = (uint16_t)((hi & 0x8000u) | 0x7f7fu);
+    const float r1 = v - bf16_to_float(hi);
+    const uint16_t mid = bf16_rne(r1);
+    const float r2 = r1 - bf16_to_float(mid);
+    t[0] = hi;
+    t[1] = mid;
+    t[2] = bf16_rne(r2);
+}
+
+// Winograd F(4x4,3x3) weights for the three-stage form (wino3s_kernels.hip): U = G g G^T exactly as pack_wino4_3x3 rounds it to
+// fp32, then split into three bf16 planes and packed per transform-domain position as the GEMM slabs of conv_dma<..., SPLIT,
+// WINO_GEMM>: [pos = 6x + v][column tile of 128 couts][chunk of 16 channels][plane][half h][cout n][8 bf16], element kk of
+// half h = input channel chunk*16 + 8h + kk.
+void pack_wino4_split(const float *w /*(Cout,Cin,3,3)*/, const std::vector<float> &scale, int Cin, int Cout, uint16_t *dst)
+{
+    static const double G[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
+                                   {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
+    const int nct = Cout / 128, nchunk = Cin / 16;
+    for (int co = 0; co < Cout; ++co)
+        for (int ci = 0; ci < Cin; ++ci) {
+            const float *g = w + ((size_t)co * Cin + ci) * 9;
+            double tmp[6][3];
+            for (int x = 0; x < 6; ++x)
+                for (int b = 0; b < 3; ++b)
+                    tmp[x][b] = G[x][0] * g[0 * 3 + b] + G[x][1] * g[1 * 3 + b] + G[x][2] * g[2 * 3 + b];
+            const int ct = co / 128, n = co % 128, ch = ci / 16, hh = (ci % 16) / 8, kk = ci % 8;
+            for (int x = 0; x < 6; ++x)
+                for (int v = 0; v < 6; ++v) {
+                    const float U = (float)((tmp[x][0] * G[v][0] + tmp[x][1] * G[v][1] + tmp[x][2] * G[v][2]) * (double)scale[co]);
+                    uint16_t t[3];
+                    split3_host(U, t);
+                    uint16_t *slab = dst + (((size_t)(6 * x + v) * nct + ct) * nchunk + ch) * (3 * 2 * 128 * 8);
+                    for (int plane = 0; plane < 3; ++plane) slab[((plane * 2 + hh) * 128 + n) * 8 + kk] = t[plane];
+                }
+        }
+}
+
 void pack_convt_split(const float *w /*(Cin,Cout,2,2)*/, int Cin, int Cout, uint16_t *dst)
 {
     const int BN = 128, KC = 16;
@@ -310,15 +360,9 @@ void pack_convt_split(const float *w /*(Cin,Cout,2,2)*/, int Cin, int Cout, uint
                         convt_column_host(ct * BN + n, Cout, ij, co);
                         for (int kk = 0; kk < 8; ++kk) {
                             const int ci = ch * KC + 8 * h + kk;
-                            const float v = w[((size_t)ci * Cout + co) * 4 + ij];
-                            uint16_t hi = bf16_rne(v);
-                            // a finite weight in the top 0.2 % of fp32's range rounds to a bf16 infinity: largest finite bf16 instead
-                            // (split3_bf16 in conv_kernels.hip clamps the activations the same way); the residuals stay finite
-                            if ((hi & 0x7fffu) == 0x7f80u && std::isfinite(v)) hi = (uint16_t)((hi & 0x8000u) | 0x7f7fu);
-                            const float r1 = v - bf16_to_float(hi);
-                            const uint16_t mid = bf16_rne(r1);
-                            const float r2 = r1 - bf16_to_float(mid);
-                            dst[o++] = plane == 0 ? hi : plane == 1 ? mid : bf16_rne(r2);
+                            uint16_t t[3];
+                            split3_host(w[((size_t)ci * Cout + co) * 4 + ij], t);
+                            dst[o++] = t[plane];
                         }
                     }
 }
@@ -448,7 +492,16 @@ enum Conv3Kernel {
     DIRECT,    // conv_mfma<float> / conv_dma<_Float16> (conv_kernels.hip)
     CONV16,    // fp16: conv16_f16
     WINO2,     // fp32: F(2x2,3x3), wino_conv_dma_f32
-    WINO4      // fp32: F(4x4,3x3), wino4_conv_f32
+    WINO4,     // fp32: F(4x4,3x3), wino4_conv_f32
+    WINO3S     // fp32, levels 3 and 4: F(4x4,3x3) in three launches with the products on the bf16 matrix cores (wino3s_kernels.hip)
+};
+// What the three-stage form needs beside the layer's arguments: its U planes and room for V and M.  The ping-pong buffers are
+// sized for the 64-channel full-resolution tensors; at levels 3 and 4 a tensor fills at most an eighth of one, so V lives behind
+// the layer's tensors in the first buffer and M in the second (forward_impl).  U == nullptr: the layer has no such form.
+struct WinoScratch {
+    const void *U = nullptr;
+    float *V = nullptr, *M = nullptr;
+    size_t v_bytes = 0, m_bytes = 0;
 };
 struct Conv3Choice {
     Conv3Kernel kernel;
@@ -461,7 +514,8 @@ struct Conv3Choice {
 // entered yet -- the fused forms add pointers, never geometry, so applicability is asked about the plain layer).
 // first: down1's second conv of a one-plane network, which may take Conv2d(1 -> 64) in;  tail: the network's last 3x3 layer where
 // the 1x1 output convolution may be fused behind it (one class, no block outputs exported: the up4 tap IS the tensor between them).
-Conv3Choice choose_conv3(const adn_unet *h, adn::ConvKind kind, const adn::ConvArgs &a, bool first = false, bool tail = false)
+Conv3Choice choose_conv3(const adn_unet *h, adn::ConvKind kind, const adn::ConvArgs &a, bool first = false, bool tail = false,
+                         const WinoScratch &sc = WinoScratch())
 {
     Conv3Choice c{DIRECT, 1, false, false};
     if (h->f16) {
@@ -511,6 +565,19 @@ Conv3Choice choose_conv3(const adn_unet *h, adn::ConvKind kind, const adn::ConvA
     const bool automatic = !h->batch_invariant && !h->force_wino4;
     const long thr = a.Cout <= 64 ? h->auto_grid64 : h->auto_grid;
     const long g4 = f4_ok ? adn::wino4_workgroups(a) : 0;
+    // Three-stage form (levels 3 and 4; sc.U is there for those layers only).  Whether V and M fit is a matter of geometry alone
+    // (every term is linear in N).  A pinned handle takes it wherever it fits -- one kernel per layer whatever the batch, and the
+    // kernel a large batch runs by default --, the automatic choice where the GEMM launch fills the chip; ADN_WINO_TILE=4 keeps
+    // F(4x4,3x3) in one launch.
+    if (h->wino_gemm && sc.U && !c.fuse_out && !first && adn::wino3s_applicable(kind, a)) {
+        const adn::Wino3sGeom g3 = adn::wino3s_geom(a);
+        const bool fits = g3.v_bytes <= sc.v_bytes && g3.m_bytes <= sc.m_bytes;
+        const bool pinned = h->batch_invariant && !h->force_wino4;
+        if (fits && (h->wino_gemm == 2 || pinned || (automatic && g3.gemm_grid >= h->gemm_grid))) {
+            c.kernel = WINO3S;
+            return c;
+        }
+    }
     if (f4_ok && (!automatic || g4 >= thr)) {
         c.kernel = WINO4;
         return done();
@@ -538,10 +605,14 @@ Conv3Choice choose_conv3(const adn_unet *h, adn::ConvKind kind, const adn::ConvA
 }
 
 // Executes a choice.  `a`: the layer with the pointers of the chosen fused forms filled in (ConvArgs::firstw / dotw).
-hipError_t launch_conv3(const adn_unet *h, adn::ConvKind kind, const Conv3Choice &c, adn::ConvArgs a, float *partial, hipStream_t st)
+hipError_t launch_conv3(const adn_unet *h, adn::ConvKind kind, const Conv3Choice &c, adn::ConvArgs a, float *partial, hipStream_t st,
+                        const WinoScratch &sc = WinoScratch())
 {
     if (c.fuse_out) kind = adn::CONV3X3_RELU_DOT;
     switch (c.kernel) {
+    case WINO3S:
+        a.wpk = sc.U;
+        return adn::launch_wino3s_conv(kind, a, sc.V, sc.M, st);
     case CONV16:
         a.wpk = a.wpk4;
         a.nchunk0 = a.s0.C / 32;                         // conv16_f16 walks K in chunks of 32 channels
@@ -645,18 +716,36 @@ int forward_impl(adn_unet *h, const float *x, float *y, int N, int F, int T, voi
         return adn::launch_nhwc_to_nchw(buf, f16, taps[idx], N, p.H[d.level], p.W[d.level], d.Cout, st);
     };
     int i = 0;                                           // next layer of NET
+    // Room for V and M of the three-stage Winograd form of layer `li`: the two ping-pong buffers behind `front` bytes, the largest
+    // tensor the layer reads or writes (whichever of them live in tA / tB start at the buffers' first byte; everything in the
+    // ratio is linear in N, so the answer is the same for every batch size)
+    auto wino_scratch = [&](int li) {
+        WinoScratch sc;
+        const LayerDesc &d = NET.v[li];
+        if (f16 || !h->lw[li].w3_off) return sc;
+        const size_t full = (size_t)N * p.H[0] * p.W[0] * 64 * sizeof(float);
+        const size_t front = (size_t)N * p.H[d.level] * p.W[d.level] * std::max(std::max(d.C0, d.C1), d.Cout) * sizeof(float);
+        if (front >= full) return sc;
+        sc.U = h->dev + h->lw[li].w3_off;
+        sc.V = reinterpret_cast<float *>(static_cast<char *>(tA) + front);
+        sc.M = reinterpret_cast<float *>(static_cast<char *>(tB) + front);
+        sc.v_bytes = sc.m_bytes = full - front;
+        return sc;
+    };
 
     // ---- down path (model.py:72-79) ----
     const void *cur = tA;
     for (int l = 0; l < 4; ++l) {
         void *skip = ws + p.skip[l], *pool = ws + p.pool[l];
         if (l > 0) {
+            const WinoScratch sc = wino_scratch(i);
             const adn::ConvArgs a = conv_args(h, p, i++, ws + p.pool[l - 1], nullptr, 0, 0, tA, nullptr);
             ADN_MARK();
-            ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, a), a, part, st));
+            ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, a, false, false, sc), a, part, st, sc));
         }
+        const WinoScratch sc = wino_scratch(i);
         adn::ConvArgs a = conv_args(h, p, i++, cur, nullptr, 0, 0, skip, pool);
-        const Conv3Choice c = choose_conv3(h, adn::CONV3X3_RELU_POOL, a, l == 0 && h->in_ch == 1);
+        const Conv3Choice c = choose_conv3(h, adn::CONV3X3_RELU_POOL, a, l == 0 && h->in_ch == 1, false, sc);
         if (l == 0) {                                    // Conv2d(in_channels -> 64): its own launch, or inside the next one (its timing slot stays empty)
             ADN_MARK();
             if (c.fuse_first) {
@@ -668,17 +757,19 @@ int forward_impl(adn_unet *h, const float *x, float *y, int N, int F, int T, voi
             }
         }
         ADN_MARK();
-        ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU_POOL, c, a, part, st));
+        ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU_POOL, c, a, part, st, sc));
         ADN_HIP(export_tap(l, skip, i - 1));
     }
     // ---- bottleneck (model.py:81) ----
     {
+        const WinoScratch sa = wino_scratch(i);
         const adn::ConvArgs a = conv_args(h, p, i++, ws + p.pool[3], nullptr, 0, 0, tA, nullptr);
         ADN_MARK();
-        ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, a), a, part, st));
+        ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, a, false, false, sa), a, part, st, sa));
+        const WinoScratch sb = wino_scratch(i);
         const adn::ConvArgs b = conv_args(h, p, i++, tA, nullptr, 0, 0, tB, nullptr);
         ADN_MARK();
-        ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, b), b, part, st));
+        ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, b, false, false, sb), b, part, st, sb));
         ADN_HIP(export_tap(4, tB, i - 1));
     }
     // ---- up path (model.py:84-91): convT -> (virtual) pad + cat([skip, up]) -> DoubleConv ----
@@ -690,19 +781,21 @@ int forward_impl(adn_unet *h, const float *x, float *y, int N, int F, int T, voi
         ADN_MARK();
         ADN_HIP(launch_convt(h, TL, choose_convt(h, TL, t), t, part, st));
         // first conv of the DoubleConv reads cat([skip, x1]) virtually
+        const WinoScratch sa = wino_scratch(i);
         const adn::ConvArgs a = conv_args(h, p, i++, ws + p.skip[l], Y, 2 * t.H, 2 * t.W, X, nullptr);
         ADN_MARK();
-        ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, a), a, part, st));
+        ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, a, false, false, sa), a, part, st, sa));
+        const WinoScratch sb = wino_scratch(i);
         adn::ConvArgs b = conv_args(h, p, i++, X, nullptr, 0, 0, Y, nullptr);
         // (the fused tails finish ONE class; UNet(..., num_classes > 1) runs the 1x1 convolution class by class below)
-        last = choose_conv3(h, adn::CONV3X3_RELU, b, false, l == 0 && !taps && h->n_classes == 1);
+        last = choose_conv3(h, adn::CONV3X3_RELU, b, false, l == 0 && !taps && h->n_classes == 1, sb);
         if (last.fuse_out) {
             b.dotw = h->dev + h->out_w;
             b.dot_out = f16 ? y : static_cast<float *>(Y);          // fp16: the network output; Winograd: the two partial planes
             if (f16) b.dot_bias = h->out_b;
         }
         ADN_MARK();
-        ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU, last, b, part, st));
+        ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU, last, b, part, st, sb));
         ADN_HIP(export_tap(5 + (3 - l), Y, i - 1));
         std::swap(X, Y);
     }
@@ -768,6 +861,7 @@ void read_switches(adn_unet &h)
     if (const char *ag = std::getenv("ADN_AUTO_GRID")) h.auto_grid = std::atol(ag);      // tuning knobs of the small-grid rule
     if (const char *ag = std::getenv("ADN_AUTO_GRID64")) h.auto_grid64 = std::atol(ag);
     if (h.f16) h.convt_split = false;
+    if (const char *wg = std::getenv("ADN_WINO_GEMM")) h.wino_gemm = std::atoi(wg) == 2 ? 2 : std::atoi(wg) != 0;
     if (const char *wt = std::getenv("ADN_WINO_TILE")) {
         h.use_wino4 = std::atoi(wt) != 2;
         h.force_wino4 = std::atoi(wt) == 4;
@@ -839,6 +933,13 @@ void pack_weights(adn_unet &h, const float *const *t, std::vector<float> &host)
             if (h.use_wino4) {
                 L.w4_off = reserve((size_t)36 * Cin * Cout);
                 pack_wino4_3x3(t[ti], scale, Cin, Cout, host.data() + L.w4_off);
+                // levels 3 and 4 from 512 input channels on: the three-stage form's planes (five layers, 0.57 GB).  down4's first conv
+                // (256 -> 512) stays on F(4x4,3x3): V and M cost it what the faster products save (0.742 -> 0.718 ms at batch 64,
+                // inside the run-to-run spread; profiles/wino_gemm_ab.md)
+                if (h.wino_gemm && d.level >= 3 && Cin >= 512 && Cin % 16 == 0 && Cout % 128 == 0) {
+                    L.w3_off = reserve((size_t)36 * Cin * Cout * 3 / 2);
+                    pack_wino4_split(t[ti], scale, Cin, Cout, reinterpret_cast<uint16_t *>(host.data() + L.w3_off));
+                }
             }
         } else if (h.f16) {
             L.w_off = reserve(n16);

@@ -411,7 +411,10 @@ ADN_API int adn_resample_stream(void *state, size_t state_bytes, const float *au
  *   ADN_BATCH_INVARIANT=1    initial value of adn_unet_set_batch_invariant (above)
  *   ADN_AUTO_GRID=n, ADN_AUTO_GRID64=n   thresholds of the small-grid rule in F(4x4,3x3) workgroups (192 / 512; tools/small_grid_probe.py)
  *   ADN_CONVT_SPLIT=0        fp32 transposed convolutions on the exact-fp32 MFMA instead of the three-term bf16 split
- *   ADN_F16_CONV=32          fp16 3x3 layers on conv_dma<_Float16> (32x32x16 MFMA) instead of conv16_f16 (16x16x32)
+ *   ADN_WINO_GEMM=0 | 2      fp32 3x3 layers at the two deepest levels as input transform + 36 split-bf16 GEMMs + output transform
+ *                            (csrc/wino3s_kernels.hip): never | wherever its buffers fit the workspace (default 1: where they fit
+ *                            and the GEMM launch fills the chip, or the handle is pinned)
+ *   ADN_F16_CONV=32         fp16 3x3 layers on conv_dma<_Float16> (32x32x16 MFMA) instead of conv16_f16 (16x16x32)
  *   ADN_F16_FIRST=0          fp16: Conv2d(1 -> 64) as its own launch instead of fused into down1's second convolution
  *   ADN_F16_CONVT=dma        fp16 transposed convolutions on conv_dma<_Float16> (32x32x16 MFMA, LDS-staged stores) instead of convt16_f16
  *

@@ -17,7 +17,7 @@ import sys
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 SWITCHES = ("ADN_BATCH_INVARIANT", "ADN_WINO_TILE", "ADN_CONV_ALGO", "ADN_WINO_SPLITK", "ADN_CONVT_SPLIT", "ADN_F16_CONV",
-            "ADN_F16_FIRST", "ADN_F16_CONVT", "ADN_AUTO_GRID", "ADN_AUTO_GRID64")
+            "ADN_F16_FIRST", "ADN_F16_CONVT", "ADN_AUTO_GRID", "ADN_AUTO_GRID64", "ADN_WINO_GEMM")
 MODES = {                                   # tests/test_gpu_variants.py::MODES + the fp16 path's switches
     "default": {},
     "batch_invariant": {"ADN_BATCH_INVARIANT": "1"},
