@@ -1,8 +1,10 @@
 // Internal declarations shared by the translation units of libadn.so (not part of the public ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 namespace adn {
 
@@ -21,6 +23,46 @@ __host__ __device__ __forceinline__ long act_off(int C, long HW, long pix, int c
     (void)C;
     return ((long)(c / B) * HW + pix) * B + (c % B);
 }
+
+#ifdef __HIPCC__
+// Vector types of the kernels: the register images of 4 / 8 / 16-byte memory operations and the operands of the MFMAs.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// volatile LDS views: keep each patch / B-fragment read of the Winograd kernels a single ds_read_b64 / ds_read_b128
+typedef const volatile f32x2 __attribute__((address_space(3))) lds_cv_f32x2;
+typedef const volatile f32x4 __attribute__((address_space(3))) lds_cv_f32x4;
+
+// Bijective remap of the workgroup id so that the workgroups sharing an XCD (ids congruent mod 8, observed round-robin placement)
+// work on neighbouring tiles: what they fetch meets in ONE L2.  Affects speed only, never results.
+__device__ __forceinline__ int xcd_remap(int b, int nwg)
+{
+    const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
+}
+
+// lane id without the work-item-id register: values derived from threadIdx.x would otherwise have to survive a K loop
+// (in registers the loop needs, i.e. as scratch spills: measured 0.3 GB of spill traffic per full-resolution wino4_conv_f32 launch)
+__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+
+// GEMM column of the transposed convolution -> sub-pixel ij = 2*di + dj and output channel:
+//   column = ((di*(Cout/64) + cg)*2 + dj)*64 + c64, co = 64*cg + c64: the 128 columns of a workgroup are both dj of one di and
+//   64 channels, so that its stores cover whole runs of output pixels (2*gx + dj) per channel block.  The kernels, the weight
+//   packers (pack_convt*, unet.hip) and the bias vector all take the order from here.
+__host__ __device__ __forceinline__ void convt_column(int col, int Cout, int &ij, int &co)
+{
+    const int c64 = col & 63, dj = (col >> 6) & 1, g = col >> 7, ncg = Cout >> 6;
+    const int di = g / ncg, cg = g - di * ncg;
+    ij = 2 * di + dj;
+    co = 64 * cg + c64;
+}
+#endif
 
 // LDS-DMA through a buffer descriptor (buffer_load_dwordx4 ... offen lds): lane l of the wave copies the 16 bytes at
 // descriptor base + voff + soff to lds_wave_base + 16 l.  The range check compares voff with the descriptor's size MINUS soff
@@ -57,10 +99,8 @@ __device__ __forceinline__ float max4_nan(float a, float b, float c, float d) { 
 // conv_kernels.hip): x = hi + mid + lo with round-to-nearest terms, 24 mantissa bits in all.  hi is clamped to
 // the largest finite bf16 so that every FINITE x splits exactly (round-to-nearest would make a bf16 infinity of |x| >= 3.3961e38);
 // x = +-inf gives hi = 3.39e38, mid = +-inf, lo = NaN: non-finite stays non-finite.
-typedef __bf16 adn_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float adn_f32x4 __attribute__((ext_vector_type(4)));
 constexpr float ADN_BF16_MAX_F = 0x1.fep127f;                  // largest finite bf16
-__device__ __forceinline__ void split3_bf16(const adn_f32x4 &x0, const adn_f32x4 &x1, adn_bf16x8 &hi, adn_bf16x8 &mid, adn_bf16x8 &lo)
+__device__ __forceinline__ void split3_bf16(const f32x4 &x0, const f32x4 &x1, bf16x8 &hi, bf16x8 &mid, bf16x8 &lo)
 {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -73,6 +113,55 @@ __device__ __forceinline__ void split3_bf16(const adn_f32x4 &x0, const adn_f32x4
         mid[e] = m;
         lo[e] = (__bf16)r2;
     }
+}
+#endif
+
+#ifdef __HIPCC__
+// The transforms of Winograd F(4x4,3x3) for the points (0, 1, -1, 2, -2, inf), on one value per lane (float) or on packed values
+// (f32x2, f32x4: the same operations element by element).  One definition: wino4_conv_f32 forms V = B^T d B and A^T M A in
+// registers with them, the three-stage form (wino3s_kernels.hip) in kernels of their own, and both give the same bits.
+template <typename V>
+__device__ __forceinline__ V wino_fma(float c, V a, V b)
+{
+    if constexpr (std::is_same_v<V, float>) return __builtin_fmaf(c, a, b);
+    else return __builtin_elementwise_fma((V)c, a, b);
+}
+// B^T x, in place:
+//   [ 4  0 -5  0  1  0 ]      twelve operations
+//   [ 0 -4 -4  1  1  0 ]
+//   [ 0  4 -4 -1  1  0 ]
+//   [ 0 -2 -1  2  1  0 ]
+//   [ 0  2 -1 -2  1  0 ]
+//   [ 0  4  0 -5  0  1 ]
+template <typename V>
+__device__ __forceinline__ void bt6(V &d0, V &d1, V &d2, V &d3, V &d4, V &d5)
+{
+    const V pe = wino_fma(-4.f, d2, d4);
+    const V po = wino_fma(-4.f, d1, d3);
+    const V se = d4 - d2;
+    const V so = d3 - d1;
+    const V r0 = wino_fma(4.f, d0, pe) - d2;
+    const V r5 = wino_fma(4.f, d1, wino_fma(-5.f, d3, d5));
+    d0 = r0;
+    d1 = pe + po;
+    d2 = pe - po;
+    d3 = wino_fma(2.f, so, se);
+    d4 = wino_fma(-2.f, so, se);
+    d5 = r5;
+}
+// A^T m (6 -> 4), ten operations:
+//   [ 1 1  1 1  1 0 ]
+//   [ 0 1 -1 2 -2 0 ]
+//   [ 0 1  1 4  4 0 ]
+//   [ 0 1 -1 8 -8 1 ]
+template <typename V>
+__device__ __forceinline__ void at6(V m0, V m1, V m2, V m3, V m4, V m5, V &y0, V &y1, V &y2, V &y3)
+{
+    const V a = m1 + m2, b = m1 - m2, c = m3 + m4, d = m3 - m4;
+    y0 = m0 + a + c;
+    y1 = wino_fma(2.f, d, b);
+    y2 = wino_fma(4.f, c, a);
+    y3 = wino_fma(8.f, d, b) + m5;
 }
 #endif
 
@@ -223,11 +312,45 @@ ConvGeom conv_geom(ConvKind kind, int Cout, bool f16);
 // conv_workgroups(a).  The one place the workspace plan, the kernel choice and the launch arguments get that grid from.
 long conv_mfma_tiles(ConvKind kind, bool f16, ConvArgs &a);
 
+// Opts KERNELS in to `bytes` of dynamic LDS (more than the 64 KB a launch may ask for by default) on the current device, once per
+// device: the attribute is per device, and a handle may be created on any.  A device's bit is marked only after every kernel of the
+// group took the attribute; the first error is returned.
+template <auto... KERNELS>
+hipError_t lds_opt_in(size_t bytes)
+{
+    static std::atomic<unsigned long long> done{0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
+    for (const void *k : {reinterpret_cast<const void *>(KERNELS)...}) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+    }
+    done.fetch_or(bit, std::memory_order_release);
+    return hipSuccess;
+}
+// CUs of the device the persistent kernels size their grids by, in whole slots on each of the 8 XCDs; looked up once (one device
+// model per process: gfx950 only, checked at handle creation).  0: the lookup failed.
+inline int device_cus()
+{
+    static std::atomic<int> cus{0};
+    int c = cus.load(std::memory_order_relaxed);
+    if (c == 0) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c < 8)
+            return 0;
+        c &= ~7;
+        cus.store(c, std::memory_order_relaxed);
+    }
+    return c;
+}
+
 // Direct implicit-GEMM kernels (conv_kernels.hip), fp32 or fp16 storage.
 hipError_t launch_conv_mfma(ConvKind kind, const ConvArgs &a, bool f16, hipStream_t st);
-// second launch of a K-split fp16 3x3 layer (launch_conv_mfma with ConvArgs::ksplit > 1 wrote fp32 sums [split][N][H][W][Cout])
-hipError_t launch_conv_reduce_f16(ConvKind kind, const float *partial, const float *bias, void *out, void *pool, int ksplit, int N,
-                                  int H, int W, int Cout, hipStream_t st);
+// second launch of a K-split 3x3 layer (conv_kernels.hip): the slices of wino_conv_dma_f32, wino4_conv_f32 (fp32) or conv_dma (fp16)
+// wrote fp32 sums [split][N][H][W][Cout] into a.partial; a.ksplit copies + a.bias, ReLU -> a.out (+ a.pool) in the blocked layout
+hipError_t launch_conv_reduce(ConvKind kind, const ConvArgs &a, bool f16, hipStream_t st);
 // second launch of a K-split transposed convolution (ConvArgs::ksplit > 1, fp32 split-bf16 form): out = sum of the copies + bias
 hipError_t launch_convt_reduce(const float *partial, const float *bias, float *out, int ksplit, int N, int Ho, int Wo, int Cout,
                                hipStream_t st);
@@ -237,8 +360,6 @@ hipError_t launch_wino_conv(ConvKind kind, const ConvArgs &a, hipStream_t st);
 // its tile grid of a layer written into a.tilesY / tilesX / nct (the launcher does the same); returns conv_workgroups(a): the
 // workgroups of one K split that have a tile to compute (what wino_ksplit() is asked about)
 long wino_tiles(ConvArgs &a);
-// second launch of a split-K 3x3 layer of either Winograd kernel (wino_kernels.hip): ConvArgs::partial -> out (+ pool)
-hipError_t launch_wino_reduce(ConvKind kind, const ConvArgs &a, hipStream_t st);
 // Winograd F(4x4,3x3) variant (wino4_kernels.hip): tile 32x32 px x 32 couts, 8-ch chunks, weights from ConvArgs::wpk
 // in pack_wino4_3x3 layout.  wino4_applicable: plain / pooled 3x3 layers whose image the 32x32 tiles cover with little
 // waste; everything else (fused first / last layer, split-K, small images) stays on F(2x2,3x3).

@@ -22,18 +22,12 @@
 #include "adn_internal.h"
 
 #include <algorithm>
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 #include <vector>
 
 namespace adn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -67,13 +61,6 @@ template <bool WRES, bool FIRST = false> struct C16Lds {
     static constexpr size_t BYTES = (size_t)SINK_OFF + (FIRST ? 2 * C16_WIN_BYTES : 0) + (WRES ? 0 : 1024);
     static_assert(BYTES <= 160 * 1024, "LDS budget");
 };
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int c16_xcd_remap(int b, int nwg)
-{
-    const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-}
 
 // One work item = (clip n, tile ty, tx, cout tile ct); items are numbered ct fastest, then tx, ty, n.
 struct C16Item {
@@ -119,7 +106,7 @@ __global__ __launch_bounds__(C16_NT, 2) void conv16_f16(const ConvArgs p)
     // workgroups of one XCD hold neighbouring positions (speed only)
     const int nitems = p.nwg_total;
     const int gsz = (int)gridDim.x;
-    const int first = __builtin_amdgcn_readfirstlane(c16_xcd_remap((int)blockIdx.x, gsz));
+    const int first = __builtin_amdgcn_readfirstlane(xcd_remap((int)blockIdx.x, gsz));
     const int cnt = first < nitems ? (nitems - first + gsz - 1) / gsz : 0;
     if (cnt == 0) return;
     const int nchunk = p.nchunk;
@@ -586,24 +573,12 @@ hipError_t launch_c16(const ConvArgs &a, hipStream_t st)
     a2.fdTx = make_fastdiv((unsigned)a2.tilesX);
     a2.fdTy = make_fastdiv((unsigned)a2.tilesY);
     a2.nwg_total = (int)nitems;
-    static std::atomic<int> cus{0};                   // (one device model per process: gfx950 only, checked at handle creation)
-    int c = cus.load(std::memory_order_relaxed);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-    if (c == 0) {
-        if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c < 8) return hipErrorInvalidDevice;
-        c &= ~7;                                       // whole slots on each of the 8 XCDs
-        cus.store(c, std::memory_order_relaxed);
-    }
-    long grid = nitems < c ? ((nitems + 7) & ~7L) : c;   // one resident workgroup per CU walks the items
-    auto kern = conv16_f16<EPI, WRES, FIRST>;
-    static std::atomic<unsigned long long> attr_mask{0};
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_mask.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L::BYTES);
-        if (e != hipSuccess) return e;
-        attr_mask.fetch_or(bit, std::memory_order_release);
-    }
+    const int c = device_cus();
+    if (c == 0) return hipErrorInvalidDevice;
+    const long grid = nitems < c ? ((nitems + 7) & ~7L) : c;   // one resident workgroup per CU walks the items
+    constexpr auto kern = conv16_f16<EPI, WRES, FIRST>;
+    const hipError_t e = lds_opt_in<kern>(L::BYTES);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C16_NT), L::BYTES, st, a2);
     return hipGetLastError();
 }

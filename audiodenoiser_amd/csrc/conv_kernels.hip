@@ -29,15 +29,9 @@
 //   the accumulator registers (the four pixels of a pool window live in one lane by construction).
 #include "adn_internal.h"
 
-#include <atomic>
 #include <cstdlib>
 
 namespace adn {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -50,27 +44,6 @@ constexpr int CONVT_KG = 2, CONVT_WPE = 4;
 template <typename T> struct Elem;
 template <> struct Elem<float> { static constexpr int EPV = 4; };       // elements per 16-byte vector
 template <> struct Elem<_Float16> { static constexpr int EPV = 8; };
-
-// Bijective remap so that workgroups sharing an XCD (ids congruent mod 8, observed round-robin placement)
-// work on neighbouring tiles; affects speed only, never results.
-__device__ __forceinline__ int xcd_remap(int b, int nwg)
-{
-    const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-    const int start = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-    return start + (b >> 3);
-}
-
-// GEMM column of the transposed convolution -> sub-pixel ij = 2*di + dj and output channel:
-//   column = ((di*(Cout/64) + cg)*2 + dj)*64 + c64, co = 64*cg + c64: the 128 columns of a workgroup are both dj of one di and
-//   64 channels, so that its stores cover whole runs of output pixels (2*gx + dj) per channel block.  pack_convt
-//   (unet.hip) and the bias vector follow the same order.
-__host__ __device__ __forceinline__ void convt_column(int col, int Cout, int &ij, int &co)
-{
-    const int c64 = col & 63, dj = (col >> 6) & 1, g = col >> 7, ncg = Cout >> 6;
-    const int di = g / ncg, cg = g - di * ncg;
-    ij = 2 * di + dj;
-    co = 64 * cg + c64;
-}
 
 // Epilogue of a K-split slice (3x3 layers): the fp32 sums as they are, pixel-major [clip][H][W][Cout] (a lane's 32 neighbours hold
 // 32 consecutive columns of one pixel: 128-byte runs).  Accumulator layout: see conv_epilogue.
@@ -391,8 +364,7 @@ __device__ __forceinline__ void conv_epilogue_staged(const ConvArgs &p, f32x16 (
                     const float recv = __shfl_xor(send, 1, 64);
                     const float lo = odd ? recv : v[r], hi = odd ? v[r + 1] : recv;
                     const int pix = pix0 + ((r + (odd ? 1 : 0)) & 3) + 8 * (r >> 2);
-                    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-                    *reinterpret_cast<h2 *>(stage + pix * RS + (col & ~1)) = h2{(_Float16)lo, (_Float16)hi};
+                    *reinterpret_cast<f16x2 *>(stage + pix * RS + (col & ~1)) = f16x2{(_Float16)lo, (_Float16)hi};
                 }
             }
         }
@@ -547,13 +519,11 @@ struct DmaCfg {
 // -inf / NaN although x is finite; hi is therefore clamped to the largest finite bf16 (3.3895e38, one v_med3_f32): every FINITE
 // operand splits exactly.  Non-finite operands stay non-finite but not bit-compatible: x = +-inf gives hi = 3.39e38, mid = +-inf,
 // lo = NaN, so the sum is NaN where the exact-fp32 form may give +-inf (tests: test_convt_split_extreme_operands).
-typedef adn_bf16x8 bf16x8;
-
 // KSPLIT = 1 (small batches, ConvArgs::ksplit > 1): the grid is ksplit copies of the tile grid; copy `split` sums chunks
 // [split * nchunk / ksplit, +nchunk / ksplit) and stores raw sums as "clip" n + split * N of ConvArgs::out = the partial buffer
 // [split][N][image].  Transposed convolutions (fp32 split-bf16 form): the usual epilogue with a zero bias from the launcher,
 // convt_reduce_kernel adds the copies in a fixed order and the bias.  fp16 3x3 layers: fp32 sums, pixel-major (conv_epilogue_raw);
-// conv_reduce_f16_kernel adds them and applies bias / ReLU / pooling.
+// conv_reduce_kernel adds them and applies bias / ReLU / pooling.
 template <typename T, int TH, int BN, int WM, int WN, int TAPS, int KG, int EPI, int WPE, int SPLIT = 0, int KSPLIT = 0>
 __global__ __launch_bounds__(64 * WM * WN, WPE) void conv_dma(const ConvArgs p)
 {
@@ -951,19 +921,10 @@ hipError_t launch_dma_cfg(const ConvArgs &a, hipStream_t st)
         a2.fdTx = make_fastdiv((unsigned)a.tilesX);
         a2.fdTy = make_fastdiv((unsigned)a.tilesY);
     }
-    auto kern = conv_dma<T, TH, BN, WM, WN, TAPS, KG, EPI, WPE, SPLIT, KSPLIT>;
+    constexpr auto kern = conv_dma<T, TH, BN, WM, WN, TAPS, KG, EPI, WPE, SPLIT, KSPLIT>;
     if (C::LDS_BYTES > 64 * 1024) {
-        // the attribute is per device: remember which devices of this process have it
-        static std::atomic<unsigned long long> attr_mask{0};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(attr_mask.load(std::memory_order_acquire) & bit)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            attr_mask.fetch_or(bit, std::memory_order_release);
-        }
+        const hipError_t e = lds_opt_in<kern>(C::LDS_BYTES);
+        if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(kern, dim3((unsigned)(nwg * ks)), dim3(C::NT), C::LDS_BYTES, st, a2);
     return hipGetLastError();
@@ -989,14 +950,16 @@ __global__ __launch_bounds__(256) void convt_reduce_kernel(const f32x4 *__restri
     out[i] = v;
 }
 
-// Second launch of a K-split fp16 3x3 layer: out = ReLU(sum over the copies (fixed order) + bias) as fp16 in the blocked activation
-// layout, plus the 2x2 max-pool.  Pooling form: one thread per (2x2 pixel block, 4 channels); plain form: per (pixel, 4 channels).
-typedef _Float16 f16x4r __attribute__((ext_vector_type(4)));
-template <bool POOL>
-__global__ __launch_bounds__(256) void conv_reduce_f16_kernel(const float *__restrict__ partial, const float *__restrict__ bias,
-                                                              _Float16 *__restrict__ out, _Float16 *__restrict__ pool, int ksplit,
-                                                              int N, int H, int W, int Cout)
+// Second launch of a K-split 3x3 layer (fp32: either Winograd kernel; fp16: conv_dma): out = ReLU(sum over the copies (fixed order)
+// + bias) as T in the blocked activation layout, plus the 2x2 max-pool.  The partial sums are pixel-major.  Pooling form: one thread
+// per (2x2 pixel block, 4 output channels); plain form: one thread per (pixel, 4 output channels) -- the layers that are split have
+// few pixels (one clip at 32x16 ... 128x64), the launch is latency: more threads, shorter threads.
+template <typename T, bool POOL>
+__global__ __launch_bounds__(256) void conv_reduce_kernel(const float *__restrict__ partial, const float *__restrict__ bias,
+                                                          T *__restrict__ out, T *__restrict__ pool, int ksplit, int N, int H, int W,
+                                                          int Cout)
 {
+    typedef T Tx4 __attribute__((ext_vector_type(4)));
     const int cq = Cout / 4, bh = POOL ? (H + 1) / 2 : H, bw = POOL ? (W + 1) / 2 : W;
     const long total = (long)N * bh * bw * cq;
     const long id = (long)blockIdx.x * 256 + threadIdx.x;
@@ -1008,9 +971,12 @@ __global__ __launch_bounds__(256) void conv_reduce_f16_kernel(const float *__res
     const int by = (int)(r % bh), n = (int)(r / bh);
     const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias + c4);
     const size_t img = (size_t)H * W * Cout, split_stride = (size_t)N * img;
-    auto half4 = [](const f32x4 &v) { return f16x4r{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w}; };
+    auto as_t = [](const f32x4 &v) {
+        if constexpr (sizeof(T) == 4) return v;
+        else return f16x4{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
+    };
     auto finish = [&](int gy, int gx) {
-        const size_t o = (size_t)n * img + ((size_t)gy * W + gx) * Cout + c4;
+        const size_t o = (size_t)n * img + ((size_t)gy * W + gx) * Cout + c4;      // partial sums: pixel-major
         f32x4 t[ADN_MAX_KSPLIT];                             // all copies in flight, then added in split order
 #pragma unroll
         for (int s = 0; s < ADN_MAX_KSPLIT; ++s)
@@ -1021,7 +987,7 @@ __global__ __launch_bounds__(256) void conv_reduce_f16_kernel(const float *__res
             if (s < ksplit) v += t[s];
         v += bv;
         v.x = relu_nan(v.x); v.y = relu_nan(v.y); v.z = relu_nan(v.z); v.w = relu_nan(v.w);
-        *reinterpret_cast<f16x4r *>(out + (size_t)n * img + act_off<_Float16>(Cout, (long)H * W, (long)gy * W + gx, c4)) = half4(v);
+        *reinterpret_cast<Tx4 *>(out + (size_t)n * img + act_off<T>(Cout, (long)H * W, (long)gy * W + gx, c4)) = as_t(v);
         return v;
     };
     if constexpr (!POOL) {
@@ -1038,8 +1004,8 @@ __global__ __launch_bounds__(256) void conv_reduce_f16_kernel(const float *__res
                 mx.x = max_nan(mx.x, v.x); mx.y = max_nan(mx.y, v.y); mx.z = max_nan(mx.z, v.z); mx.w = max_nan(mx.w, v.w);
             }
         if (by < H / 2 && bx < W / 2)
-            *reinterpret_cast<f16x4r *>(pool + (size_t)n * (H / 2) * (W / 2) * Cout +
-                                        act_off<_Float16>(Cout, (long)(H / 2) * (W / 2), (long)by * (W / 2) + bx, c4)) = half4(mx);
+            *reinterpret_cast<Tx4 *>(pool + (size_t)n * (H / 2) * (W / 2) * Cout +
+                                     act_off<T>(Cout, (long)(H / 2) * (W / 2), (long)by * (W / 2) + bx, c4)) = as_t(mx);
     }
 }
 
@@ -1131,21 +1097,28 @@ hipError_t launch_wino_gemm(const float *V, const void *U, float *M, long rows, 
     return launch_dma_cfg<float, 8, 128, 2, 2, 1, CONVT_KG, WINO_GEMM, 3, 1>(a, st);
 }
 
-hipError_t launch_conv_reduce_f16(ConvKind kind, const float *partial, const float *bias, void *out, void *pool, int ksplit, int N,
-                                  int H, int W, int Cout, hipStream_t st)
+template <typename T>
+static hipError_t launch_conv_reduce_t(bool pl, const ConvArgs &a, unsigned blocks, hipStream_t st)
+{
+    if (pl)
+        hipLaunchKernelGGL((conv_reduce_kernel<T, true>), dim3(blocks), dim3(256), 0, st, a.partial, a.bias, static_cast<T *>(a.out),
+                           static_cast<T *>(a.pool), a.ksplit, a.N, a.H, a.W, a.Cout);
+    else
+        hipLaunchKernelGGL((conv_reduce_kernel<T, false>), dim3(blocks), dim3(256), 0, st, a.partial, a.bias, static_cast<T *>(a.out),
+                           static_cast<T *>(nullptr), a.ksplit, a.N, a.H, a.W, a.Cout);
+    return hipGetLastError();
+}
+
+hipError_t launch_conv_reduce(ConvKind kind, const ConvArgs &a, bool f16, hipStream_t st)
 {
     const bool pl = kind == CONV3X3_RELU_POOL;
-    const long items = pl ? (long)N * ((H + 1) / 2) * ((W + 1) / 2) * (Cout / 4) : (long)N * H * W * (Cout / 4);
-    const long blocks = (items + 255) / 256;
-    if (ksplit < 2 || ksplit > ADN_MAX_KSPLIT || (Cout & 15) || (kind != CONV3X3_RELU && !pl) || (pl && !pool) || blocks <= 0 || blocks > 0x7fffffffL)
+    // (fp16: a lane's four channels must not straddle a 16-channel block)
+    if (a.ksplit < 2 || a.ksplit > ADN_MAX_KSPLIT || !a.partial || (a.Cout & (f16 ? 15 : 3)) || (kind != CONV3X3_RELU && !pl) || (pl && !a.pool))
         return hipErrorInvalidValue;
-    if (pl)
-        hipLaunchKernelGGL(conv_reduce_f16_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, partial, bias,
-                           static_cast<_Float16 *>(out), static_cast<_Float16 *>(pool), ksplit, N, H, W, Cout);
-    else
-        hipLaunchKernelGGL(conv_reduce_f16_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, partial, bias,
-                           static_cast<_Float16 *>(out), static_cast<_Float16 *>(nullptr), ksplit, N, H, W, Cout);
-    return hipGetLastError();
+    const long items = pl ? (long)a.N * ((a.H + 1) / 2) * ((a.W + 1) / 2) * (a.Cout / 4) : (long)a.N * a.H * a.W * (a.Cout / 4);
+    const long blocks = (items + 255) / 256;
+    if (items <= 0 || blocks > 0x7fffffffL) return hipErrorInvalidValue;
+    return f16 ? launch_conv_reduce_t<_Float16>(pl, a, (unsigned)blocks, st) : launch_conv_reduce_t<float>(pl, a, (unsigned)blocks, st);
 }
 
 hipError_t launch_convt_reduce(const float *partial, const float *bias, float *out, int ksplit, int N, int Ho, int Wo, int Cout,

@@ -25,16 +25,9 @@
 #include "adn_internal.h"
 
 #include <algorithm>
-#include <atomic>
 #include <type_traits>
 
 namespace adn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -47,12 +40,6 @@ constexpr int T16_NBUF = 4;                        // ring of LDS images; the co
 constexpr int T16_BIAS_OFF = T16_NBUF * T16_IMG_BYTES;    // bias vector (Cout floats, <= 1024) behind the images
 constexpr int T16_MAX_COUT = 1024;
 constexpr size_t T16_LDS = (size_t)T16_BIAS_OFF + T16_MAX_COUT * 4;
-
-__device__ __forceinline__ int t16_xcd_remap(int b, int nwg)
-{
-    const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-}
 
 // work item = (clip n, tile ty, tx, column tile ct); items are numbered ct fastest, then tx, ty, n (plain divisions: a handful per
 // item, beside 256 ... 2048 MFMAs per wave)
@@ -87,7 +74,7 @@ __global__ __launch_bounds__(T16_NT, 2) void convt16_f16(const ConvArgs p)
     const int wr = wave >> 1, wc = wave & 1;         // pixel rows 4 wr .. +3, column pairs 4 wc .. +3 of the item
 
     const int nitems = p.nwg_total, gsz = (int)gridDim.x;
-    const int first = __builtin_amdgcn_readfirstlane(t16_xcd_remap((int)blockIdx.x, gsz));
+    const int first = __builtin_amdgcn_readfirstlane(xcd_remap((int)blockIdx.x, gsz));
     const int cnt = first < nitems ? (nitems - first + gsz - 1) / gsz : 0;
     if (cnt == 0) return;
     const int nchunk = p.nchunk;                     // 32-channel chunks: a multiple of 4 (convt16_applicable)
@@ -284,24 +271,11 @@ hipError_t launch_convt16(const ConvArgs &a, hipStream_t st)
     const long nitems = t16_tiles(a2);
     a2.nchunk = a.s0.C / 32;
     a2.nwg_total = (int)nitems;
-    static std::atomic<int> cus{0};                    // (one device model per process: gfx950 only, checked at handle creation)
-    int c = cus.load(std::memory_order_relaxed);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-    if (c == 0) {
-        if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c < 8) return hipErrorInvalidDevice;
-        c &= ~7;
-        cus.store(c, std::memory_order_relaxed);
-    }
+    const int c = device_cus();
+    if (c == 0) return hipErrorInvalidDevice;
     const long grid = nitems < c ? ((nitems + 7) & ~7L) : c;      // one resident workgroup per CU walks the items
-    static std::atomic<unsigned long long> attr_mask{0};
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_mask.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(convt16_f16<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T16_LDS);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void *>(convt16_f16<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)T16_LDS);
-        if (e != hipSuccess) return e;
-        attr_mask.fetch_or(bit, std::memory_order_release);
-    }
+    const hipError_t e = lds_opt_in<convt16_f16<false>, convt16_f16<true>>(T16_LDS);
+    if (e != hipSuccess) return e;
     if (a2.nct == 1) hipLaunchKernelGGL(convt16_f16<true>, dim3((unsigned)grid), dim3(T16_NT), T16_LDS, st, a2);
     else hipLaunchKernelGGL(convt16_f16<false>, dim3((unsigned)grid), dim3(T16_NT), T16_LDS, st, a2);
     return hipGetLastError();

@@ -359,16 +359,6 @@ template <> struct WavePlan<128> { static constexpr int R2 = 8, R3 = 2; };
 template <> struct WavePlan<256> { static constexpr int R2 = 8, R3 = 4; };
 template <> struct WavePlan<512> { static constexpr int R2 = 8, R3 = 8; };
 
-// Bijective remap of the workgroup id so that workgroups placed on one XCD (ids congruent mod 8 under the
-// observed round-robin placement) own neighbouring frame groups: the two halves of an output cache line and the
-// overlapping audio lines then meet in ONE L2 instead of being written back / fetched partially by several.
-// Affects speed only.
-__device__ __forceinline__ int stft_xcd_remap(int b, int nwg)
-{
-    const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-}
-
 // at least 3 waves per SIMD: the register allocation granule is 8, so 169 VGPRs would already drop to 2
 template <int M, int NW, int FPB, int WPE, bool FIT>
 __global__ __launch_bounds__(NW * 64, WPE) void stft_wave_kernel(const float *__restrict__ audio, long L, int hop, int pad,
@@ -391,7 +381,9 @@ __global__ __launch_bounds__(NW * 64, WPE) void stft_wave_kernel(const float *__
     // branches run on the scalar unit
     const int slot = (TPF == 64) ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid / TPF;
     const int t = tid - slot * TPF;
-    const int lid = stft_xcd_remap(blockIdx.x, gridDim.x);
+    // workgroups placed on one XCD own neighbouring frame groups: the two halves of an output cache line and the overlapping
+    // audio lines then meet in ONE L2 instead of being written back / fetched partially by several
+    const int lid = xcd_remap(blockIdx.x, gridDim.x);
     const int clip = lid / blocks_per_clip;
     const int g_first = (lid - clip * blocks_per_clip) * gpb;
     const int g_end = min(g_first + gpb, groups_per_clip);

@@ -203,45 +203,43 @@ void pack_wino3x3(const float *w /*(Cout,Cin,3,3)*/, const std::vector<float> &s
     (void)nct;
 }
 
-// Winograd F(4x4,3x3) weights U = G g G^T (6x6, points 0, +-1, +-2, inf; double precision, BatchNorm scale folded),
-// packed for wino4_conv_f32: [column tile of 32][chunk of 8 channels][jh][group g][pass h][q][cout%16][k] with input channel
+// Winograd F(4x4,3x3): U = G g G^T (6x6, points 0, +-1, +-2, inf) of one 3x3 filter with the BatchNorm scale of its output channel
+// folded in, U[6 x + v]; double arithmetic, rounded once to fp32.  Both packers below take the layer's weights from here.
+void wino4_u(const float *g /*3x3*/, float scale, float (&U)[36])
+{
+    static const double G[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
+                                   {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
+    double tmp[6][3];
+    for (int x = 0; x < 6; ++x)
+        for (int b = 0; b < 3; ++b)
+            tmp[x][b] = G[x][0] * g[0 * 3 + b] + G[x][1] * g[1 * 3 + b] + G[x][2] * g[2 * 3 + b];
+    for (int x = 0; x < 6; ++x)
+        for (int v = 0; v < 6; ++v)
+            U[6 * x + v] = (float)((tmp[x][0] * G[v][0] + tmp[x][1] * G[v][1] + tmp[x][2] * G[v][2]) * (double)scale);
+}
+
+// U packed for wino4_conv_f32: [column tile of 32][chunk of 8 channels][jh][group g][pass h][q][cout%16][k] with input channel
 // = chunk*8 + 2q + h.  A wave owns the positions (row i, column j) of U with j / 3 = jh, numbered p = 3i + j%3; float k of
 // group g is position p = 2g + k/2 for cout block (k & 1) ^ jh (block 0 of a wave is the one it finishes, = jh): a wave's
 // B-fragment read of one group and pass is 64 lanes x 16 bytes = 1 KB contiguous.
 void pack_wino4_3x3(const float *w /*(Cout,Cin,3,3)*/, const std::vector<float> &scale, int Cin, int Cout, float *dst)
 {
-    static const double G[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                   {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
     const int nchunk = Cin / 8;
     for (int co = 0; co < Cout; ++co)
         for (int ci = 0; ci < Cin; ++ci) {
-            const float *g = w + ((size_t)co * Cin + ci) * 9;
-            double tmp[6][3];
-            for (int x = 0; x < 6; ++x)
-                for (int b = 0; b < 3; ++b)
-                    tmp[x][b] = G[x][0] * g[0 * 3 + b] + G[x][1] * g[1 * 3 + b] + G[x][2] * g[2 * 3 + b];
+            float U[36];
+            wino4_u(w + ((size_t)co * Cin + ci) * 9, scale[co], U);
             const int ct = co / 32, cb = (co % 32) / 16, n16 = co % 16, ch = ci / 8, q = (ci % 8) / 2, h = ci & 1;
             float *blk = dst + ((size_t)ct * nchunk + ch) * (36 * 8 * 32);
             for (int x = 0; x < 6; ++x)
                 for (int v = 0; v < 6; ++v) {
-                    const double U = (tmp[x][0] * G[v][0] + tmp[x][1] * G[v][1] + tmp[x][2] * G[v][2]) * (double)scale[co];
                     const int jh = v / 3, pp = 3 * x + v % 3, grp = pp >> 1, k = ((pp & 1) << 1) | (cb ^ jh);
-                    blk[(((((jh * 9 + grp) * 2 + h) * 4 + q) * 16) + n16) * 4 + k] = (float)U;
+                    blk[(((((jh * 9 + grp) * 2 + h) * 4 + q) * 16) + n16) * 4 + k] = U[6 * x + v];
                 }
         }
 }
 
-// GEMM column of the transposed convolution -> (ij = 2*di + dj, co); must match convt_column in conv_kernels.hip:
-// col = ((di*(Cout/64) + cg)*2 + dj)*64 + c64 with co = 64*cg + c64.
-void convt_column_host(int col, int Cout, int &ij, int &co)
-{
-    const int c64 = col & 63, dj = (col >> 6) & 1, g = col >> 7, ncg = Cout >> 6;
-    const int di = g / ncg, cg = g - di * ncg;
-    ij = 2 * di + dj;
-    co = 64 * cg + c64;
-}
-
-// ConvTranspose2d(k2,s2) as a GEMM with columns (sub-pixel, output channel) in convt_column_host order, K = Cin.
+// ConvTranspose2d(k2,s2) as a GEMM with columns (sub-pixel, output channel) in convt_column order (adn_internal.h), K = Cin.
 template <typename T>
 void pack_convt(const float *w /*(Cin,Cout,2,2)*/, int Cin, int Cout, T *dst)
 {
@@ -257,7 +255,7 @@ void pack_convt(const float *w /*(Cin,Cout,2,2)*/, int Cin, int Cout, T *dst)
                     for (int n = 0; n < BN; ++n) {
                         const int col = ct * BN + n;
                         int ij, co;
-                        convt_column_host(col, Cout, ij, co);
+                        adn::convt_column(col, Cout, ij, co);
                         for (int kk = 0; kk < EPV; ++kk) {
                             const int ci = ch * KC + 2 * EPV * s + EPV * h + kk;
                             dst[o++] = (T)w[((size_t)ci * Cout + co) * 4 + ij];
@@ -318,31 +316,23 @@ inline void split3_host(float v, uint16_t (&t)[3])
     t[2] = bf16_rne(r2);
 }
 
-// Winograd F(4x4,3x3) weights for the three-stage form (wino3s_kernels.hip): U = G g G^T exactly as pack_wino4_3x3 rounds it to
-// fp32, then split into three bf16 planes and packed per transform-domain position as the GEMM slabs of conv_dma<..., SPLIT,
-// WINO_GEMM>: [pos = 6x + v][column tile of 128 couts][chunk of 16 channels][plane][half h][cout n][8 bf16], element kk of
-// half h = input channel chunk*16 + 8h + kk.
+// U for the three-stage form (wino3s_kernels.hip): the fp32 values of wino4_u split into three bf16 planes and packed per
+// transform-domain position as the GEMM slabs of conv_dma<..., SPLIT, WINO_GEMM>: [pos = 6x + v][column tile of 128 couts][chunk of
+// 16 channels][plane][half h][cout n][8 bf16], element kk of half h = input channel chunk*16 + 8h + kk.
 void pack_wino4_split(const float *w /*(Cout,Cin,3,3)*/, const std::vector<float> &scale, int Cin, int Cout, uint16_t *dst)
 {
-    static const double G[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                   {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
     const int nct = Cout / 128, nchunk = Cin / 16;
     for (int co = 0; co < Cout; ++co)
         for (int ci = 0; ci < Cin; ++ci) {
-            const float *g = w + ((size_t)co * Cin + ci) * 9;
-            double tmp[6][3];
-            for (int x = 0; x < 6; ++x)
-                for (int b = 0; b < 3; ++b)
-                    tmp[x][b] = G[x][0] * g[0 * 3 + b] + G[x][1] * g[1 * 3 + b] + G[x][2] * g[2 * 3 + b];
+            float U[36];
+            wino4_u(w + ((size_t)co * Cin + ci) * 9, scale[co], U);
             const int ct = co / 128, n = co % 128, ch = ci / 16, hh = (ci % 16) / 8, kk = ci % 8;
-            for (int x = 0; x < 6; ++x)
-                for (int v = 0; v < 6; ++v) {
-                    const float U = (float)((tmp[x][0] * G[v][0] + tmp[x][1] * G[v][1] + tmp[x][2] * G[v][2]) * (double)scale[co]);
-                    uint16_t t[3];
-                    split3_host(U, t);
-                    uint16_t *slab = dst + (((size_t)(6 * x + v) * nct + ct) * nchunk + ch) * (3 * 2 * 128 * 8);
-                    for (int plane = 0; plane < 3; ++plane) slab[((plane * 2 + hh) * 128 + n) * 8 + kk] = t[plane];
-                }
+            for (int pos = 0; pos < 36; ++pos) {
+                uint16_t t[3];
+                split3_host(U[pos], t);
+                uint16_t *slab = dst + (((size_t)pos * nct + ct) * nchunk + ch) * (3 * 2 * 128 * 8);
+                for (int plane = 0; plane < 3; ++plane) slab[((plane * 2 + hh) * 128 + n) * 8 + kk] = t[plane];
+            }
         }
 }
 
@@ -357,7 +347,7 @@ void pack_convt_split(const float *w /*(Cin,Cout,2,2)*/, int Cin, int Cout, uint
                 for (int h = 0; h < 2; ++h)
                     for (int n = 0; n < BN; ++n) {
                         int ij, co;
-                        convt_column_host(ct * BN + n, Cout, ij, co);
+                        adn::convt_column(ct * BN + n, Cout, ij, co);
                         for (int kk = 0; kk < 8; ++kk) {
                             const int ci = ch * KC + 8 * h + kk;
                             uint16_t t[3];
@@ -627,7 +617,9 @@ hipError_t launch_conv3(const adn_unet *h, adn::ConvKind kind, const Conv3Choice
             sl.pool = nullptr;
             hipError_t e = adn::launch_conv_mfma(adn::CONV3X3_RELU, sl, true, st);
             if (e != hipSuccess) return e;
-            return adn::launch_conv_reduce_f16(kind, partial, a.bias, a.out, a.pool, c.ksplit, a.N, a.H, a.W, a.Cout, st);
+            a.ksplit = c.ksplit;
+            a.partial = partial;
+            return adn::launch_conv_reduce(kind, a, true, st);
         }
         return adn::launch_conv_mfma(kind, a, h->f16, st);
     case WINO4:
@@ -916,7 +908,7 @@ void pack_weights(adn_unet &h, const float *const *t, std::vector<float> &host)
             L.b_off = reserve((size_t)4 * Cout);
             for (int col = 0; col < 4 * Cout; ++col) {          // bias per GEMM column
                 int ij, c;
-                convt_column_host(col, Cout, ij, c);
+                adn::convt_column(col, Cout, ij, c);
                 host[L.b_off + col] = t[ti + 1][c];
             }
             ti += 2;

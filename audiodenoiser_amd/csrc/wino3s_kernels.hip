@@ -17,37 +17,6 @@ namespace adn {
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 vfma(float c, f32x4 a, f32x4 b) { return __builtin_elementwise_fma(f32x4{c, c, c, c}, a, b); }
-
-// B^T x and A^T m for the points (0, 1, -1, 2, -2, inf): operation for operation bt6 / at6 of wino4_kernels.hip on four
-// channels at once, so V has the bits that kernel forms in registers
-__device__ __forceinline__ void bt6v(f32x4 &d0, f32x4 &d1, f32x4 &d2, f32x4 &d3, f32x4 &d4, f32x4 &d5)
-{
-    const f32x4 pe = vfma(-4.f, d2, d4);
-    const f32x4 po = vfma(-4.f, d1, d3);
-    const f32x4 se = d4 - d2;
-    const f32x4 so = d3 - d1;
-    const f32x4 r0 = vfma(4.f, d0, pe) - d2;
-    const f32x4 r5 = vfma(4.f, d1, vfma(-5.f, d3, d5));
-    d0 = r0;
-    d1 = pe + po;
-    d2 = pe - po;
-    d3 = vfma(2.f, so, se);
-    d4 = vfma(-2.f, so, se);
-    d5 = r5;
-}
-__device__ __forceinline__ void at6v(f32x4 m0, f32x4 m1, f32x4 m2, f32x4 m3, f32x4 m4, f32x4 m5, f32x4 &y0, f32x4 &y1, f32x4 &y2,
-                                     f32x4 &y3)
-{
-    const f32x4 a = m1 + m2, b = m1 - m2, c = m3 + m4, d = m3 - m4;
-    y0 = m0 + a + c;
-    y1 = vfma(2.f, d, b);
-    y2 = vfma(4.f, c, a);
-    y3 = vfma(8.f, d, b) + m5;
-}
-
 constexpr int NT = 256;
 
 // grid: (ceil(2 rows / NT), Cin / 8); thread = (row, half of the channel block)
@@ -75,11 +44,12 @@ __global__ __launch_bounds__(NT) void wino3s_input_kernel(const ConvArgs p, floa
             d[a][b] = (y >= 0 && y < s.H && x >= 0 && x < s.W) ? *reinterpret_cast<const f32x4 *>(src + ((size_t)y * s.W + x) * 8)
                                                                 : f32x4{0.f, 0.f, 0.f, 0.f};
         }
-    // row stage (along the pixel columns of every patch row), then column stage: the order of wino4_conv_f32
+    // row stage (along the pixel columns of every patch row), then column stage: the order of wino4_conv_f32, whose transform
+    // functions these are (bt6 / at6, adn_internal.h), so V has the bits that kernel forms in registers
 #pragma unroll
-    for (int a = 0; a < 6; ++a) bt6v(d[a][0], d[a][1], d[a][2], d[a][3], d[a][4], d[a][5]);
+    for (int a = 0; a < 6; ++a) bt6(d[a][0], d[a][1], d[a][2], d[a][3], d[a][4], d[a][5]);
 #pragma unroll
-    for (int b = 0; b < 6; ++b) bt6v(d[0][b], d[1][b], d[2][b], d[3][b], d[4][b], d[5][b]);
+    for (int b = 0; b < 6; ++b) bt6(d[0][b], d[1][b], d[2][b], d[3][b], d[4][b], d[5][b]);
     const int ncb = (p.s0.C + p.s1.C) / 8;
     float *vp = V + ((size_t)cb * rows + row) * 8 + half * 4;
     const size_t pstr = (size_t)ncb * rows * 8;                       // floats between positions
@@ -109,14 +79,14 @@ __global__ __launch_bounds__(NT) void wino3s_output_kernel(const ConvArgs p, con
         f32x4 m[6];
 #pragma unroll
         for (int i = 0; i < 6; ++i) m[i] = *reinterpret_cast<const f32x4 *>(mp + (size_t)(6 * i + j) * pstr);
-        at6v(m[0], m[1], m[2], m[3], m[4], m[5], w[0][j], w[1][j], w[2][j], w[3][j]);
+        at6(m[0], m[1], m[2], m[3], m[4], m[5], w[0][j], w[1][j], w[2][j], w[3][j]);
     }
     const f32x4 bias = *reinterpret_cast<const f32x4 *>(p.bias + cb * 8 + half * 4);
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
     f32x4 y[4][4];
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
-        at6v(w[a][0], w[a][1], w[a][2], w[a][3], w[a][4], w[a][5], y[a][0], y[a][1], y[a][2], y[a][3]);
+        at6(w[a][0], w[a][1], w[a][2], w[a][3], w[a][4], w[a][5], y[a][0], y[a][1], y[a][2], y[a][3]);
 #pragma unroll
         for (int b = 0; b < 4; ++b) y[a][b] = __builtin_elementwise_maximum(y[a][b] + bias, zero);     // relu_nan: NaN stays NaN
     }

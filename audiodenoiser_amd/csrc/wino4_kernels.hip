@@ -28,18 +28,12 @@
 #include "adn_internal.h"
 
 #include <algorithm>
-#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
 #include <vector>
 
 namespace adn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef const volatile f32x2 __attribute__((address_space(3))) lds4_cv_f32x2;
-typedef const volatile f32x4 __attribute__((address_space(3))) lds4_cv_f32x4;
 
 namespace {
 
@@ -78,73 +72,11 @@ constexpr int IMG = (HSLOTS + USLOTS) * 4;   // floats per LDS image (77 824 byt
 constexpr int SUP = 32;                      // workgroups resident on one XCD (one per CU)
 constexpr size_t LDS_BYTES = (size_t)2 * IMG * sizeof(float);
 
-__device__ __forceinline__ int xcd_remap4(int b, int nwg)
-{
-    const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-}
-
 // copies: LDS-DMA through buffer descriptors, padding lanes out of range (dma16_buf, adn_internal.h)
 constexpr unsigned OOB = ADN_DMA_OOB;
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff, float *lds_wave_base)
-{
-    dma16_buf(rsrc, voff, soff, lds_wave_base);
-}
 
-// B^T x for the points (0, 1, -1, 2, -2, inf), in place:
-//   [ 4  0 -5  0  1  0 ]      twelve operations
-//   [ 0 -4 -4  1  1  0 ]
-//   [ 0  4 -4 -1  1  0 ]
-//   [ 0 -2 -1  2  1  0 ]
-//   [ 0  2 -1 -2  1  0 ]
-//   [ 0  4  0 -5  0  1 ]
-__device__ __forceinline__ void bt6(float &d0, float &d1, float &d2, float &d3, float &d4, float &d5)
-{
-    const float pe = __builtin_fmaf(-4.f, d2, d4);
-    const float po = __builtin_fmaf(-4.f, d1, d3);
-    const float se = d4 - d2;
-    const float so = d3 - d1;
-    const float r0 = __builtin_fmaf(4.f, d0, pe) - d2;
-    const float r5 = __builtin_fmaf(4.f, d1, __builtin_fmaf(-5.f, d3, d5));
-    d0 = r0;
-    d1 = pe + po;
-    d2 = pe - po;
-    d3 = __builtin_fmaf(2.f, so, se);
-    d4 = __builtin_fmaf(-2.f, so, se);
-    d5 = r5;
-}
-
-// A^T m (6 -> 4), ten operations:
-//   [ 1 1  1 1  1 0 ]
-//   [ 0 1 -1 2 -2 0 ]
-//   [ 0 1  1 4  4 0 ]
-//   [ 0 1 -1 8 -8 1 ]
-__device__ __forceinline__ void at6(float m0, float m1, float m2, float m3, float m4, float m5, float &y0, float &y1,
-                                    float &y2, float &y3)
-{
-    const float a = m1 + m2, b = m1 - m2, c = m3 + m4, d = m3 - m4;
-    y0 = m0 + a + c;
-    y1 = __builtin_fmaf(2.f, d, b);
-    y2 = __builtin_fmaf(4.f, c, a);
-    y3 = __builtin_fmaf(8.f, d, b) + m5;
-}
-
-// The same for two accumulator registers at once (packed fp32: the epilogue runs no MFMAs beside it; operation for operation the
-// arithmetic of at6, so results are bit-identical)
-__device__ __forceinline__ f32x2 pk_fma(float c, f32x2 a, f32x2 b) { return __builtin_elementwise_fma(f32x2{c, c}, a, b); }
-__device__ __forceinline__ void at6x2(f32x2 m0, f32x2 m1, f32x2 m2, f32x2 m3, f32x2 m4, f32x2 m5, f32x2 &y0, f32x2 &y1, f32x2 &y2,
-                                      f32x2 &y3)
-{
-    const f32x2 a = m1 + m2, b = m1 - m2, c = m3 + m4, d = m3 - m4;
-    y0 = m0 + a + c;
-    y1 = pk_fma(2.f, d, b);
-    y2 = pk_fma(4.f, c, a);
-    y3 = pk_fma(8.f, d, b) + m5;
-}
-
-// lane id without the work-item-id register: values derived from threadIdx.x would otherwise have to survive the K loop
-// (in registers the loop needs, i.e. as scratch spills: measured 0.3 GB of spill traffic per full-resolution launch)
-__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+// (B^T x and A^T m for the points (0, 1, -1, 2, -2, inf): bt6 / at6 in adn_internal.h.  The pooling variant runs at6 on two
+// accumulator registers at once in packed fp32: the epilogue runs no MFMAs beside it.)
 
 // Copies run ahead of the arithmetic: under the FIRST pass of chunk c go the five U pieces of chunk c + 1, under the SECOND
 // pass the five halo pieces of chunk c + 2 (a chunk's patch is read one chunk ahead, below, so the halo half of an image is
@@ -156,7 +88,7 @@ static_assert(W4_PATCH_READS * 9 >= 30, "the second pass must issue all 30 patch
 
 // KSPLIT = 1 (small grids, ConvArgs::ksplit > 1; plain variant only): the grid is ksplit copies of the tile grid; copy `ksp` sums
 // chunks [ksp * nchunk / ksplit, +nchunk / ksplit) and stores raw sums -- no bias, no ReLU -- pixel-major into ConvArgs::partial
-// [split][N][H][W][Cout]; wino_reduce_kernel (launch_wino_reduce) adds the copies in a fixed order and finishes the layer.
+// [split][N][H][W][Cout]; conv_reduce_kernel (launch_conv_reduce) adds the copies in a fixed order and finishes the layer.
 #define W4_NCHUNK (KSPLIT ? nloc : p.nchunk)             /* chunks this workgroup sums */
 #define W4_NCHUNK0 (KSPLIT ? nchunk0l : p.nchunk0)       /* (local) index of the first chunk of the second source */
 template <int EPI, int KSPLIT = 0>
@@ -186,7 +118,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     // workgroup -> (pixel tile, cout tile): SUP consecutive ids (after the XCD remap) run together on one XCD and form
     // a supertile of gc cout tiles x gp pixel tiles, so every U slab and every halo is an L2 hit for all but one of them
     // (gc = as many cout tiles as there are, up to all 32 slots: measured 0.5 % faster than capping gc at 8)
-    int lid = xcd_remap4(blockIdx.x, gridDim.x);
+    int lid = xcd_remap(blockIdx.x, gridDim.x);
     int ksp = 0;                                          // KSPLIT: which slice of the K loop this copy of the tile grid sums
     if constexpr (KSPLIT) {
         ksp = lid / p.nwg_base;
@@ -231,7 +163,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
     unsigned usoff = KSPLIT ? (unsigned)c0 * (unsigned)(USLOTS * 16) : 0u;   // byte offset of the next chunk's slab
 #pragma unroll
     for (int k = 0; k < UR; ++k)
-        if (k * NT + wave * 64 < USLOTS) dma16(urs, uoff, usoff + k * NT * 16, smem + (HSLOTS + k * NT + wave * 64) * 4);
+        if (k * NT + wave * 64 < USLOTS) dma16_buf(urs, uoff, usoff + k * NT * 16, smem + (HSLOTS + k * NT + wave * 64) * 4);
     usoff += USLOTS * 16;
 
     // DMA plan of the halo: slot s = r*NT + tid -> (row, pixel, channel half); byte offsets into the current source, OOB = zeros
@@ -293,14 +225,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
 #define W4_HALO_PIECE(k, buf)                                                                  \
     do {                                                                                       \
         float *dst_ = smem + (buf) * IMG + ((k) * NT + wave * 64) * 4;                         \
-        dma16(dma_rsrc(hptr, hrange), hcur[(k) < HR ? (k) : 0], 0u, dst_);                     \
+        dma16_buf(dma_rsrc(hptr, hrange), hcur[(k) < HR ? (k) : 0], 0u, dst_);                 \
     } while (0)
 #define W4_HALO_END() hptr += cstr
     // U slab of the next chunk: UR wave-instructions (the last round exists in waves 0-3 only)
 #define W4_U_PIECE(k, buf)                                                                     \
     do {                                                                                       \
         if ((k) * NT + wave * 64 < USLOTS)                                                     \
-            dma16(urs, uoff, usoff + (k) * NT * 16, smem + (buf) * IMG + (HSLOTS + (k) * NT + wave * 64) * 4); \
+            dma16_buf(urs, uoff, usoff + (k) * NT * 16, smem + (buf) * IMG + (HSLOTS + (k) * NT + wave * 64) * 4); \
     } while (0)
 #define W4_U_END() usoff += USLOTS * 16
     static_assert(HR == 5 && UR == 5, "w4_piece_at and the vmcnt immediates below assume five pieces per pass");
@@ -459,7 +391,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
             if (i < 30) {
                 const int ao = i / 5, k = i % 5;
                 const int a = ao < 3 ? 2 * ao : 2 * ao - 5;      // rows 0, 2, 4 first (the first MFMA groups need only those)
-                d[a][k] = *(lds4_cv_f32x2 *)(sI + (a < 4 ? a_lo : a_hi) + (a * RSL + k) * 4);
+                d[a][k] = *(lds_cv_f32x2 *)(sI + (a < 4 ? a_lo : a_hi) + (a * RSL + k) * 4);
             }
         }
     };
@@ -475,7 +407,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         for (int h = 0; h < 2; ++h) {
             if (h == 1 && more2) W4_HALO_BEGIN(c + 2);
             // B fragments: one ds_read_b128 per group of two positions x two cout blocks, read one group ahead of its MFMAs
-#define W4_LOADU_H(dst, g, hh) dst = *(lds4_cv_f32x4 *)(sB + b_lane + ((g) * 2 + (hh)) * 256)
+#define W4_LOADU_H(dst, g, hh) dst = *(lds_cv_f32x4 *)(sB + b_lane + ((g) * 2 + (hh)) * 256)
 #define W4_LOADU(dst, g) W4_LOADU_H(dst, g, h)
 #define W4_LANDED(x) asm volatile("" ::"v"(x.w))
             W4_LOADU(u[0], 0);                          // the first fragment flies under the transform below
@@ -606,7 +538,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
         f32x2 w[4][3];
 #pragma unroll
         for (int b = 0; b < 3; ++b)
-            at6x2(pr(0 * 3 + b), pr(1 * 3 + b), pr(2 * 3 + b), pr(3 * 3 + b), pr(4 * 3 + b), pr(5 * 3 + b), w[0][b], w[1][b], w[2][b], w[3][b]);
+            at6(pr(0 * 3 + b), pr(1 * 3 + b), pr(2 * 3 + b), pr(3 * 3 + b), pr(4 * 3 + b), pr(5 * 3 + b), w[0][b], w[1][b], w[2][b], w[3][b]);
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
             if (jh == 0) {
@@ -620,7 +552,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(2, 2))) void
                 y[a][0] = s;
                 y[a][1] = t + t;                          // (= 2 t exactly)
                 y[a][2] = s * f32x2{4.f, 4.f};
-                y[a][3] = pk_fma(8.f, t, w[a][2]);
+                y[a][3] = wino_fma(8.f, t, w[a][2]);
             }
         }
     };
@@ -919,32 +851,16 @@ hipError_t launch_wino4_conv(ConvKind kind, const ConvArgs &a, hipStream_t st)
     a2.nwg_base = (int)nwg;
     const long grid = nwg * ks;
     if (grid > 0x7fffffffL) return hipErrorInvalidValue;
-    static std::atomic<unsigned long long> attr_mask{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_mask.load(std::memory_order_acquire) & bit)) {
-        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void *>(wino4_conv_f32<CONV3X3_RELU_POOL>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void *>(wino4_conv_f32<CONV3X3_RELU>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        hipError_t e3 = hipFuncSetAttribute(reinterpret_cast<const void *>(wino4_conv_f32<CONV3X3_RELU_DOT>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        hipError_t e4 = hipFuncSetAttribute(reinterpret_cast<const void *>(wino4_conv_f32<CONV3X3_RELU, 1>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
-        if (e1 != hipSuccess) return e1;
-        if (e2 != hipSuccess) return e2;
-        if (e3 != hipSuccess) return e3;
-        if (e4 != hipSuccess) return e4;
-        attr_mask.fetch_or(bit, std::memory_order_release);
-    }
+    const hipError_t ae = lds_opt_in<wino4_conv_f32<CONV3X3_RELU_POOL>, wino4_conv_f32<CONV3X3_RELU>, wino4_conv_f32<CONV3X3_RELU_DOT>,
+                                     wino4_conv_f32<CONV3X3_RELU, 1>>(LDS_BYTES);
+    if (ae != hipSuccess) return ae;
     static_assert(8 * (256 * 17 + 32) * sizeof(float) <= LDS_BYTES, "staging of the fused 1x1 epilogue must fit the images");
     if (ks > 1) {
         // slices (raw sums, plain variant whatever the layer's epilogue), then sum + bias + ReLU (+ pool)
         hipLaunchKernelGGL((wino4_conv_f32<CONV3X3_RELU, 1>), dim3((unsigned)grid), dim3(NT), LDS_BYTES, st, a2);
         hipError_t le = hipGetLastError();
         if (le != hipSuccess) return le;
-        return launch_wino_reduce(kind, a2, st);
+        return launch_conv_reduce(kind, a2, false, st);
     }
     if (kind == CONV3X3_RELU_DOT)
         hipLaunchKernelGGL(wino4_conv_f32<CONV3X3_RELU_DOT>, dim3((unsigned)grid), dim3(NT), LDS_BYTES, st, a2);

@@ -23,19 +23,11 @@
 //   have to agree).
 #include "adn_internal.h"
 
-#include <atomic>
-
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 namespace adn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-// volatile LDS view: keeps each patch read a single ds_read_b64 (see the bank note in the kernel)
-typedef const volatile f32x2 __attribute__((address_space(3))) lds_cv_f32x2;
-typedef const volatile f32x4 __attribute__((address_space(3))) lds_cv_f32x4;
 
 namespace {
 
@@ -56,12 +48,6 @@ __host__ __device__ __forceinline__ void wino_supertile(int nct, long ptiles, in
     }
 }
 
-__device__ __forceinline__ int wino_xcd_remap(int b, int nwg)
-{
-    const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-}
-
 // ------------------------------------------------------------------------------------------------
 // Staging: LDS-DMA.  The halo and the U slab of chunk c+1 are copied global -> LDS with global_load_lds_dwordx4
 // (1 KiB per wave instruction, no VGPR staging, no ds_write pass) into the image that is not being consumed; the
@@ -78,13 +64,12 @@ __device__ __forceinline__ int wino_xcd_remap(int b, int nwg)
 // ------------------------------------------------------------------------------------------------
 // (the copies go through buffer descriptors, dma16_buf in adn_internal.h: padding lanes are out of range and write zeros)
 
-// Geometry of the LDS-DMA kernel for NW waves (4: 16x16 px, two workgroups per CU; 8: 16x32 px, one per CU).
-// The 8-wave tile halves the bytes staged per MFMA (U slab shared by twice the pixels): the kernel is bound by
-// the CU's ~12 B/clk ingest rate, not by the matrix cores, so bytes per MFMA is what matters.
-template <int NW>
+// Geometry of the LDS-DMA kernel: 4 waves, 16x16 px, two workgroups per CU.  (An 8-wave workgroup per CU on a 16x32-pixel tile
+// halves the bytes staged per MFMA -- the kernel is bound by the CU's ~12 B/clk ingest rate, not by the matrix cores -- but measured
+// slower, 197 against 232 TFLOP/s: its two waves per SIMD run in lockstep.)
 struct DmaGeom {
-    static constexpr int NT = 64 * NW;
-    static constexpr int TWT = NW == 8 ? 16 : 8;           // winograd tiles per tile row
+    static constexpr int NW = 4, NT = 64 * NW;
+    static constexpr int TWT = 8;                          // winograd tiles per tile row
     static constexpr int TPW = 2 * TWT;                    // output pixels per tile row
     static constexpr int HW = TPW + 2;                     // halo columns
     static constexpr int SPP = 2;                          // 16-byte slots per halo pixel (8 channels, no pad slot)
@@ -95,11 +80,11 @@ struct DmaGeom {
     static constexpr int HR = (HUSED + NT - 1) / NT;       // DMA rounds for the halo
     static constexpr int UR = 1024 / NT;                   // DMA rounds for the U slab (16 pos x 8 ch x 32 couts)
     static constexpr int DBUF = (HR + UR) * NT * 4;        // floats per LDS image
-    static constexpr int SUP = NW == 8 ? 32 : 64;          // workgroups resident on one XCD
+    static constexpr int SUP = 64;                         // workgroups resident on one XCD
 };
 
 // SPLIT = 1: split-K launch for small batches (see ConvArgs::ksplit): the workgroup sums chunks [c0, c0 + nchunk/ksplit)
-// and stores raw partial sums; wino_reduce_kernel finishes the layer.
+// and stores raw partial sums; conv_reduce_kernel (conv_kernels.hip) finishes the layer.
 // SRC = 1: the source is the 1-channel network input and the halo of Conv2d(1->64)+BN+ReLU is computed on the fly
 // (fused first layer, see ConvArgs::firstw): per chunk a thread evaluates its halo slots (4 channels x 9 taps from a
 // 20x20 input window and the first layer's weights, both kept in LDS behind the two images) and writes them where the
@@ -107,18 +92,18 @@ struct DmaGeom {
 template <int EPI, int NW, int SPLIT, int SRC = 0>
 __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(2, 2))) void wino_conv_dma_f32(const ConvArgs p)
 {
-    static_assert(SRC == 0 || (NW == 4 && SPLIT == 0), "fused first layer: 4-wave unsplit kernel only");
+    static_assert(NW == 4, "one geometry (DmaGeom); NW stays in the parameter list: profiles and tools match on the kernel's name");
+    static_assert(SRC == 0 || SPLIT == 0, "fused first layer: unsplit kernel only");
     constexpr int XS = 20;                             // input window edge (halo 18 + 1 on each side)
     constexpr int XWIN = 416;                          // floats reserved for the window (400 used, 16-byte multiple)
-    using G = DmaGeom<NW>;
+    using G = DmaGeom;
     constexpr int WBN = 32, NT = G::NT, HR = G::HR, UR = G::UR, DBUF = G::DBUF, DROW = G::DROW, PSTR = G::PSTR;
     extern __shared__ __attribute__((aligned(16))) float smem[];   // the ONLY LDS object (two images)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // provably wave-uniform (DMA base, tile block)
-    const int wr = NW == 8 ? wave >> 1 : wave;                     // tile-row pair
-    const int wc = NW == 8 ? wave & 1 : 0;                         // block of 8 tile columns
+    const int wr = wave;                                           // tile-row pair
     const int ti = lane & 15, q = lane >> 4;
 
     // Workgroup -> (pixel tile, cout tile).  After the XCD remap, SUP consecutive ids run together on one XCD;
@@ -129,7 +114,7 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(2, 2
     const int split = SPLIT ? (int)blockIdx.x / p.nwg_base : 0;
     const int nloc = SPLIT ? p.nchunk / p.ksplit : p.nchunk;      // chunks this workgroup sums
     const int c0 = split * nloc;                                   // first of them
-    int lid = SPLIT ? wino_xcd_remap((int)blockIdx.x - split * p.nwg_base, p.nwg_base) : wino_xcd_remap(blockIdx.x, gridDim.x);
+    int lid = SPLIT ? xcd_remap((int)blockIdx.x - split * p.nwg_base, p.nwg_base) : xcd_remap(blockIdx.x, gridDim.x);
     int gc, gp;
     wino_supertile(p.nct, (long)p.N * p.tilesY * p.tilesX, G::SUP, gc, gp);
     const int ncg = p.nct / gc;
@@ -160,11 +145,11 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(2, 2
     for (int r = 0; r < HR; ++r) {
         const int s = r * NT + tid;
         const int row = s / G::RSLOTS, k = s - row * G::RSLOTS;
-        // NW == 4: the row's pad slot sits in the MIDDLE (physical slot 16), so pixels 8.. are shifted by 16 bytes and
+        // the row's pad slot sits in the MIDDLE (physical slot 16), so pixels 8.. are shifted by 16 bytes and
         // the 8 even pixels a patch read touches fall on 8 different bank quads (see a_lane below)
-        const int lk = (NW == 4) ? (k < 16 ? k : k - 1) : k;          // logical slot = pixel * 2 + part
+        const int lk = k < 16 ? k : k - 1;                            // logical slot = pixel * 2 + part
         const int pix = lk / G::SPP, part = lk - pix * G::SPP;
-        const bool data = s < G::HUSED && !(NW == 4 && k == 16) && pix < G::HW;
+        const bool data = s < G::HUSED && k != 16 && pix < G::HW;
         const int gy = gy0 + row, gx = gx0 + pix;
         const int y0 = gy - p.s0.offY, x0 = gx - p.s0.offX;
         // byte offsets inside ONE 8-channel block of the source image (C8 layout; unsigned: H * W * 32 bytes may pass 2^31),
@@ -271,12 +256,12 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(2, 2
 
     // patch reads: lane (q, ti) reads channels 2q, 2q+1 of pixel column 2*(tile column) + b.  In a 32-lane LDS read
     // group the 8 tile columns are 16 dwords apart = only 4 distinct bank quads of 64; with the row's pad slot moved
-    // to the middle (NW == 4) columns 8.. are 4 dwords further and all 16 (2 rows x 8 columns) quads differ.
+    // to the middle columns 8.. are 4 dwords further and all 16 (2 rows x 8 columns) quads differ.
     int a_lane[4];
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-        const int col = 2 * (8 * wc + (ti & 7)) + b;
-        const int shift = (NW == 4 && 2 * col + (q >> 1) >= 16) ? 4 : 0;
+        const int col = 2 * (ti & 7) + b;
+        const int shift = (2 * col + (q >> 1) >= 16) ? 4 : 0;
         a_lane[b] = (2 * (2 * wr + (ti >> 3))) * DROW + col * PSTR + 2 * q + shift;
     }
     const int b_lane = (q * 16 + ti) * 4;                    // U slab [pos/2][j][q][n%16][pos%2][2]
@@ -406,7 +391,7 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(2, 2
         // Lane (q, ti) holds couts 16j + ti of the 2x2 pixels of tiles 4q .. 4q+3: it forms its two-channel partial dot
         // per pixel, the 16 lanes' partials meet in LDS ([pixel][17], the images are free after the loop's last barrier)
         // and thread p adds the 16 partials of pixel p in a fixed order: deterministic, no atomics.
-        static_assert(NW == 4 && SPLIT == 0, "fused 1x1 epilogue: 4-wave unsplit kernel only");
+        static_assert(SPLIT == 0, "fused 1x1 epilogue: unsplit kernel only");
         const float w0 = p.dotw[ct * WBN + ti], w1 = p.dotw[ct * WBN + 16 + ti];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -452,7 +437,7 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(2, 2
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int tile = 4 * q + r;
-            const int tyw = 2 * wr + (tile >> 3), txw = 8 * wc + (tile & 7);
+            const int tyw = 2 * wr + (tile >> 3), txw = tile & 7;
             float s0[4], s1[4];
 #pragma unroll
             for (int x = 0; x < 4; ++x) {
@@ -491,178 +476,59 @@ __global__ __launch_bounds__(64 * NW, 2) __attribute__((amdgpu_waves_per_eu(2, 2
     }
 }
 
-// Second launch of a split-K layer: out = ReLU(sum over splits (fixed order) + bias), plus the 2x2 max-pool.
-// Pooling form: one thread per (2x2 pixel block, 4 output channels); plain form: one thread per (pixel, 4 output channels) -- the
-// layers that are split have few pixels (one clip at 32x16 ... 128x64), the launch is latency: more threads, shorter threads.
-template <int EPI>
-__global__ __launch_bounds__(256) void wino_reduce_kernel(const float *__restrict__ partial, const float *__restrict__ bias,
-                                                          float *__restrict__ out, float *__restrict__ pool, int ksplit,
-                                                          int N, int H, int W, int Cout)
-{
-    constexpr bool POOL = EPI == CONV3X3_RELU_POOL;
-    const int cq = Cout / 4, bh = POOL ? (H + 1) / 2 : H, bw = POOL ? (W + 1) / 2 : W;
-    const long total = (long)N * bh * bw * cq;
-    const long id = (long)blockIdx.x * 256 + threadIdx.x;
-    if (id >= total) return;
-    const int c4 = (int)(id % cq) * 4;
-    long r = id / cq;
-    const int bx = (int)(r % bw);
-    r /= bw;
-    const int by = (int)(r % bh), n = (int)(r / bh);
-    const f32x4 bv = *reinterpret_cast<const f32x4 *>(bias + c4);
-    const size_t img = (size_t)H * W * Cout, split_stride = (size_t)N * img;
-    auto finish = [&](int gy, int gx) {
-        const size_t o = (size_t)n * img + ((size_t)gy * W + gx) * Cout + c4;      // partial sums: pixel-major
-        f32x4 t[ADN_MAX_KSPLIT];                             // all copies in flight, then added in split order
-#pragma unroll
-        for (int s = 0; s < ADN_MAX_KSPLIT; ++s)
-            if (s < ksplit) t[s] = *reinterpret_cast<const f32x4 *>(partial + s * split_stride + o);
-        f32x4 v = t[0];
-#pragma unroll
-        for (int s = 1; s < ADN_MAX_KSPLIT; ++s)
-            if (s < ksplit) v += t[s];
-        v += bv;
-        v.x = relu_nan(v.x); v.y = relu_nan(v.y); v.z = relu_nan(v.z); v.w = relu_nan(v.w);
-        *reinterpret_cast<f32x4 *>(out + (size_t)n * img + act_off<float>(Cout, (long)H * W, (long)gy * W + gx, c4)) = v;   // C8
-        return v;
-    };
-    if constexpr (!POOL) {
-        finish(by, bx);
-    } else {
-        f32x4 mx = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int a = 0; a < 2; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                const int gy = 2 * by + a, gx = 2 * bx + b;
-                if (gy >= H || gx >= W) continue;
-                const f32x4 v = finish(gy, gx);
-                mx.x = max_nan(mx.x, v.x); mx.y = max_nan(mx.y, v.y); mx.z = max_nan(mx.z, v.z); mx.w = max_nan(mx.w, v.w);
-            }
-        if (by < H / 2 && bx < W / 2)
-            *reinterpret_cast<f32x4 *>(pool + (size_t)n * (H / 2) * (W / 2) * Cout +
-                                       act_off<float>(Cout, (long)(H / 2) * (W / 2), (long)by * (W / 2) + bx, c4)) = mx;
-    }
-}
+}  // namespace
 
-// tile grid of the NW-wave kernel: WT x TPW pixels x WINO_BN couts per workgroup
-template <int NW>
-long wino_tiles_n(ConvArgs &a)
+// tile grid of the kernel: WT x TPW pixels x WINO_BN couts per workgroup
+long wino_tiles(ConvArgs &a)
 {
     a.tilesY = (a.H + WT - 1) / WT;
-    a.tilesX = (a.W + DmaGeom<NW>::TPW - 1) / DmaGeom<NW>::TPW;
+    a.tilesX = (a.W + DmaGeom::TPW - 1) / DmaGeom::TPW;
     a.nct = a.Cout / WINO_BN;
     return conv_workgroups(a);                          // without the padding of the last supertile: those exit at once
 }
 
-template <int NW>
-hipError_t launch_wino_dma_n(ConvKind kind, const ConvArgs &a, hipStream_t st)
+hipError_t launch_wino_conv(ConvKind kind, const ConvArgs &a, hipStream_t st)
 {
-    using G = DmaGeom<NW>;
+    using G = DmaGeom;
     constexpr size_t lds = (size_t)2 * G::DBUF * sizeof(float);
     ConvArgs a2 = a;
-    wino_tiles_n<NW>(a2);
+    wino_tiles(a2);
     // grid padded to whole supertiles (see the kernel): gp pixel tiles x gc cout tiles, gc*gp = SUP
     const long ptiles = (long)a2.N * a2.tilesY * a2.tilesX;
     int gc, gp;
     wino_supertile(a2.nct, ptiles, G::SUP, gc, gp);
     const long nwg = ((ptiles + gp - 1) / gp) * gp * a2.nct;
     if (nwg <= 0 || nwg > 0x7fffffffL) return hipErrorInvalidValue;
-    // the attribute is per device: remember which devices of this process have it (one process per GPU is the
-    // deployment model, but a handle may be created on any device)
-    static std::atomic<unsigned long long> attr_mask{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_mask.load(std::memory_order_acquire) & bit)) {
-        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void *>(wino_conv_dma_f32<CONV3X3_RELU_POOL, NW, 0>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void *>(wino_conv_dma_f32<CONV3X3_RELU, NW, 0>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipError_t e3 = hipFuncSetAttribute(reinterpret_cast<const void *>(wino_conv_dma_f32<CONV3X3_RELU, NW, 1>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e1 != hipSuccess) return e1;
-        if (e2 != hipSuccess) return e2;
-        if (e3 != hipSuccess) return e3;
-        if constexpr (NW == 4) {
-            e1 = hipFuncSetAttribute(reinterpret_cast<const void *>(wino_conv_dma_f32<CONV3X3_RELU_DOT, 4, 0>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e1 != hipSuccess) return e1;
-        }
-        attr_mask.fetch_or(bit, std::memory_order_release);
-    }
-    hipError_t le;
+    hipError_t e = lds_opt_in<wino_conv_dma_f32<CONV3X3_RELU_POOL, 4, 0>, wino_conv_dma_f32<CONV3X3_RELU, 4, 0>,
+                              wino_conv_dma_f32<CONV3X3_RELU, 4, 1>, wino_conv_dma_f32<CONV3X3_RELU_DOT, 4, 0>>(lds);
+    if (e != hipSuccess) return e;
     if (a2.ksplit > 1 && kind == CONV3X3_RELU_DOT) return hipErrorInvalidValue;      // the fused layer is never split
     if (a2.ksplit > 1) {
         // split-K: raw partial sums first (the epilogue variant does not matter), then sum + bias + ReLU (+ pool)
         if (!a2.partial || a2.nchunk % a2.ksplit || (a2.Cout & 3) || a2.ksplit > ADN_MAX_KSPLIT) return hipErrorInvalidValue;
         a2.nwg_base = (int)nwg;
-        hipLaunchKernelGGL((wino_conv_dma_f32<CONV3X3_RELU, NW, 1>), dim3((unsigned)(nwg * a2.ksplit)), dim3(64 * NW), lds,
-                           st, a2);
-        le = hipGetLastError();
-        if (le != hipSuccess) return le;
-        return launch_wino_reduce(kind, a2, st);
+        hipLaunchKernelGGL((wino_conv_dma_f32<CONV3X3_RELU, 4, 1>), dim3((unsigned)(nwg * a2.ksplit)), dim3(G::NT), lds, st, a2);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        return launch_conv_reduce(kind, a2, false, st);
     }
     if (a2.firstw) {
         // fused first layer: down1's second conv (+pool) fed by the network input
-        if constexpr (NW == 4) {
-            if (kind != CONV3X3_RELU_POOL || !a2.firstb || a2.ksplit > 1 || a2.nchunk != 8) return hipErrorInvalidValue;
-            constexpr size_t lds1 = lds + (416 + 640) * sizeof(float);
-            static std::atomic<unsigned long long> attr1{0};
-            if (!(attr1.load(std::memory_order_acquire) & bit)) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(wino_conv_dma_f32<CONV3X3_RELU_POOL, 4, 0, 1>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-                if (e != hipSuccess) return e;
-                attr1.fetch_or(bit, std::memory_order_release);
-            }
-            hipLaunchKernelGGL((wino_conv_dma_f32<CONV3X3_RELU_POOL, 4, 0, 1>), dim3((unsigned)nwg), dim3(256), lds1, st, a2);
-            return hipGetLastError();
-        } else {
-            return hipErrorInvalidValue;
-        }
+        if (kind != CONV3X3_RELU_POOL || !a2.firstb || a2.nchunk != 8) return hipErrorInvalidValue;
+        constexpr size_t lds1 = lds + (416 + 640) * sizeof(float);
+        e = lds_opt_in<wino_conv_dma_f32<CONV3X3_RELU_POOL, 4, 0, 1>>(lds1);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((wino_conv_dma_f32<CONV3X3_RELU_POOL, 4, 0, 1>), dim3((unsigned)nwg), dim3(G::NT), lds1, st, a2);
+        return hipGetLastError();
     }
     if (kind == CONV3X3_RELU_DOT) {
-        if constexpr (NW == 4) {
-            if (!a2.dotw || !a2.dot_out) return hipErrorInvalidValue;
-            hipLaunchKernelGGL((wino_conv_dma_f32<CONV3X3_RELU_DOT, 4, 0>), dim3((unsigned)nwg), dim3(256), lds, st, a2);
-        } else {
-            return hipErrorInvalidValue;
-        }
+        if (!a2.dotw || !a2.dot_out) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((wino_conv_dma_f32<CONV3X3_RELU_DOT, 4, 0>), dim3((unsigned)nwg), dim3(G::NT), lds, st, a2);
     } else if (kind == CONV3X3_RELU_POOL)
-        hipLaunchKernelGGL((wino_conv_dma_f32<CONV3X3_RELU_POOL, NW, 0>), dim3((unsigned)nwg), dim3(64 * NW), lds, st, a2);
+        hipLaunchKernelGGL((wino_conv_dma_f32<CONV3X3_RELU_POOL, 4, 0>), dim3((unsigned)nwg), dim3(G::NT), lds, st, a2);
     else
-        hipLaunchKernelGGL((wino_conv_dma_f32<CONV3X3_RELU, NW, 0>), dim3((unsigned)nwg), dim3(64 * NW), lds, st, a2);
-    le = hipGetLastError();
-    return le;
-}
-
-}  // namespace
-
-// second launch of a split-K 3x3 layer (either Winograd kernel): a.partial [split][N][H][W][Cout] -> a.out (+ a.pool)
-hipError_t launch_wino_reduce(ConvKind kind, const ConvArgs &a, hipStream_t st)
-{
-    if (a.ksplit < 2 || a.ksplit > ADN_MAX_KSPLIT || !a.partial || (a.Cout & 3) || (kind != CONV3X3_RELU && kind != CONV3X3_RELU_POOL))
-        return hipErrorInvalidValue;
-    const long items = kind == CONV3X3_RELU_POOL ? (long)a.N * ((a.H + 1) / 2) * ((a.W + 1) / 2) * (a.Cout / 4)
-                                                 : (long)a.N * a.H * a.W * (a.Cout / 4);
-    if (items <= 0 || items > 0x7fffffffL * 256L) return hipErrorInvalidValue;
-    const unsigned blocks = (unsigned)((items + 255) / 256);
-    if (kind == CONV3X3_RELU_POOL)
-        hipLaunchKernelGGL(wino_reduce_kernel<CONV3X3_RELU_POOL>, dim3(blocks), dim3(256), 0, st, a.partial, a.bias,
-                           static_cast<float *>(a.out), static_cast<float *>(a.pool), a.ksplit, a.N, a.H, a.W, a.Cout);
-    else
-        hipLaunchKernelGGL(wino_reduce_kernel<CONV3X3_RELU>, dim3(blocks), dim3(256), 0, st, a.partial, a.bias,
-                           static_cast<float *>(a.out), static_cast<float *>(nullptr), a.ksplit, a.N, a.H, a.W, a.Cout);
+        hipLaunchKernelGGL((wino_conv_dma_f32<CONV3X3_RELU, 4, 0>), dim3((unsigned)nwg), dim3(G::NT), lds, st, a2);
     return hipGetLastError();
-}
-
-long wino_tiles(ConvArgs &a) { return wino_tiles_n<4>(a); }      // (the kernel launch_wino_conv runs)
-
-hipError_t launch_wino_conv(ConvKind kind, const ConvArgs &a, hipStream_t st)
-{
-    // (an 8-wave workgroup per CU on a 16x32-pixel tile -- DmaGeom<8>: fewer staged bytes per MFMA -- measured slower, 197 vs
-    // 232 TFLOP/s: its two waves per SIMD run in lockstep)
-    return launch_wino_dma_n<4>(kind, a, st);
 }
 
 }  // namespace adn

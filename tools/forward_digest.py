@@ -26,6 +26,8 @@ MODES = {                                   # tests/test_gpu_variants.py::MODES 
     "direct": {"ADN_CONV_ALGO": "direct"},
     "splitk": {"ADN_WINO_SPLITK": "1"},
     "convt_exact": {"ADN_CONVT_SPLIT": "0"},
+    "wino_gemm_off": {"ADN_WINO_GEMM": "0"},            # the three-stage F(4x4,3x3) form never / wherever its V and M fit
+    "wino_gemm_all": {"ADN_WINO_GEMM": "2"},
     "f16_conv32": {"ADN_F16_CONV": "32"},
     "f16_first0": {"ADN_F16_FIRST": "0"},
     "f16_convt_dma": {"ADN_F16_CONVT": "dma"},
