@@ -85,6 +85,11 @@ def load() -> ctypes.CDLL:
         L.adn_stream_reset.argtypes = [vp, sz, ci, ci, ci, ci, ci, ci, ci, vp]
         L.adn_stream_analyze.argtypes = [vp, sz, vp, cl, ci, cl, ci, cl, ci, ci, ci, ci, ci, ci, vp, vp]
         L.adn_stream_emit.argtypes = [vp, sz, vp, ci, cl, ci, cl, ci, ci, ci, ci, ci, ci, vp, cl, vp]
+        L.adn_stream_pool_state_bytes.argtypes = [ci, ci, ci, ci, ci, ci, cl, ctypes.POINTER(sz)]
+        L.adn_stream_pool_reset.argtypes = [vp, sz, ci, ci, ci, ci, ci, ci, cl, ci, vp]
+        L.adn_stream_pool_write.argtypes = [vp, sz, ci, ci, ci, ci, ci, ci, cl, ci, vp, cl, cl, vp]
+        L.adn_stream_pool_analyze.argtypes = [vp, sz, ci, ci, ci, ci, ci, ci, cl, vp, ci, vp, vp]
+        L.adn_stream_pool_emit.argtypes = [vp, sz, ci, ci, ci, ci, ci, ci, cl, vp, ci, vp, vp, cl, vp]
         L.adn_resample_stream_plan.argtypes = [ci, ci, cl, ci, ctypes.POINTER(cl), ctypes.POINTER(cl), ctypes.POINTER(cl)]
         L.adn_resample_stream_state_bytes.argtypes = [ci, ci, ci, ctypes.POINTER(sz)]
         L.adn_resample_stream.argtypes = [vp, sz, vp, cl, ci, cl, cl, cl, ci, ci, ci, vp, cl, vp]
@@ -98,10 +103,17 @@ def load() -> ctypes.CDLL:
                      "adn_istft_workspace_bytes", "adn_istft",
                      "adn_denoise_plan", "adn_denoise_windows", "adn_denoise_stitch", "adn_denoise_resynth",
                      "adn_stream_plan", "adn_stream_state_bytes", "adn_stream_reset", "adn_stream_analyze", "adn_stream_emit",
+                     "adn_stream_pool_state_bytes", "adn_stream_pool_reset", "adn_stream_pool_write", "adn_stream_pool_analyze",
+                     "adn_stream_pool_emit",
                      "adn_resample_stream_plan", "adn_resample_stream_state_bytes", "adn_resample_stream"):
             getattr(L, name).restype = ci
         _lib = L
         return L
+
+
+class StreamPoolRow(ctypes.Structure):
+    """``adn_stream_pool_row`` of include/adn.h: one row of a pool call."""
+    _fields_ = [("slot", ctypes.c_int), ("step", ctypes.c_int), ("final_length", ctypes.c_int)]
 
 
 def staging_device():
@@ -131,5 +143,6 @@ EXPORTED_SYMBOLS = (
     "adn_resample_length", "adn_resample_prepare", "adn_resample", "adn_mix_snr_workspace_bytes", "adn_mix_snr", "adn_reverb",
     "adn_denoise_plan", "adn_denoise_windows", "adn_denoise_stitch", "adn_denoise_resynth",
     "adn_stream_plan", "adn_stream_state_bytes", "adn_stream_reset", "adn_stream_analyze", "adn_stream_emit",
+    "adn_stream_pool_state_bytes", "adn_stream_pool_reset", "adn_stream_pool_write", "adn_stream_pool_analyze", "adn_stream_pool_emit",
     "adn_resample_stream_plan", "adn_resample_stream_state_bytes", "adn_resample_stream",
 )

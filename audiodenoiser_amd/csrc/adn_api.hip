@@ -429,7 +429,7 @@ int adn_denoise_resynth(const float *y, const float *spec, int n_clips, long len
 static const char *stream_plan_text = ": need a power-of-two n_fft in [64, 4096], 1 <= hop <= n_fft / 4, window >= 16, block >= 1, "
                                       "lookahead >= 0, block + lookahead <= window, n_streams >= 1 and 1 <= max_steps <= 65536";
 
-// What a call of n_steps steps from `first` covers (adn_internal.h, StreamCall); every quantity follows from the step index.
+// The limits of a call of n_steps steps from `first`, then what it covers (adn_internal.h, stream_call_of).
 static int stream_call(const char *who, const adn::StreamGeom &g, long first, int n_steps, long final_length, adn::StreamCall *c)
 {
     const std::string w(who);
@@ -437,44 +437,17 @@ static int stream_call(const char *who, const adn::StreamGeom &g, long first, in
     if (n_steps > g.S - 1) return fail(ADN_ERR_INVALID, w + ": n_steps exceeds the max_steps the state was sized for");
     if (final_length < -1 || final_length == 0 || final_length >= (1L << 30))
         return fail(ADN_ERR_INVALID, w + ": final_length must be -1 (the stream runs) or the stream's length, 1 <= length < 2^30");
-    const long B = g.B, D = g.B + g.A, hop = g.hop, M = g.n_fft / 2, keep = g.n_fft - g.hop;
+    const long B = g.B, D = g.B + g.A, hop = g.hop;
     if (first >= (1L << 30)) return fail(ADN_ERR_INVALID, w + ": step index too large");
     const long last = first + n_steps - 1;
     // sample positions are 32-bit inside the kernels: the last position a call touches stays below 2^30 (flush before that)
     if ((last * B + D) * hop + 2L * g.n_fft >= (1L << 30))
         return fail(ADN_ERR_INVALID, w + ": the steps reach past sample 2^30 of the stream (32-bit positions inside the kernels); flush the stream before");
-    c->first = (int)first;
-    c->n_steps = n_steps;
-    c->T = -1;
-    c->L = -1;
-    bool closes = false;
     if (final_length > 0) {
         const long T = 1 + final_length / hop, K = (T + B - 1) / B;
         if (last >= K) return fail(ADN_ERR_INVALID, w + ": steps past the last step ceil((1 + final_length / hop) / block) of the stream");
-        c->T = (int)T;
-        c->L = (int)final_length;
-        closes = last == K - 1;
     }
-    c->base = first == 0 ? 0 : (int)((first * B + g.A - 1) * hop + M);
-    c->end = (int)((last * B + D - 1) * hop + M);
-    c->f_new0 = first == 0 ? 0 : (int)(first * B + g.A);
-    c->f_new1 = (int)(last * B + D);
-    c->slot_in = first == 0 ? 0 : (int)((first - 1) % g.S);
-    c->slot_out = (int)(last % g.S);
-    c->f_first = (int)(first * B);
-    c->f_last = (int)((last + 1) * B - 1);
-    c->p_begin = (int)(first * B * hop);
-    c->p_first = c->p_begin > M ? c->p_begin : (int)M;
-    if (closes) {
-        if (c->f_last > c->T - 1) c->f_last = c->T - 1;
-        c->p_out = (int)(final_length + M);
-        c->p_tail = 0x7fffffff;
-        c->p_end = c->p_out;
-    } else {
-        c->p_out = (int)((last + 1) * B * hop);
-        c->p_tail = c->p_out;
-        c->p_end = (int)(c->p_out + keep);
-    }
+    *c = adn::stream_call_of(g, first, n_steps, final_length);
     return ADN_OK;
 }
 
@@ -569,6 +542,156 @@ int adn_stream_emit(void *state, size_t state_bytes, const float *y, int n_strea
                                            static_cast<hipStream_t>(stream));
     if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_stream_emit: grid too large");
     ADN_LAUNCH(e, "adn_stream_emit");
+    return ADN_OK;
+}
+
+/* ---- stream pool: independent streams in one state, their ready steps batched (adn.h, "stream pool") ---------------- */
+static_assert(ADN_STREAM_POOL_MAX_ROWS == adn::STREAM_POOL_MAX_ROWS && sizeof(adn_stream_pool_row) == sizeof(adn::StreamPoolRow),
+              "adn.h and adn_internal.h disagree about the pool's row table");
+static const char *stream_pool_text = ": need the plan of the stream section (power-of-two n_fft in [64, 4096], 1 <= hop <= n_fft / 4, "
+                                      "window >= 16, block >= 1, lookahead >= 0, block + lookahead <= window), 1 <= n_slots <= 2^20 and "
+                                      "n_fft - hop + (block + lookahead - 1) hop + n_fft / 2 + block hop <= ring_samples <= 2^28";
+
+struct PoolState {
+    adn::StreamGeom g;
+    long ring_off, total, R;
+};
+
+static int pool_state(const char *who, void *state, size_t state_bytes, int n_slots, int n_fft, int hop, int window, int block,
+                      int lookahead, long ring, PoolState *p)
+{
+    const std::string w(who);
+    if (!state) return fail(ADN_ERR_INVALID, w + ": null pointer");
+    if (!adn::stream_pool_geom(n_slots, n_fft, hop, window, block, lookahead, ring, &p->g, &p->ring_off, &p->total))
+        return fail(ADN_ERR_INVALID, w + stream_pool_text);
+    if (state_bytes < (size_t)p->total * sizeof(float)) return fail(ADN_ERR_WORKSPACE, w + ": state smaller than adn_stream_pool_state_bytes");
+    if (!aligned_to(state, 8)) return fail(ADN_ERR_INVALID, w + ": state must be 8-byte aligned");
+    p->R = ring;
+    return ADN_OK;
+}
+
+// The row table of a call, every row inside the stream section's limits; max_new / max_span: the most frames a row transforms and
+// the most positions a row's emit covers (the grids are sized for them); max_out: the most samples a row writes out.
+static int pool_rows(const char *who, const PoolState &p, int n_slots, const adn_stream_pool_row *rows, int n_rows,
+                     adn::StreamPoolRows *t, int *max_new, int *max_span, long *max_out)
+{
+    const std::string w(who);
+    if (!rows) return fail(ADN_ERR_INVALID, w + ": null pointer");
+    if (n_rows < 1 || n_rows > ADN_STREAM_POOL_MAX_ROWS)
+        return fail(ADN_ERR_INVALID, w + ": need 1 <= n_rows <= ADN_STREAM_POOL_MAX_ROWS (call again for the rest)");
+    *max_new = *max_span = 0;
+    *max_out = 0;
+    for (int i = 0; i < n_rows; ++i) {
+        const adn_stream_pool_row r = rows[i];
+        if (r.slot < 0 || r.slot >= n_slots) return fail(ADN_ERR_INVALID, w + ": a row's slot is outside [0, n_slots)");
+        for (int j = 0; j < i; ++j)
+            if (rows[j].slot == r.slot) return fail(ADN_ERR_INVALID, w + ": a slot is named twice in one call (one step per stream and call)");
+        adn::StreamCall c;
+        const int rc = stream_call(who, p.g, r.step, 1, r.final_length, &c);
+        if (rc != ADN_OK) return rc;
+        if (c.f_new1 - c.f_new0 > *max_new) *max_new = c.f_new1 - c.f_new0;
+        if (c.p_end - c.p_begin > *max_span) *max_span = c.p_end - c.p_begin;
+        if ((long)c.p_out - c.p_first > *max_out) *max_out = (long)c.p_out - c.p_first;
+        t->row[i].slot = r.slot;
+        t->row[i].step = r.step;
+        t->row[i].final_length = r.final_length;
+    }
+    t->ring_off = p.ring_off;
+    t->R = (int)p.R;
+    t->n = n_rows;
+    return ADN_OK;
+}
+
+int adn_stream_pool_state_bytes(int n_slots, int n_fft, int hop, int window, int block, int lookahead, long ring_samples, size_t *bytes)
+{
+    PoolState p;
+    if (!bytes) return fail(ADN_ERR_INVALID, "adn_stream_pool_state_bytes: null pointer");
+    if (!adn::stream_pool_geom(n_slots, n_fft, hop, window, block, lookahead, ring_samples, &p.g, &p.ring_off, &p.total))
+        return fail(ADN_ERR_INVALID, std::string("adn_stream_pool_state_bytes") + stream_pool_text);
+    *bytes = (size_t)p.total * sizeof(float);
+    return ADN_OK;
+}
+
+int adn_stream_pool_reset(void *state, size_t state_bytes, int n_slots, int n_fft, int hop, int window, int block, int lookahead,
+                          long ring_samples, int slot, void *stream)
+{
+    PoolState p;
+    const int rc = pool_state("adn_stream_pool_reset", state, state_bytes, n_slots, n_fft, hop, window, block, lookahead, ring_samples, &p);
+    if (rc != ADN_OK) return rc;
+    if (slot < -1 || slot >= n_slots) return fail(ADN_ERR_INVALID, "adn_stream_pool_reset: slot must be -1 (all) or in [0, n_slots)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *s = static_cast<float *>(state);
+    if (slot < 0) {
+        ADN_HIP(hipMemsetAsync(s, 0, (size_t)p.total * sizeof(float), st));
+        return ADN_OK;
+    }
+    const long F = n_fft / 2 + 1, keep = n_fft - hop;
+    const long off[4] = {p.g.x_off + slot * 2 * F * p.g.RX, p.g.mag_off + slot * F * p.g.RM, p.g.tail_off + slot * keep * p.g.S,
+                         p.ring_off + slot * p.R};
+    const long len[4] = {2 * F * p.g.RX, F * p.g.RM, keep * p.g.S, p.R};
+    for (int i = 0; i < 4; ++i) ADN_HIP(hipMemsetAsync(s + off[i], 0, (size_t)len[i] * sizeof(float), st));
+    return ADN_OK;
+}
+
+int adn_stream_pool_write(void *state, size_t state_bytes, int n_slots, int n_fft, int hop, int window, int block, int lookahead,
+                          long ring_samples, int slot, const float *audio, long n, long position, void *stream)
+{
+    PoolState p;
+    const int rc = pool_state("adn_stream_pool_write", state, state_bytes, n_slots, n_fft, hop, window, block, lookahead, ring_samples, &p);
+    if (rc != ADN_OK) return rc;
+    if (slot < 0 || slot >= n_slots) return fail(ADN_ERR_INVALID, "adn_stream_pool_write: slot is outside [0, n_slots)");
+    if (n < 0 || n > p.R) return fail(ADN_ERR_INVALID, "adn_stream_pool_write: need 0 <= n <= ring_samples");
+    if (position < 0 || position + n >= (1L << 30))
+        return fail(ADN_ERR_INVALID, "adn_stream_pool_write: need position >= 0 and position + n < 2^30 (32-bit positions inside the kernels)");
+    if (n == 0) return ADN_OK;
+    if (!audio) return fail(ADN_ERR_INVALID, "adn_stream_pool_write: null pointer");
+    if (!aligned_to(audio, 4)) return fail(ADN_ERR_INVALID, "adn_stream_pool_write: audio must be 4-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *ring = static_cast<float *>(state) + p.ring_off + slot * p.R;
+    const long at = position % p.R, head = n < p.R - at ? n : p.R - at;
+    ADN_HIP(hipMemcpyAsync(ring + at, audio, (size_t)head * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (n > head) ADN_HIP(hipMemcpyAsync(ring, audio + head, (size_t)(n - head) * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return ADN_OK;
+}
+
+int adn_stream_pool_analyze(void *state, size_t state_bytes, int n_slots, int n_fft, int hop, int window, int block, int lookahead,
+                            long ring_samples, const adn_stream_pool_row *rows, int n_rows, float *windows_out, void *stream)
+{
+    PoolState p;
+    adn::StreamPoolRows t = {};
+    int max_new, max_span;
+    long max_out;
+    int rc = pool_state("adn_stream_pool_analyze", state, state_bytes, n_slots, n_fft, hop, window, block, lookahead, ring_samples, &p);
+    if (rc != ADN_OK) return rc;
+    if (!windows_out) return fail(ADN_ERR_INVALID, "adn_stream_pool_analyze: null pointer");
+    if (!aligned_to(windows_out, 4)) return fail(ADN_ERR_INVALID, "adn_stream_pool_analyze: windows_out must be 4-byte aligned");
+    rc = pool_rows("adn_stream_pool_analyze", p, n_slots, rows, n_rows, &t, &max_new, &max_span, &max_out);
+    if (rc != ADN_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    ADN_LAUNCH(adn::launch_stream_pool_frames(p.g, t, max_new, static_cast<float *>(state), st), "adn_stream_pool_analyze");
+    ADN_HIP(adn::launch_stream_pool_windows(static_cast<const float *>(state), p.g, t, windows_out, st));
+    return ADN_OK;
+}
+
+int adn_stream_pool_emit(void *state, size_t state_bytes, int n_slots, int n_fft, int hop, int window, int block, int lookahead,
+                         long ring_samples, const adn_stream_pool_row *rows, int n_rows, const float *y, float *audio_out,
+                         long out_stride, void *stream)
+{
+    PoolState p;
+    adn::StreamPoolRows t = {};
+    int max_new, max_span;
+    long max_out;
+    int rc = pool_state("adn_stream_pool_emit", state, state_bytes, n_slots, n_fft, hop, window, block, lookahead, ring_samples, &p);
+    if (rc != ADN_OK) return rc;
+    if (!y) return fail(ADN_ERR_INVALID, "adn_stream_pool_emit: null pointer");
+    rc = pool_rows("adn_stream_pool_emit", p, n_slots, rows, n_rows, &t, &max_new, &max_span, &max_out);
+    if (rc != ADN_OK) return rc;
+    if (max_out > 0 && !audio_out) return fail(ADN_ERR_INVALID, "adn_stream_pool_emit: null pointer");
+    if (out_stride < (long)block * hop + n_fft / 2)
+        return fail(ADN_ERR_INVALID, "adn_stream_pool_emit: out_stride must be at least block hop + n_fft / 2, the most a step emits");
+    if (!aligned_to(y, 4) || !aligned_to(audio_out, 4)) return fail(ADN_ERR_INVALID, "adn_stream_pool_emit: y and audio_out must be 4-byte aligned");
+    ADN_LAUNCH(adn::launch_stream_pool_emit(y, p.g, t, max_span, static_cast<float *>(state), audio_out, out_stride,
+                                            static_cast<hipStream_t>(stream)), "adn_stream_pool_emit");
     return ADN_OK;
 }
 

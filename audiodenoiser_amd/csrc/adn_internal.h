@@ -454,7 +454,67 @@ struct StreamCall {
     int slot_in, slot_out;
     int f_first, f_last, p_begin, p_first, p_out, p_tail, p_end;
 };
+// The arithmetic of a StreamCall, for steps first .. first + n_steps - 1 inside the limits the ABI has checked (final_length -1 or
+// the stream's length, no step past the last one of a finished stream).  The lockstep entry points evaluate it on the host, the
+// pool's kernels per row on the device: one function, so the two cannot drift apart.
+__host__ __device__ inline StreamCall stream_call_of(const StreamGeom &g, long first, int n_steps, long final_length)
+{
+    StreamCall c;
+    const long B = g.B, D = g.B + g.A, hop = g.hop, M = g.n_fft / 2, keep = g.n_fft - g.hop;
+    const long last = first + n_steps - 1;
+    c.first = (int)first;
+    c.n_steps = n_steps;
+    c.T = -1;
+    c.L = -1;
+    bool closes = false;
+    if (final_length > 0) {
+        const long T = 1 + final_length / hop, K = (T + B - 1) / B;
+        c.T = (int)T;
+        c.L = (int)final_length;
+        closes = last == K - 1;
+    }
+    c.base = first == 0 ? 0 : (int)((first * B + g.A - 1) * hop + M);
+    c.end = (int)((last * B + D - 1) * hop + M);
+    c.f_new0 = first == 0 ? 0 : (int)(first * B + g.A);
+    c.f_new1 = (int)(last * B + D);
+    c.slot_in = first == 0 ? 0 : (int)((first - 1) % g.S);
+    c.slot_out = (int)(last % g.S);
+    c.f_first = (int)(first * B);
+    c.f_last = (int)((last + 1) * B - 1);
+    c.p_begin = (int)(first * B * hop);
+    c.p_first = c.p_begin > M ? c.p_begin : (int)M;
+    if (closes) {
+        if (c.f_last > c.T - 1) c.f_last = c.T - 1;
+        c.p_out = (int)(final_length + M);
+        c.p_tail = 0x7fffffff;
+        c.p_end = c.p_out;
+    } else {
+        c.p_out = (int)((last + 1) * B * hop);
+        c.p_tail = c.p_out;
+        c.p_end = (int)(c.p_out + keep);
+    }
+    return c;
+}
 bool stream_geom(int n_streams, int n_fft, int hop, int window, int block, int lookahead, int max_steps, StreamGeom *g);
+// Stream pool (adn.h, "stream pool"): n_slots independent streams in one state, each with the geometry of max_steps = 1 (S = 2,
+// RX = B + A, RM = W), no hist section and one more section, `ring` [slot][R]: the slot's pending samples, sample s at s mod R.
+// A launch covers n rows of (slot, step, final_length); the table travels by value in the kernel arguments (3 KB of the 4 KB
+// segment) and a workgroup derives its row's StreamCall with stream_call_of.
+constexpr int STREAM_POOL_MAX_ROWS = 256;       // adn.h: ADN_STREAM_POOL_MAX_ROWS
+struct StreamPoolRow {
+    int slot, step, final_length;
+};
+struct StreamPoolRows {
+    long ring_off;                       // floats from the start of the state
+    int R, n;
+    StreamPoolRow row[STREAM_POOL_MAX_ROWS];
+};
+bool stream_pool_geom(int n_slots, int n_fft, int hop, int window, int block, int lookahead, long ring, StreamGeom *g,
+                      long *ring_off, long *total);
+hipError_t launch_stream_pool_frames(const StreamGeom &g, const StreamPoolRows &rows, int max_new_frames, float *state, hipStream_t st);
+hipError_t launch_stream_pool_windows(const float *state, const StreamGeom &g, const StreamPoolRows &rows, float *out, hipStream_t st);
+hipError_t launch_stream_pool_emit(const float *y, const StreamGeom &g, const StreamPoolRows &rows, int max_span, float *state,
+                                   float *audio, long out_stride, hipStream_t st);
 hipError_t launch_stream_frames(const float *audio, long audio_stride, int n_streams, const StreamGeom &g, const StreamCall &c,
                                 float *state, hipStream_t st);
 hipError_t launch_stream_windows(const float *state, int n_streams, const StreamGeom &g, const StreamCall &c, float *out,

@@ -23,6 +23,17 @@
 // Order of the sums: a sample is the carried partial sum plus its frames in ascending frame order, all fp32 adds of one thread
 // -- the same chain whether the frames arrive in one call or in many, so the same audio gives the same bits however it was
 // split, and a stream never reads another stream's rows.  No atomics, no workspace.
+//
+// Stream pool (adn.h, "stream pool"): n_slots streams with independent timing in one state, the same kernel bodies.  A launch has
+// ROWS of (slot, step, final_length), one step each, handed over by value in the kernel arguments; a workgroup derives its row's
+// StreamCall with stream_call_of, the function the host uses for the lockstep call.  A slot has the geometry of max_steps = 1
+// (S = 2, RX = B + A, RM = W), no hist section and
+//   ring  [slot][R]                 its pending samples, sample s of the stream at s mod R (adn_stream_pool_write fills it)
+// which serves the new samples and the n_fft - hop before them alike.  The rule above holds row for row: the frames workgroups of
+// a row only READ the ring (no launch of these kernels writes it) and WRITE the X and mag rows of their own frames; windows only
+// reads mag rows of its slot; emit reads tail slot (step - 1) mod 2 and writes tail slot step mod 2.  No two rows of a launch
+// name the same slot (the host refuses such a call), so no state word of a slot has two writers, and no workgroup reads what
+// another one writes in the same launch.  Still no atomics, no workspace.
 #include "adn_internal.h"
 #include "fft_core.h"
 
@@ -72,10 +83,54 @@ struct Samples {
     }
 };
 
+// The pool's form: the slot's ring of pending samples holds sample s at s mod R, the history included.
+struct RingSamples {
+    const float *ring;
+    int R, L;
+    __device__ __forceinline__ float at(int s) const
+    {
+        if (s < 0 || (L >= 0 && s >= L)) return 0.f;
+        return ring[s % R];
+    }
+};
+
+// Where a workgroup gets its StreamCall from: the kernels below are templates on the argument that says it.  A ROW of a launch is
+// one stream's share of it: the row indexes the launch's input and output, the SLOT the state.  Lockstep (StreamCall): one call
+// for all streams, made on the host, row = slot = stream.  Pooled (StreamPoolRows): a table of (slot, step, final_length) in the
+// kernel arguments, one step per row, the call derived here by the function the host uses.
+template <class Rows> constexpr bool POOLED = std::is_same_v<Rows, StreamPoolRows>;
+__device__ __forceinline__ StreamCall call_of(const StreamCall &c, const StreamGeom &, long) { return c; }
+__device__ __forceinline__ StreamCall call_of(const StreamPoolRows &t, const StreamGeom &g, long row)
+{
+    return stream_call_of(g, t.row[row].step, 1, t.row[row].final_length);
+}
+__device__ __forceinline__ long slot_of(const StreamCall &, long row) { return row; }
+__device__ __forceinline__ long slot_of(const StreamPoolRows &t, long row) { return t.row[row].slot; }
+__device__ __forceinline__ Samples samples_of(const StreamCall &, const StreamCall &c, const StreamGeom &g, int keep,
+                                              const float *audio, long audio_stride, long strm, const float *state)
+{
+    Samples in;
+    in.audio = audio + strm * audio_stride;
+    in.hist = state + g.hist_off + (strm * g.S + c.slot_in) * (long)keep;
+    in.base = c.base;
+    in.keep = keep;
+    in.L = c.L;
+    return in;
+}
+__device__ __forceinline__ RingSamples samples_of(const StreamPoolRows &t, const StreamCall &c, const StreamGeom &, int,
+                                                  const float *, long, long strm, const float *state)
+{
+    RingSamples in;
+    in.ring = state + t.ring_off + strm * (long)t.R;
+    in.R = t.R;
+    in.L = c.L;
+    return in;
+}
+
 // ---------------------------------------------------------------------------------------------- analysis 1: new frames
-template <int M>
+template <int M, class Rows>
 __global__ __launch_bounds__(STFT_THREADS) void stream_frames_kernel(const float *__restrict__ audio, long audio_stride,
-                                                                    StreamGeom g, StreamCall c,
+                                                                    StreamGeom g, Rows rows,
                                                                     const float *__restrict__ tables, float *__restrict__ state)
 {
     using C = StCfg<M>;
@@ -89,16 +144,14 @@ __global__ __launch_bounds__(STFT_THREADS) void stream_frames_kernel(const float
     for (int i = tid; i < C::TBL; i += STFT_THREADS) smem[i] = tables[i];
     __syncthreads();
 
-    const long strm = blockIdx.y;
+    const long strm = slot_of(rows, blockIdx.y);
+    const StreamCall &c = call_of(rows, g, blockIdx.y);
     const int keep = N - g.hop;
-    Samples in;
-    in.audio = audio + strm * audio_stride;
-    in.hist = state + g.hist_off + (strm * g.S + c.slot_in) * (long)keep;
-    in.base = c.base;
-    in.keep = keep;
-    in.L = c.L;
+    const auto in = samples_of(rows, c, g, keep, audio, audio_stride, strm, state);
 
-    if (blockIdx.x == 0) {           // the samples the next call's first frame shares with this one
+    if constexpr (POOLED<Rows>) {      // the grid is sized for the row with the most new frames (the first step brings A more)
+        if (c.f_new0 + (int)blockIdx.x * FB >= c.f_new1) return;
+    } else if (blockIdx.x == 0) {    // the samples the next call's first frame shares with this one (the pool's stay in the ring)
         float *h = state + g.hist_off + (strm * g.S + c.slot_out) * (long)keep;
         for (int i = tid; i < keep; i += STFT_THREADS) h[i] = in.at(c.end - keep + i);
     }
@@ -156,7 +209,8 @@ __global__ __launch_bounds__(STFT_THREADS) void stream_frames_kernel(const float
 // ---------------------------------------------------------------------------------------------- analysis 2: network input
 // mag ring rows are frame-major [frame][F], the network's windows bin-major [window][F][W] with the frame index fastest: a
 // 32 x 32 tile through LDS (pitch 33) keeps both sides contiguous along their fastest index, as dn_windows_kernel.
-__global__ __launch_bounds__(256) void stream_windows_kernel(const float *__restrict__ state, int F, StreamGeom g, StreamCall c,
+template <class Rows>
+__global__ __launch_bounds__(256) void stream_windows_kernel(const float *__restrict__ state, int F, StreamGeom g, Rows rows,
                                                              int tilesJ, int tilesF, float *__restrict__ out)
 {
     __shared__ float tile[32][33];
@@ -164,9 +218,10 @@ __global__ __launch_bounds__(256) void stream_windows_kernel(const float *__rest
     const int tj = (int)(b % (unsigned)tilesJ);
     b /= (unsigned)tilesJ;
     const int tf = (int)(b % (unsigned)tilesF);
-    const long win = b / (unsigned)tilesF;                       // stream * n_steps + i
-    const long strm = win / c.n_steps;
-    const int i = (int)(win - strm * c.n_steps);
+    const long win = b / (unsigned)tilesF;                       // stream * n_steps + i; the pool's row
+    const StreamCall &c = call_of(rows, g, win);
+    const long strm = POOLED<Rows> ? slot_of(rows, win) : win / c.n_steps;
+    const int i = POOLED<Rows> ? 0 : (int)(win - strm * c.n_steps);
     const int fw0 = (c.first + i) * g.B + g.B + g.A - g.W;       // first frame of the step's window
     const int j0 = tj * 32, f0 = tf * 32;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
@@ -190,9 +245,9 @@ __global__ __launch_bounds__(256) void stream_windows_kernel(const float *__rest
 // frames [f_first, f_last], emits [p_begin, p_out) and leaves [p_tail, p_tail + n_fft - hop) in the new tail (p_tail = p_out
 // while the stream runs; nothing once the stream's last sample is out).  A workgroup owns `span` positions of
 // [p_begin, p_end); the frames that cover its span and belong to this call are rebuilt in LDS as dn_resynth_kernel does.
-template <int M>
+template <int M, class Rows>
 __global__ __launch_bounds__(STFT_THREADS, (M == 256 ? 4 : 2)) void stream_emit_kernel(
-    const float *__restrict__ y, StreamGeom g, StreamCall c, int nblk, const float *__restrict__ tables,
+    const float *__restrict__ y, StreamGeom g, Rows rows, int nblk, const float *__restrict__ tables,
     float *__restrict__ state, float *__restrict__ audio, long out_stride)
 {
     using C = StCfg<M>;
@@ -208,10 +263,13 @@ __global__ __launch_bounds__(STFT_THREADS, (M == 256 ? 4 : 2)) void stream_emit_
     for (int i = tid; i < C::TBL; i += STFT_THREADS) smem[i] = tables[i];
     __syncthreads();                                            // (a workgroup past the call's last frame runs no FFT pass)
 
-    const long strm = blockIdx.x / (unsigned)nblk;
-    const int bx = (int)(blockIdx.x - strm * nblk);
+    const long row = blockIdx.x / (unsigned)nblk, strm = slot_of(rows, row);
+    const int bx = (int)(blockIdx.x - row * nblk);
+    const StreamCall &c = call_of(rows, g, row);
     const int hop = g.hop, keep = N - hop;
     const int pa = c.p_begin + bx * span;
+    if constexpr (POOLED<Rows>)                                 // nblk is sized for the longest row of the launch
+        if (pa >= c.p_end) return;
     const int pb = pa + span < c.p_end ? pa + span : c.p_end;
     // frames of this call that cover [pa, pb): ceil((pa - n_fft + 1) / hop) .. floor((pb - 1) / hop), clipped to the call's frames
     int f_begin = pa < N ? 0 : (pa - N + hop) / hop;
@@ -229,7 +287,7 @@ __global__ __launch_bounds__(STFT_THREADS, (M == 256 ? 4 : 2)) void stream_emit_
         acc[u] = (c.first > 0 && q < keep && p0 + u * STFT_THREADS < pb) ? tail_in[q] : 0.f;
     }
 
-    const float *ys = y + strm * c.n_steps * (long)F * g.W;
+    const float *ys = y + row * c.n_steps * (long)F * g.W;
     const float2 *Xs = reinterpret_cast<const float2 *>(state + g.x_off) + strm * g.RX * (long)F;
     const int fl = tid / TPF, t = tid - fl * TPF;               // FFT role: frame slot, lane inside the frame
     const int jf = tid & (SB - 1), kb = tid / SB;               // staging role: frame of the stage, first bin
@@ -319,7 +377,7 @@ __global__ __launch_bounds__(STFT_THREADS, (M == 256 ? 4 : 2)) void stream_emit_
             const float w = s_win[p - fr * hop];
             wss += w * w;
         }
-        audio[strm * out_stride + (p - c.p_first)] = wss > FLT_MIN ? acc[u] / wss : acc[u];
+        audio[row * out_stride + (p - c.p_first)] = wss > FLT_MIN ? acc[u] / wss : acc[u];
     }
 }
 
@@ -328,7 +386,7 @@ hipError_t launch_frames_m(const float *audio, long audio_stride, int n_streams,
                            const float *tables, float *state, hipStream_t st)
 {
     using C = StCfg<M>;
-    auto kern = stream_frames_kernel<M>;
+    auto kern = stream_frames_kernel<M, StreamCall>;
     if (C::LDS_FRAMES > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)C::LDS_FRAMES);
@@ -345,7 +403,7 @@ hipError_t launch_emit_m(const float *y, int n_streams, const StreamGeom &g, con
                          float *state, float *audio, long out_stride, hipStream_t st)
 {
     using C = StCfg<M>;
-    auto kern = stream_emit_kernel<M>;
+    auto kern = stream_emit_kernel<M, StreamCall>;
     if (C::LDS_EMIT > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                            (int)C::LDS_EMIT);
@@ -357,6 +415,40 @@ hipError_t launch_emit_m(const float *y, int n_streams, const StreamGeom &g, con
     if (nblk * n_streams > 0x7fffffffL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(kern, dim3((unsigned)(nblk * n_streams)), dim3(STFT_THREADS), C::LDS_EMIT, st, y, g, c, (int)nblk,
                        tables, state, audio, out_stride);
+    return hipGetLastError();
+}
+
+template <int M>
+hipError_t launch_pool_frames_m(const StreamGeom &g, const StreamPoolRows &t, int max_new_frames, const float *tables, float *state,
+                                hipStream_t st)
+{
+    using C = StCfg<M>;
+    auto kern = stream_frames_kernel<M, StreamPoolRows>;
+    if (C::LDS_FRAMES > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)C::LDS_FRAMES);
+        if (e != hipSuccess) return e;
+    }
+    dim3 grid((unsigned)((max_new_frames + C::FB - 1) / C::FB), (unsigned)t.n);
+    hipLaunchKernelGGL(kern, grid, dim3(STFT_THREADS), C::LDS_FRAMES, st, (const float *)nullptr, 0L, g, t, tables, state);
+    return hipGetLastError();
+}
+
+template <int M>
+hipError_t launch_pool_emit_m(const float *y, const StreamGeom &g, const StreamPoolRows &t, int max_span, const float *tables,
+                              float *state, float *audio, long out_stride, hipStream_t st)
+{
+    using C = StCfg<M>;
+    auto kern = stream_emit_kernel<M, StreamPoolRows>;
+    if (C::LDS_EMIT > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)C::LDS_EMIT);
+        if (e != hipSuccess) return e;
+    }
+    if (max_span <= 0) return hipSuccess;
+    const long nblk = ((long)max_span + C::SPAN - 1) / C::SPAN;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nblk * t.n)), dim3(STFT_THREADS), C::LDS_EMIT, st, y, g, t, (int)nblk, tables, state,
+                       audio, out_stride);
     return hipGetLastError();
 }
 
@@ -386,6 +478,65 @@ bool stream_geom(int n_streams, int n_fft, int hop, int window, int block, int l
     return true;
 }
 
+bool stream_pool_geom(int n_slots, int n_fft, int hop, int window, int block, int lookahead, long ring, StreamGeom *g,
+                      long *ring_off, long *total)
+{
+    if (!stream_geom(n_slots, n_fft, hop, window, block, lookahead, 1, g)) return false;
+    // what a step reads at once (history, the first step's samples) and one block more that may arrive meanwhile
+    const long keep = n_fft - hop, need = keep + ((long)block + lookahead - 1) * hop + n_fft / 2 + (long)block * hop;
+    if (ring < need || ring > (1L << 28)) return false;
+    g->hist_off = -1;                                // no hist section: the ring holds those samples
+    g->tail_off = g->mag_off + (long)n_slots * (n_fft / 2 + 1) * g->RM;
+    *ring_off = g->tail_off + (long)n_slots * keep * g->S;
+    *total = g->total = *ring_off + (long)n_slots * ring;
+    return true;
+}
+
+hipError_t launch_stream_pool_frames(const StreamGeom &g, const StreamPoolRows &t, int max_new_frames, float *state, hipStream_t st)
+{
+    const float *tables = nullptr;
+    hipError_t e = stft_tables(g.n_fft, &tables, st);
+    if (e != hipSuccess) return e;
+    switch (g.n_fft) {
+        case 64: return launch_pool_frames_m<32>(g, t, max_new_frames, tables, state, st);
+        case 128: return launch_pool_frames_m<64>(g, t, max_new_frames, tables, state, st);
+        case 256: return launch_pool_frames_m<128>(g, t, max_new_frames, tables, state, st);
+        case 512: return launch_pool_frames_m<256>(g, t, max_new_frames, tables, state, st);
+        case 1024: return launch_pool_frames_m<512>(g, t, max_new_frames, tables, state, st);
+        case 2048: return launch_pool_frames_m<1024>(g, t, max_new_frames, tables, state, st);
+        case 4096: return launch_pool_frames_m<2048>(g, t, max_new_frames, tables, state, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_stream_pool_windows(const float *state, const StreamGeom &g, const StreamPoolRows &t, float *out, hipStream_t st)
+{
+    const int F = g.n_fft / 2 + 1;
+    const long tilesJ = (g.W + 31) / 32, tilesF = (F + 31) / 32;
+    const long grid = tilesJ * tilesF * t.n;         // W <= 2^20, F <= 2049, n <= 256: below 2^31
+    hipLaunchKernelGGL(stream_windows_kernel<StreamPoolRows>, dim3((unsigned)grid), dim3(256), 0, st, state, F, g, t, (int)tilesJ, (int)tilesF,
+                       out);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_pool_emit(const float *y, const StreamGeom &g, const StreamPoolRows &t, int max_span, float *state,
+                                   float *audio, long out_stride, hipStream_t st)
+{
+    const float *tables = nullptr;
+    hipError_t e = stft_tables(g.n_fft, &tables, st);
+    if (e != hipSuccess) return e;
+    switch (g.n_fft) {
+        case 64: return launch_pool_emit_m<32>(y, g, t, max_span, tables, state, audio, out_stride, st);
+        case 128: return launch_pool_emit_m<64>(y, g, t, max_span, tables, state, audio, out_stride, st);
+        case 256: return launch_pool_emit_m<128>(y, g, t, max_span, tables, state, audio, out_stride, st);
+        case 512: return launch_pool_emit_m<256>(y, g, t, max_span, tables, state, audio, out_stride, st);
+        case 1024: return launch_pool_emit_m<512>(y, g, t, max_span, tables, state, audio, out_stride, st);
+        case 2048: return launch_pool_emit_m<1024>(y, g, t, max_span, tables, state, audio, out_stride, st);
+        case 4096: return launch_pool_emit_m<2048>(y, g, t, max_span, tables, state, audio, out_stride, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
 hipError_t launch_stream_frames(const float *audio, long audio_stride, int n_streams, const StreamGeom &g, const StreamCall &c,
                                 float *state, hipStream_t st)
 {
@@ -411,7 +562,7 @@ hipError_t launch_stream_windows(const float *state, int n_streams, const Stream
     const long tilesJ = (g.W + 31) / 32, tilesF = (F + 31) / 32;
     const long grid = tilesJ * tilesF * c.n_steps * (long)n_streams;
     if (grid > 0x7fffffffL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(stream_windows_kernel, dim3((unsigned)grid), dim3(256), 0, st, state, F, g, c, (int)tilesJ, (int)tilesF,
+    hipLaunchKernelGGL(stream_windows_kernel<StreamCall>, dim3((unsigned)grid), dim3(256), 0, st, state, F, g, c, (int)tilesJ, (int)tilesF,
                        out);
     return hipGetLastError();
 }

@@ -6,6 +6,7 @@
         out = sd.push(block)                          # (n_streams, newly final samples), possibly zero columns
     out = sd.flush()                                  # the rest: exactly as many samples out as went in
     sd = StreamDenoiser(model, input_rate=48000)      # the same for a feed at 48 kHz: samples at 48 kHz in, samples at 48 kHz out
+    pool = StreamPool(model, max_streams=64)          # feeds that start, stop and arrive independently: see StreamPool
 
     python -m audiodenoiser_amd.stream --model CKPT.pth IN.wav OUT.wav [--chunk 1024] [--window 192] [--block 16]
                                        [--lookahead 0] [--dtype f32|f16] [--live]
@@ -21,7 +22,7 @@ returned.  The result does not depend on how the audio was cut into ``push`` cal
 ``(B + A - 1) hop + n_fft`` samples lie between a sample's arrival and its return.
 
 All streams of one object advance in lockstep (one ``push`` brings the same number of samples for each); feeds with independent
-timing use separate objects.  A ``push`` that completes several steps sends them through the network as one batch,
+timing go into one ``StreamPool``, which batches their ready steps.  A ``push`` that completes several steps sends them through the network as one batch,
 ``batch_windows`` windows at a time.
 
 ``sample_rate`` is the network's working rate.  A feed at another rate names it as ``input_rate``: ``push`` then takes and returns
@@ -46,7 +47,7 @@ import torch
 
 from . import _lib
 
-__all__ = ["StreamDenoiser", "stream_plan", "stream_rate_plan"]
+__all__ = ["StreamDenoiser", "StreamPool", "PoolBook", "stream_plan", "stream_rate_plan"]
 
 
 def stream_plan(received: int, n_fft: int = 512, hop_length: int = 128, window_frames: int = 192, block_frames: int = 16,
@@ -79,6 +80,37 @@ def stream_rate_plan(received: int, input_rate: int, n_fft: int = 512, hop_lengt
 
 def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _emit_count(n_fft: int, hop: int, block: int, first_step: int, n_steps: int, final_length: int = -1) -> int:
+    """Samples ``adn_stream_emit`` returns per stream for steps ``first_step .. first_step + n_steps - 1``."""
+    half, per = n_fft // 2, block * hop
+    lo = max(0, first_step * per - half)
+    hi = max(0, (first_step + n_steps) * per - half)
+    if final_length >= 0:
+        n_frames = 1 + final_length // hop
+        if first_step + n_steps == -(-n_frames // block):
+            hi = final_length
+    return max(0, hi - lo)
+
+
+def _network(model, x: torch.Tensor, batch_windows: int, who: str) -> torch.Tensor:
+    """The U-Net over ``batch_windows`` windows at a time, into slices of one output buffer (as ``Denoiser.network``)."""
+    nw, _, f, w = x.shape
+    dev = x.device
+    y = torch.empty_like(x)
+    if model.training:
+        raise RuntimeError(f"{who}: the model is in train mode; call .eval()")
+    L = _lib.load()
+    handle = model._ensure_handle(dev)
+    per = f * w * 4
+    with torch.cuda.device(dev):
+        for i in range(0, nw, batch_windows):
+            n = min(batch_windows, nw - i)
+            ws = model._workspace_for(n, f, w, dev)
+            _lib.check(L.adn_unet_forward(handle, x.data_ptr() + i * per, y.data_ptr() + i * per, n, f, w, ws.data_ptr(),
+                                          ws.numel(), _stream(dev)), "adn_unet_forward")
+    return y
 
 
 class StreamDenoiser:
@@ -191,33 +223,11 @@ class StreamDenoiser:
 
     def network(self, x: torch.Tensor) -> torch.Tensor:
         """The U-Net over ``batch_windows`` windows at a time, into slices of one output buffer (as ``Denoiser.network``)."""
-        nw, _, f, w = x.shape
-        dev = x.device
-        y = torch.empty_like(x)
-        m = self.model
-        if m.training:
-            raise RuntimeError("StreamDenoiser: the model is in train mode; call .eval()")
-        L = _lib.load()
-        handle = m._ensure_handle(dev)
-        step, per = self.batch_windows, f * w * 4
-        with torch.cuda.device(dev):
-            for i in range(0, nw, step):
-                n = min(step, nw - i)
-                ws = m._workspace_for(n, f, w, dev)
-                _lib.check(L.adn_unet_forward(handle, x.data_ptr() + i * per, y.data_ptr() + i * per, n, f, w, ws.data_ptr(),
-                                              ws.numel(), _stream(dev)), "adn_unet_forward")
-        return y
+        return _network(self.model, x, self.batch_windows, "StreamDenoiser")
 
     def emit_count(self, first_step: int, n_steps: int, final_length: int = -1) -> int:
         """Samples per stream that ``emit`` returns for these steps."""
-        half, per = self.n_fft // 2, self.block_frames * self.hop_length
-        lo = max(0, first_step * per - half)
-        hi = max(0, (first_step + n_steps) * per - half)
-        if final_length >= 0:
-            n_frames = 1 + final_length // self.hop_length
-            if first_step + n_steps == -(-n_frames // self.block_frames):
-                hi = final_length
-        return max(0, hi - lo)
+        return _emit_count(self.n_fft, self.hop_length, self.block_frames, first_step, n_steps, final_length)
 
     def emit(self, y: torch.Tensor, first_step: int, n_steps: int, final_length: int = -1) -> torch.Tensor:
         """``adn_stream_emit``: the network's output for the windows of ``analyze`` -> ``(n_streams, emit_count)`` samples."""
@@ -325,6 +335,302 @@ class StreamDenoiser:
                 outs.append(self._run(min(self.max_steps, k - self._done), length))
         assert self._emitted + sum(o.shape[1] for o in outs) == length, (self._emitted, length)
         return outs
+
+
+POOL_MAX_ROWS = 256          # ADN_STREAM_POOL_MAX_ROWS of include/adn.h: the rows of one analyze / emit call
+
+
+class PoolBook:
+    """The host side of a ``StreamPool``, no device needed: per slot ``received`` (samples pushed) and ``done`` (steps run), and
+    what follows from them -- which step is ready, how many samples it returns, how much room the slot's ring has left.
+
+    ``ring_samples`` = ``n_fft - hop`` (the history a step's first frame shares with the step before) + ``e(0)`` (what the first
+    step reads) + ``backlog_steps`` blocks of ``B hop`` samples that may wait while their step has not run."""
+    FREE, RUNNING, CLOSED = 0, 1, 2
+
+    def __init__(self, max_streams: int = 64, backlog_steps: int = 4, n_fft: int = 512, hop_length: int = 128,
+                 window_frames: int = 192, block_frames: int = 16, lookahead_frames: int = 0):
+        if not (isinstance(max_streams, int) and 1 <= max_streams <= 1 << 20):
+            raise ValueError("StreamPool: max_streams must be in [1, 2^20]")
+        if not (isinstance(backlog_steps, int) and backlog_steps >= 1):
+            raise ValueError("StreamPool: backlog_steps must be >= 1")
+        if not (isinstance(n_fft, int) and 64 <= n_fft <= 4096 and n_fft & (n_fft - 1) == 0):
+            raise ValueError("StreamPool: n_fft must be a power of two in [64, 4096]")
+        if not (isinstance(hop_length, int) and 1 <= hop_length <= n_fft // 4):
+            raise ValueError("StreamPool: need 1 <= hop_length <= n_fft / 4")
+        if not (isinstance(window_frames, int) and window_frames >= 16):
+            raise ValueError("StreamPool: window_frames must be >= 16 (the network pools four times)")
+        if not (isinstance(block_frames, int) and block_frames >= 1):
+            raise ValueError("StreamPool: block_frames must be >= 1")
+        if not (isinstance(lookahead_frames, int) and lookahead_frames >= 0):
+            raise ValueError("StreamPool: lookahead_frames must be >= 0")
+        if block_frames + lookahead_frames > window_frames:
+            raise ValueError("StreamPool: need block_frames + lookahead_frames <= window_frames")
+        self.max_streams, self.backlog_steps = max_streams, backlog_steps
+        self.n_fft, self.hop_length, self.window_frames = n_fft, hop_length, window_frames
+        self.block_frames, self.lookahead_frames = block_frames, lookahead_frames
+        self.plan = (n_fft, hop_length, window_frames, block_frames, lookahead_frames)
+        self.keep = n_fft - hop_length
+        self.ring_samples = self.keep + self.end_of(0) + backlog_steps * block_frames * hop_length
+        if self.ring_samples > 1 << 28:
+            raise ValueError("StreamPool: backlog_steps asks for a ring of more than 2^28 samples per stream")
+        self.out_stride = block_frames * hop_length + n_fft // 2          # the most a step returns (the last one of a stream)
+        self.status = [self.FREE] * max_streams
+        self.received = [0] * max_streams
+        self.done = [0] * max_streams
+
+    def end_of(self, step: int) -> int:
+        """Samples that must have arrived for ``step`` of a running stream (``e(k)`` of adn.h; 0 for step -1)."""
+        if step < 0:
+            return 0
+        b, a = self.block_frames, self.lookahead_frames
+        return (step * b + b + a - 1) * self.hop_length + self.n_fft // 2
+
+    def n_steps(self, length: int) -> int:
+        """``K``: the steps of a finished stream of ``length`` samples (0 for an empty one)."""
+        return -(-(1 + length // self.hop_length) // self.block_frames) if length > 0 else 0
+
+    def _live(self, slot, what):
+        if not (isinstance(slot, int) and 0 <= slot < self.max_streams) or self.status[slot] == self.FREE:
+            raise ValueError(f"StreamPool.{what}: {slot!r} is not an open stream")
+
+    def open(self) -> int:
+        for slot, st in enumerate(self.status):
+            if st == self.FREE:
+                self.status[slot], self.received[slot], self.done[slot] = self.RUNNING, 0, 0
+                return slot
+        raise RuntimeError(f"StreamPool.open: all {self.max_streams} streams are taken")
+
+    def room(self, slot: int) -> int:
+        """Samples that fit before a push would overwrite one that the stream's next step still reads: the ring holds the last
+        ``ring_samples`` samples, the next step reads from ``e(done - 1) - (n_fft - hop)`` on."""
+        self._live(slot, "room")
+        oldest = max(0, self.end_of(self.done[slot] - 1) - self.keep)
+        return oldest + self.ring_samples - self.received[slot]
+
+    def take(self, slot: int, m: int) -> int:
+        """Book a push of ``m`` samples; returns the position they start at.  Changes nothing when it raises."""
+        self._live(slot, "push")
+        if self.status[slot] == self.CLOSED:
+            raise RuntimeError("StreamPool.push: the stream has been closed")
+        if m > self.room(slot):
+            raise RuntimeError(f"StreamPool.push: {m} samples do not fit, the stream has room for {self.room(slot)} before samples "
+                               "that no step has used yet would be overwritten; call step()")
+        if self.received[slot] + m >= 1 << 30:
+            raise ValueError("StreamPool.push: a stream holds fewer than 2^30 samples; close() it before")
+        at = self.received[slot]
+        self.received[slot] = at + m
+        return at
+
+    def close(self, slot: int) -> bool:
+        """The stream has ended.  True when nothing is left to run (a stream of no samples): the slot is free again."""
+        self._live(slot, "close")
+        self.status[slot] = self.CLOSED
+        if self.done[slot] >= self.n_steps(self.received[slot]):
+            self.status[slot] = self.FREE
+            return True
+        return False
+
+    def ready(self, slot: int):
+        """``(step, final_length)`` of the step the stream in ``slot`` can run now, or None."""
+        st, k = self.status[slot], self.done[slot]
+        if st == self.RUNNING and self.received[slot] >= self.end_of(k):
+            return k, -1
+        if st == self.CLOSED and k < self.n_steps(self.received[slot]):
+            return k, self.received[slot]
+        return None
+
+    def rows(self):
+        """The ready rows ``(slot, step, final_length)`` of one tick, in ascending slot order."""
+        out = []
+        for slot in range(self.max_streams):
+            r = self.ready(slot)
+            if r is not None:
+                out.append((slot,) + r)
+        return out
+
+    def count(self, step: int, final_length: int) -> int:
+        """Samples the step returns (``adn_stream_emit``'s count for one step)."""
+        return _emit_count(self.n_fft, self.hop_length, self.block_frames, step, 1, final_length)
+
+    def ran(self, slot: int) -> bool:
+        """Book the step that ``ready`` named as run; True when it was the last one of a closed stream (the slot is free again)."""
+        self.done[slot] += 1
+        if self.status[slot] == self.CLOSED and self.done[slot] >= self.n_steps(self.received[slot]):
+            self.status[slot] = self.FREE
+            return True
+        return False
+
+
+class StreamPool:
+    """Live streams that start, stop and arrive independently, served from one card: every ``step()`` runs ONE step of every
+    stream that has one ready, all of them through the network as one batch.
+
+        pool = StreamPool(model, max_streams=64)      # an audiodenoiser_amd.model.UNet(1, 1) on a ROCm device, .eval()
+        sid = pool.open()                             # a free slot; RuntimeError when all are taken
+        pool.push(sid, block)                         # the next m >= 0 samples of THAT stream, (m,) float32, numpy or device tensor
+        pool.close(sid)                               # the stream has ended; its remaining steps run in the following ticks
+        for sid, samples, finished in pool.step():    # the newly final samples of every stream that ran a step
+            ...
+
+    Definition: ``include/adn.h``, "stream pool" -- ``max_streams`` independent instances of the "stream" definition; kernels:
+    ``csrc/stream_kernels.hip``, the lockstep kernels' bodies with one (slot, step, final_length) row per stream in the kernel
+    arguments.  A stream's samples wait in a ring on the device (``backlog_steps`` blocks beyond what one step reads); the frames
+    still to be emitted, the magnitudes of the last ``window_frames`` frames and the overlap-add tail live there too.  The host
+    keeps two numbers per stream, ``received`` and ``done`` (``PoolBook``).  Step ``k`` of a running stream is ready once
+    ``(k B + B + A - 1) hop + n_fft / 2`` samples have arrived; every remaining step of a closed stream is ready.  A tick gathers
+    the ready rows in ascending slot order, analyses them (``adn_stream_pool_analyze``, at most 256 rows a call), sends the
+    windows through the U-Net ``batch_windows`` at a time, and takes the result back to audio (``adn_stream_pool_emit``).
+
+    What is claimed: a stream's output is a function of its own samples and its own step index only -- bit for bit, with
+    ``model.set_batch_invariant(True)``, what a ``StreamDenoiser(n_streams=1)`` returns for the same samples, whatever the other
+    slots carry, whenever they were opened and however the pushes and ticks interleave (within the network's per-batch-size
+    bound otherwise); each stream returns exactly as many samples as it received; a slot is free again, and reusable without a
+    reset, once the tick that reports ``finished=True`` has run.  ``push`` beyond ``room`` raises and changes nothing.
+    What is NOT claimed: anything ``StreamDenoiser`` does not claim; fairness, priorities or deadlines between streams; more than
+    one step per stream and tick (a stream that is several steps behind catches up one tick at a time); another rate than the
+    network's working rate (put a ``StreamResampler(n_streams=1)`` on each side of a stream); graph capture of a tick.  There is
+    no CPU path.  Samples come back in the kind (numpy / device tensor) of the stream's last ``push``."""
+
+    def __init__(self, model, max_streams: int = 64, backlog_steps: int = 4, n_fft: int = 512, hop_length: int = 128,
+                 window_frames: int = 192, block_frames: int = 16, lookahead_frames: int = 0, batch_windows: int = 64):
+        self.book = PoolBook(max_streams, backlog_steps, n_fft, hop_length, window_frames, block_frames, lookahead_frames)
+        if not (isinstance(batch_windows, int) and batch_windows >= 1):
+            raise ValueError("StreamPool: batch_windows must be >= 1")
+        from .model import UNet
+        if not isinstance(model, UNet) or model.in_channels != 1 or model.num_classes != 1:
+            raise ValueError("StreamPool: model must be an audiodenoiser_amd.model.UNet(1, 1)")
+        if model.training:
+            raise RuntimeError("StreamPool: the model is in train mode; call .eval() (the HIP forward is the eval forward)")
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("StreamPool: the model must live on a ROCm device (model.to('cuda')); there is no CPU path")
+        self.model, self.device, self.batch_windows = model, dev, batch_windows
+        self.max_streams, self.n_bins = max_streams, n_fft // 2 + 1
+        self._args = (max_streams,) + self.book.plan + (self.book.ring_samples,)
+        need = ctypes.c_size_t()
+        _lib.check(_lib.load().adn_stream_pool_state_bytes(*self._args, ctypes.byref(need)), "adn_stream_pool_state_bytes")
+        self._state = torch.empty(need.value, dtype=torch.uint8, device=dev)
+        self._numpy = [True] * max_streams
+        self.reset()
+
+    @property
+    def latency_samples(self) -> int:
+        return stream_plan(0, *self.book.plan)[2]
+
+    def reset(self):
+        """Forget every stream: all slots are free."""
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().adn_stream_pool_reset(self._state.data_ptr(), self._state.numel(), *self._args, -1,
+                                                         _stream(self.device)), "adn_stream_pool_reset")
+        b = self.book
+        b.status, b.received, b.done = [b.FREE] * self.max_streams, [0] * self.max_streams, [0] * self.max_streams
+
+    # ------------------------------------------------------------------ streams
+    def open(self) -> int:
+        """A free slot for a new stream (the lowest one); ``RuntimeError`` when all ``max_streams`` are taken."""
+        return self.book.open()
+
+    def room(self, sid: int) -> int:
+        """Samples that still fit before a ``push`` would overwrite samples no step has used yet."""
+        return self.book.room(sid)
+
+    def received(self, sid: int) -> int:
+        self.book._live(sid, "received")
+        return self.book.received[sid]
+
+    def push(self, sid: int, block) -> None:
+        """The next ``m >= 0`` samples of stream ``sid``: ``(m,)`` float32, numpy or a tensor on the ROCm device.  More than
+        ``room(sid)`` raises ``RuntimeError`` and changes nothing: call ``step()`` first."""
+        self.book._live(sid, "push")
+        as_numpy = not isinstance(block, torch.Tensor)
+        if as_numpy:
+            x = torch.from_numpy(np.ascontiguousarray(block, dtype=np.float32))
+        else:
+            x = block
+            if not x.is_cuda:
+                raise RuntimeError("StreamPool.push: a tensor must live on a ROCm device (no CPU path); pass numpy to have it staged")
+            if x.dtype != torch.float32:
+                raise TypeError("StreamPool.push: expected float32 audio")
+        if x.dim() != 1:
+            raise ValueError("StreamPool.push: audio must be (m,), the samples of one stream")
+        m = x.shape[0]
+        at = self.book.take(sid, m)
+        self._numpy[sid] = as_numpy
+        if m == 0:
+            return
+        x = x.to(self.device).contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().adn_stream_pool_write(self._state.data_ptr(), self._state.numel(), *self._args, sid, x.data_ptr(),
+                                                         m, at, _stream(self.device)), "adn_stream_pool_write")
+
+    def close(self, sid: int) -> bool:
+        """The stream has ended; its remaining steps run in the following ticks, the last of which reports ``finished=True``.
+        Returns True when there is nothing left to run -- a stream of no samples -- and the slot is free already."""
+        return self.book.close(sid)
+
+    # ------------------------------------------------------------------ building blocks (device tensors)
+    def _rows(self, rows):
+        return (_lib.StreamPoolRow * len(rows))(*[_lib.StreamPoolRow(*r) for r in rows])
+
+    def analyze(self, rows) -> torch.Tensor:
+        """``adn_stream_pool_analyze``: rows ``(slot, step, final_length)``, at most 256 -> network input ``(n_rows, 1, F, W)``."""
+        out = torch.empty((len(rows), 1, self.n_bins, self.book.window_frames), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().adn_stream_pool_analyze(self._state.data_ptr(), self._state.numel(), *self._args, self._rows(rows),
+                                                           len(rows), out.data_ptr(), _stream(self.device)), "adn_stream_pool_analyze")
+        return out
+
+    def network(self, x: torch.Tensor) -> torch.Tensor:
+        return _network(self.model, x, self.batch_windows, "StreamPool")
+
+    def emit(self, y: torch.Tensor, rows) -> torch.Tensor:
+        """``adn_stream_pool_emit``: the network's output for the windows of ``analyze`` -> ``(n_rows, B hop + n_fft / 2)``, row i
+        holding ``book.count(step, final_length)`` samples."""
+        y = y.contiguous()
+        out = torch.empty((len(rows), self.book.out_stride), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().adn_stream_pool_emit(self._state.data_ptr(), self._state.numel(), *self._args, self._rows(rows),
+                                                        len(rows), y.data_ptr(), out.data_ptr(), self.book.out_stride,
+                                                        _stream(self.device)), "adn_stream_pool_emit")
+        return out
+
+    # ------------------------------------------------------------------ ticks
+    def step(self):
+        """ONE step of every stream that has one ready -> a list of ``(sid, samples, finished)`` in ascending ``sid``; ``samples``
+        are the stream's newly final ones (possibly none, while ``B hop < n_fft / 2`` in a stream's first steps)."""
+        rows = self.book.rows()
+        if not rows:
+            return []
+        group = POOL_MAX_ROWS
+        groups = [rows[i:i + group] for i in range(0, len(rows), group)]
+        x = torch.cat([self.analyze(g) for g in groups]) if len(groups) > 1 else self.analyze(rows)
+        y = self.network(x)
+        outs = [self.emit(y[i * group:i * group + len(g)], g) for i, g in enumerate(groups)]
+        out = torch.cat(outs) if len(outs) > 1 else outs[0]
+        host = out.cpu().numpy() if any(self._numpy[r[0]] for r in rows) else None
+        result = []
+        for i, (slot, k, final) in enumerate(rows):
+            n = self.book.count(k, final)
+            samples = host[i, :n].copy() if self._numpy[slot] else out[i, :n].clone()
+            result.append((slot, samples, self.book.ran(slot)))
+        return result
+
+    def drain(self):
+        """``step()`` until nothing is ready -> ``(sid, samples, finished)`` per stream that ran, its samples concatenated."""
+        order, parts, fin = [], {}, {}
+        while True:
+            tick = self.step()
+            if not tick:
+                break
+            for sid, samples, finished in tick:
+                if sid not in parts:
+                    order.append(sid)
+                    parts[sid] = []
+                parts[sid].append(samples)
+                fin[sid] = finished
+        return [(sid, np.concatenate(parts[sid]) if isinstance(parts[sid][0], np.ndarray) else torch.cat(parts[sid]), fin[sid])
+                for sid in sorted(order)]
 
 
 def main(argv=None) -> int:

@@ -14,7 +14,7 @@
  *     message.  Nothing throws or aborts across the ABI.
  *   - work is enqueued on the caller's stream.  The only calls that block or allocate: adn_unet_create / adn_unet_destroy
  *     (one-time weight upload / free), adn_prepare, and the FIRST call per (device, n_fft) of an STFT-family entry point
- *     (adn_stft_mag, adn_stft_mag_fit, adn_stft_complex, adn_istft, adn_griffin_lim, adn_denoise_resynth, adn_stream_analyze, adn_stream_emit) or per device of adn_perceptual_loss / adn_perceptual_loss_backward, which
+ *     (adn_stft_mag, adn_stft_mag_fit, adn_stft_complex, adn_istft, adn_griffin_lim, adn_denoise_resynth, adn_stream_analyze, adn_stream_emit, adn_stream_pool_analyze, adn_stream_pool_emit) or per device of adn_perceptual_loss / adn_perceptual_loss_backward, which
  *     builds a few KB of constant tables (window, twiddles, mel filters) with a blocking upload -- unless adn_prepare did so
  *     before; and the FIRST adn_resample or adn_resample_stream per (device, rate pair), which builds its coefficient table
  *     (adn_resample_prepare builds both).  Such a cold call on a stream that is being captured enqueues nothing and returns ADN_ERR_INVALID (never a HIP
@@ -33,7 +33,7 @@
 
 #include <stddef.h>
 
-/* The 48 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 53 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -365,6 +365,56 @@ ADN_API int adn_stream_analyze(void *state, size_t state_bytes, const float *aud
 ADN_API int adn_stream_emit(void *state, size_t state_bytes, const float *y, int n_streams, long first_step, int n_steps,
                             long final_length, int n_fft, int hop, int window, int block, int lookahead, int max_steps,
                             float *audio_out, long out_stride, void *stream);
+
+/* ---- stream pool: streams that start, stop and advance independently, their ready steps batched ---------------------------------
+ * These entry points DEFINE the pool as n_slots independent instances of the stream definition above: there is no new arithmetic.
+ * The stream in a slot has its own step index and its own end; what it returns is a function of its own samples and its own step
+ * index only, bit for bit what adn_stream_analyze / adn_stream_emit return for a state of one stream (n_streams = 1) that runs
+ * the same steps one per call.  Not claimed: anything about the order or the timing in which a caller serves its streams.
+ *
+ * State (adn_stream_pool_state_bytes, caller-owned, opaque, 8-byte aligned): per slot the sections of a stream state with
+ * max_steps = 1 -- X, (B + A) F complex frames; mag, W F magnitudes; tail, 2 (n_fft - hop) partial sums -- and, in place of the
+ * history section, a RING of ring_samples pending samples, sample s of the slot's stream at s mod ring_samples:
+ *   floats = n_slots (2 (B + A) F + W F + 2 (n_fft - hop) + ring_samples), F = n_fft / 2 + 1.
+ * adn_stream_pool_reset clears one slot, or all for slot = -1.  A stream that starts at step 0 reads nothing an earlier stream
+ * of its slot has left, so a slot may be reused without a reset.
+ *   adn_stream_pool_write: the n samples of the stream in `slot` from absolute position `position` on (audio, device memory) go
+ *     into its ring, the wrap handled inside: at most two device copies.  0 <= n <= ring_samples, position >= 0.
+ *   adn_stream_pool_analyze: `rows`, a HOST array read during the call, names n_rows (slot, step, final_length): row i runs step
+ *     `step` of the stream in `slot`, final_length as in adn_stream_analyze (-1 while that stream runs).  windows_out:
+ *     (n_rows, 1, F, W) fp32, window i from row i: the input of adn_unet_forward.  CONTRACT of the caller: the ring of the slot
+ *     holds the samples [e(step - 1) - (n_fft - hop), e(step)) of its stream (cut at 0 and at final_length) when the call runs.
+ *   adn_stream_pool_emit: the same rows; y, the network's output for those windows.  Row i's samples go to
+ *     audio_out + i out_stride: as many as adn_stream_emit returns for (step, 1, final_length).  out_stride >= B hop + n_fft/2,
+ *     the most a step emits (the last one of a stream).
+ * A slot's steps go in step order, and a step is emitted before the slot's next one is analysed, as in the stream section.
+ * The kernels are the stream section's, the rows handed to them by value in the kernel arguments (no host -> device copy, no
+ * workspace, no atomics); no state word is written by one workgroup and read by another in the same launch, for which a call
+ * must not name a slot twice.  Cold-call and capture behaviour as for adn_stream_analyze / adn_stream_emit.
+ * Limits (ADN_ERR_INVALID otherwise, nothing is launched): the stream section's, applied to every row with n_steps = 1;
+ * 1 <= n_rows <= ADN_STREAM_POOL_MAX_ROWS (a caller with more ready streams calls again); 0 <= slot < n_slots; no slot twice in
+ * a call; ring_samples >= (n_fft - hop) + (B + A - 1) hop + n_fft/2 + B hop (what the first step reads and one block more) and
+ * <= 2^28; 1 <= n_slots <= 2^20.  ADN_ERR_WORKSPACE: state_bytes below adn_stream_pool_state_bytes.
+ * adn_stream_pool_state_bytes is host-only (no device needed). */
+#define ADN_STREAM_POOL_MAX_ROWS 256
+typedef struct adn_stream_pool_row {
+    int slot;
+    int step;
+    int final_length;
+} adn_stream_pool_row;
+ADN_API int adn_stream_pool_state_bytes(int n_slots, int n_fft, int hop, int window, int block, int lookahead, long ring_samples,
+                                        size_t *bytes);
+ADN_API int adn_stream_pool_reset(void *state, size_t state_bytes, int n_slots, int n_fft, int hop, int window, int block,
+                                  int lookahead, long ring_samples, int slot, void *stream);
+ADN_API int adn_stream_pool_write(void *state, size_t state_bytes, int n_slots, int n_fft, int hop, int window, int block,
+                                  int lookahead, long ring_samples, int slot, const float *audio, long n, long position,
+                                  void *stream);
+ADN_API int adn_stream_pool_analyze(void *state, size_t state_bytes, int n_slots, int n_fft, int hop, int window, int block,
+                                    int lookahead, long ring_samples, const adn_stream_pool_row *rows, int n_rows,
+                                    float *windows_out, void *stream);
+ADN_API int adn_stream_pool_emit(void *state, size_t state_bytes, int n_slots, int n_fft, int hop, int window, int block,
+                                 int lookahead, long ring_samples, const adn_stream_pool_row *rows, int n_rows, const float *y,
+                                 float *audio_out, long out_stride, void *stream);
 
 /* ---- resample stream: adn_resample for audio that is still arriving ----------------------------------------------------------------
  * The resampler definition above (up, down, q, half = 32 q, the taps h, y[m] = sum_i x[i] h[m down - i up] with zero extension)
