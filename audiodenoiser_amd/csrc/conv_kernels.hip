@@ -1145,6 +1145,7 @@ hipError_t launch_conv_first(const float *x, const float *w9x64, const float *bi
     // pixel does not depend on the tile it falls into
     while ((long)N * tiles_y * tiles_x < 512 && (W + 2 * tiles_x - 1) / (2 * tiles_x) >= 64) tiles_x *= 2;
     const int cols = (W + tiles_x - 1) / tiles_x;
+    tiles_x = (W + cols - 1) / cols;               // equal tiles of `cols` columns may cover W in fewer: no tile starts at or beyond W
     const long blocks = (long)N * tiles_y * tiles_x;
     const size_t lds = (size_t)Cin * (FIRST_ROWS + 2) * (cols + 2) * sizeof(float);
     if (blocks <= 0 || blocks > 0x7fffffffL || lds > 160 * 1024) return hipErrorInvalidValue;

@@ -384,6 +384,7 @@ adn::ConvArgs geom_args(const LayerDesc &d, bool f16, bool wino, int N, int H, i
 struct Plan {
     int N, H[5], W[5];
     size_t tA, tB, skip[4], pool[4], part, total;   // BYTE offsets into the workspace (part: split-K partial sums)
+    size_t part_bytes;                              // capacity of `part`, the last region: what a K-split launch may write
 };
 
 bool make_plan(int N, int F, int T, bool f16, Plan &p)
@@ -434,7 +435,8 @@ bool make_plan(int N, int F, int T, bool f16, Plan &p)
         }
         if (ks > 1) need = std::max(need, (size_t)ks * outf);
     }
-    o += (need * 4 + 255) & ~size_t(255);
+    p.part_bytes = (need * 4 + 255) & ~size_t(255);
+    o += p.part_bytes;
     p.total = o;
     return true;
 }
@@ -595,8 +597,8 @@ Conv3Choice choose_conv3(const adn_unet *h, adn::ConvKind kind, const adn::ConvA
 }
 
 // Executes a choice.  `a`: the layer with the pointers of the chosen fused forms filled in (ConvArgs::firstw / dotw).
-hipError_t launch_conv3(const adn_unet *h, adn::ConvKind kind, const Conv3Choice &c, adn::ConvArgs a, float *partial, hipStream_t st,
-                        const WinoScratch &sc = WinoScratch())
+hipError_t launch_conv3_kernels(const adn_unet *h, adn::ConvKind kind, const Conv3Choice &c, adn::ConvArgs a, float *partial, hipStream_t st,
+                                const WinoScratch &sc)
 {
     if (c.fuse_out) kind = adn::CONV3X3_RELU_DOT;
     switch (c.kernel) {
@@ -633,6 +635,33 @@ hipError_t launch_conv3(const adn_unet *h, adn::ConvKind kind, const Conv3Choice
     return hipErrorInvalidValue;
 }
 
+// A launch's status as the entry points return it.
+inline int hip_status(hipError_t e, const char *what)
+{
+    return e == hipSuccess ? ADN_OK : fail_hip(e, what);
+}
+
+// make_plan sizes the partial buffer, choose_conv3 / choose_convt decide the split again at launch from the real arguments: a
+// choice of `ks` copies of `out_floats` floats that the buffer does not hold is refused before anything is launched.
+int check_part(int layer, int ks, size_t out_floats, size_t part_bytes)
+{
+    if (ks <= 1 || (size_t)ks * out_floats * sizeof(float) <= part_bytes) return ADN_OK;
+    const LayerDesc &d = NET.v[layer];
+    return fail(ADN_ERR_WORKSPACE, "adn_unet_forward: layer " + std::to_string(layer) + " (" + (d.kind == CONVT ? "transposed convolution" : "3x3 convolution") +
+                " at level " + std::to_string(d.level) + ", " + std::to_string(d.C0 + d.C1) + " -> " + std::to_string(d.Cout) + " channels): " +
+                std::to_string(ks) + " K-split copies of " + std::to_string(out_floats * sizeof(float)) + " bytes do not fit the " +
+                std::to_string(part_bytes) + " bytes the workspace plan reserves for them");
+}
+
+// Executes a choice for layer `layer` of NET.  `a`: the layer with the pointers of the chosen fused forms filled in
+// (ConvArgs::firstw / dotw).  part_bytes: capacity of `partial`.  Returns an ADN status.
+int launch_conv3(const adn_unet *h, int layer, adn::ConvKind kind, const Conv3Choice &c, adn::ConvArgs a, float *partial, size_t part_bytes,
+                 hipStream_t st, const WinoScratch &sc = WinoScratch())
+{
+    if (int rc = check_part(layer, c.ksplit, (size_t)a.N * a.H * a.W * a.Cout, part_bytes)) return rc;
+    return hip_status(launch_conv3_kernels(h, kind, c, a, partial, st, sc), "launch_conv3");
+}
+
 struct ConvTChoice {
     bool t16;      // fp16: convt16_f16 (convt16_kernels.hip) instead of conv_dma
     int ksplit;    // > 1: K-split slices into the partial buffer + a reduce launch (fp32 split-bf16 form)
@@ -652,7 +681,7 @@ ConvTChoice choose_convt(const adn_unet *h, const LayerWeights &L, const adn::Co
     return c;
 }
 
-hipError_t launch_convt(const adn_unet *h, const LayerWeights &L, const ConvTChoice &c, adn::ConvArgs a, float *partial, hipStream_t st)
+hipError_t launch_convt_kernels(const adn_unet *h, const LayerWeights &L, const ConvTChoice &c, adn::ConvArgs a, float *partial, hipStream_t st)
 {
     if (c.t16) {
         a.wpk = h->dev + L.w16_off;
@@ -669,6 +698,12 @@ hipError_t launch_convt(const adn_unet *h, const LayerWeights &L, const ConvTCho
         return adn::launch_convt_reduce(partial, h->dev + L.braw_off, out, c.ksplit, a.N, 2 * a.H, 2 * a.W, a.Cout, st);
     }
     return adn::launch_conv_mfma(adn::CONVT2X2, a, h->f16, st);
+}
+
+int launch_convt(const adn_unet *h, int layer, const ConvTChoice &c, const adn::ConvArgs &a, float *partial, size_t part_bytes, hipStream_t st)
+{
+    if (int rc = check_part(layer, c.ksplit, (size_t)a.N * (2 * a.H) * (2 * a.W) * a.Cout, part_bytes)) return rc;
+    return hip_status(launch_convt_kernels(h, h->lw[layer], c, a, partial, st), "launch_convt");
 }
 
 // ---- forward -------------------------------------------------------------------------------------------------------------------
@@ -699,6 +734,10 @@ int forward_impl(adn_unet *h, const float *x, float *y, int N, int F, int T, voi
 #define ADN_MARK()                                          \
     do {                                                    \
         if (timed) ADN_HIP(hipEventRecord(ev[evi++], st));  \
+    } while (0)
+#define ADN_TRY(call)                                       \
+    do {                                                    \
+        if (int rc_ = (call)) return rc_;                   \
     } while (0)
 
     // block output `idx` = what layer `layer` of NET wrote to `buf`
@@ -733,7 +772,7 @@ int forward_impl(adn_unet *h, const float *x, float *y, int N, int F, int T, voi
             const WinoScratch sc = wino_scratch(i);
             const adn::ConvArgs a = conv_args(h, p, i++, ws + p.pool[l - 1], nullptr, 0, 0, tA, nullptr);
             ADN_MARK();
-            ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, a, false, false, sc), a, part, st, sc));
+            ADN_TRY(launch_conv3(h, i - 1, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, a, false, false, sc), a, part, p.part_bytes, st, sc));
         }
         const WinoScratch sc = wino_scratch(i);
         adn::ConvArgs a = conv_args(h, p, i++, cur, nullptr, 0, 0, skip, pool);
@@ -749,7 +788,7 @@ int forward_impl(adn_unet *h, const float *x, float *y, int N, int F, int T, voi
             }
         }
         ADN_MARK();
-        ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU_POOL, c, a, part, st, sc));
+        ADN_TRY(launch_conv3(h, i - 1, adn::CONV3X3_RELU_POOL, c, a, part, p.part_bytes, st, sc));
         ADN_HIP(export_tap(l, skip, i - 1));
     }
     // ---- bottleneck (model.py:81) ----
@@ -757,26 +796,25 @@ int forward_impl(adn_unet *h, const float *x, float *y, int N, int F, int T, voi
         const WinoScratch sa = wino_scratch(i);
         const adn::ConvArgs a = conv_args(h, p, i++, ws + p.pool[3], nullptr, 0, 0, tA, nullptr);
         ADN_MARK();
-        ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, a, false, false, sa), a, part, st, sa));
+        ADN_TRY(launch_conv3(h, i - 1, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, a, false, false, sa), a, part, p.part_bytes, st, sa));
         const WinoScratch sb = wino_scratch(i);
         const adn::ConvArgs b = conv_args(h, p, i++, tA, nullptr, 0, 0, tB, nullptr);
         ADN_MARK();
-        ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, b, false, false, sb), b, part, st, sb));
+        ADN_TRY(launch_conv3(h, i - 1, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, b, false, false, sb), b, part, p.part_bytes, st, sb));
         ADN_HIP(export_tap(4, tB, i - 1));
     }
     // ---- up path (model.py:84-91): convT -> (virtual) pad + cat([skip, up]) -> DoubleConv ----
     void *X = tB, *Y = tA;   // X holds the current tensor
     Conv3Choice last{};                                  // of the network's last 3x3 layer
     for (int l = 3; l >= 0; --l) {
-        const LayerWeights &TL = h->lw[i];
         const adn::ConvArgs t = convt_args(h, p, i++, X, Y);
         ADN_MARK();
-        ADN_HIP(launch_convt(h, TL, choose_convt(h, TL, t), t, part, st));
+        ADN_TRY(launch_convt(h, i - 1, choose_convt(h, h->lw[i - 1], t), t, part, p.part_bytes, st));
         // first conv of the DoubleConv reads cat([skip, x1]) virtually
         const WinoScratch sa = wino_scratch(i);
         const adn::ConvArgs a = conv_args(h, p, i++, ws + p.skip[l], Y, 2 * t.H, 2 * t.W, X, nullptr);
         ADN_MARK();
-        ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, a, false, false, sa), a, part, st, sa));
+        ADN_TRY(launch_conv3(h, i - 1, adn::CONV3X3_RELU, choose_conv3(h, adn::CONV3X3_RELU, a, false, false, sa), a, part, p.part_bytes, st, sa));
         const WinoScratch sb = wino_scratch(i);
         adn::ConvArgs b = conv_args(h, p, i++, X, nullptr, 0, 0, Y, nullptr);
         // (the fused tails finish ONE class; UNet(..., num_classes > 1) runs the 1x1 convolution class by class below)
@@ -787,7 +825,7 @@ int forward_impl(adn_unet *h, const float *x, float *y, int N, int F, int T, voi
             if (f16) b.dot_bias = h->out_b;
         }
         ADN_MARK();
-        ADN_HIP(launch_conv3(h, adn::CONV3X3_RELU, last, b, part, st, sb));
+        ADN_TRY(launch_conv3(h, i - 1, adn::CONV3X3_RELU, last, b, part, p.part_bytes, st, sb));
         ADN_HIP(export_tap(5 + (3 - l), Y, i - 1));
         std::swap(X, Y);
     }
@@ -807,6 +845,7 @@ int forward_impl(adn_unet *h, const float *x, float *y, int N, int F, int T, voi
         ++h->timing_count;
     }
 #undef ADN_MARK
+#undef ADN_TRY
     if (taps && taps[9])
         ADN_HIP(hipMemcpyAsync(taps[9], y, (size_t)N * h->n_classes * F * T * sizeof(float), hipMemcpyDeviceToDevice, st));
     return ADN_OK;
