@@ -9,14 +9,11 @@
 // Kernels:
 //   dn_windows   X -> |X| cut into K windows per clip (frames >= T zero), 32 x 32 tile through LDS
 //   dn_stitch    y (windows) -> Y or max(Y, 0), (clip, F, T): linear cross-fade of the V shared frames, same layout both sides
-//   dn_resynth   y, X -> audio (clip, L).  A workgroup owns up to SPAN output samples and walks the frames that cover them (its own
-//                and the n_fft/hop - 1 halo frames of its neighbours, recomputed) in stages of SB frames: the stitched, clamped
-//                magnitudes of a stage are read along the frame axis and parked in LDS [frame][bin], then passes of FB frames
-//                rescale X, run the inverse real FFT (fft_frame<M>, as istft_frames_kernel), window the frame in place and
-//                every thread GATHERS its samples from the pass's frames in ascending frame order (as istft_ola_kernel):
-//                no atomics, no frame buffer, no stitched spectrogram, no workspace.
-#include "adn_internal.h"
-#include "fft_core.h"
+//   dn_resynth   y, X -> audio (clip, L): resynthesis in stages and passes (ResynthCfg<M>, spectral.h) over the frames that cover a
+//                workgroup's span (its own and the n_fft/hop - 1 halo frames of its neighbours, recomputed), fed with the
+//                stitched magnitudes; the sums are normalised as the inverse STFT normalises them.  No stitched spectrogram,
+//                no workspace.
+#include "spectral.h"
 
 #include <cfloat>
 
@@ -47,8 +44,11 @@ __device__ __forceinline__ Cover cover_of(int f, const DenoiseGeom &g)
     return c;
 }
 
-// Y = a_lo * y_lo + a_hi * y_hi, two rounded products and one rounded sum (never contracted: the stitch kernel and the fused
-// kernel give the same bits); a frame that one window covers is passed through untouched
+// Y = a_lo * y_lo + a_hi * y_hi; a frame that one window covers is passed through untouched.  hipcc's __fmul_rn / __fadd_rn are
+// the plain operators, so fp contraction may fuse either product, per call site: NOT always two rounded products and a rounded
+// sum.  What is pinned: 4 eps sum_k a_k |y_k| for the stitch kernel (test_stitch_against_restatement; a fused product only
+// tightens it), TOL between the fused kernel and the composed form (test_resynth), and each kernel's own bits as
+// tools/spectral_digest.py records them -- run that tool before reshaping a loop that calls this.
 __device__ __forceinline__ float blend(const Cover &c, float lo, float hi)
 {
     return __fadd_rn(__fmul_rn(c.a_lo, lo), __fmul_rn(c.a_hi, hi));
@@ -60,9 +60,6 @@ __device__ __forceinline__ float stitch_at(const float *__restrict__ yc, int bin
     const float lo = yc[((long)(c.k_hi - 1) * F + bin) * g.Wd + c.j_hi + g.S];
     return blend(c, lo, hi);
 }
-
-// |X| as adn.h fixes it: one product, one fma, one square root
-__device__ __forceinline__ float mag_of(float2 x) { return sqrtf(fmaf(x.x, x.x, __fmul_rn(x.y, x.y))); }
 
 // ---------------------------------------------------------------------------------------------- windows
 __global__ __launch_bounds__(256) void dn_windows_kernel(const float2 *__restrict__ X, int F, DenoiseGeom g, int tilesJ,
@@ -134,46 +131,24 @@ __global__ __launch_bounds__(256) void dn_stitch_kernel(const float *__restrict_
 }
 
 // ---------------------------------------------------------------------------------------------- fused resynthesis
-template <int M>
-struct DnCfg {
-    static constexpr int N = 2 * M, TPF = M / 8, FB = STFT_THREADS / TPF;   // FB frames per FFT pass (GlCfg<M>'s split)
-    static constexpr int TBL = N + 2 * M + (M + 2);                         // window, twiddles, half-step twiddles
-    static constexpr int SB0 = 16384 / M < 32 ? 16384 / M : 32;
-    static constexpr int SB = FB > SB0 ? FB : SB0;                          // frames per stage: 32 (128-byte runs of y) while the
-                                                                            // tile stays near 64 KB: 16 at n_fft 2048, 8 at 4096
-    static constexpr int PITCH = M + 1;                                     // odd: lanes along the frame axis hit distinct banks
-    static constexpr int SPT = 8, SPAN = STFT_THREADS * SPT;                // output samples per thread / per workgroup
-    static constexpr size_t LDS = (size_t)(TBL + 2 * FB * M + SB * PITCH) * sizeof(float);
-    static_assert(SB % FB == 0 && STFT_THREADS % SB == 0 && (SB & (SB - 1)) == 0, "bad stage size");
-    static_assert(LDS <= 160 * 1024, "stage does not fit the LDS of a CU");
-};
-
-// S^[k] = M[k] * X[k] / |X[k]|, M real where |X| = 0
-__device__ __forceinline__ float2 rephase(float2 x, float m)
-{
-    const float mag = mag_of(x);
-    if (mag == 0.f) return make_float2(m, 0.f);
-    const float s = m / mag;
-    return make_float2(x.x * s, x.y * s);
-}
-
 // at the default n_fft 512 (70 KB of LDS) two workgroups fit a CU: the registers are capped at 128 there (fits without spills)
 template <int M>
 __global__ __launch_bounds__(STFT_THREADS, (M == 256 ? 4 : 2)) void dn_resynth_kernel(
     const float *__restrict__ y, const float2 *__restrict__ X, long L, int hop, DenoiseGeom g, int span, int nblk,
     const float *__restrict__ tables, float *__restrict__ audio)
 {
-    using C = DnCfg<M>;
-    constexpr int N = C::N, TPF = C::TPF, FB = C::FB, SB = C::SB, F = M + 1, P = C::PITCH, SPT = C::SPT;
+    using C = ResynthCfg<M>;
+    using S = SpecCfg<M>;
+    constexpr int N = S::N, TPF = S::TPF, FB = S::FB, SB = C::SB, F = S::F, P = C::PITCH, SPT = C::SPT;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *s_win = smem;
     float2 *s_tw = reinterpret_cast<float2 *>(smem + N);
     float2 *s_tw2 = s_tw + M;                                   // exp(-2 pi i k / N), k = 0 .. M/2
-    float2 *s_sc = reinterpret_cast<float2 *>(smem + C::TBL);
-    float *s_fr = smem + C::TBL;                                // the same storage once a pass's frames are windowed: [FB][N]
-    float *s_tile = smem + C::TBL + 2 * FB * M;                 // [SB][P] stitched, clamped magnitudes of the stage
+    float2 *s_sc = reinterpret_cast<float2 *>(smem + S::TBL);
+    float *s_fr = smem + S::TBL;                                // the same storage once a pass's frames are windowed: [FB][N]
+    float *s_tile = smem + S::TBL + 2 * FB * M;                 // [SB][P] stitched, clamped magnitudes of the stage
     const int tid = threadIdx.x;
-    for (int i = tid; i < C::TBL; i += STFT_THREADS) smem[i] = tables[i];
+    for (int i = tid; i < S::TBL; i += STFT_THREADS) smem[i] = tables[i];
 
     const long clip = blockIdx.x / (unsigned)nblk;
     const int bx = (int)(blockIdx.x - clip * nblk);
@@ -181,7 +156,7 @@ __global__ __launch_bounds__(STFT_THREADS, (M == 256 ? 4 : 2)) void dn_resynth_k
     const long n1 = n0 + span < L ? n0 + span : L;
     const int T = g.T;
     // frames that cover the span: sample n sits at p = n + n_fft/2 of the untrimmed signal, inside frames
-    // ceil((p - n_fft + 1) / hop) .. floor(p / hop), clipped to [0, T)   (istft_ola_kernel's range)
+    // ceil((p - n_fft + 1) / hop) .. floor(p / hop), clipped to [0, T)
     const int f_begin = n0 + M < N ? 0 : (int)((n0 + M - N + hop) / hop);
     int f_end = (int)((n1 - 1 + M) / hop);
     if (f_end > T - 1) f_end = T - 1;
@@ -257,7 +232,7 @@ __global__ __launch_bounds__(STFT_THREADS, (M == 256 ? 4 : 2)) void dn_resynth_k
                 sc[n] = make_float2(s_win[2 * n] * (z.x * inv), s_win[2 * n + 1] * (-z.y * inv));
             }
             __syncthreads();
-            // gather: frame fr holds the sample at j = p - fr * hop when 0 <= j < n_fft; frames ascend, as in istft_ola_kernel
+            // gather: frame fr holds the sample at j = p - fr * hop when 0 <= j < n_fft; frames ascend
             const int fr_last = fp + FB - 1 < f_end ? fp + FB - 1 : f_end;
             for (int fr = fp; fr <= fr_last; ++fr) {
                 const float *frame = s_fr + (fr - fp) * N;
@@ -278,7 +253,7 @@ __global__ __launch_bounds__(STFT_THREADS, (M == 256 ? 4 : 2)) void dn_resynth_k
     for (int u = 0; u < SPT; ++u) {
         const long n = n0 + tid + u * STFT_THREADS;
         if (n >= n1) continue;
-        // window sum-of-squares of the frames that cover the sample: istft_ola_kernel's range, order and arithmetic
+        // window sum-of-squares of the frames that cover the sample, the inverse STFT's normalisation
         const int p = p0 + u * STFT_THREADS;
         int f_hi = p / hop;
         if (f_hi > T - 1) f_hi = T - 1;
@@ -296,18 +271,16 @@ template <int M>
 hipError_t launch_resynth_m(const float *y, const float2 *X, int n_clips, long L, int hop, const DenoiseGeom &g,
                             const float *tables, float *audio, hipStream_t st)
 {
-    using C = DnCfg<M>;
-    auto kern = dn_resynth_kernel<M>;
-    if (C::LDS > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)C::LDS);
-        if (e != hipSuccess) return e;
-    }
+    using C = ResynthCfg<M>;
+    constexpr auto kern = dn_resynth_kernel<M>;
+    const hipError_t e = lds_opt_in<kern>(C::LDS);
+    if (e != hipSuccess) return e;
     // span: the most samples (<= SPAN) whose frames, halo included, fill whole FFT passes: hop * (k * FB - halo)
-    const int halo = (C::N + hop - 1) / hop - 1;
+    constexpr int FB = SpecCfg<M>::FB;
+    const int halo = (2 * M + hop - 1) / hop - 1;
     int span = C::SPAN;
-    for (long k = 1; hop * (k * C::FB - halo) <= C::SPAN; ++k)
-        if (k * C::FB > halo) span = (int)(hop * (k * C::FB - halo));
+    for (long k = 1; hop * (k * FB - halo) <= C::SPAN; ++k)
+        if (k * FB > halo) span = (int)(hop * (k * FB - halo));
     const long nblk = (L + span - 1) / span;
     if (nblk * n_clips > 0x7fffffffL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(kern, dim3((unsigned)(nblk * n_clips)), dim3(STFT_THREADS), C::LDS, st, y, X, L, hop, g, span,
@@ -364,16 +337,7 @@ hipError_t launch_denoise_resynth(const float *y, const void *spec, int n_clips,
     hipError_t e = stft_tables(n_fft, &tables, st);
     if (e != hipSuccess) return e;
     const float2 *X = static_cast<const float2 *>(spec);
-    switch (n_fft) {
-        case 64: return launch_resynth_m<32>(y, X, n_clips, L, hop, g, tables, audio, st);
-        case 128: return launch_resynth_m<64>(y, X, n_clips, L, hop, g, tables, audio, st);
-        case 256: return launch_resynth_m<128>(y, X, n_clips, L, hop, g, tables, audio, st);
-        case 512: return launch_resynth_m<256>(y, X, n_clips, L, hop, g, tables, audio, st);
-        case 1024: return launch_resynth_m<512>(y, X, n_clips, L, hop, g, tables, audio, st);
-        case 2048: return launch_resynth_m<1024>(y, X, n_clips, L, hop, g, tables, audio, st);
-        case 4096: return launch_resynth_m<2048>(y, X, n_clips, L, hop, g, tables, audio, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_n_fft(n_fft, [&](auto m) { return launch_resynth_m<m()>(y, X, n_clips, L, hop, g, tables, audio, st); });
 }
 
 }  // namespace adn

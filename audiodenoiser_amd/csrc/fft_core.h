@@ -1,4 +1,5 @@
-// Workgroup-synchronous Stockham FFT building blocks shared by the STFT, inverse-STFT and Griffin-Lim kernels.
+// Workgroup-synchronous Stockham FFT building blocks of the spectral kernels (STFT, inverse STFT, Griffin-Lim, denoise, stream);
+// what those kernels share around the FFT -- tables, real-FFT split, overlap-add, resynthesis -- is spectral.h.
 // An M-point complex FFT runs with 8 points per thread in registers (radix-8 passes, one radix-4/2 tail pass),
 // exchanging through an LDS image between passes; STFT_THREADS / (M/8) frames run side by side in a workgroup.
 #pragma once

@@ -17,8 +17,7 @@
 //                  and is normalised by the window sum-of-squares computed from the same frame range
 //   stft_complex   audio (N,L) -> spec (N,T,F), centred, zero padded (the magnitude kernel's transform, complex out)
 // The "S = |Z| * exp(i angle(Z))" step of test.py:46 is the identity on Z up to two roundings; the loop keeps Z.
-#include "adn_internal.h"
-#include "fft_core.h"
+#include "spectral.h"
 
 #include <cfloat>
 
@@ -26,13 +25,6 @@ namespace adn {
 namespace {
 
 using namespace fftcore;
-
-template <int M>
-struct GlCfg {
-    static constexpr int N = 2 * M, TPF = M / 8, FB = STFT_THREADS / TPF;   // FB frames per workgroup pass
-    static constexpr int TBL = N + 2 * M + (M + 2);
-    static constexpr size_t LDS = (size_t)(TBL + 2 * FB * M) * sizeof(float);
-};
 
 // ---------------------------------------------------------------------------------------------- polar
 __global__ __launch_bounds__(256) void gl_polar_kernel(const float *__restrict__ mag, const float *__restrict__ rnd,
@@ -67,18 +59,14 @@ __global__ __launch_bounds__(STFT_THREADS) void istft_frames_kernel(const float2
                                                                    const float *__restrict__ tables,
                                                                    float *__restrict__ buf)
 {
-    using C = GlCfg<M>;
-    constexpr int N = C::N, TPF = C::TPF, FB = C::FB, F = M + 1;
+    using C = SpecCfg<M>;
+    constexpr int N = C::N, TPF = C::TPF, FB = C::FB, F = C::F;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *s_win = smem;
-    float2 *s_tw = reinterpret_cast<float2 *>(smem + N);
-    float2 *s_tw2 = s_tw + M;                                   // exp(-2 pi i k / N), k = 0 .. M/2
-    float2 *s_sc = reinterpret_cast<float2 *>(smem + C::TBL);
-    const int tid = threadIdx.x;
-    for (int i = tid; i < C::TBL; i += STFT_THREADS) smem[i] = tables[i];
+    const SpecTables tb = C::view(smem);
+    C::load(smem, tables);
     __syncthreads();
 
-    const int fl = tid / TPF, t = tid - fl * TPF;
+    const int tid = threadIdx.x, fl = tid / TPF, t = tid - fl * TPF;
     const long clip = blockIdx.y;
     const int f = blockIdx.x * FB + fl;
     const bool live = f < T;
@@ -88,21 +76,18 @@ __global__ __launch_bounds__(STFT_THREADS) void istft_frames_kernel(const float2
     for (int u = 0; u < 8; ++u) {
         const int k = t + u * TPF;                               // 0 .. M-1
         float2 xk = X[k], xm = X[M - k];
-        if (k == 0) { xk.y = 0.f; xm.y = 0.f; }                  // irfft ignores Im X[0], Im X[M]
-        // Ev = (X[k] + conj X[M-k]) / 2,  w^k Od = (X[k] - conj X[M-k]) / 2
+        if (k == 0) { xk.y = 0.f; xm.y = 0.f; }                  // (the inverse real-FFT split: spectral.h)
         const float2 ev = make_float2(0.5f * (xk.x + xm.x), 0.5f * (xk.y - xm.y));
         const float2 d = make_float2(0.5f * (xk.x - xm.x), 0.5f * (xk.y + xm.y));
-        // w^{-k}: conj(tw2[k]) for k <= M/2, -tw2[M-k] above (w^M = -1)
         float2 wi;
-        if (k <= M / 2) { const float2 w = s_tw2[k]; wi = make_float2(w.x, -w.y); }
-        else { const float2 w = s_tw2[M - k]; wi = make_float2(-w.x, -w.y); }
+        if (k <= M / 2) { const float2 w = tb.tw2[k]; wi = make_float2(w.x, -w.y); }
+        else { const float2 w = tb.tw2[M - k]; wi = make_float2(-w.x, -w.y); }
         const float2 od = cmul(wi, d);
-        // Z = Ev + i Od; the inverse transform is run as conj(FFT(conj Z))
         const float2 z = make_float2(ev.x - od.y, ev.y + od.x);
         v[u] = live ? make_float2(z.x, -z.y) : make_float2(0.f, 0.f);
     }
-    float2 *sc = s_sc + fl * M;
-    fft_frame<M>(sc, s_tw, t, v);
+    float2 *sc = C::frames(smem) + fl * M;
+    fft_frame<M>(sc, tb.tw, t, v);
     if (live) {
         float *o = buf + (clip * T + f) * (long)N;
         const float inv = 1.0f / (float)M;
@@ -111,7 +96,7 @@ __global__ __launch_bounds__(STFT_THREADS) void istft_frames_kernel(const float2
             const int n = t + u * TPF;
             const float2 z = sc[n];                              // conj -> x[2n] = Re, x[2n+1] = -Im
             *reinterpret_cast<float2 *>(o + 2 * n) =
-                make_float2(s_win[2 * n] * (z.x * inv), s_win[2 * n + 1] * (-z.y * inv));
+                make_float2(tb.win[2 * n] * (z.x * inv), tb.win[2 * n + 1] * (-z.y * inv));
         }
     }
 }
@@ -146,18 +131,14 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_complex_kernel(const float 
                                                                    int pad, int T, const float *__restrict__ tables,
                                                                    float2 *__restrict__ spec)
 {
-    using C = GlCfg<M>;
-    constexpr int N = C::N, TPF = C::TPF, FB = C::FB, F = M + 1;
+    using C = SpecCfg<M>;
+    constexpr int TPF = C::TPF, FB = C::FB, F = C::F;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *s_win = smem;
-    float2 *s_tw = reinterpret_cast<float2 *>(smem + N);
-    float2 *s_tw2 = s_tw + M;
-    float2 *s_sc = reinterpret_cast<float2 *>(smem + C::TBL);
-    const int tid = threadIdx.x;
-    for (int i = tid; i < C::TBL; i += STFT_THREADS) smem[i] = tables[i];
+    const SpecTables tb = C::view(smem);
+    C::load(smem, tables);
     __syncthreads();
 
-    const int fl = tid / TPF, t = tid - fl * TPF;
+    const int tid = threadIdx.x, fl = tid / TPF, t = tid - fl * TPF;
     const long clip = blockIdx.y;
     const int f = blockIdx.x * FB + fl;
     const bool live = f < T;
@@ -170,50 +151,26 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_complex_kernel(const float 
         const long s = s0 + n2;
         const float x0 = (live && s >= 0 && s < L) ? a[s] : 0.f;
         const float x1 = (live && s + 1 >= 0 && s + 1 < L) ? a[s + 1] : 0.f;
-        v[u] = make_float2(s_win[n2] * x0, s_win[n2 + 1] * x1);
+        v[u] = make_float2(tb.win[n2] * x0, tb.win[n2 + 1] * x1);
     }
-    float2 *sc = s_sc + fl * M;
-    fft_frame<M>(sc, s_tw, t, v);
+    float2 *sc = C::frames(smem) + fl * M;
+    fft_frame<M>(sc, tb.tw, t, v);
     if (live) {
         float2 *o = spec + (clip * T + f) * (long)F;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int k = t + b * TPF;                            // 0 .. M/2-1
-            if (k == 0) {
-                const float2 z0 = sc[0];
-                o[0] = make_float2(z0.x + z0.y, 0.f);
-                o[M] = make_float2(z0.x - z0.y, 0.f);
-                const float2 zh = sc[M / 2];
-                o[M / 2] = make_float2(zh.x, -zh.y);
-            } else {
-                const float2 A = sc[k], Bc = sc[M - k];
-                const float2 ev = make_float2(0.5f * (A.x + Bc.x), 0.5f * (A.y - Bc.y));
-                const float2 d = make_float2(0.5f * (A.x - Bc.x), 0.5f * (A.y + Bc.y));
-                const float2 wo = cmul(s_tw2[k], make_float2(d.y, -d.x));     // w^k * (d / i)
-                o[k] = cadd(ev, wo);
-                const float2 xb = csub(ev, wo);
-                o[M - k] = make_float2(xb.x, -xb.y);
-            }
-        }
+        forward_split<M>(sc, tb.tw2, t, [&](int k, float2 xa, float2 xb) { o[k] = xa; o[M - k] = xb; },
+                         [&](float2 x0, float2 xM, float2 xh) { o[0] = x0; o[M] = xM; o[M / 2] = xh; });
     }
-}
-
-template <int M>
-hipError_t set_lds(const void *fn)
-{
-    if (GlCfg<M>::LDS > 64 * 1024)
-        return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GlCfg<M>::LDS);
-    return hipSuccess;
 }
 
 template <int M>
 hipError_t launch_istft_frames_m(const float2 *spec, int n_clips, int T, const float *tables, float *buf, hipStream_t st)
 {
-    auto kern = istft_frames_kernel<M>;
-    hipError_t e = set_lds<M>(reinterpret_cast<const void *>(kern));
+    using C = SpecCfg<M>;
+    constexpr auto kern = istft_frames_kernel<M>;
+    const hipError_t e = lds_opt_in<kern>(C::LDS);
     if (e != hipSuccess) return e;
-    dim3 grid((unsigned)((T + GlCfg<M>::FB - 1) / GlCfg<M>::FB), (unsigned)n_clips);
-    hipLaunchKernelGGL(kern, grid, dim3(STFT_THREADS), GlCfg<M>::LDS, st, spec, T, tables, buf);
+    dim3 grid((unsigned)((T + C::FB - 1) / C::FB), (unsigned)n_clips);
+    hipLaunchKernelGGL(kern, grid, dim3(STFT_THREADS), C::LDS, st, spec, T, tables, buf);
     return hipGetLastError();
 }
 
@@ -221,11 +178,12 @@ template <int M>
 hipError_t launch_stft_complex_m(const float *audio, int n_clips, long L, int hop, int pad, int T, const float *tables,
                                  float2 *spec, hipStream_t st)
 {
-    auto kern = stft_complex_kernel<M>;
-    hipError_t e = set_lds<M>(reinterpret_cast<const void *>(kern));
+    using C = SpecCfg<M>;
+    constexpr auto kern = stft_complex_kernel<M>;
+    const hipError_t e = lds_opt_in<kern>(C::LDS);
     if (e != hipSuccess) return e;
-    dim3 grid((unsigned)((T + GlCfg<M>::FB - 1) / GlCfg<M>::FB), (unsigned)n_clips);
-    hipLaunchKernelGGL(kern, grid, dim3(STFT_THREADS), GlCfg<M>::LDS, st, audio, L, hop, pad, T, tables, spec);
+    dim3 grid((unsigned)((T + C::FB - 1) / C::FB), (unsigned)n_clips);
+    hipLaunchKernelGGL(kern, grid, dim3(STFT_THREADS), C::LDS, st, audio, L, hop, pad, T, tables, spec);
     return hipGetLastError();
 }
 
@@ -244,16 +202,7 @@ hipError_t launch_istft_frames(const void *spec, int n_clips, int T, int n_fft, 
     hipError_t e = stft_tables(n_fft, &tables, st);
     if (e != hipSuccess) return e;
     const float2 *s = static_cast<const float2 *>(spec);
-    switch (n_fft) {
-        case 64: return launch_istft_frames_m<32>(s, n_clips, T, tables, buf, st);
-        case 128: return launch_istft_frames_m<64>(s, n_clips, T, tables, buf, st);
-        case 256: return launch_istft_frames_m<128>(s, n_clips, T, tables, buf, st);
-        case 512: return launch_istft_frames_m<256>(s, n_clips, T, tables, buf, st);
-        case 1024: return launch_istft_frames_m<512>(s, n_clips, T, tables, buf, st);
-        case 2048: return launch_istft_frames_m<1024>(s, n_clips, T, tables, buf, st);
-        case 4096: return launch_istft_frames_m<2048>(s, n_clips, T, tables, buf, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_n_fft(n_fft, [&](auto m) { return launch_istft_frames_m<m()>(s, n_clips, T, tables, buf, st); });
 }
 
 hipError_t launch_istft_ola(const float *buf, int n_clips, int T, int n_fft, int hop, float *audio, hipStream_t st)
@@ -276,16 +225,7 @@ hipError_t launch_stft_complex(const float *audio, int n_clips, long L, int n_ff
     if (e != hipSuccess) return e;
     float2 *s = static_cast<float2 *>(spec);
     const int pad = n_fft / 2;
-    switch (n_fft) {
-        case 64: return launch_stft_complex_m<32>(audio, n_clips, L, hop, pad, T, tables, s, st);
-        case 128: return launch_stft_complex_m<64>(audio, n_clips, L, hop, pad, T, tables, s, st);
-        case 256: return launch_stft_complex_m<128>(audio, n_clips, L, hop, pad, T, tables, s, st);
-        case 512: return launch_stft_complex_m<256>(audio, n_clips, L, hop, pad, T, tables, s, st);
-        case 1024: return launch_stft_complex_m<512>(audio, n_clips, L, hop, pad, T, tables, s, st);
-        case 2048: return launch_stft_complex_m<1024>(audio, n_clips, L, hop, pad, T, tables, s, st);
-        case 4096: return launch_stft_complex_m<2048>(audio, n_clips, L, hop, pad, T, tables, s, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_n_fft(n_fft, [&](auto m) { return launch_stft_complex_m<m()>(audio, n_clips, L, hop, pad, T, tables, s, st); });
 }
 
 }  // namespace adn

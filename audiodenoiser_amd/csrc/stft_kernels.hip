@@ -14,8 +14,7 @@
 // HBM-bound by design (about 10 FLOP/B): a workgroup owns FPB consecutive frames of one clip, stages the
 // overlapping audio span in LDS once (75 % overlap at hop = n_fft/4 is served on-chip), and transposes the
 // magnitudes through LDS so that stores run along the frame axis.
-#include "adn_internal.h"
-#include "fft_core.h"
+#include "spectral.h"
 
 #include <hip/hip_fp16.h>
 
@@ -45,32 +44,31 @@ __device__ __forceinline__ float stft_emit(float v, int quantize)
     return quantize ? __half2float(__float2half_rn(v)) : v;
 }
 
+// stft_mag_kernel's own tiling.  Of SpecCfg<M> it takes the tables only (T::TBL, T::view, T::load): its FFT images sit behind
+// the magnitude image, not at SpecCfg's frames(), and its LDS size is launch_m's.
 template <int M>
 struct StftCfg {
-    static constexpr int N = 2 * M;
-    static constexpr int TPF = M / 8;                                  // threads per frame
-    static constexpr int FPW = STFT_THREADS / TPF;                      // frames the workgroup can run at once
+    using T = SpecCfg<M>;
+    static constexpr int N = T::N, TPF = T::TPF;
+    static constexpr int FPW = T::FB;                                   // frames the workgroup can run at once
     static constexpr int FPB = (M <= 512) ? (FPW > 16 ? FPW : 16) : 8192 / M;   // frames per workgroup
     static constexpr int FB = FPW < FPB ? FPW : FPB;                    // frames per batch
     static constexpr int NBATCH = FPB / FB;
     static constexpr int MAGSTR = FPB + 1;
 };
 
-// tables (device, fp32, computed in double on the host): win[N], tw[M] = exp(-2 pi i j / M),
-// tw2[M/2+1] = exp(-2 pi i k / N)
+// LDS: the tables, the [bin][frame] magnitude image, then the work area (a batch's audio span, then its FFT images)
 template <int M>
 __global__ __launch_bounds__(STFT_THREADS) void stft_mag_kernel(const float *__restrict__ audio, long L, int hop, int pad,
                                                                long n_frames, int groups_per_clip,
                                                                const float *__restrict__ tables, float *__restrict__ out,
-                                                               int work_floats, const StftOut o)
+                                                               const StftOut o)
 {
     using C = StftCfg<M>;
     constexpr int N = C::N, TPF = C::TPF, FPB = C::FPB, FB = C::FB, NBATCH = C::NBATCH, MAGSTR = C::MAGSTR;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *s_win = smem;                                             // N
-    float2 *s_tw = reinterpret_cast<float2 *>(smem + N);             // M
-    float2 *s_tw2 = s_tw + M;                                        // M/2 + 1 (padded to even count)
-    float *s_mag = smem + N + 2 * M + (M + 2);                       // (M+1) * MAGSTR
+    const SpecTables tb = C::T::view(smem);
+    float *s_mag = smem + C::T::TBL;                                    // (M+1) * MAGSTR
     float *s_work = s_mag + (M + 1) * MAGSTR + (((M + 1) * MAGSTR) & 1);   // keep 8-byte alignment
     float2 *s_sc = reinterpret_cast<float2 *>(s_work);
 
@@ -80,11 +78,10 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_mag_kernel(const float *__r
     const long f0 = (long)grp * FPB;
     const float *aud = audio + clip * L;
 
-    for (int i = tid; i < N + 2 * M + (M + 2); i += STFT_THREADS) smem[i] = tables[i];
+    C::T::load(smem, tables);
 
     const int fl = tid / TPF, t = tid - fl * TPF;
     const int span = (FB - 1) * hop + N;
-    (void)work_floats;
 
 #pragma unroll 1
     for (int bt = 0; bt < NBATCH; ++bt) {
@@ -102,7 +99,7 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_mag_kernel(const float *__r
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int n2 = 2 * (t + u * TPF);
-                v[u] = make_float2(s_win[n2] * a[n2], s_win[n2 + 1] * a[n2 + 1]);
+                v[u] = make_float2(tb.win[n2] * a[n2], tb.win[n2 + 1] * a[n2 + 1]);
             }
         } else {
 #pragma unroll
@@ -110,9 +107,10 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_mag_kernel(const float *__r
         }
         // frames beyond FB (possible only when FPW > FPB, never with the configs above) share slot 0 harmlessly
         float2 *sc = s_sc + (fl < FB ? fl : 0) * M;
-        fft_frame<M>(sc, s_tw, t, v);      // first pass syncs before it overwrites the audio span
+        fft_frame<M>(sc, tb.tw, t, v);     // first pass syncs before it overwrites the audio span
 
-        // ---- real-FFT post-processing + magnitude, into the [bin][frame] LDS image ----
+        // ---- real-FFT split (forward_split of spectral.h, written out: only |X| is kept, and the fp contraction of
+        // these sums follows their shape) + magnitude, into the [bin][frame] LDS image ----
         if (fl < FB) {
             const int fcol = bt * FB + fl;
 #pragma unroll
@@ -131,7 +129,7 @@ __global__ __launch_bounds__(STFT_THREADS) void stft_mag_kernel(const float *__r
                     const float2 ev = make_float2(0.5f * (A.x + Bz.x), 0.5f * (A.y + Bz.y));
                     const float2 d = make_float2(0.5f * (A.x - Bz.x), 0.5f * (A.y - Bz.y));
                     const float2 od = make_float2(d.y, -d.x);          // d / i
-                    const float2 wo = cmul(s_tw2[k], od);
+                    const float2 wo = cmul(tb.tw2[k], od);
                     const float2 xa = cadd(ev, wo), xb = csub(ev, wo);
                     s_mag[k * MAGSTR + fcol] = sqrtf(xa.x * xa.x + xa.y * xa.y);
                     s_mag[(M - k) * MAGSTR + fcol] = sqrtf(xb.x * xb.x + xb.y * xb.y);
@@ -172,77 +170,44 @@ __device__ __forceinline__ void ADN_XWR(v2f *p, v2f val) { *(lds_v_v2f *)p = val
 // Complex arithmetic on the packed-fp32 pipe with the rotations folded into the VOP3P operand modifiers (op_sel picks which
 // half of a 64-bit source feeds the low result, op_sel_hi the high result; neg_lo / neg_hi negate the selected half).  hipcc
 // does not form these from vector code: a multiplication by -i or a conjugate became v_mov / v_xor pairs in front of a plain
-// v_pk_add_f32 -- 85 v_mov per frame against 154 packed operations.  (ADN_STFT_OPSEL=0: the plain vector-code form.)
-#ifndef ADN_STFT_OPSEL
-#define ADN_STFT_OPSEL 1
-#endif
-#if !ADN_STFT_OPSEL
-__device__ __forceinline__ v2f vnegi(v2f a) { return v2f{a.y, -a.x}; }
-#endif
+// v_pk_add_f32 -- 85 v_mov per frame against 154 packed operations.
 __device__ __forceinline__ v2f vadd_negi(v2f a, v2f b)   // a + (-i) b = (a.x + b.y, a.y - b.x)
 {
-#if ADN_STFT_OPSEL
     v2f r;
     asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
     return r;
-#else
-    return a + vnegi(b);
-#endif
 }
 __device__ __forceinline__ v2f vsub_negi(v2f a, v2f b)   // a - (-i) b = (a.x - b.y, a.y + b.x)
 {
-#if ADN_STFT_OPSEL
     v2f r;
     asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
     return r;
-#else
-    return a - vnegi(b);
-#endif
 }
 __device__ __forceinline__ v2f vadd_conj(v2f a, v2f b)   // a + conj(b)
 {
-#if ADN_STFT_OPSEL
     v2f r;
     asm("v_pk_add_f32 %0, %1, %2 neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
     return r;
-#else
-    return a + v2f{b.x, -b.y};
-#endif
 }
 __device__ __forceinline__ v2f vsub_conj(v2f a, v2f b)   // a - conj(b)
 {
-#if ADN_STFT_OPSEL
     v2f r;
     asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
     return r;
-#else
-    return a - v2f{b.x, -b.y};
-#endif
 }
 __device__ __forceinline__ v2f vmul(v2f a, v2f b)   // complex multiply a * b = a.x * (b.x, b.y) + a.y * (-b.y, b.x)
 {
-#if ADN_STFT_OPSEL
     v2f t, r;
     asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,1]" : "=v"(t) : "v"(a), "v"(b));
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]" : "=v"(r) : "v"(a), "v"(b), "v"(t));
     return r;
-#else
-    const v2f bs = {-b.y, b.x};
-    return a.x * b + a.y * bs;
-#endif
 }
 __device__ __forceinline__ v2f vmul_negi(v2f a, v2f d)   // a * ((-i) d) = a.x * (d.y, -d.x) + a.y * (d.x, d.y)
 {
-#if ADN_STFT_OPSEL
     v2f t, r;
     asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[0,0] neg_hi:[0,1]" : "=v"(t) : "v"(a), "v"(d));
     asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1]" : "=v"(r) : "v"(a), "v"(d), "v"(t));
     return r;
-#else
-    const v2f b = vnegi(d);
-    const v2f bs = {-b.y, b.x};
-    return a.x * b + a.y * bs;
-#endif
 }
 
 template <int R>
@@ -351,13 +316,15 @@ __device__ __forceinline__ void load_pass_twiddles(const float *tables, int t, v
     }
 }
 
-// radix plan: pass 1 is always radix 8 (P=1, no twiddles); then (R2,P2=8) and (R3,P3=8*R2) where present
+// radix plan: pass 1 is always radix 8 (P=1, no twiddles); then (R2,P2=8) and (R3,P3=8*R2) where present.
+// NW waves per workgroup, FPB frames per group of stft_wave_kernel.
 template <int M> struct WavePlan;
-template <> struct WavePlan<32>  { static constexpr int R2 = 4, R3 = 1; };
-template <> struct WavePlan<64>  { static constexpr int R2 = 8, R3 = 1; };
-template <> struct WavePlan<128> { static constexpr int R2 = 8, R3 = 2; };
-template <> struct WavePlan<256> { static constexpr int R2 = 8, R3 = 4; };
-template <> struct WavePlan<512> { static constexpr int R2 = 8, R3 = 8; };
+template <> struct WavePlan<32>  { static constexpr int R2 = 4, R3 = 1, NW = 1, FPB = 16; };
+template <> struct WavePlan<64>  { static constexpr int R2 = 8, R3 = 1, NW = 2, FPB = 16; };
+template <> struct WavePlan<128> { static constexpr int R2 = 8, R3 = 2, NW = 4, FPB = 16; };
+// <NW, FPB> measured on 10 k x 3 s clips (ms): <8,16> 9.31, <4,16> 5.42, <2,32> 6.08, <2,16> 4.78, <4,32> 4.71
+template <> struct WavePlan<256> { static constexpr int R2 = 8, R3 = 4, NW = 4, FPB = 32; };
+template <> struct WavePlan<512> { static constexpr int R2 = 8, R3 = 8, NW = 4, FPB = 16; };
 
 // at least 3 waves per SIMD: the register allocation granule is 8, so 169 VGPRs would already drop to 2
 template <int M, int NW, int FPB, int WPE, bool FIT>
@@ -428,7 +395,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void stft_wave_kernel(const float *__
     // there: 10 KB of L2->CU traffic per workgroup instead of 53 KB of per-lane gathers (the kernel is bound by
     // the CU's ingest path, not by HBM).
     {
-        constexpr int TBL = N + 2 * M + (M + 2);
+        constexpr int TBL = SpecCfg<M>::TBL;
         static_assert(TBL <= (M + 1) * MAGSTR, "table must fit the magnitude image");
         for (int i = tid * 4; i < TBL; i += NT * 4) {
             if (i + 4 <= TBL) *reinterpret_cast<f4 *>(s_mag + i) = *reinterpret_cast<const f4 *>(tables + i);
@@ -450,7 +417,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void stft_wave_kernel(const float *__
     __syncthreads();                                      // everyone holds its constants: the image may be written
 
     int g = g_first, fi = 0;
-    // one frame of this slot's sequence (the body of the frame loop; see the two loops below)
+    // one frame of this slot's sequence (the body of the frame loop)
     auto frame = [&](const int it) __attribute__((always_inline)) {
         const int fcol = slot * FPS + fi;
         v2f v[8];
@@ -584,7 +551,7 @@ __global__ __launch_bounds__(NW * 64, WPE) void stft_fit_kernel(const float *__r
     constexpr int SLOTS = NT / TPF, FPS = FPB / SLOTS;       // frames per slot and group, processed in sequence
     constexpr int SCSZ = exch_size<M>();
     constexpr int R2 = WavePlan<M>::R2, R3 = WavePlan<M>::R3;
-    constexpr int TBL = N + 2 * M + (M + 2);
+    constexpr int TBL = SpecCfg<M>::TBL;
     static_assert(TPF <= 64 && FPB % SLOTS == 0 && FPS >= 1 && M >= 128, "bad STFT tiling");
     static_assert(TBL * 4 <= (M + 1) * FPB * 2, "table must fit the magnitude image");
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -728,9 +695,9 @@ __global__ __launch_bounds__(NW * 64, WPE) void stft_fit_kernel(const float *__r
     }
 }
 
-template <int M, int NW, int FPB, int WPE = 3>
-hipError_t launch_wave(const float *audio, int n_clips, long L, int hop, int pad, long n_frames, const float *tables,
-                       float *out, const StftOut &o, hipStream_t st, int gpb)
+template <auto KERN, int M, int NW, int FPB>
+hipError_t launch_wave_k(const float *audio, int n_clips, long L, int hop, int pad, long n_frames, const float *tables,
+                         float *out, const StftOut &o, hipStream_t st, int gpb)
 {
     constexpr int TPF = M / 8, SLOTS = NW * 64 / TPF;
     const long groups = (n_frames + FPB - 1) / FPB;
@@ -740,16 +707,20 @@ hipError_t launch_wave(const float *audio, int n_clips, long L, int hop, int pad
     const long nwg = bpc * n_clips;
     if (nwg <= 0 || nwg > 0x7fffffffL) return hipErrorInvalidValue;
     const size_t lds = (size_t)((((M + 1) * (FPB + 1) + 1) & ~1) + 2 * SLOTS * exch_size<M>()) * sizeof(float);
-    const bool fit = o.quantize != 0;
-    auto kern = fit ? stft_wave_kernel<M, NW, FPB, WPE, true> : stft_wave_kernel<M, NW, FPB, WPE, false>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(NW * 64), lds, st, audio, L, hop, pad, n_frames, (int)groups,
+    const hipError_t e = lds_opt_in<KERN>(lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(KERN, dim3((unsigned)nwg), dim3(NW * 64), lds, st, audio, L, hop, pad, n_frames, (int)groups,
                        gpb, (int)bpc, tables, out, o);
     return hipGetLastError();
+}
+// The fitted form of the wave kernel serves the sizes stft_fit_kernel does not (M < 128).
+template <int M, int NW, int FPB, int WPE = 3>
+hipError_t launch_wave(const float *audio, int n_clips, long L, int hop, int pad, long n_frames, const float *tables,
+                       float *out, const StftOut &o, hipStream_t st, int gpb)
+{
+    if constexpr (M < 128)
+        if (o.quantize) return launch_wave_k<stft_wave_kernel<M, NW, FPB, WPE, true>, M, NW, FPB>(audio, n_clips, L, hop, pad, n_frames, tables, out, o, st, gpb);
+    return launch_wave_k<stft_wave_kernel<M, NW, FPB, WPE, false>, M, NW, FPB>(audio, n_clips, L, hop, pad, n_frames, tables, out, o, st, gpb);
 }
 
 template <int M, int NW, int WPE = 3>
@@ -761,7 +732,7 @@ hipError_t launch_fit(const float *audio, int n_clips, long L, int hop, int pad,
     const long total = gpc * n_clips;
     if (total <= 0 || total > 0x7fffffffL || n_frames > 0x7fffffffL) return hipErrorInvalidValue;
     const size_t lds = (size_t)((((M + 1) * FPB / 2 + 3) & ~3) + 2 * SLOTS * exch_size<M>()) * sizeof(float);
-    auto kern = stft_fit_kernel<M, NW, WPE>;
+    constexpr auto kern = stft_fit_kernel<M, NW, WPE>;
     // persistent grid: exactly as many workgroups as the chip holds at once (asked of the runtime for THIS kernel and LDS size)
     struct Res { int dev = -1, wgs = 0; };
     static thread_local Res cache;
@@ -769,10 +740,8 @@ hipError_t launch_fit(const float *audio, int n_clips, long L, int hop, int pad,
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (cache.dev != dev) {
-        if (lds > 64 * 1024) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
+        e = lds_opt_in<kern>(lds);
+        if (e != hipSuccess) return e;
         int per_cu = 0, cus = 0;
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, NW * 64, lds);
         if (e != hipSuccess) return e;
@@ -838,16 +807,13 @@ hipError_t launch_m(const float *audio, int n_clips, long L, int hop, int pad, l
     const long scratch = (long)C::FB * M * 2;
     const long work = span > scratch ? span : scratch;
     const long mag = (long)(M + 1) * C::MAGSTR;
-    const size_t lds = (size_t)(C::N + 2 * M + (M + 2) + mag + (mag & 1) + work) * sizeof(float);
+    const size_t lds = (size_t)(C::T::TBL + mag + (mag & 1) + work) * sizeof(float);
     if (lds > 160 * 1024) return hipErrorInvalidValue;   // hop too large for the LDS staging scheme
-    auto kern = stft_mag_kernel<M>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
+    constexpr auto kern = stft_mag_kernel<M>;
+    const hipError_t e = lds_opt_in<kern>(160 * 1024);   // lds grows with hop: opted in once, for the most a launch may ask
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(STFT_THREADS), lds, st, audio, L, hop, pad, n_frames,
-                       (int)groups, tables, out, (int)work, o);
+                       (int)groups, tables, out, o);
     return hipGetLastError();
 }
 
@@ -874,26 +840,17 @@ hipError_t launch_stft_mag(const float *audio, int n_clips, long L, int n_fft, i
     if (e != hipSuccess) return e;
     const int pad = center ? n_fft / 2 : 0;
     constexpr int gpb = 1;                                // frame groups per workgroup (1 measured best: no in-loop barriers)
-    if (quantize) {                                       // adn_stft_mag_fit: persistent whole-line kernel (above)
-        switch (n_fft) {
-            case 256: return launch_fit<128, 4>(audio, n_clips, L, hop, pad, n_frames, tables, out, o, st);
-            case 512: return launch_fit<256, 4>(audio, n_clips, L, hop, pad, n_frames, tables, out, o, st);
-            case 1024: return launch_fit<512, 4>(audio, n_clips, L, hop, pad, n_frames, tables, out, o, st);
-            default: break;
+    return dispatch_n_fft(n_fft, [&](auto m) {
+        constexpr int M = m();
+        if constexpr (M > 512) {                          // larger transforms: the workgroup-synchronous kernel
+            return launch_m<M>(audio, n_clips, L, hop, pad, n_frames, tables, out, o, st);
+        } else {                                          // a frame fits one wave
+            using P = WavePlan<M>;
+            if constexpr (M >= 128)                       // adn_stft_mag_fit: persistent whole-line kernel
+                if (quantize) return launch_fit<M, P::NW>(audio, n_clips, L, hop, pad, n_frames, tables, out, o, st);
+            return launch_wave<M, P::NW, P::FPB>(audio, n_clips, L, hop, pad, n_frames, tables, out, o, st, gpb);
         }
-    }
-    switch (n_fft) {                                      // a frame fits one wave: the wave-synchronous kernel
-        case 64: return launch_wave<32, 1, 16>(audio, n_clips, L, hop, pad, n_frames, tables, out, o, st, gpb);
-        case 128: return launch_wave<64, 2, 16>(audio, n_clips, L, hop, pad, n_frames, tables, out, o, st, gpb);
-        case 256: return launch_wave<128, 4, 16>(audio, n_clips, L, hop, pad, n_frames, tables, out, o, st, gpb);
-        // <waves, frames per group>, measured on 10 k x 3 s clips (ms): <8,16> 9.31, <4,16> 5.42, <2,32> 6.08, <2,16> 4.78, <4,32> 4.71
-        case 512: return launch_wave<256, 4, 32>(audio, n_clips, L, hop, pad, n_frames, tables, out, o, st, gpb);
-        case 1024: return launch_wave<512, 4, 16>(audio, n_clips, L, hop, pad, n_frames, tables, out, o, st, gpb);
-        // larger transforms: the workgroup-synchronous kernel
-        case 2048: return launch_m<1024>(audio, n_clips, L, hop, pad, n_frames, tables, out, o, st);
-        case 4096: return launch_m<2048>(audio, n_clips, L, hop, pad, n_frames, tables, out, o, st);
-        default: return hipErrorInvalidValue;
-    }
+    });
 }
 
 }  // namespace adn

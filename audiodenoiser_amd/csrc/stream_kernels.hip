@@ -34,8 +34,7 @@
 // reads mag rows of its slot; emit reads tail slot (step - 1) mod 2 and writes tail slot step mod 2.  No two rows of a launch
 // name the same slot (the host refuses such a call), so no state word of a slot has two writers, and no workgroup reads what
 // another one writes in the same launch.  Still no atomics, no workspace.
-#include "adn_internal.h"
-#include "fft_core.h"
+#include "spectral.h"
 
 #include <cfloat>
 
@@ -43,33 +42,6 @@ namespace adn {
 namespace {
 
 using namespace fftcore;
-
-template <int M>
-struct StCfg {
-    static constexpr int N = 2 * M, TPF = M / 8, FB = STFT_THREADS / TPF;   // FB frames per FFT pass (GlCfg<M>'s split)
-    static constexpr int TBL = N + 2 * M + (M + 2);                         // window, twiddles, half-step twiddles
-    static constexpr size_t LDS_FRAMES = (size_t)(TBL + 2 * FB * M) * sizeof(float);
-    // emit: DnCfg<M>'s budget (denoise_kernels.hip) -- stages of SB frames of y parked in LDS [frame][bin] with an odd pitch
-    static constexpr int SB0 = 16384 / M < 32 ? 16384 / M : 32;
-    static constexpr int SB = FB > SB0 ? FB : SB0;
-    static constexpr int PITCH = M + 1;
-    static constexpr int SPT = 8, SPAN = STFT_THREADS * SPT;                // samples per thread / per workgroup
-    static constexpr size_t LDS_EMIT = (size_t)(TBL + 2 * FB * M + SB * PITCH) * sizeof(float);
-    static_assert(SB % FB == 0 && STFT_THREADS % SB == 0 && (SB & (SB - 1)) == 0, "bad stage size");
-    static_assert(LDS_EMIT <= 160 * 1024, "stage does not fit the LDS of a CU");
-};
-
-// |X| as adn.h fixes it ("denoise", rule 2): one product, one fma, one square root
-__device__ __forceinline__ float mag_of(float2 x) { return sqrtf(fmaf(x.x, x.x, __fmul_rn(x.y, x.y))); }
-
-// S^[k] = M[k] * X[k] / |X[k]|, M real where |X| = 0 ("denoise", rule 5)
-__device__ __forceinline__ float2 rephase(float2 x, float m)
-{
-    const float mag = mag_of(x);
-    if (mag == 0.f) return make_float2(m, 0.f);
-    const float s = m / mag;
-    return make_float2(x.x * s, x.y * s);
-}
 
 // Sample s of the stream: zero before the start and, once the length is known, from the end on; the call's new samples start at
 // `base`, the n_fft - hop before them are the carried history.
@@ -133,15 +105,12 @@ __global__ __launch_bounds__(STFT_THREADS) void stream_frames_kernel(const float
                                                                     StreamGeom g, Rows rows,
                                                                     const float *__restrict__ tables, float *__restrict__ state)
 {
-    using C = StCfg<M>;
-    constexpr int N = C::N, TPF = C::TPF, FB = C::FB, F = M + 1;
+    using C = SpecCfg<M>;
+    constexpr int N = C::N, TPF = C::TPF, FB = C::FB, F = C::F;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *s_win = smem;
-    float2 *s_tw = reinterpret_cast<float2 *>(smem + N);
-    float2 *s_tw2 = s_tw + M;
-    float2 *s_sc = reinterpret_cast<float2 *>(smem + C::TBL);
+    const SpecTables tb = C::view(smem);
     const int tid = threadIdx.x;
-    for (int i = tid; i < C::TBL; i += STFT_THREADS) smem[i] = tables[i];
+    C::load(smem, tables);
     __syncthreads();
 
     const long strm = slot_of(rows, blockIdx.y);
@@ -166,49 +135,27 @@ __global__ __launch_bounds__(STFT_THREADS) void stream_frames_kernel(const float
         const int n2 = 2 * (t + u * TPF);
         const float x0 = live ? in.at(s0 + n2) : 0.f;
         const float x1 = live ? in.at(s0 + n2 + 1) : 0.f;
-        v[u] = make_float2(s_win[n2] * x0, s_win[n2 + 1] * x1);
+        v[u] = make_float2(tb.win[n2] * x0, tb.win[n2 + 1] * x1);
     }
-    float2 *sc = s_sc + fl * M;
-    fft_frame<M>(sc, s_tw, t, v);
+    float2 *sc = C::frames(smem) + fl * M;
+    fft_frame<M>(sc, tb.tw, t, v);
     if (live) {
         // frames from T on (after the end of the stream) are zero in the windows and never emitted
         const bool past = c.T >= 0 && f >= c.T;
         float2 *o = reinterpret_cast<float2 *>(state + g.x_off) + (strm * g.RX + f % g.RX) * (long)F;
         float *m = state + g.mag_off + (strm * g.RM + f % g.RM) * (long)F;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {                                 // the real-input split of stft_complex_kernel
-            const int k = t + b * TPF;                                // 0 .. M/2-1
-            if (k == 0) {
-                const float2 z0 = sc[0];
-                const float2 a0 = make_float2(z0.x + z0.y, 0.f), aM = make_float2(z0.x - z0.y, 0.f);
-                const float2 zh = sc[M / 2];
-                const float2 ah = make_float2(zh.x, -zh.y);
-                o[0] = a0;
-                o[M] = aM;
-                o[M / 2] = ah;
-                m[0] = past ? 0.f : mag_of(a0);
-                m[M] = past ? 0.f : mag_of(aM);
-                m[M / 2] = past ? 0.f : mag_of(ah);
-            } else {
-                const float2 A = sc[k], Bc = sc[M - k];
-                const float2 ev = make_float2(0.5f * (A.x + Bc.x), 0.5f * (A.y - Bc.y));
-                const float2 d = make_float2(0.5f * (A.x - Bc.x), 0.5f * (A.y + Bc.y));
-                const float2 wo = cmul(s_tw2[k], make_float2(d.y, -d.x));     // w^k * (d / i)
-                const float2 xa = cadd(ev, wo);
-                const float2 xb0 = csub(ev, wo);
-                const float2 xb = make_float2(xb0.x, -xb0.y);
-                o[k] = xa;
-                o[M - k] = xb;
-                m[k] = past ? 0.f : mag_of(xa);
-                m[M - k] = past ? 0.f : mag_of(xb);
-            }
-        }
+        const auto put = [&](int k, float2 x) {
+            o[k] = x;
+            m[k] = past ? 0.f : mag_of(x);
+        };
+        forward_split<M>(sc, tb.tw2, t, [&](int k, float2 xa, float2 xb) { put(k, xa); put(M - k, xb); },
+                         [&](float2 x0, float2 xM, float2 xh) { put(0, x0); put(M, xM); put(M / 2, xh); });
     }
 }
 
 // ---------------------------------------------------------------------------------------------- analysis 2: network input
 // mag ring rows are frame-major [frame][F], the network's windows bin-major [window][F][W] with the frame index fastest: a
-// 32 x 32 tile through LDS (pitch 33) keeps both sides contiguous along their fastest index, as dn_windows_kernel.
+// 32 x 32 tile through LDS (pitch 33) keeps both sides contiguous along their fastest index.
 template <class Rows>
 __global__ __launch_bounds__(256) void stream_windows_kernel(const float *__restrict__ state, int F, StreamGeom g, Rows rows,
                                                              int tilesJ, int tilesF, float *__restrict__ out)
@@ -244,23 +191,24 @@ __global__ __launch_bounds__(256) void stream_windows_kernel(const float *__rest
 // have emitted p < p_begin = first B hop and left the partial sums of [p_begin, p_begin + n_fft - hop) in the tail; this call adds
 // frames [f_first, f_last], emits [p_begin, p_out) and leaves [p_tail, p_tail + n_fft - hop) in the new tail (p_tail = p_out
 // while the stream runs; nothing once the stream's last sample is out).  A workgroup owns `span` positions of
-// [p_begin, p_end); the frames that cover its span and belong to this call are rebuilt in LDS as dn_resynth_kernel does.
+// [p_begin, p_end); the frames that cover its span and belong to this call are rebuilt in LDS stage by stage (ResynthCfg<M>, spectral.h).
 template <int M, class Rows>
 __global__ __launch_bounds__(STFT_THREADS, (M == 256 ? 4 : 2)) void stream_emit_kernel(
     const float *__restrict__ y, StreamGeom g, Rows rows, int nblk, const float *__restrict__ tables,
     float *__restrict__ state, float *__restrict__ audio, long out_stride)
 {
-    using C = StCfg<M>;
-    constexpr int N = C::N, TPF = C::TPF, FB = C::FB, SB = C::SB, F = M + 1, P = C::PITCH, SPT = C::SPT, span = C::SPAN;
+    using C = ResynthCfg<M>;
+    using S = SpecCfg<M>;
+    constexpr int N = S::N, TPF = S::TPF, FB = S::FB, SB = C::SB, F = S::F, P = C::PITCH, SPT = C::SPT, span = C::SPAN;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *s_win = smem;
     float2 *s_tw = reinterpret_cast<float2 *>(smem + N);
     float2 *s_tw2 = s_tw + M;                                   // exp(-2 pi i k / N), k = 0 .. M/2
-    float2 *s_sc = reinterpret_cast<float2 *>(smem + C::TBL);
-    float *s_fr = smem + C::TBL;                                // the same storage once a pass's frames are windowed: [FB][N]
-    float *s_tile = smem + C::TBL + 2 * FB * M;                 // [SB][P] clamped magnitudes of the stage
+    float2 *s_sc = reinterpret_cast<float2 *>(smem + S::TBL);
+    float *s_fr = smem + S::TBL;                                // the same storage once a pass's frames are windowed: [FB][N]
+    float *s_tile = smem + S::TBL + 2 * FB * M;                 // [SB][P] clamped magnitudes of the stage
     const int tid = threadIdx.x;
-    for (int i = tid; i < C::TBL; i += STFT_THREADS) smem[i] = tables[i];
+    for (int i = tid; i < S::TBL; i += STFT_THREADS) smem[i] = tables[i];
     __syncthreads();                                            // (a workgroup past the call's last frame runs no FFT pass)
 
     const long row = blockIdx.x / (unsigned)nblk, strm = slot_of(rows, row);
@@ -368,7 +316,7 @@ __global__ __launch_bounds__(STFT_THREADS, (M == 256 ? 4 : 2)) void stream_emit_
         if (p >= pb) continue;
         if (p >= c.p_tail) tail_out[p - c.p_tail] = acc[u];     // partial sums the next call goes on from (p_tail >= p_out)
         if (p >= c.p_out || p < M) continue;                    // positions before n_fft/2 are the trimmed front
-        // window sum-of-squares of the frames that cover the sample: dn_resynth_kernel's range, order and arithmetic
+        // window sum-of-squares of the frames that cover the sample (no last frame while the stream runs)
         int f_hi = p / hop;
         if (c.T >= 0 && f_hi > c.T - 1) f_hi = c.T - 1;
         const int f_lo = p < N ? 0 : (p - N + hop) / hop;
@@ -381,73 +329,33 @@ __global__ __launch_bounds__(STFT_THREADS, (M == 256 ? 4 : 2)) void stream_emit_
     }
 }
 
-template <int M>
-hipError_t launch_frames_m(const float *audio, long audio_stride, int n_streams, const StreamGeom &g, const StreamCall &c,
+// Rows = StreamCall: the lockstep call of n_rows streams; Rows = StreamPoolRows: its rows.  max_new_frames / max_span: the row with
+// the most new frames / positions to emit sizes the grid.
+template <int M, class Rows>
+hipError_t launch_frames_m(const float *audio, long audio_stride, int n_rows, const StreamGeom &g, const Rows &rows, int max_new_frames,
                            const float *tables, float *state, hipStream_t st)
 {
-    using C = StCfg<M>;
-    auto kern = stream_frames_kernel<M, StreamCall>;
-    if (C::LDS_FRAMES > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)C::LDS_FRAMES);
-        if (e != hipSuccess) return e;
-    }
-    const int nf = c.f_new1 - c.f_new0;
-    dim3 grid((unsigned)((nf + C::FB - 1) / C::FB), (unsigned)n_streams);
-    hipLaunchKernelGGL(kern, grid, dim3(STFT_THREADS), C::LDS_FRAMES, st, audio, audio_stride, g, c, tables, state);
+    using C = SpecCfg<M>;
+    constexpr auto kern = stream_frames_kernel<M, Rows>;
+    const hipError_t e = lds_opt_in<kern>(C::LDS);
+    if (e != hipSuccess) return e;
+    dim3 grid((unsigned)((max_new_frames + C::FB - 1) / C::FB), (unsigned)n_rows);
+    hipLaunchKernelGGL(kern, grid, dim3(STFT_THREADS), C::LDS, st, audio, audio_stride, g, rows, tables, state);
     return hipGetLastError();
 }
 
-template <int M>
-hipError_t launch_emit_m(const float *y, int n_streams, const StreamGeom &g, const StreamCall &c, const float *tables,
+template <int M, class Rows>
+hipError_t launch_emit_m(const float *y, int n_rows, const StreamGeom &g, const Rows &rows, long max_span, const float *tables,
                          float *state, float *audio, long out_stride, hipStream_t st)
 {
-    using C = StCfg<M>;
-    auto kern = stream_emit_kernel<M, StreamCall>;
-    if (C::LDS_EMIT > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)C::LDS_EMIT);
-        if (e != hipSuccess) return e;
-    }
-    const long total = (long)c.p_end - c.p_begin;
-    if (total <= 0) return hipSuccess;
-    const long nblk = (total + C::SPAN - 1) / C::SPAN;
-    if (nblk * n_streams > 0x7fffffffL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nblk * n_streams)), dim3(STFT_THREADS), C::LDS_EMIT, st, y, g, c, (int)nblk,
-                       tables, state, audio, out_stride);
-    return hipGetLastError();
-}
-
-template <int M>
-hipError_t launch_pool_frames_m(const StreamGeom &g, const StreamPoolRows &t, int max_new_frames, const float *tables, float *state,
-                                hipStream_t st)
-{
-    using C = StCfg<M>;
-    auto kern = stream_frames_kernel<M, StreamPoolRows>;
-    if (C::LDS_FRAMES > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)C::LDS_FRAMES);
-        if (e != hipSuccess) return e;
-    }
-    dim3 grid((unsigned)((max_new_frames + C::FB - 1) / C::FB), (unsigned)t.n);
-    hipLaunchKernelGGL(kern, grid, dim3(STFT_THREADS), C::LDS_FRAMES, st, (const float *)nullptr, 0L, g, t, tables, state);
-    return hipGetLastError();
-}
-
-template <int M>
-hipError_t launch_pool_emit_m(const float *y, const StreamGeom &g, const StreamPoolRows &t, int max_span, const float *tables,
-                              float *state, float *audio, long out_stride, hipStream_t st)
-{
-    using C = StCfg<M>;
-    auto kern = stream_emit_kernel<M, StreamPoolRows>;
-    if (C::LDS_EMIT > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)C::LDS_EMIT);
-        if (e != hipSuccess) return e;
-    }
+    using C = ResynthCfg<M>;
+    constexpr auto kern = stream_emit_kernel<M, Rows>;
+    const hipError_t e = lds_opt_in<kern>(C::LDS);
+    if (e != hipSuccess) return e;
     if (max_span <= 0) return hipSuccess;
-    const long nblk = ((long)max_span + C::SPAN - 1) / C::SPAN;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nblk * t.n)), dim3(STFT_THREADS), C::LDS_EMIT, st, y, g, t, (int)nblk, tables, state,
+    const long nblk = (max_span + C::SPAN - 1) / C::SPAN;
+    if (nblk * n_rows > 0x7fffffffL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(nblk * n_rows)), dim3(STFT_THREADS), C::LDS, st, y, g, rows, (int)nblk, tables, state,
                        audio, out_stride);
     return hipGetLastError();
 }
@@ -497,16 +405,9 @@ hipError_t launch_stream_pool_frames(const StreamGeom &g, const StreamPoolRows &
     const float *tables = nullptr;
     hipError_t e = stft_tables(g.n_fft, &tables, st);
     if (e != hipSuccess) return e;
-    switch (g.n_fft) {
-        case 64: return launch_pool_frames_m<32>(g, t, max_new_frames, tables, state, st);
-        case 128: return launch_pool_frames_m<64>(g, t, max_new_frames, tables, state, st);
-        case 256: return launch_pool_frames_m<128>(g, t, max_new_frames, tables, state, st);
-        case 512: return launch_pool_frames_m<256>(g, t, max_new_frames, tables, state, st);
-        case 1024: return launch_pool_frames_m<512>(g, t, max_new_frames, tables, state, st);
-        case 2048: return launch_pool_frames_m<1024>(g, t, max_new_frames, tables, state, st);
-        case 4096: return launch_pool_frames_m<2048>(g, t, max_new_frames, tables, state, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_n_fft(g.n_fft, [&](auto m) {
+        return launch_frames_m<m()>(nullptr, 0L, t.n, g, t, max_new_frames, tables, state, st);
+    });
 }
 
 hipError_t launch_stream_pool_windows(const float *state, const StreamGeom &g, const StreamPoolRows &t, float *out, hipStream_t st)
@@ -525,16 +426,9 @@ hipError_t launch_stream_pool_emit(const float *y, const StreamGeom &g, const St
     const float *tables = nullptr;
     hipError_t e = stft_tables(g.n_fft, &tables, st);
     if (e != hipSuccess) return e;
-    switch (g.n_fft) {
-        case 64: return launch_pool_emit_m<32>(y, g, t, max_span, tables, state, audio, out_stride, st);
-        case 128: return launch_pool_emit_m<64>(y, g, t, max_span, tables, state, audio, out_stride, st);
-        case 256: return launch_pool_emit_m<128>(y, g, t, max_span, tables, state, audio, out_stride, st);
-        case 512: return launch_pool_emit_m<256>(y, g, t, max_span, tables, state, audio, out_stride, st);
-        case 1024: return launch_pool_emit_m<512>(y, g, t, max_span, tables, state, audio, out_stride, st);
-        case 2048: return launch_pool_emit_m<1024>(y, g, t, max_span, tables, state, audio, out_stride, st);
-        case 4096: return launch_pool_emit_m<2048>(y, g, t, max_span, tables, state, audio, out_stride, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_n_fft(g.n_fft, [&](auto m) {
+        return launch_emit_m<m()>(y, t.n, g, t, (long)max_span, tables, state, audio, out_stride, st);
+    });
 }
 
 hipError_t launch_stream_frames(const float *audio, long audio_stride, int n_streams, const StreamGeom &g, const StreamCall &c,
@@ -543,16 +437,9 @@ hipError_t launch_stream_frames(const float *audio, long audio_stride, int n_str
     const float *tables = nullptr;
     hipError_t e = stft_tables(g.n_fft, &tables, st);
     if (e != hipSuccess) return e;
-    switch (g.n_fft) {
-        case 64: return launch_frames_m<32>(audio, audio_stride, n_streams, g, c, tables, state, st);
-        case 128: return launch_frames_m<64>(audio, audio_stride, n_streams, g, c, tables, state, st);
-        case 256: return launch_frames_m<128>(audio, audio_stride, n_streams, g, c, tables, state, st);
-        case 512: return launch_frames_m<256>(audio, audio_stride, n_streams, g, c, tables, state, st);
-        case 1024: return launch_frames_m<512>(audio, audio_stride, n_streams, g, c, tables, state, st);
-        case 2048: return launch_frames_m<1024>(audio, audio_stride, n_streams, g, c, tables, state, st);
-        case 4096: return launch_frames_m<2048>(audio, audio_stride, n_streams, g, c, tables, state, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_n_fft(g.n_fft, [&](auto m) {
+        return launch_frames_m<m()>(audio, audio_stride, n_streams, g, c, c.f_new1 - c.f_new0, tables, state, st);
+    });
 }
 
 hipError_t launch_stream_windows(const float *state, int n_streams, const StreamGeom &g, const StreamCall &c, float *out,
@@ -573,16 +460,9 @@ hipError_t launch_stream_emit(const float *y, int n_streams, const StreamGeom &g
     const float *tables = nullptr;
     hipError_t e = stft_tables(g.n_fft, &tables, st);
     if (e != hipSuccess) return e;
-    switch (g.n_fft) {
-        case 64: return launch_emit_m<32>(y, n_streams, g, c, tables, state, audio, out_stride, st);
-        case 128: return launch_emit_m<64>(y, n_streams, g, c, tables, state, audio, out_stride, st);
-        case 256: return launch_emit_m<128>(y, n_streams, g, c, tables, state, audio, out_stride, st);
-        case 512: return launch_emit_m<256>(y, n_streams, g, c, tables, state, audio, out_stride, st);
-        case 1024: return launch_emit_m<512>(y, n_streams, g, c, tables, state, audio, out_stride, st);
-        case 2048: return launch_emit_m<1024>(y, n_streams, g, c, tables, state, audio, out_stride, st);
-        case 4096: return launch_emit_m<2048>(y, n_streams, g, c, tables, state, audio, out_stride, st);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_n_fft(g.n_fft, [&](auto m) {
+        return launch_emit_m<m()>(y, n_streams, g, c, (long)c.p_end - c.p_begin, tables, state, audio, out_stride, st);
+    });
 }
 
 }  // namespace adn

@@ -1,0 +1,166 @@
+"""SHA-256 digests of the spectral entry points (STFT, fitted STFT, complex STFT, inverse STFT, Griffin-Lim, the denoiser's
+windows / stitch / resynth, StreamDenoiser, StreamPool) at every n_fft the library supports: one line per call.
+
+A change that must not move a bit of their output (a refactoring of csrc/{stft,gl,denoise,stream}_kernels.hip or spectral.h) is
+checked by running this script against both libraries on the same machine and comparing the two outputs as text:
+
+    python -m audiodenoiser_amd.build --variant parent        # in a worktree of the other commit; copy the .so over
+    ADN_LIBADN_PATH=.../libadn_parent.so python tools/spectral_digest.py > before.txt
+    python tools/spectral_digest.py > after.txt ; diff before.txt after.txt
+
+Fixed seeds.  The network is replaced by a fixed elementwise map of its input (a random gain and offset, negative values
+included so that the clamp works): the digests then depend on the spectral kernels alone.  Shapes are small -- 3 clips of
+4 n_fft + 37 and 2 hop - 1 samples (both odd), windows of 32 frames overlapping by 16, the stream plan W = 32, B = 8, A = 4 --
+with three additions: clips of 20 n_fft + 37 samples where the denoiser needs more frames than one window to cross-fade at
+all; the fitted STFT of those clips into 96 frames, three 32-frame groups per clip, so that the persistent kernel steps from
+group to group inside a clip; and, for the fitted STFT at n_fft 512 and 1024, 2100 one-group clips.  The persistent kernel
+launches min(items, workgroups the card holds) workgroups; the library does not report that grid, so the line gives the items
+and the CUs, and `more_items_than_8_per_cu` says whether the items exceed even 8 workgroups on every CU (the kernel's
+registers allow 3): then some workgroup must walk from one clip into the next.  Not covered here: fitted windows wider than
+96 frames and the reference's 513 x 256 at scale -- tests/test_gpu_parity.py has those.  This is the only place resynth and
+the stream kernels run at n_fft 2048 and 4096."""
+import hashlib
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from audiodenoiser_amd.denoise import Denoiser  # noqa: E402
+from audiodenoiser_amd.griffin_lim import griffin_lim_reconstruction, istft, stft_complex  # noqa: E402
+from audiodenoiser_amd.model import UNet  # noqa: E402
+from audiodenoiser_amd.stft import stft_magnitude, stft_magnitude_fit  # noqa: E402
+from audiodenoiser_amd.stream import StreamDenoiser, StreamPool  # noqa: E402
+
+N_FFTS = (64, 128, 256, 512, 1024, 2048, 4096)
+DEV = torch.device("cuda", 0)
+W, V, B, A = 32, 16, 8, 4
+_GAIN = {}
+
+
+def rand(seed, *shape):
+    return torch.rand(shape, generator=torch.Generator().manual_seed(seed))
+
+
+def audio(seed, n, length):
+    return (rand(seed, n, length) * 2 - 1).to(DEV)
+
+
+def say(what, *tensors):
+    torch.cuda.synchronize()
+    h = hashlib.sha256()
+    for t in tensors:
+        t = torch.view_as_real(t) if t.is_complex() else t
+        h.update(str(tuple(t.shape)).encode())
+        h.update(np.ascontiguousarray(t.cpu().numpy()).tobytes())
+    print(f"{what} {h.hexdigest()}", flush=True)
+
+
+def fake_network(x):
+    """In place of the U-Net: y = x * gain + offset with a fixed random gain in [-0.25, 1.25) and offset in [-0.1, 0.1)."""
+    key = tuple(x.shape)
+    if key not in _GAIN:
+        _GAIN[key] = (rand(11, *key).to(x.device) * 1.5 - 0.25, rand(12, *key).to(x.device) * 0.2 - 0.1)
+    g, o = _GAIN[key]
+    return x * g + o
+
+
+def transforms(n_fft):
+    hop = n_fft // 4
+    for length in (4 * n_fft + 37, 2 * hop - 1):
+        a = audio(length, 3, length)
+        tag = f"n_fft={n_fft} hop={hop} L={length}"
+        for center in (True, False):
+            if not center and length < n_fft:
+                continue
+            say(f"stft {tag} center={int(center)}", stft_magnitude(a, n_fft, hop, center))
+            for h, w in ((n_fft // 2 + 1, W), (n_fft // 2 - 3, 12)):
+                say(f"stft_fit {tag} center={int(center)} {h}x{w}", stft_magnitude_fit(a, (h, w), n_fft, hop, center))
+        spec = stft_complex(a, n_fft, hop)
+        say(f"stft_complex {tag}", spec)
+        say(f"istft {tag}", istft(spec, hop))
+        say(f"griffin_lim {tag} iterations=10",
+            griffin_lim_reconstruction(spec.abs().transpose(1, 2).contiguous(), n_fft, hop, 10, rand=rand(5, *spec.shape)))
+    if n_fft >= 256:                               # the sizes stft_fit_kernel serves (and, above 1024, stft_mag_kernel's fitted form)
+        length = 20 * n_fft + 37
+        a = audio(length, 3, length)
+        for center in (True, False):
+            say(f"stft_fit n_fft={n_fft} hop={hop} L={length} center={int(center)} {n_fft // 2 + 1}x96 groups_per_clip=3",
+                stft_magnitude_fit(a, (n_fft // 2 + 1, 96), n_fft, hop, center))
+    if n_fft in (512, 1024):
+        n, length = 2100, 4 * n_fft + 37
+        a = audio(77, n, length)
+        cus = torch.cuda.get_device_properties(DEV).multi_processor_count
+        for center in (True, False):
+            say(f"stft_fit n_fft={n_fft} hop={hop} L={length} center={int(center)} 65x{W} items={n} cus={cus} more_items_than_8_per_cu={int(n > 8 * cus)}",
+                stft_magnitude_fit(a, (65, W), n_fft, hop, center))
+
+
+def denoiser(model, n_fft):
+    hop = n_fft // 4
+    dn = Denoiser(model, n_fft=n_fft, hop_length=hop, window_frames=W, overlap_frames=V)
+    for length in (4 * n_fft + 37, 2 * hop - 1, 20 * n_fft + 37):
+        a = audio(1000 + length, 3, length)
+        spec = stft_complex(a, n_fft, hop)
+        x = dn.windows(spec)
+        y = fake_network(x)
+        tag = f"n_fft={n_fft} hop={hop} L={length} W={W} V={V}"
+        say(f"denoise.windows {tag}", x)
+        for clamp in (False, True):
+            say(f"denoise.stitch {tag} clamp={int(clamp)}", dn.stitch(y, 3, spec.shape[1], clamp))
+        say(f"denoise.resynth {tag}", dn.resynth(y, spec, length))
+
+
+def stream(model, n_fft):
+    hop = n_fft // 4
+    length = 20 * n_fft + 37
+    a = audio(2000 + n_fft, 3, length)
+    sd = StreamDenoiser(model, n_streams=3, n_fft=n_fft, hop_length=hop, window_frames=W, block_frames=B, lookahead_frames=A,
+                        batch_windows=9)
+    sd.network = fake_network
+    outs, pos = [], 0
+    for m in (1, n_fft // 2 + 3, 7 * n_fft + 1, 0, 5 * hop, length):          # uneven pushes; the last takes the rest
+        outs.append(sd.push(a[:, pos:pos + m]))
+        pos = min(pos + m, length)
+    outs.append(sd.flush())
+    say(f"stream n_fft={n_fft} hop={hop} L={length} W={W} B={B} A={A} streams=3", torch.cat(outs, dim=1))
+
+    pool = StreamPool(model, max_streams=3, n_fft=n_fft, hop_length=hop, window_frames=W, block_frames=B, lookahead_frames=A)
+    pool.network = fake_network
+    lengths = (length, 9 * n_fft + 2, 2 * hop - 1)                            # slot 2 opens late and ends first
+    got = {s: [] for s in range(3)}
+    sent = [0, 0, 0]
+    open_at = (0, 0, 3)
+    sids = {}
+    for tick in range(400):
+        for s in range(3):
+            if tick == open_at[s]:
+                sids[s] = pool.open()
+            if s in sids and sent[s] < lengths[s]:
+                m = min((s + 1) * hop + 5 * (tick % 3), lengths[s] - sent[s], pool.room(sids[s]))
+                pool.push(sids[s], a[s, sent[s]:sent[s] + m])
+                sent[s] += m
+                if sent[s] == lengths[s]:
+                    pool.close(sids[s])
+        ran = pool.step()
+        for sid, samples, _ in ran:
+            got[sid].append(samples)
+        if not ran and all(sent[s] == lengths[s] for s in range(3)):
+            break
+    outs = [torch.cat(got[sids[s]]) if got[sids[s]] else torch.empty(0, device=DEV) for s in range(3)]
+    assert [o.shape[0] for o in outs] == list(lengths), ([o.shape[0] for o in outs], lengths)
+    say(f"stream_pool n_fft={n_fft} hop={hop} lengths={lengths} W={W} B={B} A={A} slots=3", *outs)
+
+
+def main():
+    model = UNet(1, 1).eval().to(DEV)              # the classes ask for one; fake_network runs in its place
+    with torch.no_grad():
+        for n_fft in N_FFTS:
+            transforms(n_fft)
+            denoiser(model, n_fft)
+            stream(model, n_fft)
+
+
+if __name__ == "__main__":
+    main()
