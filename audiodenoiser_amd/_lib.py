@@ -93,6 +93,9 @@ def load() -> ctypes.CDLL:
         L.adn_resample_stream_plan.argtypes = [ci, ci, cl, ci, ctypes.POINTER(cl), ctypes.POINTER(cl), ctypes.POINTER(cl)]
         L.adn_resample_stream_state_bytes.argtypes = [ci, ci, ci, ctypes.POINTER(sz)]
         L.adn_resample_stream.argtypes = [vp, sz, vp, cl, ci, cl, cl, cl, ci, ci, ci, vp, cl, vp]
+        L.adn_stream_pool_rate_state_bytes.argtypes = [ci, ci, ctypes.POINTER(sz)]
+        L.adn_stream_pool_push_rate.argtypes = [vp, sz, ci, ci, ci, ci, ci, ci, cl, vp, sz, ci, ci, vp, ci, vp, vp]
+        L.adn_stream_pool_emit_rate.argtypes = [vp, sz, ci, ci, ci, vp, ci, vp, cl, vp, cl, vp]
         for name in ("adn_device_count", "adn_prepare", "adn_unet_create", "adn_unet_create_ex", "adn_unet_create_general", "adn_unet_channels",
                      "adn_unet_set_batch_invariant", "adn_unet_destroy", "adn_unet_workspace_bytes", "adn_unet_forward", "adn_unet_forward_taps", "adn_unet_set_timing", "adn_unet_get_timing",
                      "adn_stft_n_frames", "adn_stft_mag", "adn_stft_mag_fit", "adn_quantize_pad", "adn_per_clip_l1",
@@ -105,10 +108,17 @@ def load() -> ctypes.CDLL:
                      "adn_stream_plan", "adn_stream_state_bytes", "adn_stream_reset", "adn_stream_analyze", "adn_stream_emit",
                      "adn_stream_pool_state_bytes", "adn_stream_pool_reset", "adn_stream_pool_write", "adn_stream_pool_analyze",
                      "adn_stream_pool_emit",
-                     "adn_resample_stream_plan", "adn_resample_stream_state_bytes", "adn_resample_stream"):
+                     "adn_resample_stream_plan", "adn_resample_stream_state_bytes", "adn_resample_stream",
+                     "adn_stream_pool_rate_state_bytes", "adn_stream_pool_push_rate", "adn_stream_pool_emit_rate"):
             getattr(L, name).restype = ci
         _lib = L
         return L
+
+
+class StreamPoolRateRow(ctypes.Structure):
+    """``adn_stream_pool_rate_row`` of include/adn.h: one row of a push_rate / emit_rate call."""
+    _fields_ = [("slot", ctypes.c_int), ("rate", ctypes.c_int), ("call_index", ctypes.c_long), ("received_before", ctypes.c_long),
+                ("n_new", ctypes.c_long), ("final", ctypes.c_int), ("audio_offset", ctypes.c_long)]
 
 
 class StreamPoolRow(ctypes.Structure):
@@ -145,4 +155,5 @@ EXPORTED_SYMBOLS = (
     "adn_stream_plan", "adn_stream_state_bytes", "adn_stream_reset", "adn_stream_analyze", "adn_stream_emit",
     "adn_stream_pool_state_bytes", "adn_stream_pool_reset", "adn_stream_pool_write", "adn_stream_pool_analyze", "adn_stream_pool_emit",
     "adn_resample_stream_plan", "adn_resample_stream_state_bytes", "adn_resample_stream",
+    "adn_stream_pool_rate_state_bytes", "adn_stream_pool_push_rate", "adn_stream_pool_emit_rate",
 )

@@ -771,4 +771,122 @@ int adn_resample_stream(void *state, size_t state_bytes, const float *audio, lon
     return ADN_OK;
 }
 
+/* ---- stream pool at a rate: rows of adn_resample_stream calls, into the rings and back (adn.h, "stream pool at a rate") ---- */
+static_assert(ADN_STREAM_POOL_RATE_MAX_ROWS == adn::STREAM_POOL_RATE_MAX_ROWS, "adn.h and adn_internal.h disagree about the rate rows");
+
+static int rate_state_check(const char *who, const void *rate_state, size_t rate_state_bytes, int n_slots, int max_history)
+{
+    const std::string w(who);
+    if (n_slots < 1 || n_slots > (1 << 20) || max_history < 0 || max_history > adn::ADN_RESAMPLE_STREAM_MAX_H)
+        return fail(ADN_ERR_INVALID, w + ": need 1 <= n_slots <= 2^20 and 0 <= max_history <= 16384");
+    if (!rate_state && max_history > 0) return fail(ADN_ERR_INVALID, w + ": null pointer");
+    if (!aligned_to(rate_state, 8)) return fail(ADN_ERR_INVALID, w + ": rate_state must be 8-byte aligned");
+    if (rate_state_bytes < (size_t)n_slots * 4 * (size_t)max_history * sizeof(float))
+        return fail(ADN_ERR_WORKSPACE, w + ": rate state smaller than adn_stream_pool_rate_state_bytes");
+    return ADN_OK;
+}
+
+// The rows of a call, each inside adn_resample_stream's limits; push: src = the row's rate, dst = work_rate, direction 0.
+// max_new / max_out: the most samples a row reads / writes.
+static int rate_rows(const char *who, bool push, int n_slots, int max_history, int work_rate, const adn_stream_pool_rate_row *rows,
+                     int n_rows, adn::ResampleStreamRow *t, long *max_new, long *max_out)
+{
+    const std::string w(who);
+    if (!rows) return fail(ADN_ERR_INVALID, w + ": null pointer");
+    if (n_rows < 1 || n_rows > ADN_STREAM_POOL_RATE_MAX_ROWS)
+        return fail(ADN_ERR_INVALID, w + ": need 1 <= n_rows <= ADN_STREAM_POOL_RATE_MAX_ROWS (call again for the rest)");
+    *max_new = *max_out = 0;
+    for (int i = 0; i < n_rows; ++i) {
+        const adn_stream_pool_rate_row r = rows[i];
+        adn::ResampleStreamRow &o = t[i];
+        if (r.slot < 0 || r.slot >= n_slots) return fail(ADN_ERR_INVALID, w + ": a row's slot is outside [0, n_slots)");
+        for (int j = 0; j < i; ++j)
+            if (rows[j].slot == r.slot) return fail(ADN_ERR_INVALID, w + ": a (slot, direction) is named twice in one call");
+        if (!resample_stream_plan_ok(push ? r.rate : work_rate, push ? work_rate : r.rate, &o.g)) return fail(ADN_ERR_INVALID, w + resample_stream_text);
+        if (o.g.H > max_history) return fail(ADN_ERR_INVALID, w + ": a row's rate pair carries more samples than max_history");
+        if (r.final != 0 && r.final != 1) return fail(ADN_ERR_INVALID, w + ": final must be 0 or 1");
+        if (r.n_new < (r.final ? 0 : 1)) return fail(ADN_ERR_INVALID, w + ": need n_new >= 1 (>= 0 in the final call)");
+        if (r.call_index < 0 || r.received_before < 0 || (r.call_index == 0) != (r.received_before == 0))
+            return fail(ADN_ERR_INVALID, w + ": need call_index >= 0 and received_before >= 0, both 0 in the first call of a stream and only there");
+        if (r.received_before >= (1L << 31) || r.n_new >= (1L << 31) || r.received_before + r.n_new >= (1L << 31))
+            return fail(ADN_ERR_INVALID, w + ": input positions must be < 2^31; end the stream before");
+        const long m0 = adn::resample_stream_emitted(o.g, r.received_before, false);
+        const long m1 = adn::resample_stream_emitted(o.g, r.received_before + r.n_new, r.final != 0);
+        if (m1 >= (1L << 31)) return fail(ADN_ERR_INVALID, w + ": output positions must be < 2^31; end the stream before");
+        if (r.audio_offset < 0) return fail(ADN_ERR_INVALID, w + ": audio_offset must be >= 0");
+        o.slot = r.slot, o.direction = push ? 0 : 1;
+        o.call_index = r.call_index, o.received_before = r.received_before, o.n_new = r.n_new;
+        o.src_off = r.audio_offset;
+        o.final = r.final != 0;
+        if (r.n_new > *max_new) *max_new = r.n_new;
+        if (m1 - m0 > *max_out) *max_out = m1 - m0;
+        if (push && m1 >= (1L << 30)) return fail(ADN_ERR_INVALID, w + ": a pool's stream holds fewer than 2^30 samples at the working rate");
+    }
+    return ADN_OK;
+}
+
+static int rate_launch(const char *who, hipError_t e)
+{
+    const std::string w(who);
+    if (e == adn::ADN_COLD_IN_CAPTURE)
+        return fail(ADN_ERR_INVALID, w + ": first use of a (device, rate pair) on a stream that is being captured -- the coefficient "
+                    "table is built with a blocking upload; call adn_resample_prepare(device, src_rate, dst_rate) before the capture");
+    if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, w + ": grid too large (output blocks >= 2^31)");
+    if (e != hipSuccess) return fail_hip(e, who);
+    return ADN_OK;
+}
+
+int adn_stream_pool_rate_state_bytes(int n_slots, int max_history, size_t *bytes)
+{
+    if (!bytes) return fail(ADN_ERR_INVALID, "adn_stream_pool_rate_state_bytes: null pointer");
+    if (n_slots < 1 || n_slots > (1 << 20) || max_history < 0 || max_history > adn::ADN_RESAMPLE_STREAM_MAX_H)
+        return fail(ADN_ERR_INVALID, "adn_stream_pool_rate_state_bytes: need 1 <= n_slots <= 2^20 and 0 <= max_history <= 16384");
+    *bytes = (size_t)n_slots * 4 * (size_t)max_history * sizeof(float);
+    return ADN_OK;
+}
+
+int adn_stream_pool_push_rate(void *state, size_t state_bytes, int n_slots, int n_fft, int hop, int window, int block, int lookahead,
+                              long ring_samples, void *rate_state, size_t rate_state_bytes, int max_history, int work_rate,
+                              const adn_stream_pool_rate_row *rows, int n_rows, const float *audio, void *stream)
+{
+    static const char *who = "adn_stream_pool_push_rate";
+    PoolState p;
+    adn::ResampleStreamRow t[ADN_STREAM_POOL_RATE_MAX_ROWS];
+    long max_new, max_out;
+    int rc = pool_state(who, state, state_bytes, n_slots, n_fft, hop, window, block, lookahead, ring_samples, &p);
+    if (rc != ADN_OK) return rc;
+    rc = rate_state_check(who, rate_state, rate_state_bytes, n_slots, max_history);
+    if (rc != ADN_OK) return rc;
+    rc = rate_rows(who, true, n_slots, max_history, work_rate, rows, n_rows, t, &max_new, &max_out);
+    if (rc != ADN_OK) return rc;
+    if (max_out > p.R) return fail(ADN_ERR_INVALID, "adn_stream_pool_push_rate: a row writes more samples than ring_samples");
+    if (!audio && max_new > 0) return fail(ADN_ERR_INVALID, "adn_stream_pool_push_rate: null pointer");
+    if (!aligned_to(audio, 4)) return fail(ADN_ERR_INVALID, "adn_stream_pool_push_rate: audio must be 4-byte aligned");
+    return rate_launch(who, adn::launch_resample_stream_rows(t, n_rows, audio, static_cast<float *>(rate_state), max_history,
+                                                             static_cast<float *>(state), 0, true, p.ring_off, p.R,
+                                                             static_cast<hipStream_t>(stream)));
+}
+
+int adn_stream_pool_emit_rate(void *rate_state, size_t rate_state_bytes, int n_slots, int max_history, int work_rate,
+                              const adn_stream_pool_rate_row *rows, int n_rows, const float *audio_in, long in_stride, float *out,
+                              long out_stride, void *stream)
+{
+    static const char *who = "adn_stream_pool_emit_rate";
+    adn::ResampleStreamRow t[ADN_STREAM_POOL_RATE_MAX_ROWS];
+    long max_new, max_out;
+    int rc = rate_state_check(who, rate_state, rate_state_bytes, n_slots, max_history);
+    if (rc != ADN_OK) return rc;
+    rc = rate_rows(who, false, n_slots, max_history, work_rate, rows, n_rows, t, &max_new, &max_out);
+    if (rc != ADN_OK) return rc;
+    if ((!audio_in && max_new > 0) || (!out && max_out > 0)) return fail(ADN_ERR_INVALID, "adn_stream_pool_emit_rate: null pointer");
+    if (in_stride < 0 || (n_rows > 1 && in_stride < max_new))
+        return fail(ADN_ERR_INVALID, "adn_stream_pool_emit_rate: in_stride is smaller than a row's n_new");
+    if (out_stride < 0 || (n_rows > 1 && out_stride < max_out))
+        return fail(ADN_ERR_INVALID, "adn_stream_pool_emit_rate: out_stride is smaller than the samples a row emits");
+    if (!aligned_to(audio_in, 4) || !aligned_to(out, 4)) return fail(ADN_ERR_INVALID, "adn_stream_pool_emit_rate: audio_in and out must be 4-byte aligned");
+    for (int i = 0; i < n_rows; ++i) t[i].src_off += (long)i * in_stride;
+    return rate_launch(who, adn::launch_resample_stream_rows(t, n_rows, audio_in, static_cast<float *>(rate_state), max_history, out,
+                                                             out_stride, false, 0, 0, static_cast<hipStream_t>(stream)));
+}
+
 }  // extern "C"

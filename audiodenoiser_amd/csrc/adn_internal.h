@@ -547,6 +547,19 @@ hipError_t resample_stream_prepare(const ResampleStreamGeom &g, hipStream_t st);
 hipError_t launch_resample_stream(float *state, const float *audio, long audio_stride, int n_streams, const ResampleStreamGeom &g,
                                   long call_index, long received_before, long n_new, bool final, float *out, long out_stride,
                                   hipStream_t st);
+// The same kernel over a table of rows that each carry their own stream (adn.h, "stream pool at a rate"): row i is call
+// `call_index` of the stream in (slot, direction), its history slots in rate_state, [2 slot + direction][2][max_history] floats,
+// its new samples at audio + src_off.  Linear: row i writes at out + i out_stride.  Ring: `out` is the pool state and output m
+// goes to word m mod R of the ring of `slot`, out + ring_off + slot R.  One launch; the caller has checked every row.
+constexpr int STREAM_POOL_RATE_MAX_ROWS = 64;   // adn.h: ADN_STREAM_POOL_RATE_MAX_ROWS
+struct ResampleStreamRow {
+    ResampleStreamGeom g;
+    int slot, direction;
+    long call_index, received_before, n_new, src_off;
+    bool final;
+};
+hipError_t launch_resample_stream_rows(const ResampleStreamRow *rows, int n_rows, const float *audio, float *rate_state,
+                                       long max_history, float *out, long out_stride, bool ring, long ring_off, long R, hipStream_t st);
 size_t mix_snr_workspace_floats(int n_clips, long L);
 hipError_t launch_mix_snr(const float *clean, const float *noise, int n_clips, long L, float inv_snr_linear, float *workspace,
                           float *out, hipStream_t st);

@@ -40,6 +40,7 @@
 
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace adn {
@@ -75,15 +76,76 @@ struct StreamIn {
 // staged word u lives at u + u / 32 (header, "LDS banks")
 __host__ __device__ __forceinline__ int skew(int u) { return u + (u >> 5); }
 
+// Where a workgroup gets its call from: the kernel is a template on the argument that says it, as in stream_kernels.hip.
+// Lockstep (SrCall): one call for all streams, made on the host; workgroup x belongs to stream x / nblk.  Pooled (SrPoolRows,
+// adn.h "stream pool at a rate"): a table in the kernel arguments in which every ROW is a call of its own stream -- its own rate
+// pair, table, position and span size OW; blk0 is the prefix of the rows' workgroup counts, and a workgroup finds its row by
+// bisection.  A row's two history slots lie max_history floats apart in a caller-owned rate state, [2 slot + direction][2][max_history];
+// the who-writes-what rule of the header holds row by row, for which a call names no (slot, direction) twice.
+constexpr int SR_POOL_ROWS = STREAM_POOL_RATE_MAX_ROWS;
+struct SrPoolRow {             // 48 bytes
+    const float *tab;          // coefficient table of the row's rate pair; null for equal rates: a copy, no history
+    long src_off;              // the row's new samples start at audio + src_off
+    int hslot;                 // 2 slot + direction
+    int rb, n_new;             // samples received before this call, and new ones
+    int m0, n_out;             // first output and outputs
+    int bits;                  // OW | slot_in << 16 | write_hist << 17
+    unsigned short up, down, K, H;
+};
+struct SrPoolRows {
+    long ring_off;             // ring destination: floats from the start of the pool state to slot 0's ring
+    int R, max_history, n;
+    int blk0[SR_POOL_ROWS + 1];
+    SrPoolRow row[SR_POOL_ROWS];
+};
+static_assert(sizeof(SrPoolRow) == 48 && sizeof(SrPoolRows) + 6 * 8 <= 4096, "the row table must fit the kernel-argument segment");
+template <class Rows> constexpr bool SR_POOLED = std::is_same_v<Rows, SrPoolRows>;
+
+// RING (pooled only): output m of the row's stream goes to word m mod R of its slot's ring inside the pool state (`out`), the wrap
+// handled per output; otherwise row i writes its outputs from out + i out_stride on.
+template <class Rows, bool RING>
 __global__ __launch_bounds__(SR_THREADS) void stream_resample_kernel(const float *__restrict__ audio, long audio_stride,
-                                                                    float *__restrict__ state, SrCall c,
+                                                                    float *__restrict__ state, Rows rows,
                                                                     const float *__restrict__ tab, float *__restrict__ out,
                                                                     long out_stride)
 {
+    static_assert(SR_POOLED<Rows> || !RING, "only a pool has rings");
     extern __shared__ float xs[];
-    const int stream = blockIdx.x / c.nblk, blk = blockIdx.x - stream * c.nblk;
-    float *hist = state + (long)stream * 2 * c.H;
-    const StreamIn in{audio + (long)stream * audio_stride, hist + c.slot_in * c.H, c.rb, c.end, c.H};
+    SrCall c;
+    int stream, blk;                                      // the row of the launch and the workgroup inside it
+    float *hist;
+    long hist_stride;                                     // between the two history slots of a row
+    if constexpr (SR_POOLED<Rows>) {
+        int lo = 0, hi = rows.n;                          // blk0[lo] <= x < blk0[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (rows.blk0[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
+        }
+        const SrPoolRow &r = rows.row[lo];
+        stream = lo, blk = (int)blockIdx.x - rows.blk0[lo];
+        c.m0 = r.m0, c.n_out = r.n_out, c.rb = r.rb, c.end = (long)r.rb + r.n_new;
+        c.up = r.up, c.down = r.down, c.K = r.K, c.H = r.H;
+        c.OW = r.bits & 0xffff, c.slot_in = (r.bits >> 16) & 1, c.slot_out = c.slot_in ^ 1, c.write_hist = (r.bits >> 17) & 1;
+        audio += r.src_off;
+        tab = r.tab;
+        hist_stride = rows.max_history;
+        hist = state + (long)r.hslot * 2 * hist_stride;
+        if constexpr (RING) out += rows.ring_off + (long)(r.hslot >> 1) * rows.R;
+        else out += (long)stream * out_stride;
+        if (tab == nullptr) {                             // equal rates: output m is input m
+            const long rel = (long)blk * c.OW + threadIdx.x;
+            if (rel < c.n_out) out[RING ? (c.m0 + rel) % rows.R : rel] = audio[rel];
+            return;
+        }
+    } else {
+        c = rows;
+        stream = blockIdx.x / c.nblk, blk = blockIdx.x - stream * c.nblk;
+        audio += (long)stream * audio_stride;
+        hist_stride = c.H;
+        hist = state + (long)stream * 2 * hist_stride;
+        out += (long)stream * out_stride;
+    }
+    const StreamIn in{audio, hist + c.slot_in * hist_stride, c.rb, c.end, c.H};
     const long rel0 = (long)blk * c.OW;                   // first output of this workgroup, relative to m0
     const long mA = c.m0 + rel0;
     const long t0 = mA * c.down, A0 = t0 / c.up;
@@ -97,7 +159,7 @@ __global__ __launch_bounds__(SR_THREADS) void stream_resample_kernel(const float
         for (int u = threadIdx.x; u < cnt; u += SR_THREADS) xs[skew(u)] = in.at(lo + u);
     }
     if (blk == 0 && c.write_hist) {
-        float *ho = hist + c.slot_out * c.H;
+        float *ho = hist + c.slot_out * hist_stride;
         for (int j = threadIdx.x; j < c.H; j += SR_THREADS) ho[j] = in.at(c.end - c.H + j);
     }
     __syncthreads();
@@ -108,7 +170,8 @@ __global__ __launch_bounds__(SR_THREADS) void stream_resample_kernel(const float
         float acc = 0.f;
 #pragma unroll 16
         for (int s = 0; s < steps; ++s) acc = fmaf(xs[skew(rel + s)], t[s * c.up], acc);
-        out[(long)stream * out_stride + rel0 + threadIdx.x] = acc;
+        if constexpr (RING) out[(mA + threadIdx.x) % rows.R] = acc;
+        else out[rel0 + threadIdx.x] = acc;
     }
 }
 
@@ -155,6 +218,21 @@ hipError_t get_tab(const ResampleStreamGeom &g, const float **out, hipStream_t s
 // staged samples of a workgroup of `ow` outputs, at the worst phase
 long staged(const ResampleStreamGeom &g, int ow) { return ((long)(g.up - 1) + (long)(ow - 1) * g.down) / g.up + 2L * g.K + 2; }
 
+// outputs per workgroup for a rate pair: 256, halved down to 64 where the span would not fit the LDS; *words: its LDS floats
+int span_outputs(const ResampleStreamGeom &g, long *words)
+{
+    int ow = SR_THREADS;
+    while (ow > 64 && skew((int)staged(g, ow)) + 1 > SR_MAX_LDS_FLOATS) ow /= 2;
+    *words = skew((int)staged(g, ow)) + 1;
+    return ow;
+}
+
+hipError_t allow_lds(const void *kernel, long words)
+{
+    const size_t lds = (size_t)words * sizeof(float);
+    return lds > 64 * 1024 ? hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+}
+
 }  // namespace
 
 bool resample_stream_geom(int src_rate, int dst_rate, ResampleStreamGeom *g)
@@ -194,9 +272,8 @@ hipError_t launch_resample_stream(float *state, const float *audio, long audio_s
     c.slot_in = (int)((call_index - 1) & 1), c.slot_out = (int)(call_index & 1);
     c.write_hist = final ? 0 : 1;                         // nothing follows the last call
     if (c.n_out == 0 && !c.write_hist) return hipSuccess;
-    c.OW = SR_THREADS;
-    while (c.OW > 64 && skew((int)staged(g, c.OW)) + 1 > SR_MAX_LDS_FLOATS) c.OW /= 2;
-    const long words = skew((int)staged(g, c.OW)) + 1;
+    long words = 0;
+    c.OW = span_outputs(g, &words);
     if (words > SR_MAX_LDS_FLOATS) return hipErrorInvalidValue;
     const long nblk = c.n_out > 0 ? (c.n_out + c.OW - 1) / c.OW : 1;
     if (nblk * n_streams > 0x7fffffffL) return hipErrorInvalidValue;
@@ -204,13 +281,57 @@ hipError_t launch_resample_stream(float *state, const float *audio, long audio_s
     const float *tab = nullptr;
     hipError_t e = get_tab(g, &tab, st);
     if (e != hipSuccess) return e;
-    const size_t lds = (size_t)words * sizeof(float);
-    if (lds > 64 * 1024) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(stream_resample_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
+    const auto kernel = stream_resample_kernel<SrCall, false>;
+    e = allow_lds(reinterpret_cast<const void *>(kernel), words);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(nblk * n_streams)), dim3(SR_THREADS), (size_t)words * sizeof(float), st, audio,
+                       audio_stride, state, c, tab, out, out_stride);
+    return hipGetLastError();
+}
+
+hipError_t launch_resample_stream_rows(const ResampleStreamRow *rows, int n_rows, const float *audio, float *rate_state,
+                                       long max_history, float *out, long out_stride, bool ring, long ring_off, long R, hipStream_t st)
+{
+    SrPoolRows t{};
+    t.ring_off = ring_off, t.R = (int)R, t.max_history = (int)max_history, t.n = n_rows;
+    long max_words = 1, total = 0;
+    for (int i = 0; i < n_rows; ++i) {
+        const ResampleStreamRow &r = rows[i];
+        const ResampleStreamGeom &g = r.g;
+        SrPoolRow &w = t.row[i];
+        const long end = r.received_before + r.n_new;
+        const long m0 = resample_stream_emitted(g, r.received_before, false);
+        const long n_out = resample_stream_emitted(g, end, r.final) - m0;
+        const bool copy = g.up == g.down, write_hist = !copy && !r.final;      // nothing follows the last call
+        long words = 1;
+        const int OW = copy ? SR_THREADS : span_outputs(g, &words);
+        if (words > SR_MAX_LDS_FLOATS) return hipErrorInvalidValue;
+        if (!copy) {                                      // one lookup per rate pair of the call, not per row
+            int j = 0;
+            while (j < i && (rows[j].g.up != g.up || rows[j].g.down != g.down)) ++j;
+            if (j < i) w.tab = t.row[j].tab;
+            else {
+                const hipError_t e = get_tab(g, &w.tab, st);
+                if (e != hipSuccess) return e;            // (cold in a capture: nothing has been enqueued)
+            }
+        }
+        w.src_off = r.src_off;
+        w.hslot = 2 * r.slot + r.direction;
+        w.rb = (int)r.received_before, w.n_new = (int)r.n_new, w.m0 = (int)m0, w.n_out = (int)n_out;
+        w.bits = OW | (int)((r.call_index - 1) & 1) << 16 | (write_hist ? 1 : 0) << 17;
+        w.up = (unsigned short)g.up, w.down = (unsigned short)g.down, w.K = (unsigned short)g.K, w.H = (unsigned short)g.H;
+        t.blk0[i] = (int)total;
+        total += n_out > 0 ? (n_out + OW - 1) / OW : write_hist ? 1 : 0;
+        if (total > 0x7fffffffL) return hipErrorInvalidValue;
+        if (n_out > 0 && words > max_words) max_words = words;
     }
-    hipLaunchKernelGGL(stream_resample_kernel, dim3((unsigned)(nblk * n_streams)), dim3(SR_THREADS), lds, st, audio, audio_stride,
-                       state, c, tab, out, out_stride);
+    for (int i = n_rows; i <= SR_POOL_ROWS; ++i) t.blk0[i] = (int)total;
+    if (total == 0) return hipSuccess;
+    const auto kernel = ring ? stream_resample_kernel<SrPoolRows, true> : stream_resample_kernel<SrPoolRows, false>;
+    const hipError_t e = allow_lds(reinterpret_cast<const void *>(kernel), max_words);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)total), dim3(SR_THREADS), (size_t)max_words * sizeof(float), st, audio, 0L, rate_state,
+                       t, static_cast<const float *>(nullptr), out, out_stride);
     return hipGetLastError();
 }
 

@@ -6,7 +6,7 @@
         out = sd.push(block)                          # (n_streams, newly final samples), possibly zero columns
     out = sd.flush()                                  # the rest: exactly as many samples out as went in
     sd = StreamDenoiser(model, input_rate=48000)      # the same for a feed at 48 kHz: samples at 48 kHz in, samples at 48 kHz out
-    pool = StreamPool(model, max_streams=64)          # feeds that start, stop and arrive independently: see StreamPool
+    pool = StreamPool(model, max_streams=64)          # feeds that start, stop and arrive independently, at their own rates: see StreamPool
 
     python -m audiodenoiser_amd.stream --model CKPT.pth IN.wav OUT.wav [--chunk 1024] [--window 192] [--block 16]
                                        [--lookahead 0] [--dtype f32|f16] [--live]
@@ -46,6 +46,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .resample import prepare_resample, resample_stream_plan
 
 __all__ = ["StreamDenoiser", "StreamPool", "PoolBook", "stream_plan", "stream_rate_plan"]
 
@@ -338,6 +339,11 @@ class StreamDenoiser:
 
 
 POOL_MAX_ROWS = 256          # ADN_STREAM_POOL_MAX_ROWS of include/adn.h: the rows of one analyze / emit call
+POOL_RATE_MAX_ROWS = 64      # ADN_STREAM_POOL_RATE_MAX_ROWS: the rows of one push_rate / emit_rate call
+
+
+def _rs_emitted(received: int, src: int, dst: int, final: bool = False) -> int:
+    return resample_stream_plan(received, src, dst, final)[0]
 
 
 class PoolBook:
@@ -345,11 +351,24 @@ class PoolBook:
     what follows from them -- which step is ready, how many samples it returns, how much room the slot's ring has left.
 
     ``ring_samples`` = ``n_fft - hop`` (the history a step's first frame shares with the step before) + ``e(0)`` (what the first
-    step reads) + ``backlog_steps`` blocks of ``B hop`` samples that may wait while their step has not run."""
+    step reads) + ``backlog_steps`` blocks of ``B hop`` samples that may wait while their step has not run.
+
+    ``input_rates``: the rates streams may be opened at (None: the working rate only, and nothing below applies).  A stream at
+    another rate than ``sample_rate`` has, per slot, ``rate``, the calls made so far to its two resamplers (``calls_in``,
+    ``calls_out``), ``received_in`` (samples pushed, at its rate), ``work_out`` (working-rate samples its steps have returned, all
+    handed to the resampler out) and ``emitted_in`` (samples returned, at its rate); ``received`` stays what the ring has received,
+    at the working rate.  All of it follows from ``adn_resample_stream_plan``.  The ring grows by ``reserve`` samples, the most the
+    resampler in still releases when a stream ends, and ``room`` keeps them free."""
     FREE, RUNNING, CLOSED = 0, 1, 2
 
     def __init__(self, max_streams: int = 64, backlog_steps: int = 4, n_fft: int = 512, hop_length: int = 128,
-                 window_frames: int = 192, block_frames: int = 16, lookahead_frames: int = 0):
+                 window_frames: int = 192, block_frames: int = 16, lookahead_frames: int = 0, input_rates=None,
+                 sample_rate: int = 8000):
+        if not (isinstance(sample_rate, int) and sample_rate >= 1):
+            raise ValueError("StreamPool: sample_rate must be >= 1")
+        rates = () if input_rates is None else tuple(input_rates)
+        if not all(isinstance(r, int) and r >= 1 for r in rates):
+            raise ValueError("StreamPool: input_rates must be None or integers >= 1")
         if not (isinstance(max_streams, int) and 1 <= max_streams <= 1 << 20):
             raise ValueError("StreamPool: max_streams must be in [1, 2^20]")
         if not (isinstance(backlog_steps, int) and backlog_steps >= 1):
@@ -371,13 +390,29 @@ class PoolBook:
         self.block_frames, self.lookahead_frames = block_frames, lookahead_frames
         self.plan = (n_fft, hop_length, window_frames, block_frames, lookahead_frames)
         self.keep = n_fft - hop_length
-        self.ring_samples = self.keep + self.end_of(0) + backlog_steps * block_frames * hop_length
+        self.out_stride = block_frames * hop_length + n_fft // 2          # the most a step returns (the last one of a stream)
+        # the rates: history both ways, what the resampler in releases at a stream's end, the most a step returns at a stream's rate
+        self.sample_rate, self.input_rates = sample_rate, tuple(sorted(set(rates) - {sample_rate}))
+        self.max_history = self.reserve = self.rate_out_stride = 0
+        for r in self.input_rates:
+            g = math.gcd(r, sample_rate)
+            up, down = sample_rate // g, r // g                           # rate -> working rate
+            half = 32 * max(up, down)                                     # adn.h, "resample": half = ZEROS max(up, down)
+            if resample_stream_plan(0, r, sample_rate)[2] != -(-half // up) or resample_stream_plan(0, sample_rate, r)[2] != -(-half // down):
+                raise RuntimeError("StreamPool: the library's resampling filter is not the one the ring reserve is sized for")
+            self.max_history = max(self.max_history, resample_stream_plan(0, r, sample_rate)[1], resample_stream_plan(0, sample_rate, r)[1])
+            # ceil(n up / down) - emitted(n) <= (half + 1) / down + 2 for every n;  back out: up and down change places
+            self.reserve = max(self.reserve, (half + 1) // down + 2)
+            self.rate_out_stride = max(self.rate_out_stride, (self.out_stride * down + half + 1) // up + 2)
+        self.ring_samples = self.keep + self.end_of(0) + backlog_steps * block_frames * hop_length + self.reserve
         if self.ring_samples > 1 << 28:
             raise ValueError("StreamPool: backlog_steps asks for a ring of more than 2^28 samples per stream")
-        self.out_stride = block_frames * hop_length + n_fft // 2          # the most a step returns (the last one of a stream)
         self.status = [self.FREE] * max_streams
         self.received = [0] * max_streams
         self.done = [0] * max_streams
+        self.rate = [None] * max_streams                                  # None: the stream is at the working rate
+        self.calls_in, self.calls_out = [0] * max_streams, [0] * max_streams
+        self.received_in, self.work_out, self.emitted_in = [0] * max_streams, [0] * max_streams, [0] * max_streams
 
     def end_of(self, step: int) -> int:
         """Samples that must have arrived for ``step`` of a running stream (``e(k)`` of adn.h; 0 for step -1)."""
@@ -394,22 +429,42 @@ class PoolBook:
         if not (isinstance(slot, int) and 0 <= slot < self.max_streams) or self.status[slot] == self.FREE:
             raise ValueError(f"StreamPool.{what}: {slot!r} is not an open stream")
 
-    def open(self) -> int:
+    def open(self, input_rate=None) -> int:
+        if input_rate is not None and input_rate != self.sample_rate and input_rate not in self.input_rates:
+            raise ValueError(f"StreamPool.open: input_rate {input_rate!r} is not among the pool's input_rates {self.input_rates}")
         for slot, st in enumerate(self.status):
             if st == self.FREE:
                 self.status[slot], self.received[slot], self.done[slot] = self.RUNNING, 0, 0
+                self.rate[slot] = None if input_rate == self.sample_rate else input_rate
+                self.calls_in[slot] = self.calls_out[slot] = 0
+                self.received_in[slot] = self.work_out[slot] = self.emitted_in[slot] = 0
                 return slot
         raise RuntimeError(f"StreamPool.open: all {self.max_streams} streams are taken")
 
     def room(self, slot: int) -> int:
         """Samples that fit before a push would overwrite one that the stream's next step still reads: the ring holds the last
-        ``ring_samples`` samples, the next step reads from ``e(done - 1) - (n_fft - hop)`` on."""
+        ``ring_samples`` samples, the next step reads from ``e(done - 1) - (n_fft - hop)`` on.  For a stream at a rate of its own,
+        in samples at that rate: the largest ``m`` after which the stream could still END inside the ring --
+        ``ceil((received_in + m) up / down)`` working-rate samples, what the resampler in releases at the end included."""
         self._live(slot, "room")
         oldest = max(0, self.end_of(self.done[slot] - 1) - self.keep)
-        return oldest + self.ring_samples - self.received[slot]
+        if self.rate[slot] is None:
+            return oldest + self.ring_samples - self.received[slot]
+        if self.status[slot] == self.CLOSED:
+            return 0
+        g = math.gcd(self.rate[slot], self.sample_rate)
+        up, down = self.sample_rate // g, self.rate[slot] // g
+        return max(0, (oldest + self.ring_samples) * down // up - self.received_in[slot])
 
     def take(self, slot: int, m: int) -> int:
         """Book a push of ``m`` samples; returns the position they start at.  Changes nothing when it raises."""
+        self.check(slot, m)
+        at = self.received[slot]
+        self.received[slot] = at + m
+        return at
+
+    def check(self, slot: int, m: int) -> None:
+        """What ``take`` raises, without booking anything."""
         self._live(slot, "push")
         if self.status[slot] == self.CLOSED:
             raise RuntimeError("StreamPool.push: the stream has been closed")
@@ -418,9 +473,73 @@ class PoolBook:
                                "that no step has used yet would be overwritten; call step()")
         if self.received[slot] + m >= 1 << 30:
             raise ValueError("StreamPool.push: a stream holds fewer than 2^30 samples; close() it before")
-        at = self.received[slot]
-        self.received[slot] = at + m
-        return at
+
+    def check_rate(self, slot: int, m: int) -> None:
+        """What ``take_rate`` raises, without booking anything."""
+        self._live(slot, "push")
+        if self.status[slot] == self.CLOSED:
+            raise RuntimeError("StreamPool.push: the stream has been closed")
+        if m > self.room(slot):
+            raise RuntimeError(f"StreamPool.push: {m} samples do not fit, the stream has room for {self.room(slot)} at its rate before "
+                               "samples that no step has used yet would be overwritten; call step()")
+        if self.received_in[slot] + m >= 1 << 31 or _rs_emitted(self.received_in[slot] + m, self.rate[slot], self.sample_rate, True) >= 1 << 30:
+            raise ValueError("StreamPool.push: a stream holds fewer than 2^30 samples at the working rate; close() it before")
+
+    def take_rate(self, slot: int, m: int):
+        """Book a push of ``m >= 1`` samples at the stream's own rate -> ``(call_index, received_before)`` of the call to the
+        resampler in; ``received`` becomes what the ring holds after it.  Changes nothing when it raises."""
+        self.check_rate(slot, m)
+        call = self.calls_in[slot], self.received_in[slot]
+        self.calls_in[slot] += 1
+        self.received_in[slot] += m
+        self.received[slot] = _rs_emitted(self.received_in[slot], self.rate[slot], self.sample_rate)
+        return call
+
+    def close_rate(self, slot: int):
+        """The end of a stream at a rate of its own with ``received_in > 0``: -> ``(call_index, received_before)`` of the resampler
+        in's final call (``n_new = 0``), which the caller has to enqueue; ``received`` becomes the stream's working-rate length."""
+        call = self.calls_in[slot], self.received_in[slot]
+        self.calls_in[slot] += 1
+        self.received[slot] = _rs_emitted(self.received_in[slot], self.rate[slot], self.sample_rate, True)
+        return call
+
+    def count_rate(self, slot: int, n: int, last: bool) -> int:
+        """Samples at the stream's rate that the resampler out returns for the ``n`` working-rate samples of the stream's next
+        step; ``last``: it is the stream's last step, and the result is cut to the samples the stream received."""
+        total = _rs_emitted(self.work_out[slot] + n, self.sample_rate, self.rate[slot], last)
+        if last:                                                          # ceil(ceil(L up / down) down / up) >= L
+            total = self.received_in[slot]
+        return total - self.emitted_in[slot]
+
+    def ran_rate(self, slot: int, n: int, last: bool):
+        """Book the call to the resampler out for a step that returned ``n`` working-rate samples -> ``(call_index,
+        received_before, samples returned at the stream's rate)``, or None when there is no call (nothing new, not the end)."""
+        if n == 0 and not last:
+            return None
+        call = self.calls_out[slot], self.work_out[slot], self.count_rate(slot, n, last)
+        self.calls_out[slot] += 1
+        self.work_out[slot] += n
+        self.emitted_in[slot] += call[2]
+        return call
+
+    def rate_calls(self, rows):
+        """Book the resampler out's calls of a tick's ``rows`` (``self.rows()``) -> ``(calls, where)``: ``calls`` = ``(row, rate row)``
+        per row that makes one, in row order, the rate row ``(slot, rate, call_index, received_before, n_new, final, 0)``;
+        ``where[row]`` = ``(index into calls or None, samples returned at the stream's rate)`` for every row of a stream at a rate
+        of its own.  Rows of working-rate streams and rows that returned nothing yet make no call."""
+        calls, where = [], {}
+        for i, (slot, k, final) in enumerate(rows):
+            if self.rate[slot] is None:
+                continue
+            n = self.count(k, final)
+            last = final >= 0 and k == self.n_steps(final) - 1
+            call = self.ran_rate(slot, n, last)
+            if call is None:
+                where[i] = (None, 0)
+            else:
+                where[i] = (len(calls), call[2])
+                calls.append((i, (slot, self.rate[slot], call[0], call[1], n, 1 if last else 0, 0)))
+        return calls, where
 
     def close(self, slot: int) -> bool:
         """The stream has ended.  True when nothing is left to run (a stream of no samples): the slot is free again."""
@@ -488,13 +607,29 @@ class StreamPool:
     bound otherwise); each stream returns exactly as many samples as it received; a slot is free again, and reusable without a
     reset, once the tick that reports ``finished=True`` has run.  ``push`` beyond ``room`` raises and changes nothing.
     What is NOT claimed: anything ``StreamDenoiser`` does not claim; fairness, priorities or deadlines between streams; more than
-    one step per stream and tick (a stream that is several steps behind catches up one tick at a time); another rate than the
-    network's working rate (put a ``StreamResampler(n_streams=1)`` on each side of a stream); graph capture of a tick.  There is
-    no CPU path.  Samples come back in the kind (numpy / device tensor) of the stream's last ``push``."""
+    one step per stream and tick (a stream that is several steps behind catches up one tick at a time); graph capture of a tick.
+    There is no CPU path.  Samples come back in the kind (numpy / device tensor) of the stream's last ``push``.
+
+    Feeds at their own rates (``include/adn.h``, "stream pool at a rate"; kernel: ``csrc/stream_resample_kernels.hip``, the
+    lockstep resampler's body over a by-value table of rows that each carry their own stream):
+
+        pool = StreamPool(model, input_rates=(48000, 44100, 16000))      # the rates streams may be opened at
+        sid = pool.open(input_rate=48000)                                # push, room and the samples of step(): at 48 kHz
+        pool.push_many({sid: block, other: block2})                      # all blocks: one staging copy, one launch per 64 streams
+
+    ``input_rates`` sizes the resamplers' history (``max_history``), the row of a step's samples at the fastest rate and the
+    ring's reserve; None gives exactly the pool above.  A push goes through ``adn_stream_pool_push_rate`` straight into the ring,
+    the rows of a tick that ran go back through ``adn_stream_pool_emit_rate``; ``close`` enqueues the resampler in's last call,
+    for whose samples ``room`` has kept the ring free, and the stream's last step is cut so that it has returned exactly as many
+    samples as it received.  Claimed: a stream's output is, bit for bit with ``set_batch_invariant(True)``, that of
+    ``StreamDenoiser(n_streams=1, input_rate=rate)`` for the same samples, whatever rates and timing its neighbours have.  Not
+    claimed: rates outside ``adn_resample``'s limits; anything ``StreamDenoiser(input_rate=...)`` does not claim."""
 
     def __init__(self, model, max_streams: int = 64, backlog_steps: int = 4, n_fft: int = 512, hop_length: int = 128,
-                 window_frames: int = 192, block_frames: int = 16, lookahead_frames: int = 0, batch_windows: int = 64):
-        self.book = PoolBook(max_streams, backlog_steps, n_fft, hop_length, window_frames, block_frames, lookahead_frames)
+                 window_frames: int = 192, block_frames: int = 16, lookahead_frames: int = 0, batch_windows: int = 64,
+                 input_rates=None, sample_rate: int = 8000):
+        self.book = PoolBook(max_streams, backlog_steps, n_fft, hop_length, window_frames, block_frames, lookahead_frames,
+                             input_rates, sample_rate)
         if not (isinstance(batch_windows, int) and batch_windows >= 1):
             raise ValueError("StreamPool: batch_windows must be >= 1")
         from .model import UNet
@@ -512,6 +647,16 @@ class StreamPool:
         _lib.check(_lib.load().adn_stream_pool_state_bytes(*self._args, ctypes.byref(need)), "adn_stream_pool_state_bytes")
         self._state = torch.empty(need.value, dtype=torch.uint8, device=dev)
         self._numpy = [True] * max_streams
+        # streams at a rate of their own: the histories of their resamplers, two directions per slot (none without input_rates)
+        self._rate_state = None
+        if self.book.input_rates:
+            _lib.check(_lib.load().adn_stream_pool_rate_state_bytes(max_streams, self.book.max_history, ctypes.byref(need)),
+                       "adn_stream_pool_rate_state_bytes")
+            self._rate_state = torch.empty(max(need.value, 8), dtype=torch.uint8, device=dev)
+            self._rate_args = (self._rate_state.data_ptr(), need.value, max_streams, self.book.max_history, self.book.sample_rate)
+            for r in self.book.input_rates:                  # the coefficient tables, so that no push builds one
+                prepare_resample(r, self.book.sample_rate, dev)
+                prepare_resample(self.book.sample_rate, r, dev)
         self.reset()
 
     @property
@@ -527,22 +672,40 @@ class StreamPool:
         b.status, b.received, b.done = [b.FREE] * self.max_streams, [0] * self.max_streams, [0] * self.max_streams
 
     # ------------------------------------------------------------------ streams
-    def open(self) -> int:
-        """A free slot for a new stream (the lowest one); ``RuntimeError`` when all ``max_streams`` are taken."""
-        return self.book.open()
+    def open(self, input_rate=None) -> int:
+        """A free slot for a new stream (the lowest one); ``RuntimeError`` when all ``max_streams`` are taken.  ``input_rate``: the
+        rate of the stream's samples, in and out, one of the pool's ``input_rates`` (None: the working rate)."""
+        return self.book.open(input_rate)
 
     def room(self, sid: int) -> int:
-        """Samples that still fit before a ``push`` would overwrite samples no step has used yet."""
+        """Samples, at the stream's rate, that still fit before a ``push`` would overwrite samples no step has used yet."""
         return self.book.room(sid)
 
     def received(self, sid: int) -> int:
+        """Samples pushed so far, at the stream's rate."""
         self.book._live(sid, "received")
-        return self.book.received[sid]
+        return self.book.received[sid] if self.book.rate[sid] is None else self.book.received_in[sid]
 
     def push(self, sid: int, block) -> None:
         """The next ``m >= 0`` samples of stream ``sid``: ``(m,)`` float32, numpy or a tensor on the ROCm device.  More than
         ``room(sid)`` raises ``RuntimeError`` and changes nothing: call ``step()`` first."""
         self.book._live(sid, "push")
+        if self.book.rate[sid] is not None:
+            return self.push_many({sid: block})
+        x, as_numpy = self._block(block)
+        m = x.shape[0]
+        at = self.book.take(sid, m)
+        self._numpy[sid] = as_numpy
+        if m == 0:
+            return
+        x = x.to(self.device).contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().adn_stream_pool_write(self._state.data_ptr(), self._state.numel(), *self._args, sid, x.data_ptr(),
+                                                         m, at, _stream(self.device)), "adn_stream_pool_write")
+
+    @staticmethod
+    def _block(block):
+        """``block`` as a float32 tensor of one dimension (on the host for numpy) and whether it was numpy."""
         as_numpy = not isinstance(block, torch.Tensor)
         if as_numpy:
             x = torch.from_numpy(np.ascontiguousarray(block, dtype=np.float32))
@@ -554,20 +717,79 @@ class StreamPool:
                 raise TypeError("StreamPool.push: expected float32 audio")
         if x.dim() != 1:
             raise ValueError("StreamPool.push: audio must be (m,), the samples of one stream")
-        m = x.shape[0]
-        at = self.book.take(sid, m)
-        self._numpy[sid] = as_numpy
-        if m == 0:
-            return
-        x = x.to(self.device).contiguous()
+        return x, as_numpy
+
+    def _rate_rows(self, rows):
+        return (_lib.StreamPoolRateRow * len(rows))(*[_lib.StreamPoolRateRow(*r) for r in rows])
+
+    def _push_rate(self, rows, audio) -> None:
+        """``adn_stream_pool_push_rate``: rows ``(slot, rate, call_index, received_before, n_new, final, audio_offset)`` -> rings."""
+        L = _lib.load()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().adn_stream_pool_write(self._state.data_ptr(), self._state.numel(), *self._args, sid, x.data_ptr(),
-                                                         m, at, _stream(self.device)), "adn_stream_pool_write")
+            for i in range(0, len(rows), POOL_RATE_MAX_ROWS):
+                g = rows[i:i + POOL_RATE_MAX_ROWS]
+                _lib.check(L.adn_stream_pool_push_rate(self._state.data_ptr(), self._state.numel(), *self._args, *self._rate_args[:2],
+                                                       *self._rate_args[3:], self._rate_rows(g), len(g),
+                                                       audio.data_ptr() if audio is not None else None, _stream(self.device)),
+                           "adn_stream_pool_push_rate")
+
+    def push_many(self, blocks) -> None:
+        """``{sid: block}``: the next samples of several streams, each at its stream's rate.  The blocks of the streams at a rate of
+        their own are staged with one host-to-device copy when all of them are numpy (device tensors: one concatenation; mixed: a
+        copy per numpy block) and resampled into their rings by one ``adn_stream_pool_push_rate`` call per 64 of them (a pool
+        with ``input_rates`` takes its working-rate streams along as copy rows; without, they go the way of ``push``).  When one
+        block does not fit its stream's ``room``, ``RuntimeError`` is raised and NO stream has changed; the same holds when
+        the library refuses the call."""
+        book = self.book
+        items = []
+        for sid, block in blocks.items():
+            book._live(sid, "push")
+            x, as_numpy = self._block(block)
+            (book.check if book.rate[sid] is None else book.check_rate)(sid, x.shape[0])
+            items.append((sid, x, as_numpy))
+        rows, parts, offset, undo = [], [], 0, []
+        for sid, x, as_numpy in items:
+            m = x.shape[0]
+            if book.rate[sid] is None and self._rate_state is None:
+                self.push(sid, x if not as_numpy else x.numpy())
+                continue
+            if m == 0:
+                self._numpy[sid] = as_numpy
+                continue
+            undo.append((sid, book.received[sid], book.received_in[sid], book.calls_in[sid], self._numpy[sid]))
+            self._numpy[sid] = as_numpy
+            if book.rate[sid] is None:                       # at the working rate among others: a copy row of the same call
+                before = book.take(sid, m)
+                rows.append((sid, book.sample_rate, min(before, 1), before, m, 0, offset))
+            else:
+                call, before = book.take_rate(sid, m)
+                rows.append((sid, book.rate[sid], call, before, m, 0, offset))
+            parts.append((x, as_numpy))
+            offset += m
+        if not rows:
+            return
+        host = [x for x, as_numpy in parts if as_numpy]
+        if len(host) == len(parts):                          # all numpy: one staging buffer, one copy
+            audio = (torch.cat(host) if len(host) > 1 else host[0]).to(self.device)
+        else:
+            audio = torch.cat([x.to(self.device) for x, _ in parts]) if len(parts) > 1 else parts[0][0].to(self.device).contiguous()
+        try:
+            self._push_rate(rows, audio)
+        except Exception:                                    # refused by the library: the book does not run ahead of the device
+            for sid, received, received_in, calls_in, as_numpy in undo:
+                book.received[sid], book.received_in[sid], book.calls_in[sid], self._numpy[sid] = received, received_in, calls_in, as_numpy
+            raise
 
     def close(self, sid: int) -> bool:
         """The stream has ended; its remaining steps run in the following ticks, the last of which reports ``finished=True``.
-        Returns True when there is nothing left to run -- a stream of no samples -- and the slot is free already."""
-        return self.book.close(sid)
+        Returns True when there is nothing left to run -- a stream of no samples -- and the slot is free already.  For a stream at
+        a rate of its own the resampler in's last call goes into the ring here (``room`` has kept its samples free)."""
+        book = self.book
+        book._live(sid, "close")
+        if book.rate[sid] is not None and book.status[sid] == book.RUNNING and book.received_in[sid] > 0:
+            call, before = book.close_rate(sid)
+            self._push_rate([(sid, book.rate[sid], call, before, 0, 1, 0)], None)
+        return book.close(sid)
 
     # ------------------------------------------------------------------ building blocks (device tensors)
     def _rows(self, rows):
@@ -608,13 +830,39 @@ class StreamPool:
         y = self.network(x)
         outs = [self.emit(y[i * group:i * group + len(g)], g) for i, g in enumerate(groups)]
         out = torch.cat(outs) if len(outs) > 1 else outs[0]
-        host = out.cpu().numpy() if any(self._numpy[r[0]] for r in rows) else None
+        book = self.book
+        calls, rated = book.rate_calls(rows)             # the rows of streams at a rate of their own go back to it
+        rout = self.emit_rate(out, calls) if calls else None
+        plain = any(self._numpy[r[0]] and i not in rated for i, r in enumerate(rows))
+        host = out.cpu().numpy() if plain else None
+        rhost = rout.cpu().numpy() if rout is not None and any(self._numpy[rows[i][0]] for i, _ in calls) else None
         result = []
         for i, (slot, k, final) in enumerate(rows):
-            n = self.book.count(k, final)
-            samples = host[i, :n].copy() if self._numpy[slot] else out[i, :n].clone()
-            result.append((slot, samples, self.book.ran(slot)))
+            if i in rated:
+                j, n = rated[i]
+                if j is None:
+                    samples = np.empty(0, dtype=np.float32) if self._numpy[slot] else out.new_empty(0)
+                else:
+                    samples = rhost[j, :n].copy() if self._numpy[slot] else rout[j, :n].clone()
+            else:
+                n = book.count(k, final)
+                samples = host[i, :n].copy() if self._numpy[slot] else out[i, :n].clone()
+            result.append((slot, samples, book.ran(slot)))
         return result
+
+    def emit_rate(self, out: torch.Tensor, calls) -> torch.Tensor:
+        """``adn_stream_pool_emit_rate``: ``calls`` as ``PoolBook.rate_calls`` returns them, ``out`` what ``emit`` wrote for the
+        tick; -> ``(len(calls), book.rate_out_stride)``, row j holding call j's samples at its stream's rate.  One call per 64
+        of them, whichever rows of ``out`` they are: a row names the rows left out before it in its ``audio_offset``."""
+        stride, in_stride = self.book.rate_out_stride, out.stride(0)
+        rout = torch.empty((len(calls), stride), dtype=torch.float32, device=self.device)
+        L = _lib.load()
+        with torch.cuda.device(self.device):
+            for j in range(0, len(calls), POOL_RATE_MAX_ROWS):
+                g = [c[:6] + ((row - i) * in_stride,) for i, (row, c) in enumerate(calls[j:j + POOL_RATE_MAX_ROWS])]
+                _lib.check(L.adn_stream_pool_emit_rate(*self._rate_args, self._rate_rows(g), len(g), out.data_ptr(), in_stride,
+                                                       rout[j].data_ptr(), stride, _stream(self.device)), "adn_stream_pool_emit_rate")
+        return rout
 
     def drain(self):
         """``step()`` until nothing is ready -> ``(sid, samples, finished)`` per stream that ran, its samples concatenated."""

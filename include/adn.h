@@ -450,6 +450,59 @@ ADN_API int adn_resample_stream(void *state, size_t state_bytes, const float *au
                                 long call_index, long received_before, long n_new, int final, int src_rate, int dst_rate,
                                 float *out, long out_stride, void *stream);
 
+/* ---- stream pool at a rate: the pool's streams resampled into their rings and back, all rows of a call in one launch ------------
+ * These entry points define no new arithmetic: a ROW is one adn_resample_stream call of one stream, and a row's outputs are, bit
+ * for bit, adn_resample_stream's for a state of one stream (n_streams = 1) given the same calls -- hence adn_resample's of the
+ * finished signal, however it was cut.  What is new is where the rows come from and go to: every row names its own slot, rate,
+ * call_index, received_before, n_new and final (their meaning and the finality rule: "resample stream" above), the table is
+ * handed to one kernel launch by value (no host -> device copy, no workspace, no atomics), and a row's outputs go either into the
+ * slot's ring inside a pool state or to a row of a plain buffer.  work_rate is the rate of the pool's rings.
+ *
+ * Rate state (adn_stream_pool_rate_state_bytes, caller-owned, opaque, 8-byte aligned, separate from the pool state, whose layout
+ * and size do not change): per slot and DIRECTION (0: into the pool, 1: out of it) two slots of max_history floats,
+ *   floats = n_slots * 2 * 2 * max_history,
+ * used as adn_resample_stream uses its state: call 0 of a stream reads none of it, so a slot is reused without a reset, at
+ * another rate too.  max_history >= the H of every rate pair the state is used with (adn_resample_stream_plan).
+ *   adn_stream_pool_push_rate: row i brings the next n_new samples of the stream in `slot`, at src_rate, found at
+ *     audio + audio_offset (ONE device buffer holds the blocks of all rows); direction 0.  Its outputs at work_rate, the samples
+ *     [emitted(received_before), emitted(received_before + n_new, final)) of the stream, go to the words m mod ring_samples of the
+ *     slot's ring; a range that straddles the wrap is handled in the kernel.  The first arguments are the pool state and its
+ *     geometry, as in the "stream pool" section.  CONTRACT of the caller: the ring has room for them (no step still reads the
+ *     words they replace).
+ *   adn_stream_pool_emit_rate: row i takes the stream in `slot` from work_rate to dst_rate (`rate`); direction 1.  It reads n_new
+ *     samples at audio_in + i in_stride + audio_offset -- with audio_offset = 0 the layout adn_stream_pool_emit writes; a caller
+ *     that leaves rows of that buffer out (streams at work_rate, steps that returned nothing) names the rows it skipped there, so
+ *     that any subset of a tick's rows is one call -- and writes its outputs from out + i out_stride on.
+ * Equal rates are a copy that reads and writes no history.  No state word is written by one workgroup and read by another in
+ * the same launch, for which a call must not name a (slot, direction) twice.
+ * Limits (ADN_ERR_INVALID before any launch): for every row everything adn_resample_stream refuses -- the rate limits,
+ * n_new >= 1 unless final, final 0 or 1, call_index >= 0 and call_index == 0 exactly when received_before == 0, positions < 2^31;
+ * H of the row's rate pair <= max_history <= 16384; 0 <= slot < n_slots, 1 <= n_slots <= 2^20; the same slot twice in a call;
+ * 1 <= n_rows <= ADN_STREAM_POOL_RATE_MAX_ROWS (a caller with more rows calls again); audio_offset >= 0; null pointers;
+ * push: more outputs than ring_samples in one row, outputs at or beyond sample 2^30 of the stream (the pool's limit), the pool
+ * section's limits on the state and its geometry; emit: in_stride below a row's n_new or out_stride below its outputs when
+ * n_rows > 1.  ADN_ERR_WORKSPACE: rate_state_bytes below adn_stream_pool_rate_state_bytes (or the pool state below its size).
+ * Cold coefficient tables behave as in adn_resample_stream: adn_resample_prepare(device, src, dst) warms them; a cold call on a
+ * capturing stream enqueues nothing and returns ADN_ERR_INVALID.  adn_stream_pool_rate_state_bytes is host-only. */
+#define ADN_STREAM_POOL_RATE_MAX_ROWS 64
+typedef struct adn_stream_pool_rate_row {
+    int slot;
+    int rate;              /* push: src_rate; emit: dst_rate */
+    long call_index;
+    long received_before;
+    long n_new;
+    int final;
+    long audio_offset;     /* floats from `audio` (push) or from audio_in + i in_stride (emit) to the row's samples */
+} adn_stream_pool_rate_row;
+ADN_API int adn_stream_pool_rate_state_bytes(int n_slots, int max_history, size_t *bytes);
+ADN_API int adn_stream_pool_push_rate(void *state, size_t state_bytes, int n_slots, int n_fft, int hop, int window, int block,
+                                      int lookahead, long ring_samples, void *rate_state, size_t rate_state_bytes, int max_history,
+                                      int work_rate, const adn_stream_pool_rate_row *rows, int n_rows, const float *audio,
+                                      void *stream);
+ADN_API int adn_stream_pool_emit_rate(void *rate_state, size_t rate_state_bytes, int n_slots, int max_history, int work_rate,
+                                      const adn_stream_pool_rate_row *rows, int n_rows, const float *audio_in, long in_stride,
+                                      float *out, long out_stride, void *stream);
+
 /* ---- environment switches -------------------------------------------------------------------------------------------------
  * Read ONCE, when a U-Net handle is created (never per call).  None is needed in production: the defaults are the measured best
  * and every family below is covered by the parity tests (tests/test_gpu_variants.py::MODES).  They select between kernel
