@@ -96,6 +96,10 @@ def load() -> ctypes.CDLL:
         L.adn_stream_pool_rate_state_bytes.argtypes = [ci, ci, ctypes.POINTER(sz)]
         L.adn_stream_pool_push_rate.argtypes = [vp, sz, ci, ci, ci, ci, ci, ci, cl, vp, sz, ci, ci, vp, ci, vp, vp]
         L.adn_stream_pool_emit_rate.argtypes = [vp, sz, ci, ci, ci, vp, ci, vp, cl, vp, cl, vp]
+        L.adn_quality_workspace_bytes.argtypes = [ci, cl, ctypes.POINTER(sz)]
+        L.adn_quality.argtypes = [vp, vp, vp, ci, cl, ci, vp, sz, vp, vp]
+        L.adn_stoi_workspace_bytes.argtypes = [ci, cl, ctypes.POINTER(sz)]
+        L.adn_stoi.argtypes = [vp, vp, vp, ci, cl, vp, sz, vp, vp]
         for name in ("adn_device_count", "adn_prepare", "adn_unet_create", "adn_unet_create_ex", "adn_unet_create_general", "adn_unet_channels",
                      "adn_unet_set_batch_invariant", "adn_unet_destroy", "adn_unet_workspace_bytes", "adn_unet_forward", "adn_unet_forward_taps", "adn_unet_set_timing", "adn_unet_get_timing",
                      "adn_stft_n_frames", "adn_stft_mag", "adn_stft_mag_fit", "adn_quantize_pad", "adn_per_clip_l1",
@@ -109,7 +113,8 @@ def load() -> ctypes.CDLL:
                      "adn_stream_pool_state_bytes", "adn_stream_pool_reset", "adn_stream_pool_write", "adn_stream_pool_analyze",
                      "adn_stream_pool_emit",
                      "adn_resample_stream_plan", "adn_resample_stream_state_bytes", "adn_resample_stream",
-                     "adn_stream_pool_rate_state_bytes", "adn_stream_pool_push_rate", "adn_stream_pool_emit_rate"):
+                     "adn_stream_pool_rate_state_bytes", "adn_stream_pool_push_rate", "adn_stream_pool_emit_rate",
+                     "adn_quality_workspace_bytes", "adn_quality", "adn_stoi_workspace_bytes", "adn_stoi"):
             getattr(L, name).restype = ci
         _lib = L
         return L
@@ -156,4 +161,5 @@ EXPORTED_SYMBOLS = (
     "adn_stream_pool_state_bytes", "adn_stream_pool_reset", "adn_stream_pool_write", "adn_stream_pool_analyze", "adn_stream_pool_emit",
     "adn_resample_stream_plan", "adn_resample_stream_state_bytes", "adn_resample_stream",
     "adn_stream_pool_rate_state_bytes", "adn_stream_pool_push_rate", "adn_stream_pool_emit_rate",
+    "adn_quality_workspace_bytes", "adn_quality", "adn_stoi_workspace_bytes", "adn_stoi",
 )

@@ -1,5 +1,5 @@
 // C ABI of libadn.so (include/adn.h) outside the U-Net (unet.hip): version, last error, device queries and the argument checks in
-// front of the STFT, loader, loss, Griffin-Lim, resampler, mixer, reverb, long-form and streaming denoising launchers.
+// front of the STFT, loader, loss, Griffin-Lim, resampler, mixer, reverb, quality-metric, long-form and streaming denoising launchers.
 #include "adn_host.h"
 
 #include <cmath>
@@ -223,6 +223,52 @@ int adn_reverb(const float *audio, int n_clips, long length, int sample_rate, fl
                                       static_cast<hipStream_t>(stream));
     if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_reverb: unsupported sample_rate");
     if (e != hipSuccess) return fail_hip(e, "adn_reverb");
+    return ADN_OK;
+}
+
+int adn_quality_workspace_bytes(int n_clips, long length, size_t *bytes)
+{
+    if (!bytes || n_clips < 1 || length < 1 || length >= adn::ADN_QUALITY_MAX_LENGTH)
+        return fail(ADN_ERR_INVALID, "adn_quality_workspace_bytes: need n_clips >= 1 and 1 <= length < 2^30");
+    *bytes = adn::quality_workspace_bytes(n_clips, length);
+    return ADN_OK;
+}
+
+int adn_quality(const float *est, const float *ref, const long *lengths, int n_clips, long length, int seg_frame, void *workspace,
+                size_t workspace_bytes, float *out, void *stream)
+{
+    if (!est || !ref || !out) return fail(ADN_ERR_INVALID, "adn_quality: null pointer");
+    size_t need = 0;
+    if (adn_quality_workspace_bytes(n_clips, length, &need) != ADN_OK) return ADN_ERR_INVALID;
+    if (seg_frame < adn::ADN_SEG_FRAME_MIN || seg_frame > adn::ADN_SEG_FRAME_MAX)
+        return fail(ADN_ERR_INVALID, "adn_quality: seg_frame must be in [16, 8192]");
+    if (!workspace || workspace_bytes < need) return fail(ADN_ERR_WORKSPACE, "adn_quality: workspace too small");
+    if (!aligned_to(workspace, 16)) return fail(ADN_ERR_INVALID, "adn_quality: workspace must be 16-byte aligned");
+    hipError_t e = adn::launch_quality(est, ref, lengths, n_clips, length, seg_frame, workspace, out, static_cast<hipStream_t>(stream));
+    if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_quality: grid too large (n_clips x length / 8192 >= 2^31)");
+    if (e != hipSuccess) return fail_hip(e, "adn_quality");
+    return ADN_OK;
+}
+
+int adn_stoi_workspace_bytes(int n_clips, long length, size_t *bytes)
+{
+    if (!bytes || n_clips < 1 || length < 1 || length >= adn::ADN_QUALITY_MAX_LENGTH)
+        return fail(ADN_ERR_INVALID, "adn_stoi_workspace_bytes: need n_clips >= 1 and 1 <= length < 2^30");
+    *bytes = adn::stoi_plan(n_clips, length).total;
+    return ADN_OK;
+}
+
+int adn_stoi(const float *est, const float *ref, const long *lengths, int n_clips, long length, void *workspace,
+             size_t workspace_bytes, float *out, void *stream)
+{
+    if (!est || !ref || !out) return fail(ADN_ERR_INVALID, "adn_stoi: null pointer");
+    size_t need = 0;
+    if (adn_stoi_workspace_bytes(n_clips, length, &need) != ADN_OK) return ADN_ERR_INVALID;
+    if (!workspace || workspace_bytes < need) return fail(ADN_ERR_WORKSPACE, "adn_stoi: workspace too small");
+    if (!aligned_to(workspace, 16)) return fail(ADN_ERR_INVALID, "adn_stoi: workspace must be 16-byte aligned");
+    hipError_t e = adn::launch_stoi(est, ref, lengths, n_clips, length, workspace, out, static_cast<hipStream_t>(stream));
+    if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_stoi: grid too large (n_clips x frames / 64 >= 2^31)");
+    if (e != hipSuccess) return fail_hip(e, "adn_stoi");
     return ADN_OK;
 }
 

@@ -569,6 +569,22 @@ constexpr int ADN_REVERB_MIN_RATE = 2000, ADN_REVERB_MAX_RATE = 128000;
 bool reverb_rate_ok(int sample_rate);
 hipError_t launch_reverb(const float *audio, int n_clips, int L, int sample_rate, float feedback, float damp, float wet1, float dry,
                          int clip, float *out, hipStream_t st);
+// Quality metrics (quality_kernels.hip; definitions in adn.h, "quality").  `lengths` (device, may be null) is read by the kernels.
+// adn_quality: fp64 partial sums per 8192-sample block, six per block.  adn_stoi: StoiPlan lays out the workspace for the row pitch
+// L -- nf_max frames and j_max compacted frames per clip at most, wgs workgroups of segments per clip -- in byte offsets.
+constexpr int ADN_SEG_FRAME_MIN = 16, ADN_SEG_FRAME_MAX = 8192;
+constexpr long ADN_QUALITY_MAX_LENGTH = 1L << 30;
+size_t quality_workspace_bytes(int n_clips, long L);
+hipError_t launch_quality(const float *est, const float *ref, const long *lengths, int n_clips, long L, int seg_frame,
+                          void *workspace, float *out, hipStream_t st);
+struct StoiPlan {
+    long nf_max, j_max;
+    int wgs;
+    size_t norm_off, idx_off, kept_off, env_off, rho_off, total;
+};
+StoiPlan stoi_plan(int n_clips, long L);
+hipError_t launch_stoi(const float *est, const float *ref, const long *lengths, int n_clips, long L, void *workspace, float *out,
+                       hipStream_t st);
 size_t perceptual_loss_workspace_floats(int n_clips, int F, int T);
 // LDS the finishing kernel needs for T frames (ADN_LOSS_MAX_LDS: 160 KiB per CU minus the kernel's static reduction scratch):
 // up to ADN_LOSS_LDS_T frames a clip's series and mel spectra are held on chip, longer clips keep the series in the workspace

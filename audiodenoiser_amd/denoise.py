@@ -6,7 +6,7 @@
     dn.denoise_file("noisy.wav", "clean.wav")
 
     python -m audiodenoiser_amd.denoise --model CKPT.pth IN OUT [--phase noisy|griffin_lim] [--window 256] [--overlap 32]
-                                        [--dtype f32|f16]
+                                        [--dtype f32|f16] [--reference CLEAN]
 
 The reference only ever feeds one fixed 257 x 188 spectrogram per clip to the network (``test.py:100-114``) and returns to
 audio through Griffin-Lim from a random phase (``test.py:29-48``).  This module joins the stages that exist on the device --
@@ -32,7 +32,9 @@ What is NOT claimed: parity of the STFT with librosa stays unpinned, as everywhe
 ``overlap_frames=32`` are design defaults; their audible quality is not validated (no trained checkpoint exists where this was
 written).  The result of overlapping windows differs from one forward over the whole spectrogram by design -- the network's
 receptive field is wider than the overlap -- which is why the single-window case is exact and the multi-window case is defined by
-the restatement.  The command line handles a folder file after file; pooling the windows of different files into one batch is out
+the restatement.  ``--reference`` (a clean wav, or a folder with the input folder's file names) prints, after each output is
+written, one JSON line with the four metrics of ``audiodenoiser_amd.metrics`` for the noisy input and for the denoised output
+against the reference; they measure this run, not the audible quality of a network.  The command line handles a folder file after file; pooling the windows of different files into one batch is out
 of scope.  There is no CPU path.
 """
 from __future__ import annotations
@@ -254,6 +256,23 @@ def _load_model(path, dtype, device):
     return model.to(device).eval().set_compute_dtype(dtype)
 
 
+def _report(src, dst, ref_path) -> str:
+    """One JSON line: the four metrics of the noisy input and of the denoised output against the clean reference, at the
+    file's rate, each pair cut to the shorter of the two (mono mixes)."""
+    import json
+    from .metrics import evaluate
+    ref, ref_rate = read_wav(ref_path, mono=True)
+    row = {"file": src, "reference": ref_path, "sample_rate": int(ref_rate)}
+    for key, path in (("noisy", src), ("denoised", dst)):
+        audio, rate = read_wav(path, mono=True)
+        if rate != ref_rate:
+            raise ValueError(f"--reference: {ref_path} is at {ref_rate} Hz, {path} at {rate} Hz")
+        n = min(len(audio), len(ref))
+        m = evaluate(audio[:n], ref[:n], sr=int(rate))
+        row[key] = {k: float(v[0]) for k, v in m.items()}
+    return json.dumps(row)
+
+
 def main(argv=None) -> int:
     import argparse
     ap = argparse.ArgumentParser(prog="python -m audiodenoiser_amd.denoise", description="Denoise a wav file or a folder of wav files.")
@@ -264,6 +283,8 @@ def main(argv=None) -> int:
     ap.add_argument("--window", type=int, default=256)
     ap.add_argument("--overlap", type=int, default=32)
     ap.add_argument("--dtype", choices=("f32", "f16"), default="f32")
+    ap.add_argument("--reference", metavar="CLEAN", default=None,
+                    help="the clean wav of IN (or a folder with IN's file names): print one JSON line of metrics per file")
     args = ap.parse_args(argv)
     dev = _lib.staging_device()
     dn = Denoiser(_load_model(args.model, args.dtype, dev), window_frames=args.window, overlap_frames=args.overlap, phase=args.phase)
@@ -275,6 +296,9 @@ def main(argv=None) -> int:
     for src, dst in jobs:
         n, rate = dn.denoise_file(src, dst)
         print(f"{src} -> {dst}: {n} samples at {rate} Hz")
+        if args.reference is not None:
+            ref = os.path.join(args.reference, os.path.basename(src)) if os.path.isdir(args.reference) else args.reference
+            print(_report(src, dst, ref))
     return 0
 
 

@@ -1,0 +1,152 @@
+"""Objective quality metrics on the device: SNR, SI-SDR, segmental SNR and STOI of an estimate against a clean reference.
+
+    from audiodenoiser_amd.metrics import evaluate
+    m = evaluate(denoised, clean, sr=8000)            # {"snr", "si_sdr", "seg_snr", "stoi"}: (N,) tensors, dB / STOI units
+    gain = m["si_sdr"] - evaluate(noisy, clean, sr=8000)["si_sdr"]
+
+The operators are ``adn_quality`` and ``adn_stoi`` (definitions: ``include/adn.h``, "quality"; float64 restatement:
+``tests/quality_ref.py``).  The library defines them itself -- STOI follows Taal et al. 2011 as the header states it and is
+unpinned against ``pystoi`` -- so the numbers compare runs of THIS package; nothing here is a claim about a trained network.
+
+Inputs are ``(L,)`` or ``(N, L)`` float32, est and ref of one shape.  Tensors on a ROCm device are used in place and the results
+stay there; numpy arrays are staged onto the current device and the results are still tensors (on that device).  There is no CPU
+path.  ``evaluate``'s ``lengths`` (``N`` integers, any array-like) gives every row its own length inside a padded batch: samples
+beyond it are never read, and the row's results are bit for bit those of the clip alone.  Work is enqueued on the current stream;
+workspaces are ``torch.empty`` per call, which torch's caching allocator serves from its per-stream pool (as in ``loss.py``).
+
+``stoi`` is defined at 10 kHz: audio at another rate is resampled with ``resample`` first (both signals, rows zeroed beyond their
+length -- the resampler zero-extends, so a row of a padded batch resamples exactly as it does alone), and the per-clip lengths
+become ``resample_length(len, sr, 10000)``.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from .resample import _resample_device, resample_length
+
+__all__ = ["snr", "si_sdr", "seg_snr", "stoi", "evaluate", "STOI_RATE"]
+
+STOI_RATE = 10000
+
+
+def _pair(est, ref, what):
+    """-> (est, ref) as contiguous (N, L) float32 tensors on one ROCm device, and whether the caller passed single clips."""
+    def one(a):
+        if isinstance(a, torch.Tensor):
+            if not a.is_cuda:
+                raise RuntimeError(f"{what}: a tensor must live on a ROCm device (no CPU path); pass numpy to have it staged")
+            if a.dtype != torch.float32:
+                raise TypeError(f"{what}: expected float32 audio")
+            return a
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(_lib.staging_device())
+    e, r = one(est), one(ref)
+    if e.shape != r.shape or e.dim() not in (1, 2) or e.device != r.device:
+        raise ValueError(f"{what}: est and ref must have one shape, (L,) or (N, L), on one device")
+    single = e.dim() == 1
+    e = (e[None] if single else e).contiguous()
+    r = (r[None] if single else r).contiguous()
+    if e.shape[0] < 1 or e.shape[1] < 1:
+        raise ValueError(f"{what}: need at least one clip of at least one sample")
+    return e, r, single
+
+
+def _host_lengths(lengths, n, length, what):
+    if lengths is None:
+        return None
+    v = lengths.detach().cpu().numpy() if isinstance(lengths, torch.Tensor) else np.asarray(lengths)
+    v = v.astype(np.int64).reshape(-1)
+    if v.shape[0] != n or (v < 0).any() or (v > length).any():
+        raise ValueError(f"{what}: lengths must be {n} integers in [0, {length}]")
+    return v
+
+
+def _quality(e, r, lens, seg_frame):
+    """adn_quality on (N, L) device tensors -> (N, 3)."""
+    n, length = e.shape
+    lib = _lib.load()
+    need = ctypes.c_size_t()
+    _lib.check(lib.adn_quality_workspace_bytes(n, length, ctypes.byref(need)), "adn_quality_workspace_bytes")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=e.device)
+    out = torch.empty((n, 3), dtype=torch.float32, device=e.device)
+    ld = None if lens is None else torch.from_numpy(lens).to(e.device)
+    with torch.cuda.device(e.device):
+        _lib.check(lib.adn_quality(e.data_ptr(), r.data_ptr(), None if ld is None else ld.data_ptr(), n, length, int(seg_frame),
+                                   ws.data_ptr(), ws.numel(), out.data_ptr(), torch.cuda.current_stream(e.device).cuda_stream),
+                   "adn_quality")
+    return out
+
+
+def _stoi_10k(e, r, lens):
+    """adn_stoi on (N, L) device tensors at 10 kHz -> (N,)."""
+    n, length = e.shape
+    lib = _lib.load()
+    need = ctypes.c_size_t()
+    _lib.check(lib.adn_stoi_workspace_bytes(n, length, ctypes.byref(need)), "adn_stoi_workspace_bytes")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=e.device)
+    out = torch.empty((n,), dtype=torch.float32, device=e.device)
+    ld = None if lens is None else torch.from_numpy(lens).to(e.device)
+    with torch.cuda.device(e.device):
+        _lib.check(lib.adn_stoi(e.data_ptr(), r.data_ptr(), None if ld is None else ld.data_ptr(), n, length, ws.data_ptr(),
+                                ws.numel(), out.data_ptr(), torch.cuda.current_stream(e.device).cuda_stream), "adn_stoi")
+    return out
+
+
+def _stoi(e, r, lens, sr):
+    sr = int(sr)
+    if sr == STOI_RATE:
+        return _stoi_10k(e, r, lens)
+    if lens is not None:                                   # zero beyond each row's length: the resampler zero-extends
+        keep = torch.arange(e.shape[1], device=e.device)[None] < torch.from_numpy(lens).to(e.device)[:, None]
+        e, r = torch.where(keep, e, 0.0), torch.where(keep, r, 0.0)
+        lens = np.array([resample_length(int(v), sr, STOI_RATE) if v > 0 else 0 for v in lens], dtype=np.int64)
+    return _stoi_10k(_resample_device(e, sr, STOI_RATE), _resample_device(r, sr, STOI_RATE), lens)
+
+
+def _seg_frame(sr, frame):
+    f = int(0.03 * int(sr)) if frame is None else int(frame)
+    if not 16 <= f <= 8192:
+        raise ValueError("seg_snr: the frame must hold 16 to 8192 samples (default int(0.03 * sr))")
+    return f
+
+
+def _finish(t, single):
+    return t[0] if single else t
+
+
+def snr(est, ref):
+    """``10 log10(sum ref^2 / sum (est - ref)^2)`` per clip, dB."""
+    e, r, single = _pair(est, ref, "snr")
+    return _finish(_quality(e, r, None, 240)[:, 0], single)
+
+
+def si_sdr(est, ref):
+    """Scale-invariant SDR per clip, dB: ref scaled by ``<est, ref> / <ref, ref>`` against what is left of est."""
+    e, r, single = _pair(est, ref, "si_sdr")
+    return _finish(_quality(e, r, None, 240)[:, 1], single)
+
+
+def seg_snr(est, ref, sr, frame=None):
+    """Mean over whole non-overlapping frames of ``frame`` samples (default ``int(0.03 * sr)``) of the frame SNR clamped to
+    [-10, 35] dB; NaN for a clip shorter than one frame."""
+    e, r, single = _pair(est, ref, "seg_snr")
+    return _finish(_quality(e, r, None, _seg_frame(sr, frame))[:, 2], single)
+
+
+def stoi(est, ref, sr):
+    """Short-time objective intelligibility per clip (``adn_stoi``), the audio resampled to 10 kHz when ``sr`` differs; NaN for
+    a clip that keeps fewer than 31 frames (about 0.4 s) after silent-frame removal."""
+    e, r, single = _pair(est, ref, "stoi")
+    return _finish(_stoi(e, r, None, sr), single)
+
+
+def evaluate(est, ref, sr, lengths=None):
+    """All four metrics of a batch: ``{"snr", "si_sdr", "seg_snr", "stoi"}`` -> ``(N,)`` float32 tensors on the device (``(N,)``
+    with N = 1 for a single clip)."""
+    e, r, _ = _pair(est, ref, "evaluate")
+    lens = _host_lengths(lengths, *e.shape, "evaluate")
+    q = _quality(e, r, lens, _seg_frame(sr, None))
+    return {"snr": q[:, 0], "si_sdr": q[:, 1], "seg_snr": q[:, 2], "stoi": _stoi(e, r, lens, sr)}

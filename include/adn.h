@@ -33,7 +33,7 @@
 
 #include <stddef.h>
 
-/* The 53 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 60 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -502,6 +502,67 @@ ADN_API int adn_stream_pool_push_rate(void *state, size_t state_bytes, int n_slo
 ADN_API int adn_stream_pool_emit_rate(void *rate_state, size_t rate_state_bytes, int n_slots, int max_history, int work_rate,
                                       const adn_stream_pool_rate_row *rows, int n_rows, const float *audio_in, long in_stride,
                                       float *out, long out_stride, void *stream);
+
+/* ---- quality: objective metrics of an estimate against a clean reference, clip by clip ------------------------------------------
+ * No reference counterpart (the reference judges by ear and by its training loss).  The library DEFINES the operators below; the
+ * float64 restatement is tests/quality_ref.py.  est, ref: device (n_clips, length) fp32, `length` the row pitch in samples.
+ * lengths: device array of n_clips `long`, or NULL = every clip is `length` long; it is read ON THE DEVICE (no host
+ * synchronisation), each value is taken as min(max(value, 0), length), and no sample at or beyond a clip's own length is read.
+ * Results are fp32, one row per clip.  Nothing is allocated and nothing blocks; no constant table is needed (a capture may hold a
+ * first call).  No atomics, one fixed order of summation laid out by sample position inside the clip: two calls are bit-identical,
+ * a clip's result is bit-identical whatever batch it sits in, and a row cut by `lengths` equals the same clip passed unpadded.
+ * Workspaces: 16-byte aligned (ADN_ERR_INVALID otherwise), ADN_ERR_WORKSPACE below the size function's bytes.
+ * Limits (ADN_ERR_INVALID before any launch): n_clips >= 1, 1 <= length < 2^30, launch grids < 2^31 workgroups, null est / ref / out.
+ *
+ * adn_quality: out (n_clips, 3) = {SNR, SI-SDR, segmental SNR} in dB.  With e = est, r = ref over the clip's own samples:
+ *   SNR     = 10 log10(Srr / Sdd),  Srr = sum r^2,  Sdd = sum (e - r)^2
+ *   SI-SDR  = 10 log10( sum (alpha r)^2 / sum (e - alpha r)^2 ),  alpha = Ser / Srr,  Ser = sum e r.  The residual sum is
+ *             accumulated from the per-sample differences in a second pass over the audio once alpha is known -- never as
+ *             sum e^2 - Ser^2 / Srr, which loses everything above about 60 dB in fp32.
+ *   segSNR  = mean over the floor(len / seg_frame) whole, non-overlapping frames of seg_frame samples of
+ *             clamp(10 log10((Srr_f + 1e-10) / (Sdd_f + 1e-10)), -10, 35);  16 <= seg_frame <= 8192 (the Python mirror's default is
+ *             int(0.03 * sample_rate)); a trailing partial frame is not counted; with no whole frame the result is NaN.
+ *   Accumulation: fp64 everywhere.  A sample is widened to fp64 first (products and differences of fp32 values are then exact),
+ *   a block of 8192 samples is summed by 256 lanes of 32 strided fma terms each and a fixed tree, a frame likewise by 64 lanes (16
+ *   below 64 samples); the block sums of a clip, alpha, the ratios and the logarithms are fp64, and each result is rounded to fp32
+ *   once.  The audio is read twice (four array reads); the segmental frames are summed in the first pass.
+ *   Degenerate inputs follow IEEE arithmetic: est == ref gives +inf for SNR and SI-SDR (any ratio x / 0, x > 0); a silent ref with
+ *   a non-zero error gives -inf for SNR and NaN for SI-SDR (alpha = 0 / 0); a clip of length 0 gives NaN three times.
+ *
+ * adn_stoi: out (n_clips,) = the short-time objective intelligibility measure of Taal, Hendriks, Heusdens and Jensen (2011), for
+ * audio ALREADY AT 10 kHz (the rate conversion is the caller's; the Python mirror uses adn_resample).  The definition below is
+ * this project's own statement of it and is UNPINNED against pystoi, which no machine of this project has.
+ *   Constants: frame 256, hop 128, FFT 512, 15 bands, segment N = 30, beta = -15 dB, dynamic range 40 dB;
+ *   window w = numpy.hanning(258)[1:-1] (256 values);  EPS = 2^-52.
+ *   1. Frames.  Start positions range(0, L - 256, 128) -- the bound is exclusive, so L = 256 + 128 k yields k frames, not k + 1.
+ *      x_i = w . ref[s_i : s_i + 256], and the same for est.
+ *   2. Silent-frame removal, decided on ref alone.  E_i = 20 log10(||x_i||_2 + EPS); frame i is kept when E_i > max_i E_i - 40.
+ *      idx[0..K) are the kept frames in order.
+ *   3. Compacted signals: the overlap-add of the kept windowed frames at hop 128, for ref and est:
+ *        c[n] = sum over j in {floor(n / 128) - 1, floor(n / 128)}, 0 <= j < K, of w[n - 128 j] . sig[128 idx[j] + n - 128 j],
+ *      of length 128 (K + 1).
+ *   4. Spectra of the compacted signals.  The same framing rule applied to c gives exactly J = K - 1 frames; each is windowed by w
+ *      again, zero padded to 512 and takes a real FFT to 257 bins; |X|^2 is kept.
+ *   5. One-third-octave envelopes.  X_tob[b, j] = sqrt(sum over k in [lo_b, hi_b) of |X[k, j]|^2), and the same for est.  The bin
+ *      ranges follow from f = linspace(0, 10000, 513)[:257], centres 150 . 2^(b/3), edges 150 . 2^((2b -+ 1)/6), nearest bin by
+ *      squared distance:  (7,9) (9,11) (11,14) (14,17) (17,22) (22,27) (27,34) (34,43) (43,55) (55,69) (69,87) (87,109) (109,138)
+ *      (138,174) (174,219).
+ *   6. Per segment and band.  For every m = 30 ... J inclusive and every band, over the 30 frames [m - 30, m), x of ref, y of est:
+ *      a = ||x|| / (||y|| + EPS);  y' = min(a . y, x . (1 + 10^(15/20)));  the mean of x and of y' over the 30 frames is removed;
+ *      each is divided by its norm plus EPS;  rho = sum x^ y^'.
+ *   7. Result.  d = sum rho / (15 . (J - 29)).  If J < 30, that is K < 31, d = NaN -- pystoi returns 1e-5 with a warning there.
+ *   Arithmetic: the window is computed in fp64 and rounded once to fp32; steps 1-5 are fp32 (frame norms: four fma terms per lane
+ *   and a wave tree; the 512-point transform as 256 packed complex points on the library's Stockham passes; band sums in ascending
+ *   bin order); the comparison of step 2 is made on the norms, n_i + EPS > (n_max + EPS) / 100, in fp64; steps 6 and 7 are fp64,
+ *   the correlations of a clip added in a fixed order.  A frame whose E_i lies within rounding of the threshold may fall on either
+ *   side of it; everything else is continuous in the input.  The compacted signals are never stored: each of their frames is
+ *   built from the source frames idx[j - 1], idx[j], idx[j + 1], and only the 2 x 15 envelopes per frame reach the workspace. */
+ADN_API int adn_quality_workspace_bytes(int n_clips, long length, size_t *bytes);
+ADN_API int adn_quality(const float *est, const float *ref, const long *lengths, int n_clips, long length, int seg_frame,
+                        void *workspace, size_t workspace_bytes, float *out, void *stream);
+ADN_API int adn_stoi_workspace_bytes(int n_clips, long length, size_t *bytes);
+ADN_API int adn_stoi(const float *est, const float *ref, const long *lengths, int n_clips, long length, void *workspace,
+                     size_t workspace_bytes, float *out, void *stream);
 
 /* ---- environment switches -------------------------------------------------------------------------------------------------
  * Read ONCE, when a U-Net handle is created (never per call).  None is needed in production: the defaults are the measured best
