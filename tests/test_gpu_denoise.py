@@ -16,6 +16,8 @@ Bounds (derived, not tuned; eps = 2^-24):
   last `hop` samples, where the window sum-of-squares falls from 1.5 to as little as 0.26, that figure times 1.5 / 0.26: 6e-5.
 * U-Net: the tree's TOL = 1e-4 of max |ref| in fp32, 1e-2 in fp16 (test_gpu_parity.py).
 Measured on the MI355X: the windows use up to 0.94 of their bound, the stitch 0.67.
+The cases here are n_fft 256, 512 and 1024 at hop = n_fft / 4; the other sizes, the hops that do not divide n_fft and bounds per
+frame and per sample (not of the maximum) are tests/test_gpu_spectral_grid.py's.
 """
 import os
 import subprocess

@@ -13,6 +13,8 @@ Bounds (the tree's own, none tuned here):
   documented per-batch-size bound, 2e-5 of the maximum in fp32 (UNet.set_batch_invariant).
 Measured on the MI355X, worst over all cases: windows 2.1e-7 of the maximum, round trip 3.6e-7 (body) / 2.4e-7 (last hop samples)
 absolute, end to end 4.6e-6 (fp32) / 2.0e-3 (fp16) of the maximum, splits without batch invariance 2.0e-6 of the maximum.
+The plans here are n_fft 64, 256 and 512 at hop = n_fft / 4; the other sizes, a hop that does not divide n_fft and bounds per frame
+and per sample (not of the maximum) are tests/test_gpu_spectral_grid.py's.
 """
 import os
 import sys

@@ -17,8 +17,9 @@ group to group inside a clip; and, for the fitted STFT at n_fft 512 and 1024, 21
 launches min(items, workgroups the card holds) workgroups; the library does not report that grid, so the line gives the items
 and the CUs, and `more_items_than_8_per_cu` says whether the items exceed even 8 workgroups on every CU (the kernel's
 registers allow 3): then some workgroup must walk from one clip into the next.  Not covered here: fitted windows wider than
-96 frames and the reference's 513 x 256 at scale -- tests/test_gpu_parity.py has those.  This is the only place resynth and
-the stream kernels run at n_fft 2048 and 4096."""
+96 frames and the reference's 513 x 256 at scale -- tests/test_gpu_parity.py has those.  A digest only says that a value has
+not moved: whether resynth and the stream kernels are RIGHT at n_fft 2048 and 4096, and at every other size, is checked against
+float64 by tests/test_gpu_spectral_grid.py."""
 import hashlib
 import os
 import sys
