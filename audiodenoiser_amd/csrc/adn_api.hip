@@ -471,6 +471,41 @@ int adn_denoise_resynth(const float *y, const float *spec, int n_clips, long len
     return ADN_OK;
 }
 
+/* ---- spectral baseline: noise tracking + Wiener gain (adn.h, "baseline") ----------------------------------------- */
+int adn_spectral_gain(const float *spec, int n_clips, int n_frames, int n_bins, const adn_spectral_params *params,
+                      const float *state_in, float *state_out, float *out, int width, int col0, void *stream)
+{
+    if (!spec || !out) return fail(ADN_ERR_INVALID, "adn_spectral_gain: null pointer");
+    if (n_clips < 1 || n_frames < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, "adn_spectral_gain: n_clips, n_frames and n_bins must be >= 1");
+    if (col0 < 0 || width < 1 || (long)col0 + n_frames > width)
+        return fail(ADN_ERR_INVALID, "adn_spectral_gain: need col0 >= 0 and col0 + n_frames <= width");
+    const adn_spectral_params defaults = {0.7f, 0.96f, 0.998f, 0.98f, 0.1f, 1.0f};
+    const adn_spectral_params p = params ? *params : defaults;
+    // written so that a NaN fails every test
+    if (!(p.smooth >= 0.f && p.smooth < 1.f) || !(p.beta >= 0.f && p.beta < 1.f) || !(p.alpha >= 0.f && p.alpha < 1.f))
+        return fail(ADN_ERR_INVALID, "adn_spectral_gain: need 0 <= smooth, beta, alpha < 1");
+    if (!(p.gamma > 0.f && p.gamma < 1.f)) return fail(ADN_ERR_INVALID, "adn_spectral_gain: need 0 < gamma < 1");
+    if (!(p.gain_floor > 0.f && p.gain_floor <= 1.f)) return fail(ADN_ERR_INVALID, "adn_spectral_gain: need 0 < gain_floor <= 1");
+    if (!(p.bias > 0.f && p.bias <= 100.f)) return fail(ADN_ERR_INVALID, "adn_spectral_gain: need 0 < bias <= 100");
+    if (!aligned_to(spec, 8) || !aligned_to(out, 4) || !aligned_to(state_in, 4) || !aligned_to(state_out, 4))
+        return fail(ADN_ERR_INVALID, "adn_spectral_gain: spec must be 8-byte aligned, out and the states 4-byte aligned");
+    adn::SpectralConsts k;
+    k.smooth = p.smooth;
+    k.one_minus_smooth = 1.f - p.smooth;
+    k.beta = p.beta;
+    k.gamma = p.gamma;
+    k.growth = (1.f - p.gamma) / (1.f - p.beta);
+    k.alpha = p.alpha;
+    k.one_minus_alpha = 1.f - p.alpha;
+    k.gain_floor = p.gain_floor;
+    k.bias = p.bias;
+    hipError_t e = adn::launch_spectral_gain(spec, n_clips, n_frames, n_bins, k, state_in, state_out, out, width, col0,
+                                             static_cast<hipStream_t>(stream));
+    if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_spectral_gain: grid too large (n_clips x ceil(n_bins / 64) >= 2^31)");
+    ADN_LAUNCH(e, "adn_spectral_gain");
+    return ADN_OK;
+}
+
 /* ---- streaming denoiser: plan, state, analysis, emit (adn.h, "stream") ------------------------------------------- */
 static const char *stream_plan_text = ": need a power-of-two n_fft in [64, 4096], 1 <= hop <= n_fft / 4, window >= 16, block >= 1, "
                                       "lookahead >= 0, block + lookahead <= window, n_streams >= 1 and 1 <= max_steps <= 65536";

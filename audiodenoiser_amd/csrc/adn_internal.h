@@ -438,6 +438,14 @@ hipError_t launch_denoise_stitch(const float *y, int n_clips, int F, const Denoi
                                  hipStream_t st);
 hipError_t launch_denoise_resynth(const float *y, const void *spec, int n_clips, long L, int n_fft, int hop,
                                   const DenoiseGeom &g, float *audio, hipStream_t st);
+// Spectral baseline (baseline_kernels.hip; adn.h, "baseline").  SpectralConsts: the six parameters and the three constants derived
+// from them once per call on the host, in fp32: 1 - smooth, (1 - gamma) / (1 - beta), 1 - alpha.  spec frame-major float2, out
+// bin-major [clip][F][width] written at columns [col0, col0 + T), state [clip][3][F] (P, Pmin, S; NULL in = fresh, NULL out = dropped).
+struct SpectralConsts {
+    float smooth, one_minus_smooth, beta, gamma, growth, alpha, one_minus_alpha, gain_floor, bias;
+};
+hipError_t launch_spectral_gain(const void *spec, int n_clips, int T, int F, const SpectralConsts &k, const float *state_in,
+                                float *state_out, float *out, int width, int col0, hipStream_t st);
 // Streaming denoiser (stream_kernels.hip; adn.h, "stream").  StreamGeom: the plan and the layout of the state buffer of one batch
 // of streams, in floats (sections X, mag, hist, tail; `total` floats in all); stream_geom is false outside the limits of adn.h.
 // StreamCall: what one call of n_steps steps from step `first` covers, derived from the step index alone (stream_call):

@@ -33,7 +33,7 @@
 
 #include <stddef.h>
 
-/* The 60 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 61 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -563,6 +563,53 @@ ADN_API int adn_quality(const float *est, const float *ref, const long *lengths,
 ADN_API int adn_stoi_workspace_bytes(int n_clips, long length, size_t *bytes);
 ADN_API int adn_stoi(const float *est, const float *ref, const long *lengths, int n_clips, long length, void *workspace,
                      size_t workspace_bytes, float *out, void *stream);
+
+/* ---- baseline: a classical spectral denoiser that needs no weights ---------------------------------------------------------------
+ * No reference counterpart and no checkpoint.  The library DEFINES the operator below (float64 restatement: tests/baseline_ref.py);
+ * it is UNPINNED against any package.  The recursions are Doblinger's continuous minimum tracking (1995) for the noise power,
+ * Ephraim and Malah's decision-directed a-priori SNR (1984) and a Wiener gain with a floor.  It is causal and carries three floats
+ * per bin.  Its place: real denoised audio without a trained network, and the figure a trained network has to beat.
+ * Not validated: the defaults are the values of the host prototype; they were not tuned by ear.
+ *
+ * Every (clip, bin) row is independent.  Over its frames t = 0 ... T-1, in fp32, with X the row's complex values:
+ *   p_t  = fmaf(re, re, im * im)                      (the |X|^2 of rule 2 of "denoise", before the square root)
+ *   first frame of a row:   P_t = p_t,  Pmin_t = p_t,  S_{t-1} = 0
+ *   otherwise:              P_t    = a_s P_{t-1} + (1 - a_s) p_t
+ *                           Pmin_t = Pmin_{t-1} < P_t ?  g Pmin_{t-1} + ((1 - g) / (1 - b)) (P_t - b P_{t-1})  :  P_t
+ *   N_t  = max(bias Pmin_t, 1e-30)
+ *   xi_t = (alpha S_{t-1}) / N_t + (1 - alpha) max(p_t / N_t - 1, 0)
+ *   G_t  = max(xi_t / (1 + xi_t), g_min)
+ *   M_t  = G_t sqrtf(p_t)                             (the output magnitude)
+ *   S_t  = (G_t G_t) p_t
+ * max(x, c) is `x < c ? c : x`: a NaN x stays NaN.  The parameters are the fp32 values of the struct; 1 - a_s, (1 - g) / (1 - b)
+ * and 1 - alpha are computed from them once, in fp32.  Divisions and the square root are correctly rounded.
+ * Parameters (adn_spectral_params; NULL = the defaults): smooth a_s 0.7, beta b 0.96, gamma g 0.998, alpha 0.98, gain_floor g_min
+ * 0.1, bias 1.0.  Legal (ADN_ERR_INVALID otherwise, nothing is launched; a NaN is illegal): 0 <= smooth, beta, alpha < 1;
+ * 0 < gamma < 1; 0 < gain_floor <= 1; 0 < bias <= 100.
+ * Non-finite input: a non-finite p_t poisons its own (clip, bin) row from that frame on (NaN magnitudes, NaN state), and nothing
+ * else.  An all-zero row gives zeros.
+ *
+ * What is pinned.  The result is bounded against the float64 restatement (tests/test_gpu_baseline.py: per clip
+ * max |M - M64| <= 4 FLOOR max M64, FLOOR the error of the same statements run in fp32 on the host); it is NOT pinned bit for bit to
+ * numpy.  Two things are pinned bit for bit: the result does not depend on how a row's frames were cut into calls (the state
+ * carried from call to call), and it does not depend on which batch the clip is in.  Every frame goes through one step, compiled
+ * with fp contraction off.  Deterministic: no atomics, two calls are bit-identical.
+ *
+ * Layouts: spec is frame-major (n_clips, n_frames, n_bins, 2) fp32 as adn_stft_complex writes it (8-byte aligned).  out is
+ * (n_clips, 1, n_bins, width) fp32, the network-output layout adn_denoise_resynth reads: the call writes columns
+ * [col0, col0 + n_frames) of every row and not one byte else -- zeroing padding columns is the caller's job.  State:
+ * (n_clips, 3, n_bins) fp32, the rows P, Pmin, S of the last frame.  state_in NULL: every row starts fresh; a row whose P is
+ * negative starts fresh as well, so one batch can hold clips that start and clips that continue.  state_out may be NULL (the
+ * state is dropped) and may equal state_in (each row is read before it is written, by the lane that writes it); otherwise spec,
+ * out and the states may not overlap.
+ * Cost: one launch, n_clips x ceil(n_bins / 64) waves that each walk their frames in order; 12 n_clips n_frames n_bins bytes.  No
+ * workspace, no atomics, no constant table (a capture may hold a first call); nothing blocks or allocates.
+ * Limits (ADN_ERR_INVALID before any launch): n_clips, n_frames, n_bins >= 1; col0 >= 0, col0 + n_frames <= width; launch grid
+ * n_clips x ceil(n_bins / 64) < 2^31 workgroups.  Element offsets are 64-bit.
+ * Not here: a bin-major magnitude input (what the stream classes would feed), log-MMSE gains, any phase but the noisy one. */
+typedef struct { float smooth, beta, gamma, alpha, gain_floor, bias; } adn_spectral_params;
+ADN_API int adn_spectral_gain(const float *spec, int n_clips, int n_frames, int n_bins, const adn_spectral_params *params,
+                              const float *state_in, float *state_out, float *out, int width, int col0, void *stream);
 
 /* ---- environment switches -------------------------------------------------------------------------------------------------
  * Read ONCE, when a U-Net handle is created (never per call).  None is needed in production: the defaults are the measured best

@@ -1,0 +1,145 @@
+#!/usr/bin/env python3
+"""Device time of the spectral baseline (adn_spectral_gain; SpectralDenoiser.denoise stage by stage), its SI-SDR figures on the
+device, and the float32 host loop of the restatement -- the only other form of the operator that exists.  Buffers are allocated
+once; device events around a window of calls (at least `--window-ms` long, sized from a calibration call) after a warm-up, median
+of `--groups` windows.  One JSON line per measurement:
+
+    adn_spectral_gain   the C entry point on the device's own STFT; `bound_ms` = its 12 n T F bytes (8 read, 4 written) at 8 TB/s,
+                        `share_of_bound`
+    stages              adn_stft_complex, adn_spectral_gain (into the zeroed buffer, the memset included), adn_denoise_resynth, and
+                        SpectralDenoiser.denoise as a whole (device tensor in, device tensor out); `audio_s_per_s`
+    host_float32_loop   tests/baseline_ref.py in float32 (numpy, one clip), scaled to the case's clip count
+    si_sdr              noisy -> denoised on the 0 / 8 / 15 dB white mixes of tests/baseline_cases.py, by metrics.evaluate
+
+Workloads: one hour of 8 kHz audio as 60 clips of 60 s, and one clip of 3 s.
+
+    python tools/bench_baseline.py [--cases 0,1]
+
+Kernel-level numbers: rocprofv3 --kernel-trace --stats -- python tools/bench_baseline.py --cases 0 (a run of its own).
+"""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+HBM_BPS = 8.0e12
+RATE = 8000
+N_FFT, HOP = 512, 128
+CASES = (("one_hour", 60, 60 * RATE), ("one_clip_3s", 1, 3 * RATE))
+
+
+def time_ms(fn, warmup, groups, window_ms):
+    import torch
+    for _ in range(warmup):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    fn()
+    e1.record()
+    torch.cuda.synchronize()
+    steps = max(3, int(math.ceil(window_ms / max(e0.elapsed_time(e1), 1e-3))))
+    out = []
+    for _ in range(groups):
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(steps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) / steps)
+    return {"ms": round(statistics.median(out), 4), "ms_min": round(min(out), 4), "ms_max": round(max(out), 4), "steps_per_window": steps}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cases", default="0,1", help="indices into CASES")
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--groups", type=int, default=5)
+    ap.add_argument("--window-ms", type=float, default=300.0)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    import baseline_cases as bc
+    import baseline_ref as br
+    from audiodenoiser_amd import _lib
+    from audiodenoiser_amd.baseline import SpectralDenoiser, spectral_gain
+    from audiodenoiser_amd.griffin_lim import stft_complex
+    from audiodenoiser_amd.metrics import evaluate
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_baseline: no ROCm device is visible; nothing is measured without one")
+    L = _lib.load()
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(L.adn_prepare(0, N_FFT), "adn_prepare")
+    dn = SpectralDenoiser(dev)
+
+    for snr in (0.0, 8.0, 15.0):
+        noisy, clean = bc.quality_case(snr)
+        nd, cd = torch.from_numpy(noisy).to(dev), torch.from_numpy(clean).to(dev)
+        out = dn.denoise(nd)
+        before, after = float(evaluate(nd, cd, sr=RATE)["si_sdr"][0]), float(evaluate(out, cd, sr=RATE)["si_sdr"][0])
+        want = br.si_sdr(br.denoise(noisy.astype(np.float64), N_FFT, HOP), clean)
+        print(json.dumps({"what": "si_sdr", "mix_db": snr, "noisy": round(before, 3), "denoised": round(after, 3),
+                          "restatement_float64": round(float(want), 3)}), flush=True)
+
+    for k in (int(v) for v in args.cases.split(",")):
+        name, n, length = CASES[k]
+        # the burst signal + white noise at 8 dB, one 60 s (or 3 s) mix per clip seed; random data, not zeros
+        x = torch.from_numpy(np.stack([bc.white_mix(length, 8.0, 100 + c)[0] for c in range(n)])).to(dev)
+        t, f = 1 + length // HOP, N_FFT // 2 + 1
+        spec = stft_complex(x, N_FFT, HOP)
+        s = torch.view_as_real(spec)
+        y = torch.zeros((n, 1, f, max(t, 16)), device=dev)
+        state = torch.empty((n, 3, f), device=dev)
+        audio = torch.empty((n, length), device=dev)
+
+        def gain():
+            _lib.check(L.adn_spectral_gain(s.data_ptr(), n, t, f, None, None, state.data_ptr(), y.data_ptr(), int(y.shape[3]), 0, st),
+                       "adn_spectral_gain")
+        row = time_ms(gain, args.warmup, args.groups, args.window_ms)
+        nbytes = 12 * n * t * f
+        bound = nbytes / HBM_BPS * 1e3
+        print(json.dumps({"case": name, "what": "adn_spectral_gain", "shape": [n, t, f], **row, "bytes": nbytes,
+                          "GBps": round(nbytes / (row["ms"] * 1e-3) / 1e9, 1), "bound": "memory (12 n T F bytes at 8 TB/s)",
+                          "bound_ms": round(bound, 4), "share_of_bound": round(bound / row["ms"], 4),
+                          "waves": n * -(-f // 64), "us_per_frame": round(row["ms"] * 1e3 / t, 4)}), flush=True)
+
+        def stft():
+            _lib.check(L.adn_stft_complex(x.data_ptr(), n, length, N_FFT, HOP, s.data_ptr(), st), "adn_stft_complex")
+
+        def gain_zeroed():
+            y.zero_()
+            gain()
+
+        def resynth():
+            _lib.check(L.adn_denoise_resynth(y.data_ptr(), s.data_ptr(), n, length, N_FFT, HOP, int(y.shape[3]), 0, audio.data_ptr(), st),
+                       "adn_denoise_resynth")
+        stages = {"adn_stft_complex": time_ms(stft, args.warmup, args.groups, args.window_ms)["ms"],
+                  "zero + adn_spectral_gain": time_ms(gain_zeroed, args.warmup, args.groups, args.window_ms)["ms"],
+                  "adn_denoise_resynth": time_ms(resynth, args.warmup, args.groups, args.window_ms)["ms"]}
+        whole = time_ms(lambda: dn.denoise(x), args.warmup, args.groups, args.window_ms)
+        print(json.dumps({"case": name, "what": "stages", "shape": [n, length], "stages_ms": stages, "denoise": whole,
+                          "audio_s_per_s": round(n * length / RATE / (whole["ms"] * 1e-3), 1)}), flush=True)
+        assert torch.equal(dn.denoise(x), audio)
+
+        host_spec = spec[0].cpu().numpy()
+        t0 = time.perf_counter()
+        m32, _ = br.spectral_gain(host_spec, dtype=np.float32)
+        host_ms = (time.perf_counter() - t0) * 1e3
+        err = float(np.abs(y[0, 0, :, :t].cpu().numpy().astype(np.float64) - m32).max() / m32.max())
+        print(json.dumps({"case": name, "what": "host_float32_loop", "one_clip_ms": round(host_ms, 1), "all_clips_ms": round(host_ms * n, 1),
+                          "max_rel_diff_device_vs_host_float32": err}), flush=True)
+        del x, spec, s, y, audio
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
