@@ -8,7 +8,8 @@ __version__ = "0.1.0"
 __all__ = ["UNet", "SpectrogramDataset", "WavToSpecDataset", "audio_to_magnitude_spectrogram",
            "audio_to_spectrogram", "stft_magnitude", "per_clip_l1", "CombinedPerceptualLoss", "NoiseMixDataset",
            "resample_length", "mix_snr", "load_audio", "StreamResampler", "Denoiser", "StreamDenoiser", "StreamPool", "ReverbSettings",
-           "snr", "si_sdr", "seg_snr", "stoi", "evaluate", "SpectralDenoiser", "SpectralParams"]
+           "snr", "si_sdr", "seg_snr", "stoi", "evaluate", "SpectralDenoiser", "SpectralParams",
+           "StreamSpectralDenoiser", "SpectralStreamPool", "spectral_gain_windows"]
 # (resample / reverb themselves: audiodenoiser_amd.resample.resample, audiodenoiser_amd.reverb.reverb -- the modules own the names)
 
 
@@ -31,7 +32,7 @@ def __getattr__(name):
     if name == "Denoiser":
         import importlib
         return importlib.import_module(".denoise", __name__).Denoiser
-    if name in ("SpectralDenoiser", "SpectralParams"):
+    if name in ("SpectralDenoiser", "SpectralParams", "StreamSpectralDenoiser", "SpectralStreamPool", "spectral_gain_windows"):
         import importlib
         return getattr(importlib.import_module(".baseline", __name__), name)
     if name in ("StreamDenoiser", "StreamPool"):

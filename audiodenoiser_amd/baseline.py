@@ -5,7 +5,12 @@
     clean = dn.denoise(noisy, sr=44100)                # (L,) or (N, L); numpy -> numpy, device tensor -> device tensor
     dn.denoise_file("noisy.wav", "clean.wav")
 
+    sd = StreamSpectralDenoiser()                      # the same operator on audio that is still arriving: a StreamDenoiser
+    out = sd.push(block); out = sd.flush()             # without a network, 112 ms behind the feed at the defaults
+    pool = SpectralStreamPool(max_streams=64)          # a StreamPool of such feeds: open / push / close / step
+
     python -m audiodenoiser_amd.baseline IN OUT [--reference CLEAN] [--bias 1.0] [--gain-floor 0.1]
+    python -m audiodenoiser_amd.baseline IN OUT --live [--chunk 1024] [--block 4] [--reference CLEAN]
 
 The operator is DEFINED in ``include/adn.h`` ("baseline"; float64 restatement: ``tests/baseline_ref.py``) and is unpinned against
 any package: Doblinger's continuous minimum tracking for the noise power, the decision-directed a-priori SNR of Ephraim and Malah,
@@ -19,9 +24,16 @@ network has to beat in the ``--reference`` report.  ``SpectralDenoiser`` is ``De
 
 ``denoise``, ``denoise_file``, the rate handling and the every-channel-a-clip rule are ``Denoiser``'s, unchanged.
 
-What is NOT here: streaming (the state layout and the per-row fresh-start sentinel are there for it; ``StreamDenoiser`` /
-``StreamPool`` would need a bin-major magnitude input form of the kernel), Griffin-Lim phase, log-MMSE gains, any tuning of the
-defaults by ear.  There is no CPU path.
+Streaming: ``adn_spectral_gain_windows`` (``spectral_gain_windows``) is the same operator in its magnitude form (``adn.h``, "The
+magnitude form": ``X = m + 0i`` through the same one step) on the bin-major windows the stream kernels write and read, in place
+on the ``block_frames`` columns a step keeps, with the three floats per bin carried in a state the caller owns.
+``StreamSpectralDenoiser`` is ``StreamDenoiser`` and ``SpectralStreamPool`` is ``StreamPool`` with that call in the network's
+place; everything those classes claim about cuts into pushes, neighbours, rates and slot reuse holds bit for bit, since the
+gain is a function of a row's own frames in order.  A stream's result is NOT bit-equal to ``SpectralDenoiser``'s on the same
+audio: the stream hands over ``|X| = sqrtf(p)`` and ``sqrtf(p)^2 != p`` in the last bits (the float64 restatements agree to 4e-16).
+
+What is NOT here: Griffin-Lim phase, log-MMSE gains, any tuning of the defaults by ear (``block_frames = 4`` included).  There is
+no CPU path.
 """
 from __future__ import annotations
 
@@ -34,8 +46,12 @@ import torch
 from . import _lib
 from .denoise import Denoiser, _report, _stream
 from .griffin_lim import stft_complex
+from .stream import PoolBook, StreamDenoiser, StreamPool, _check_stream_args
 
-__all__ = ["SpectralParams", "spectral_gain", "SpectralDenoiser"]
+__all__ = ["SpectralParams", "spectral_gain", "SpectralDenoiser", "spectral_gain_windows", "StreamSpectralDenoiser",
+           "SpectralStreamPool"]
+
+SPECTRAL_MAX_ROWS = 256      # ADN_SPECTRAL_MAX_ROWS of include/adn.h: the rows of one call that names its slots
 
 
 @dataclasses.dataclass(frozen=True)
@@ -147,6 +163,145 @@ class SpectralDenoiser(Denoiser):
         return out
 
 
+def spectral_gain_windows(windows: torch.Tensor, state: torch.Tensor, col0: int, n_cols: int, n_steps: int = 1,
+                          params: SpectralParams = None, rows=None, out: torch.Tensor = None) -> torch.Tensor:
+    """``adn_spectral_gain_windows`` on the current stream.  ``windows``: contiguous float32 ``(n_rows * n_steps, 1, F, W)`` on a
+    ROCm device, a row's steps consecutive (what ``StreamDenoiser.analyze`` / ``StreamPool.analyze`` return).  Columns
+    ``[col0, col0 + n_cols)`` of every step are a row's frames in order; their gained magnitudes go to the same columns of ``out``
+    and nothing else is written: ``out=None`` allocates a buffer (its other columns hold nothing), ``out=windows`` runs in place.
+    ``state``: contiguous float32 ``(n_slots, 3, F)`` there, updated IN PLACE (rows ``P``, ``Pmin``, ``S``; a negative ``P``
+    starts fresh).  ``rows=None``: row i uses slot i; otherwise ``(slot, fresh)`` per row, at most 256, no slot twice, and a row
+    with ``fresh`` true starts fresh whatever its slot holds.  Returns ``out``."""
+    if (not isinstance(windows, torch.Tensor) or not windows.is_cuda or windows.dtype != torch.float32 or windows.dim() != 4
+            or windows.shape[1] != 1 or not windows.is_contiguous()):
+        raise ValueError("spectral_gain_windows: expected a contiguous (n_rows * n_steps, 1, n_bins, window) float32 tensor on a ROCm device")
+    nw, _, f, w = windows.shape
+    if not (isinstance(n_steps, int) and n_steps >= 1) or nw < 1 or nw % n_steps or f < 1 or w < 1:
+        raise ValueError("spectral_gain_windows: need n_steps >= 1 dividing the number of windows, and at least one row, bin and frame")
+    if not (isinstance(col0, int) and isinstance(n_cols, int) and col0 >= 0 and n_cols >= 1 and col0 + n_cols <= w):
+        raise ValueError("spectral_gain_windows: need col0 >= 0, n_cols >= 1 and col0 + n_cols <= window")
+    n_rows, dev = nw // n_steps, windows.device
+    if (not isinstance(state, torch.Tensor) or not state.is_cuda or state.device != dev or state.dtype != torch.float32
+            or state.dim() != 3 or tuple(state.shape[1:]) != (3, f) or state.shape[0] < 1 or not state.is_contiguous()):
+        raise ValueError("spectral_gain_windows: state must be a contiguous (n_slots, 3, n_bins) float32 tensor on windows' device")
+    if out is None:
+        out = torch.empty((nw, 1, f, w), dtype=torch.float32, device=dev)
+    elif (not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != dev or out.dtype != torch.float32
+          or out.shape != windows.shape or not out.is_contiguous()):
+        raise ValueError("spectral_gain_windows: out must be a contiguous float32 tensor of windows' shape on its device")
+    table = None
+    if rows is not None:
+        if len(rows) != n_rows:
+            raise ValueError("spectral_gain_windows: rows must name a (slot, fresh) for each of the n_rows rows")
+        # the table as the 2 n_rows ints it is (adn_spectral_row = {int slot; int fresh;}): a tick builds one per call
+        table = (ctypes.c_int * (2 * n_rows))(*[v for slot, fresh in rows for v in (int(slot), 1 if fresh else 0)])
+    p = ctypes.byref(params.to_struct()) if params is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().adn_spectral_gain_windows(windows.data_ptr(), out.data_ptr(), n_rows, n_steps, f, w, col0, n_cols, p,
+                                                         state.data_ptr(), int(state.shape[0]), table, _stream(dev)),
+                   "adn_spectral_gain_windows")
+    return out
+
+
+def _spectral_device(who, device, params):
+    if params is not None and not isinstance(params, SpectralParams):
+        raise TypeError(f"{who}: params must be a SpectralParams")
+    dev = _lib.staging_device() if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"{who}: the device must be a ROCm device; there is no CPU path")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
+class StreamSpectralDenoiser(StreamDenoiser):
+    """``StreamDenoiser`` with the spectral baseline in the network's place: no model, noisy phase only, the same surface --
+    ``push``, ``flush``, ``reset``, ``received``, ``emitted``, ``latency_samples``, ``analyze``, ``emit``, ``input_rate``.
+
+    The operator is causal, so ``lookahead_frames`` is 0 and ``window_frames = max(16, block_frames)`` is only the carrier the
+    stream geometry needs: each run of steps calls ``adn_spectral_gain_windows`` in place on the analysed windows, on the
+    ``block_frames`` columns ``adn_stream_emit`` reads, and the gain's three floats per bin live in ``(n_streams, 3, F)`` on the
+    device (``reset`` fills it with the fresh-start sentinel).  ``block_frames = 4`` gives a latency of 896 samples, 112 ms at
+    8 kHz; it is a design value and has not been tuned by ear."""
+
+    def __init__(self, device=None, n_streams: int = 1, sample_rate: int = 8000, n_fft: int = 512, hop_length: int = 128,
+                 block_frames: int = 4, params: SpectralParams = None, input_rate=None):
+        window = max(16, block_frames) if isinstance(block_frames, int) else 16
+        _check_stream_args("StreamSpectralDenoiser", n_streams, sample_rate, n_fft, hop_length, window, block_frames, 0, 64, input_rate)
+        dev = _spectral_device("StreamSpectralDenoiser", device, params)
+        self.model = None
+        self.params = SpectralParams() if params is None else params
+        self._gain_state = torch.empty((n_streams, 3, n_fft // 2 + 1), dtype=torch.float32, device=dev)
+        self._setup(dev, n_streams, sample_rate, n_fft, hop_length, window, block_frames, 0, 64, input_rate)
+
+    def reset(self):
+        """Forget the running stream, the noise estimate included: the object is ready for a new one."""
+        super().reset()
+        self._gain_state.fill_(-1.0)
+
+    def network(self, x):
+        raise RuntimeError("StreamSpectralDenoiser: there is no network; the gain runs between analyze and emit (spectral_gain_windows)")
+
+    def _net(self, x: torch.Tensor, first_step: int, n_steps: int) -> torch.Tensor:
+        w, b = self.window_frames, self.block_frames
+        return spectral_gain_windows(x, self._gain_state, w - b, b, n_steps, self.params, None, x)
+
+
+class SpectralStreamPool(StreamPool):
+    """``StreamPool`` with the spectral baseline in the network's place: ``open``, ``push``, ``push_many``, ``close``, ``step``,
+    ``drain``, ``room``, ``received`` and the rates are the parent's.  A tick calls ``adn_spectral_gain_windows`` once per group of
+    up to 256 rows, in place on the analysed windows, with ``rows = (slot, step == 0)``: a stream's first step starts its slot's
+    noise estimate afresh, so a slot is reusable without a reset here as well.  Each stream is, bit for bit, what a solo
+    ``StreamSpectralDenoiser`` (at its ``input_rate``) returns for the same samples.  ``block_frames = 4``: as there."""
+
+    def __init__(self, device=None, max_streams: int = 64, backlog_steps: int = 4, sample_rate: int = 8000, n_fft: int = 512,
+                 hop_length: int = 128, block_frames: int = 4, params: SpectralParams = None, input_rates=None):
+        window = max(16, block_frames) if isinstance(block_frames, int) else 16
+        self.book = PoolBook(max_streams, backlog_steps, n_fft, hop_length, window, block_frames, 0, input_rates, sample_rate)
+        dev = _spectral_device("SpectralStreamPool", device, params)
+        self.model, self.batch_windows = None, SPECTRAL_MAX_ROWS
+        self.params = SpectralParams() if params is None else params
+        self._gain_state = torch.empty((max_streams, 3, n_fft // 2 + 1), dtype=torch.float32, device=dev)
+        self._setup(dev)
+
+    def reset(self):
+        """Forget every stream, the noise estimates included: all slots are free."""
+        super().reset()
+        self._gain_state.fill_(-1.0)
+
+    def network(self, x):
+        raise RuntimeError("SpectralStreamPool: there is no network; the gain runs between analyze and emit (spectral_gain_windows)")
+
+    def _net(self, x: torch.Tensor, rows) -> torch.Tensor:
+        w, b = self.book.window_frames, self.book.block_frames
+        for i in range(0, len(rows), SPECTRAL_MAX_ROWS):
+            part = x[i:i + SPECTRAL_MAX_ROWS]
+            spectral_gain_windows(part, self._gain_state, w - b, b, 1, self.params,
+                                  [(slot, step == 0) for slot, step, _ in rows[i:i + SPECTRAL_MAX_ROWS]], part)
+        return x
+
+
+def _live(args, params) -> int:
+    """``--live``: the file pushed through ``StreamSpectralDenoiser`` at its own rate, ``--chunk`` samples at a time."""
+    import numpy as np
+
+    from .wav import read_wav, write_wav
+    audio, rate = read_wav(args.src, mono=False)             # (L, channels): every channel is a stream
+    dev = _lib.staging_device()
+    x = torch.from_numpy(np.ascontiguousarray(audio.T, dtype=np.float32)).to(dev)
+    sd = StreamSpectralDenoiser(dev, n_streams=x.shape[0], block_frames=args.block, params=params, input_rate=int(rate))
+    outs = [sd.push(x[:, i:i + args.chunk]) for i in range(0, x.shape[1], args.chunk)]
+    latency = sd.latency_input_samples
+    outs.append(sd.flush())
+    out = torch.cat(outs, dim=1)
+    write_wav(args.dst, np.ascontiguousarray(out.cpu().numpy().T), rate)
+    print(f"{args.src} -> {args.dst}: {x.shape[1]} samples at {rate} Hz in pushes of {args.chunk} at its own rate, "
+          f"latency {latency} samples")
+    if args.reference is not None:
+        print(_report(args.src, args.dst, args.reference))
+    return 0
+
+
 def main(argv=None) -> int:
     import argparse
     ap = argparse.ArgumentParser(prog="python -m audiodenoiser_amd.baseline",
@@ -157,8 +312,19 @@ def main(argv=None) -> int:
                     help="the clean wav of IN (or a folder with IN's file names): print one JSON line of metrics per file")
     ap.add_argument("--bias", type=float, default=SpectralParams.bias, help="noise over-estimation factor (0, 100]")
     ap.add_argument("--gain-floor", type=float, default=SpectralParams.gain_floor, help="smallest gain (0, 1]")
+    ap.add_argument("--live", action="store_true",
+                    help="push the file (not a folder) through the streaming form at its own rate, as a live feed arrives")
+    ap.add_argument("--chunk", type=int, default=1024, help="with --live: samples per push, at the file's rate")
+    ap.add_argument("--block", type=int, default=4, help="with --live: frames per step (latency (block - 1) hop + n_fft samples)")
     args = ap.parse_args(argv)
-    dn = SpectralDenoiser(params=SpectralParams(bias=args.bias, gain_floor=args.gain_floor))
+    params = SpectralParams(bias=args.bias, gain_floor=args.gain_floor)
+    if args.live:
+        if args.chunk < 1 or args.block < 1:
+            ap.error("--chunk and --block must be >= 1")
+        if os.path.isdir(args.src):
+            ap.error("--live takes one wav file")
+        return _live(args, params)
+    dn = SpectralDenoiser(params=params)
     if os.path.isdir(args.src):
         os.makedirs(args.dst, exist_ok=True)
         jobs = [(os.path.join(args.src, f), os.path.join(args.dst, f)) for f in sorted(os.listdir(args.src)) if f.lower().endswith(".wav")]

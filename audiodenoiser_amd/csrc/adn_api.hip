@@ -1,5 +1,6 @@
 // C ABI of libadn.so (include/adn.h) outside the U-Net (unet.hip): version, last error, device queries and the argument checks in
 // front of the STFT, loader, loss, Griffin-Lim, resampler, mixer, reverb, quality-metric, long-form and streaming denoising launchers.
+#include <algorithm>
 #include "adn_host.h"
 
 #include <cmath>
@@ -472,6 +473,30 @@ int adn_denoise_resynth(const float *y, const float *spec, int n_clips, long len
 }
 
 /* ---- spectral baseline: noise tracking + Wiener gain (adn.h, "baseline") ----------------------------------------- */
+// The parameters of a call (NULL = the defaults), refused outside their legal ranges, and the constants derived from them once.
+static int spectral_consts(const char *who, const adn_spectral_params *params, adn::SpectralConsts *k)
+{
+    const std::string w(who);
+    const adn_spectral_params defaults = {0.7f, 0.96f, 0.998f, 0.98f, 0.1f, 1.0f};
+    const adn_spectral_params p = params ? *params : defaults;
+    // written so that a NaN fails every test
+    if (!(p.smooth >= 0.f && p.smooth < 1.f) || !(p.beta >= 0.f && p.beta < 1.f) || !(p.alpha >= 0.f && p.alpha < 1.f))
+        return fail(ADN_ERR_INVALID, w + ": need 0 <= smooth, beta, alpha < 1");
+    if (!(p.gamma > 0.f && p.gamma < 1.f)) return fail(ADN_ERR_INVALID, w + ": need 0 < gamma < 1");
+    if (!(p.gain_floor > 0.f && p.gain_floor <= 1.f)) return fail(ADN_ERR_INVALID, w + ": need 0 < gain_floor <= 1");
+    if (!(p.bias > 0.f && p.bias <= 100.f)) return fail(ADN_ERR_INVALID, w + ": need 0 < bias <= 100");
+    k->smooth = p.smooth;
+    k->one_minus_smooth = 1.f - p.smooth;
+    k->beta = p.beta;
+    k->gamma = p.gamma;
+    k->growth = (1.f - p.gamma) / (1.f - p.beta);
+    k->alpha = p.alpha;
+    k->one_minus_alpha = 1.f - p.alpha;
+    k->gain_floor = p.gain_floor;
+    k->bias = p.bias;
+    return ADN_OK;
+}
+
 int adn_spectral_gain(const float *spec, int n_clips, int n_frames, int n_bins, const adn_spectral_params *params,
                       const float *state_in, float *state_out, float *out, int width, int col0, void *stream)
 {
@@ -479,30 +504,60 @@ int adn_spectral_gain(const float *spec, int n_clips, int n_frames, int n_bins, 
     if (n_clips < 1 || n_frames < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, "adn_spectral_gain: n_clips, n_frames and n_bins must be >= 1");
     if (col0 < 0 || width < 1 || (long)col0 + n_frames > width)
         return fail(ADN_ERR_INVALID, "adn_spectral_gain: need col0 >= 0 and col0 + n_frames <= width");
-    const adn_spectral_params defaults = {0.7f, 0.96f, 0.998f, 0.98f, 0.1f, 1.0f};
-    const adn_spectral_params p = params ? *params : defaults;
-    // written so that a NaN fails every test
-    if (!(p.smooth >= 0.f && p.smooth < 1.f) || !(p.beta >= 0.f && p.beta < 1.f) || !(p.alpha >= 0.f && p.alpha < 1.f))
-        return fail(ADN_ERR_INVALID, "adn_spectral_gain: need 0 <= smooth, beta, alpha < 1");
-    if (!(p.gamma > 0.f && p.gamma < 1.f)) return fail(ADN_ERR_INVALID, "adn_spectral_gain: need 0 < gamma < 1");
-    if (!(p.gain_floor > 0.f && p.gain_floor <= 1.f)) return fail(ADN_ERR_INVALID, "adn_spectral_gain: need 0 < gain_floor <= 1");
-    if (!(p.bias > 0.f && p.bias <= 100.f)) return fail(ADN_ERR_INVALID, "adn_spectral_gain: need 0 < bias <= 100");
+    adn::SpectralConsts k;
+    const int rc = spectral_consts("adn_spectral_gain", params, &k);
+    if (rc != ADN_OK) return rc;
     if (!aligned_to(spec, 8) || !aligned_to(out, 4) || !aligned_to(state_in, 4) || !aligned_to(state_out, 4))
         return fail(ADN_ERR_INVALID, "adn_spectral_gain: spec must be 8-byte aligned, out and the states 4-byte aligned");
-    adn::SpectralConsts k;
-    k.smooth = p.smooth;
-    k.one_minus_smooth = 1.f - p.smooth;
-    k.beta = p.beta;
-    k.gamma = p.gamma;
-    k.growth = (1.f - p.gamma) / (1.f - p.beta);
-    k.alpha = p.alpha;
-    k.one_minus_alpha = 1.f - p.alpha;
-    k.gain_floor = p.gain_floor;
-    k.bias = p.bias;
     hipError_t e = adn::launch_spectral_gain(spec, n_clips, n_frames, n_bins, k, state_in, state_out, out, width, col0,
                                              static_cast<hipStream_t>(stream));
     if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_spectral_gain: grid too large (n_clips x ceil(n_bins / 64) >= 2^31)");
     ADN_LAUNCH(e, "adn_spectral_gain");
+    return ADN_OK;
+}
+
+static_assert(ADN_SPECTRAL_MAX_ROWS == adn::SPECTRAL_MAX_ROWS && sizeof(adn_spectral_row) == sizeof(adn::SpectralRow),
+              "adn.h and adn_internal.h disagree about the baseline's row table");
+
+int adn_spectral_gain_windows(const float *windows, float *y, int n_rows, int n_steps, int n_bins, int window, int col0, int n_cols,
+                              const adn_spectral_params *params, float *state, int n_slots, const adn_spectral_row *rows, void *stream)
+{
+    if (!windows || !y || !state) return fail(ADN_ERR_INVALID, "adn_spectral_gain_windows: null pointer");
+    if (n_rows < 1 || n_steps < 1 || n_bins < 1 || window < 1 || n_cols < 1 || n_slots < 1)
+        return fail(ADN_ERR_INVALID, "adn_spectral_gain_windows: n_rows, n_steps, n_bins, window, n_cols and n_slots must be >= 1");
+    if (col0 < 0 || (long)col0 + n_cols > window)
+        return fail(ADN_ERR_INVALID, "adn_spectral_gain_windows: need col0 >= 0 and col0 + n_cols <= window");
+    if ((long)n_steps * n_cols >= (1L << 31))
+        return fail(ADN_ERR_INVALID, "adn_spectral_gain_windows: n_steps x n_cols must be < 2^31 frames");
+    adn::SpectralRows t = {};
+    if (!rows) {
+        if (n_rows > n_slots) return fail(ADN_ERR_INVALID, "adn_spectral_gain_windows: without rows, row i uses slot i: need n_rows <= n_slots");
+    } else {
+        if (n_rows > ADN_SPECTRAL_MAX_ROWS)
+            return fail(ADN_ERR_INVALID, "adn_spectral_gain_windows: need n_rows <= ADN_SPECTRAL_MAX_ROWS with rows (call again for the rest)");
+        int slots[ADN_SPECTRAL_MAX_ROWS];
+        for (int i = 0; i < n_rows; ++i) {
+            const adn_spectral_row r = rows[i];
+            if (r.slot < 0 || r.slot >= n_slots) return fail(ADN_ERR_INVALID, "adn_spectral_gain_windows: a row's slot is outside [0, n_slots)");
+            slots[i] = r.slot;
+            t.row[i].slot = r.slot;
+            t.row[i].fresh = r.fresh != 0;
+        }
+        std::sort(slots, slots + n_rows);                    // a tick pays for this check: n log n, not n^2
+        if (std::adjacent_find(slots, slots + n_rows) != slots + n_rows)
+            return fail(ADN_ERR_INVALID, "adn_spectral_gain_windows: a slot is named twice in one call");
+        t.n = n_rows;
+    }
+    adn::SpectralConsts k;
+    const int rc = spectral_consts("adn_spectral_gain_windows", params, &k);
+    if (rc != ADN_OK) return rc;
+    if (!aligned_to(windows, 4) || !aligned_to(y, 4) || !aligned_to(state, 4))
+        return fail(ADN_ERR_INVALID, "adn_spectral_gain_windows: windows, y and state must be 4-byte aligned");
+    hipError_t e = adn::launch_spectral_gain_windows(windows, y, n_rows, n_steps, n_bins, window, col0, n_cols, k, state, t,
+                                                     static_cast<hipStream_t>(stream));
+    if (e == hipErrorInvalidValue)
+        return fail(ADN_ERR_INVALID, "adn_spectral_gain_windows: grid too large (n_rows x ceil(n_bins / 64) >= 2^31)");
+    ADN_LAUNCH(e, "adn_spectral_gain_windows");
     return ADN_OK;
 }
 

@@ -446,6 +446,20 @@ struct SpectralConsts {
 };
 hipError_t launch_spectral_gain(const void *spec, int n_clips, int T, int F, const SpectralConsts &k, const float *state_in,
                                 float *state_out, float *out, int width, int col0, hipStream_t st);
+// The magnitude form on stream windows (adn.h, "baseline", "The magnitude form"): windows / y bin-major [row * n_steps + s][F][W],
+// columns [col0, col0 + n_cols) of every step read and written, state [slot][3][F] in place.  SpectralRows travels by value in the
+// kernel arguments as the pool's table does (2 KB of the 4 KB segment): n = 0 means row i is slot i and continues, otherwise
+// row i uses row[i].slot and starts fresh when row[i].fresh != 0.
+constexpr int SPECTRAL_MAX_ROWS = 256;          // adn.h: ADN_SPECTRAL_MAX_ROWS
+struct SpectralRow {
+    int slot, fresh;
+};
+struct SpectralRows {
+    int n;
+    SpectralRow row[SPECTRAL_MAX_ROWS];
+};
+hipError_t launch_spectral_gain_windows(const float *windows, float *y, int n_rows, int n_steps, int F, int W, int col0, int n_cols,
+                                        const SpectralConsts &k, float *state, const SpectralRows &rows, hipStream_t st);
 // Streaming denoiser (stream_kernels.hip; adn.h, "stream").  StreamGeom: the plan and the layout of the state buffer of one batch
 // of streams, in floats (sections X, mag, hist, tail; `total` floats in all); stream_geom is false outside the limits of adn.h.
 // StreamCall: what one call of n_steps steps from step `first` covers, derived from the step index alone (stream_call):

@@ -122,7 +122,117 @@ __global__ __launch_bounds__(64) void bl_spectral_gain_kernel(const float2 *__re
     }
 }
 
+// The magnitude form (adn.h, "baseline", "The magnitude form"): the same rows of work on the layout of the stream classes.
+//
+// Layouts: windows and y are bin-major [row * n_steps + s][F][W] with the frame fastest -- what adn_stream_analyze writes and
+// adn_stream_emit reads; frame t = s * n_cols + j of a row is column col0 + j of its step s.  The state is [slot][3][F], read and
+// written in place by the lane that owns the row; the row's slot and its forced fresh start come from the table in the kernel
+// arguments (t.n == 0: row i is slot i and continues).
+//
+// Shape of the work: as above, one lane per (row, bin), a wave is 64 consecutive bins of one row, one wave per workgroup, frames
+// in order through the one `step` with X = (m, 0).
+//   reads   the input's fastest index is the frame as well: a direct read would be 64 scattered 4-byte loads per frame.  A tile of
+//           up to TF frames comes in the way it leaves: a half-wave reads the row segment of one bin (lane & 31 = the frame of the
+//           tile: consecutive columns while the tile stays inside a step, and a tile may span steps -- n_cols need not divide 32 --
+//           so every lane derives its frame's address from t / n_cols and t mod n_cols, once per tile), two bins per
+//           wave-instruction, 32 registers per lane, and writes them into tile[frame][bin] at banks (j + b) mod 32.  The lanes
+//           then read tile[j][lane], overwrite it with M, and the transposed store path of the kernel above writes it out: one
+//           tile serves both directions.  The 32 loads of tile k + 1 are issued before tile k is computed, as above.
+//   alias   y may be windows: every element of a tile is loaded before any store of that tile (the loads of tile k sit in
+//           registers since tile k - 1; the loads of tile k + 1, issued before the stores of tile k, are other frames), and a
+//           (row, bin) belongs to one lane of one workgroup.
+// Lanes past the last bin walk the last bin again and frames past the end of a tile load the last frame again -- valid addresses --
+// and store nothing.
+// Expected cost, NOT MEASURED for this kernel: chain-bound like its sibling, whose 0.253 us per frame is the only time measured
+// so far; carried over from that, about 1 us for a step of four frames.  A single feed at n_fft 512 is five waves and
+// launch-bound; a tick of 256 feeds is 1280 waves, still about one wave per SIMD.  What was measured: profiles/bench_baseline_stream.md.
+__global__ __launch_bounds__(64) void bl_spectral_gain_windows_kernel(const float *win, float *y, int n_steps, int F, int W, int col0,
+                                                                      int n_cols, int T, int wavesF, SpectralConsts k,
+                                                                      float *state, SpectralRows t)
+{
+    __shared__ float tile[BL_TF * BL_PITCH];
+    const int lane = threadIdx.x;
+    const int row = blockIdx.x / (unsigned)wavesF;
+    const int b0 = (int)(blockIdx.x - (unsigned)row * wavesF) * 64;
+    const bool live = b0 + lane < F;
+    const int bin = live ? b0 + lane : F - 1;
+    const long slot = t.n ? t.row[row].slot : row;
+    const bool forced = t.n ? t.row[row].fresh != 0 : false;
+
+    RowState s;
+    float *sp = state + slot * 3L * F + bin;
+    s.P = sp[0];
+    s.Pmin = sp[F];
+    s.S = sp[2L * F];
+    s.fresh = forced || s.P < 0.f;                               // a NaN P is no fresh start unless the row table forces one
+
+    const long FW = (long)F * W;
+    const long base = (long)row * n_steps * FW + col0;           // column col0 of bin 0 of the row's step 0
+    const int jr = lane & 31, half = lane >> 5;
+    // the address of this lane's frame of the tile at t0, bin 0 (the last frame again past the end: valid, never used)
+    const auto frame_at = [&](long t0) -> long {
+        const int f = (int)(t0 + jr < T ? t0 + jr : T - 1);
+        const int st = f / n_cols;
+        return base + st * FW + (f - st * n_cols);
+    };
+    // a lane's 32 loads of a tile: its frame, bins b0 + 2 r + half (the last bin again past it)
+    float cur[BL_TF], nxt[BL_TF];
+    {
+        const long at = frame_at(0);
+#pragma unroll
+        for (int r = 0; r < BL_TF; ++r) {
+            const int b = b0 + 2 * r + half;
+            cur[r] = win[at + (long)(b < F ? b : F - 1) * W];
+        }
+    }
+    for (long t0 = 0; t0 < T; t0 += BL_TF) {
+        const int nf = T - t0 < BL_TF ? (int)(T - t0) : BL_TF;
+        {
+            const long at = frame_at(t0 + BL_TF);
+#pragma unroll
+            for (int r = 0; r < BL_TF; ++r) {
+                const int b = b0 + 2 * r + half;
+                nxt[r] = win[at + (long)(b < F ? b : F - 1) * W];
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < BL_TF; ++r) tile[jr * BL_PITCH + 2 * r + half] = cur[r];
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < BL_TF; ++j)
+            if (j < nf) tile[j * BL_PITCH + lane] = step(make_float2(tile[j * BL_PITCH + lane], 0.f), s, k);
+        __syncthreads();
+        if (jr < nf) {
+            const long at = frame_at(t0);
+#pragma unroll 4
+            for (int r = 0; r < 32; ++r) {
+                const int b = 2 * r + half;
+                if (b0 + b < F) y[at + (long)(b0 + b) * W] = tile[jr * BL_PITCH + b];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < BL_TF; ++r) cur[r] = nxt[r];
+    }
+    if (live) {
+        sp[0] = s.P;
+        sp[F] = s.Pmin;
+        sp[2L * F] = s.S;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_spectral_gain_windows(const float *windows, float *y, int n_rows, int n_steps, int F, int W, int col0, int n_cols,
+                                        const SpectralConsts &k, float *state, const SpectralRows &rows, hipStream_t st)
+{
+    const long wavesF = ((long)F + 63) / 64;
+    const long grid = wavesF * n_rows, T = (long)n_steps * n_cols;
+    if (grid > 0x7fffffffL || T > 0x7fffffffL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bl_spectral_gain_windows_kernel, dim3((unsigned)grid), dim3(64), 0, st, windows, y, n_steps, F, W, col0,
+                       n_cols, (int)T, (int)wavesF, k, state, rows);
+    return hipGetLastError();
+}
 
 hipError_t launch_spectral_gain(const void *spec, int n_clips, int T, int F, const SpectralConsts &k, const float *state_in,
                                 float *state_out, float *out, int width, int col0, hipStream_t st)

@@ -114,31 +114,38 @@ def _network(model, x: torch.Tensor, batch_windows: int, who: str) -> torch.Tens
     return y
 
 
+def _check_stream_args(who, n_streams, sample_rate, n_fft, hop_length, window_frames, block_frames, lookahead_frames, batch_windows,
+                       input_rate):
+    """The model-free argument checks of ``StreamDenoiser`` (``who``: the class the messages name)."""
+    if not (isinstance(n_streams, int) and n_streams >= 1):
+        raise ValueError(f"{who}: n_streams must be >= 1")
+    if not (isinstance(n_fft, int) and 64 <= n_fft <= 4096 and n_fft & (n_fft - 1) == 0):
+        raise ValueError(f"{who}: n_fft must be a power of two in [64, 4096]")
+    if not (isinstance(hop_length, int) and 1 <= hop_length <= n_fft // 4):
+        raise ValueError(f"{who}: need 1 <= hop_length <= n_fft / 4 (the inverse transform of the whole input length "
+                         "divides by a window sum-of-squares that falls to 2e-8 at n_fft / 2)")
+    if not (isinstance(window_frames, int) and window_frames >= 16):
+        raise ValueError(f"{who}: window_frames must be >= 16 (the network pools four times)")
+    if not (isinstance(block_frames, int) and block_frames >= 1):
+        raise ValueError(f"{who}: block_frames must be >= 1")
+    if not (isinstance(lookahead_frames, int) and lookahead_frames >= 0):
+        raise ValueError(f"{who}: lookahead_frames must be >= 0")
+    if block_frames + lookahead_frames > window_frames:
+        raise ValueError(f"{who}: need block_frames + lookahead_frames <= window_frames")
+    if not (isinstance(batch_windows, int) and batch_windows >= 1):
+        raise ValueError(f"{who}: batch_windows must be >= 1")
+    if not (isinstance(sample_rate, int) and sample_rate >= 1):
+        raise ValueError(f"{who}: sample_rate must be >= 1")
+    if input_rate is not None and not (isinstance(input_rate, int) and input_rate >= 1):
+        raise ValueError(f"{who}: input_rate must be None (the feed is at sample_rate) or an integer >= 1")
+
+
 class StreamDenoiser:
     def __init__(self, model, n_streams: int = 1, sample_rate: int = 8000, n_fft: int = 512, hop_length: int = 128,
                  window_frames: int = 192, block_frames: int = 16, lookahead_frames: int = 0, batch_windows: int = 64,
                  input_rate=None):
-        if not (isinstance(n_streams, int) and n_streams >= 1):
-            raise ValueError("StreamDenoiser: n_streams must be >= 1")
-        if not (isinstance(n_fft, int) and 64 <= n_fft <= 4096 and n_fft & (n_fft - 1) == 0):
-            raise ValueError("StreamDenoiser: n_fft must be a power of two in [64, 4096]")
-        if not (isinstance(hop_length, int) and 1 <= hop_length <= n_fft // 4):
-            raise ValueError("StreamDenoiser: need 1 <= hop_length <= n_fft / 4 (the inverse transform of the whole input length "
-                             "divides by a window sum-of-squares that falls to 2e-8 at n_fft / 2)")
-        if not (isinstance(window_frames, int) and window_frames >= 16):
-            raise ValueError("StreamDenoiser: window_frames must be >= 16 (the network pools four times)")
-        if not (isinstance(block_frames, int) and block_frames >= 1):
-            raise ValueError("StreamDenoiser: block_frames must be >= 1")
-        if not (isinstance(lookahead_frames, int) and lookahead_frames >= 0):
-            raise ValueError("StreamDenoiser: lookahead_frames must be >= 0")
-        if block_frames + lookahead_frames > window_frames:
-            raise ValueError("StreamDenoiser: need block_frames + lookahead_frames <= window_frames")
-        if not (isinstance(batch_windows, int) and batch_windows >= 1):
-            raise ValueError("StreamDenoiser: batch_windows must be >= 1")
-        if not (isinstance(sample_rate, int) and sample_rate >= 1):
-            raise ValueError("StreamDenoiser: sample_rate must be >= 1")
-        if input_rate is not None and not (isinstance(input_rate, int) and input_rate >= 1):
-            raise ValueError("StreamDenoiser: input_rate must be None (the feed is at sample_rate) or an integer >= 1")
+        _check_stream_args("StreamDenoiser", n_streams, sample_rate, n_fft, hop_length, window_frames, block_frames, lookahead_frames,
+                           batch_windows, input_rate)
         from .model import UNet
         if not isinstance(model, UNet) or model.in_channels != 1 or model.num_classes != 1:
             raise ValueError("StreamDenoiser: model must be an audiodenoiser_amd.model.UNet(1, 1)")
@@ -147,7 +154,14 @@ class StreamDenoiser:
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("StreamDenoiser: the model must live on a ROCm device (model.to('cuda')); there is no CPU path")
-        self.model, self.device = model, dev
+        self.model = model
+        self._setup(dev, n_streams, sample_rate, n_fft, hop_length, window_frames, block_frames, lookahead_frames, batch_windows,
+                    input_rate)
+
+    def _setup(self, dev, n_streams, sample_rate, n_fft, hop_length, window_frames, block_frames, lookahead_frames, batch_windows,
+               input_rate):
+        """Everything of the constructor that needs no model: the plan, the device state, the pending buffer, the resamplers."""
+        self.device = dev
         self.n_streams, self.sample_rate, self.n_fft, self.hop_length = n_streams, sample_rate, n_fft, hop_length
         self.window_frames, self.block_frames, self.lookahead_frames = window_frames, block_frames, lookahead_frames
         self.batch_windows = batch_windows
@@ -226,6 +240,11 @@ class StreamDenoiser:
         """The U-Net over ``batch_windows`` windows at a time, into slices of one output buffer (as ``Denoiser.network``)."""
         return _network(self.model, x, self.batch_windows, "StreamDenoiser")
 
+    def _net(self, x: torch.Tensor, first_step: int, n_steps: int) -> torch.Tensor:
+        """What stands between ``analyze`` and ``emit`` for steps ``first_step ..`` (``x``: a stream's ``n_steps`` steps consecutive):
+        here the network, which needs neither number."""
+        return self.network(x)
+
     def emit_count(self, first_step: int, n_steps: int, final_length: int = -1) -> int:
         """Samples per stream that ``emit`` returns for these steps."""
         return _emit_count(self.n_fft, self.hop_length, self.block_frames, first_step, n_steps, final_length)
@@ -245,7 +264,7 @@ class StreamDenoiser:
         """Steps ``_done .. _done + n_steps - 1`` on the pending samples; what they bring leaves the pending buffer."""
         first = self._done
         x = self.analyze(self._pend, self._cap, first, n_steps, final_length)
-        out = self.emit(self.network(x), first, n_steps, final_length)
+        out = self.emit(self._net(x, first, n_steps), first, n_steps, final_length)
         end = self._end_of(first + n_steps - 1)
         used = min(max(end - self._base, 0), self._fill)
         rest = self._fill - used
@@ -640,8 +659,14 @@ class StreamPool:
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("StreamPool: the model must live on a ROCm device (model.to('cuda')); there is no CPU path")
-        self.model, self.device, self.batch_windows = model, dev, batch_windows
-        self.max_streams, self.n_bins = max_streams, n_fft // 2 + 1
+        self.model, self.batch_windows = model, batch_windows
+        self._setup(dev)
+
+    def _setup(self, dev):
+        """Everything of the constructor that needs no model, ``self.book`` given: the device state and the rates' histories."""
+        max_streams = self.book.max_streams
+        self.device = dev
+        self.max_streams, self.n_bins = max_streams, self.book.n_fft // 2 + 1
         self._args = (max_streams,) + self.book.plan + (self.book.ring_samples,)
         need = ctypes.c_size_t()
         _lib.check(_lib.load().adn_stream_pool_state_bytes(*self._args, ctypes.byref(need)), "adn_stream_pool_state_bytes")
@@ -806,6 +831,11 @@ class StreamPool:
     def network(self, x: torch.Tensor) -> torch.Tensor:
         return _network(self.model, x, self.batch_windows, "StreamPool")
 
+    def _net(self, x: torch.Tensor, rows) -> torch.Tensor:
+        """What stands between ``analyze`` and ``emit`` for a tick's ``rows`` (``(slot, step, final_length)``, window i from row i):
+        here the network, which needs none of them."""
+        return self.network(x)
+
     def emit(self, y: torch.Tensor, rows) -> torch.Tensor:
         """``adn_stream_pool_emit``: the network's output for the windows of ``analyze`` -> ``(n_rows, B hop + n_fft / 2)``, row i
         holding ``book.count(step, final_length)`` samples."""
@@ -827,7 +857,7 @@ class StreamPool:
         group = POOL_MAX_ROWS
         groups = [rows[i:i + group] for i in range(0, len(rows), group)]
         x = torch.cat([self.analyze(g) for g in groups]) if len(groups) > 1 else self.analyze(rows)
-        y = self.network(x)
+        y = self._net(x, rows)
         outs = [self.emit(y[i * group:i * group + len(g)], g) for i, g in enumerate(groups)]
         out = torch.cat(outs) if len(outs) > 1 else outs[0]
         book = self.book

@@ -33,7 +33,7 @@
 
 #include <stddef.h>
 
-/* The 61 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 62 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -606,10 +606,39 @@ ADN_API int adn_stoi(const float *est, const float *ref, const long *lengths, in
  * workspace, no atomics, no constant table (a capture may hold a first call); nothing blocks or allocates.
  * Limits (ADN_ERR_INVALID before any launch): n_clips, n_frames, n_bins >= 1; col0 >= 0, col0 + n_frames <= width; launch grid
  * n_clips x ceil(n_bins / 64) < 2^31 workgroups.  Element offsets are 64-bit.
- * Not here: a bin-major magnitude input (what the stream classes would feed), log-MMSE gains, any phase but the noisy one. */
+ *
+ * The magnitude form (adn_spectral_gain_windows: what the stream classes feed).  The input is a magnitude m_t >= 0 instead of a
+ * complex value, and the operator is the definition above applied to X_t = m_t + 0i, with no new arithmetic:
+ *   p_t = fmaf(m, m, 0 * 0) = round(m * m),   M_t = G_t sqrtf(p_t),   every other rule unchanged.
+ * The device runs it through the same one step as adn_spectral_gain, so the result equals, bit for bit, adn_spectral_gain on the
+ * same magnitudes rearranged to frame-major (m, 0); tests/baseline_ref.py stays its float64 restatement, called with
+ * m.astype(complex).  Streaming gains are therefore NOT bit-equal to the offline gains of the same audio: the stream hands over
+ * |X| = sqrtf(p), and sqrtf(p)^2 != p in the last bits.
+ * Layouts: windows and y are (n_rows * n_steps, 1, n_bins, window) fp32 with the frame fastest and a row's steps consecutive --
+ * what adn_stream_analyze / adn_stream_pool_analyze write and adn_stream_emit / adn_stream_pool_emit read.  Row i, bin f is one
+ * recurrence over the frames t = s n_cols + j, s < n_steps, j < n_cols: m_t = windows[i n_steps + s, 0, f, col0 + j], and M_t
+ * goes to the same index of y.  The call writes those columns of y and not one byte else; y may equal windows (every element is
+ * read before it is written), no other overlap is allowed.  The stream classes call it with col0 = W - B - A and n_cols = B,
+ * the only columns adn_stream_emit reads.
+ * State: (n_slots, 3, n_bins) fp32, read and written in place by the lane that owns the row.  rows NULL: row i uses slot i and
+ * continues; a row whose P is negative starts fresh, as above.  Otherwise rows is a HOST array read during the call and handed to
+ * the kernel by value, as the pool's tables are: row i uses rows[i].slot, and with rows[i].fresh != 0 it starts fresh whatever
+ * the slot holds -- which lets a pool slot be reused without a reset (fresh = (step == 0)).  Slots no row names are not touched.
+ * Pinned bit for bit, besides the equality above: the result does not depend on how a row's frames are cut into calls or steps,
+ * on which rows share the call, or on which slot the state sits in.
+ * Cost: one launch, n_rows x ceil(n_bins / 64) waves; no workspace, no atomics, no table (a capture may hold a first call).
+ * Limits (ADN_ERR_INVALID before any launch): no NULL or misaligned (4-byte) windows, y, state; every count >= 1; col0 >= 0,
+ * col0 + n_cols <= window; n_rows <= n_slots without rows; n_rows <= ADN_SPECTRAL_MAX_ROWS with rows, every slot in [0, n_slots)
+ * and named once; n_steps x n_cols < 2^31; n_rows x ceil(n_bins / 64) < 2^31; the parameters as above.
+ * Not here: log-MMSE gains, any phase but the noisy one. */
 typedef struct { float smooth, beta, gamma, alpha, gain_floor, bias; } adn_spectral_params;
 ADN_API int adn_spectral_gain(const float *spec, int n_clips, int n_frames, int n_bins, const adn_spectral_params *params,
                               const float *state_in, float *state_out, float *out, int width, int col0, void *stream);
+#define ADN_SPECTRAL_MAX_ROWS 256
+typedef struct adn_spectral_row { int slot; int fresh; } adn_spectral_row;
+ADN_API int adn_spectral_gain_windows(const float *windows, float *y, int n_rows, int n_steps, int n_bins, int window,
+                                      int col0, int n_cols, const adn_spectral_params *params,
+                                      float *state, int n_slots, const adn_spectral_row *rows, void *stream);
 
 /* ---- environment switches -------------------------------------------------------------------------------------------------
  * Read ONCE, when a U-Net handle is created (never per call).  None is needed in production: the defaults are the measured best
