@@ -9,7 +9,7 @@ __all__ = ["UNet", "SpectrogramDataset", "WavToSpecDataset", "audio_to_magnitude
            "audio_to_spectrogram", "stft_magnitude", "per_clip_l1", "CombinedPerceptualLoss", "NoiseMixDataset",
            "resample_length", "mix_snr", "load_audio", "StreamResampler", "Denoiser", "StreamDenoiser", "StreamPool", "ReverbSettings",
            "snr", "si_sdr", "seg_snr", "stoi", "evaluate", "SpectralDenoiser", "SpectralParams",
-           "StreamSpectralDenoiser", "SpectralStreamPool", "spectral_gain_windows"]
+           "StreamSpectralDenoiser", "SpectralStreamPool", "spectral_gain_windows", "Dereverberator", "WpeParams"]
 # (resample / reverb themselves: audiodenoiser_amd.resample.resample, audiodenoiser_amd.reverb.reverb -- the modules own the names)
 
 
@@ -35,6 +35,9 @@ def __getattr__(name):
     if name in ("SpectralDenoiser", "SpectralParams", "StreamSpectralDenoiser", "SpectralStreamPool", "spectral_gain_windows"):
         import importlib
         return getattr(importlib.import_module(".baseline", __name__), name)
+    if name in ("Dereverberator", "WpeParams"):
+        import importlib
+        return getattr(importlib.import_module(".dereverb", __name__), name)
     if name in ("StreamDenoiser", "StreamPool"):
         import importlib
         return getattr(importlib.import_module(".stream", __name__), name)

@@ -102,6 +102,8 @@ def load() -> ctypes.CDLL:
         L.adn_stoi.argtypes = [vp, vp, vp, ci, cl, vp, sz, vp, vp]
         L.adn_spectral_gain.argtypes = [vp, ci, ci, ci, ctypes.POINTER(SpectralParamsStruct), vp, vp, vp, ci, ci, vp]
         L.adn_spectral_gain_windows.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(SpectralParamsStruct), vp, ci, vp, vp]
+        L.adn_wpe_workspace_bytes.argtypes = [ci, ci, ci, ctypes.POINTER(WpeParamsStruct), ctypes.POINTER(sz)]
+        L.adn_wpe.argtypes = [vp, ci, ci, ci, ctypes.POINTER(WpeParamsStruct), vp, sz, vp, vp, ci, vp]
         for name in ("adn_device_count", "adn_prepare", "adn_unet_create", "adn_unet_create_ex", "adn_unet_create_general", "adn_unet_channels",
                      "adn_unet_set_batch_invariant", "adn_unet_destroy", "adn_unet_workspace_bytes", "adn_unet_forward", "adn_unet_forward_taps", "adn_unet_set_timing", "adn_unet_get_timing",
                      "adn_stft_n_frames", "adn_stft_mag", "adn_stft_mag_fit", "adn_quantize_pad", "adn_per_clip_l1",
@@ -117,7 +119,7 @@ def load() -> ctypes.CDLL:
                      "adn_resample_stream_plan", "adn_resample_stream_state_bytes", "adn_resample_stream",
                      "adn_stream_pool_rate_state_bytes", "adn_stream_pool_push_rate", "adn_stream_pool_emit_rate",
                      "adn_quality_workspace_bytes", "adn_quality", "adn_stoi_workspace_bytes", "adn_stoi",
-                     "adn_spectral_gain", "adn_spectral_gain_windows"):
+                     "adn_spectral_gain", "adn_spectral_gain_windows", "adn_wpe_workspace_bytes", "adn_wpe"):
             getattr(L, name).restype = ci
         _lib = L
         return L
@@ -126,6 +128,12 @@ def load() -> ctypes.CDLL:
 class SpectralParamsStruct(ctypes.Structure):
     """``adn_spectral_params`` of include/adn.h (the Python face is ``audiodenoiser_amd.baseline.SpectralParams``)."""
     _fields_ = [(name, ctypes.c_float) for name in ("smooth", "beta", "gamma", "alpha", "gain_floor", "bias")]
+
+
+class WpeParamsStruct(ctypes.Structure):
+    """``adn_wpe_params`` of include/adn.h (the Python face is ``audiodenoiser_amd.dereverb.WpeParams``)."""
+    _fields_ = [("taps", ctypes.c_int), ("delay", ctypes.c_int), ("iterations", ctypes.c_int), ("loading", ctypes.c_float),
+                ("power_floor", ctypes.c_float)]
 
 
 class SpectralRow(ctypes.Structure):
@@ -175,5 +183,5 @@ EXPORTED_SYMBOLS = (
     "adn_resample_stream_plan", "adn_resample_stream_state_bytes", "adn_resample_stream",
     "adn_stream_pool_rate_state_bytes", "adn_stream_pool_push_rate", "adn_stream_pool_emit_rate",
     "adn_quality_workspace_bytes", "adn_quality", "adn_stoi_workspace_bytes", "adn_stoi",
-    "adn_spectral_gain", "adn_spectral_gain_windows",
+    "adn_spectral_gain", "adn_spectral_gain_windows", "adn_wpe_workspace_bytes", "adn_wpe",
 )

@@ -561,6 +561,67 @@ int adn_spectral_gain_windows(const float *windows, float *y, int n_rows, int n_
     return ADN_OK;
 }
 
+/* ---- dereverberation baseline: per-bin WPE (adn.h, "dereverb") ---------------------------------------------------- */
+// The parameters of a call (NULL = the defaults), refused outside their legal ranges; the message names the field.
+static int wpe_consts(const char *who, const adn_wpe_params *params, adn::WpeConsts *k)
+{
+    const std::string w(who);
+    const adn_wpe_params defaults = {20, 3, 3, 1e-3f, 1e-3f};
+    const adn_wpe_params p = params ? *params : defaults;
+    if (p.taps < 1 || p.taps > 32) return fail(ADN_ERR_INVALID, w + ": need 1 <= taps <= 32");
+    if (p.delay < 1 || p.delay > 8) return fail(ADN_ERR_INVALID, w + ": need 1 <= delay <= 8");
+    if (p.iterations < 1 || p.iterations > 8) return fail(ADN_ERR_INVALID, w + ": need 1 <= iterations <= 8");
+    // written so that a NaN fails every test
+    if (!(p.loading >= 1e-6f && p.loading <= 1.f)) return fail(ADN_ERR_INVALID, w + ": need 1e-6 <= loading <= 1");
+    if (!(p.power_floor > 0.f && p.power_floor <= 1.f)) return fail(ADN_ERR_INVALID, w + ": need 0 < power_floor <= 1");
+    k->K = p.taps;
+    k->D = p.delay;
+    k->I = p.iterations;
+    k->loading = p.loading;
+    k->rho = p.power_floor;
+    return ADN_OK;
+}
+
+static int wpe_shape(const char *who, int n_clips, int n_frames, int n_bins, const adn_wpe_params *params, adn::WpeConsts *k)
+{
+    const std::string w(who);
+    if (n_clips < 1 || n_frames < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, w + ": n_clips, n_frames and n_bins must be >= 1");
+    const int rc = wpe_consts(who, params, k);
+    if (rc != ADN_OK) return rc;
+    if (adn::wpe_grid(n_clips, n_bins, k->K) > 0x7fffffffL)
+        return fail(ADN_ERR_INVALID, w + ": grid too large (n_clips x ceil(n_bins / bins per workgroup) >= 2^31)");
+    return ADN_OK;
+}
+
+int adn_wpe_workspace_bytes(int n_clips, int n_frames, int n_bins, const adn_wpe_params *params, size_t *bytes)
+{
+    adn::WpeConsts k;
+    if (!bytes) return fail(ADN_ERR_INVALID, "adn_wpe_workspace_bytes: null pointer");
+    const int rc = wpe_shape("adn_wpe_workspace_bytes", n_clips, n_frames, n_bins, params, &k);
+    if (rc != ADN_OK) return rc;
+    *bytes = 0;                                          // R, P, the factor and the taps of a row never leave the chip
+    return ADN_OK;
+}
+
+int adn_wpe(const float *spec, int n_clips, int n_frames, int n_bins, const adn_wpe_params *params, void *workspace,
+            size_t workspace_bytes, float *spec_out, float *mag_out, int width, void *stream)
+{
+    adn::WpeConsts k;
+    if (!spec || !spec_out) return fail(ADN_ERR_INVALID, "adn_wpe: null pointer (spec, spec_out)");
+    const int rc = wpe_shape("adn_wpe", n_clips, n_frames, n_bins, params, &k);
+    if (rc != ADN_OK) return rc;
+    if (mag_out && width < n_frames) return fail(ADN_ERR_INVALID, "adn_wpe: need width >= n_frames");
+    if (!aligned_to(spec, 8) || !aligned_to(spec_out, 8) || !aligned_to(mag_out, 4))
+        return fail(ADN_ERR_INVALID, "adn_wpe: spec and spec_out must be 8-byte aligned, mag_out 4-byte aligned");
+    const size_t need = 0;                               // adn_wpe_workspace_bytes
+    if (workspace_bytes < need || (need && !workspace)) return fail(ADN_ERR_WORKSPACE, "adn_wpe: workspace smaller than adn_wpe_workspace_bytes");
+    const char *a = reinterpret_cast<const char *>(spec), *b = reinterpret_cast<const char *>(spec_out);
+    const size_t span = (size_t)n_clips * (size_t)n_frames * (size_t)n_bins * 2 * sizeof(float);
+    if (a < b + span && b < a + span) return fail(ADN_ERR_INVALID, "adn_wpe: spec and spec_out may not overlap");
+    ADN_LAUNCH(adn::launch_wpe(spec, n_clips, n_frames, n_bins, k, spec_out, mag_out, width, static_cast<hipStream_t>(stream)), "adn_wpe");
+    return ADN_OK;
+}
+
 /* ---- streaming denoiser: plan, state, analysis, emit (adn.h, "stream") ------------------------------------------- */
 static const char *stream_plan_text = ": need a power-of-two n_fft in [64, 4096], 1 <= hop <= n_fft / 4, window >= 16, block >= 1, "
                                       "lookahead >= 0, block + lookahead <= window, n_streams >= 1 and 1 <= max_steps <= 65536";

@@ -460,6 +460,16 @@ struct SpectralRows {
 };
 hipError_t launch_spectral_gain_windows(const float *windows, float *y, int n_rows, int n_steps, int F, int W, int col0, int n_cols,
                                         const SpectralConsts &k, float *state, const SpectralRows &rows, hipStream_t st);
+// Dereverberation baseline (dereverb_kernels.hip; adn.h, "dereverb"): I iterations of K-tap WPE at delay D on every (clip, bin)
+// row of a frame-major float2 spectrogram, in one launch without a workspace.  mag_out (may be null) is bin-major
+// [clip][F][width], columns [0, T) written.  wpe_grid: the workgroups of the launch, n_clips x ceil(F / (256 / lanes per bin)).
+struct WpeConsts {
+    int K, D, I;
+    float loading, rho;
+};
+long wpe_grid(int n_clips, int F, int K);
+hipError_t launch_wpe(const void *spec, int n_clips, int T, int F, const WpeConsts &k, void *spec_out, float *mag_out, int width,
+                      hipStream_t st);
 // Streaming denoiser (stream_kernels.hip; adn.h, "stream").  StreamGeom: the plan and the layout of the state buffer of one batch
 // of streams, in floats (sections X, mag, hist, tail; `total` floats in all); stream_geom is false outside the limits of adn.h.
 // StreamCall: what one call of n_steps steps from step `first` covers, derived from the step index alone (stream_call):

@@ -33,7 +33,7 @@
 
 #include <stddef.h>
 
-/* The 62 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 64 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -639,6 +639,60 @@ typedef struct adn_spectral_row { int slot; int fresh; } adn_spectral_row;
 ADN_API int adn_spectral_gain_windows(const float *windows, float *y, int n_rows, int n_steps, int n_bins, int window,
                                       int col0, int n_cols, const adn_spectral_params *params,
                                       float *state, int n_slots, const adn_spectral_row *rows, void *stream);
+
+/* ---- dereverb: weighted prediction error per frequency bin, no weights ----------------------------------------------------------
+ * No reference counterpart and no checkpoint.  The library DEFINES the operator below (float64 restatement: tests/dereverb_ref.py);
+ * it is UNPINNED against any package.  It is single-channel WPE, delayed linear prediction per frequency bin with the variance
+ * re-estimated from the last result (Nakatani et al. 2010).  Reverberation is a filter, and no gain per bin ("baseline") undoes a
+ * filter: this is the classical operator for the "reverb" noise type, and a front end to the gain of "baseline".
+ * Not validated: the defaults are the values of the host prototype; they were not tuned by ear.
+ *
+ * Every (clip, bin) row is independent.  X_t are the row's complex values, t = 0 ... T-1, and X_t = 0 for t < 0.  In fp32:
+ *   p_t   = fmaf(re, re, im * im)
+ *   phi   = max(rho (sum_t p_t) / T, 1e-30)
+ *   d^(0) = X
+ *   for i = 1 ... I:
+ *       lam_t = max(|d^(i-1)_t|^2, phi),  w_t = 1 / lam_t                       (|.|^2 as p_t above)
+ *       R_jk  = sum_t (w_t X_{t-D-j}) conj(X_{t-D-k})                           j, k = 0 ... K-1
+ *       P_j   = sum_t (w_t X_{t-D-j}) conj(X_t)
+ *       A     = R + ((delta tr(R)) / K + 1e-30) I                               (tr(R) = sum_j Re R_jj, j ascending; A_jj is real)
+ *       solve A g = P by Cholesky: A = L L^H column by column, L y = P, L^H g = y
+ *       d^(i)_t = X_t - sum_j conj(g_j) X_{t-D-j}                               (j ascending over the taps with t - D - j >= 0)
+ *   output d^(I); optional magnitude M_t = sqrtf(fmaf(dre, dre, dim * dim))
+ * The weight is applied once, as the product w_t X_{t-D-j} (each component rounded), before the multiply-add with the conjugate;
+ * complex multiply-adds are two fmaf per component.  max(x, c) is `x < c ? c : x`: a NaN x stays NaN.  Divisions and square roots
+ * are correctly rounded.  The sums over t run in a fixed order that is the implementation's own (the device: frame after frame from
+ * t = 0; phi: the partial sums of the frames t = q mod LPB chunk by chunk, added for q ascending, LPB = 16, 32 or 64 from K alone);
+ * the order does not depend on the batch or on which bins share the call.  Inner sums of the factorisation and the substitutions
+ * run over k ascending (k descending in L^H g = y).
+ * Parameters (adn_wpe_params; NULL = the defaults): taps K 20, delay D 3, iterations I 3, loading delta 1e-3, power_floor rho 1e-3.
+ * Legal (ADN_ERR_INVALID otherwise, before any launch, the message names the field; a NaN is illegal): 1 <= taps <= 32;
+ * 1 <= delay <= 8; 1 <= iterations <= 8; 1e-6 <= loading <= 1; 0 < power_floor <= 1.
+ * Consequences: a row with T <= D comes back bit for bit (no tap has a frame); the first D frames of any row come back bit for
+ * bit; an all-zero row gives zeros (A = 1e-30 I, P = 0).  A non-finite value is confined to its own (clip, bin) row, whose content
+ * is then unspecified.
+ *
+ * What is pinned.  The result is bounded against the float64 restatement (tests/test_gpu_dereverb.py: per clip
+ * max |d - d64| <= 4 FLOOR max |d64|, FLOOR the error of the same statements run in fp32 on the host); it is NOT pinned bit for bit
+ * to numpy.  Pinned bit for bit: two calls give the same result; a clip gives the same bits alone or in any batch; a bin gives the
+ * same bits whichever other bins are in the call.  Deterministic: no atomics.
+ *
+ * Layouts: spec and spec_out are frame-major (n_clips, n_frames, n_bins, 2) fp32 as adn_stft_complex writes it, 8-byte aligned;
+ * they may not overlap.  mag_out may be NULL; otherwise it is (n_clips, 1, n_bins, width) fp32 with width >= n_frames, the
+ * network-output layout adn_denoise_resynth reads.  The call writes columns [0, n_frames) of mag_out, all of spec_out and not one
+ * byte else -- zeroing padding columns is the caller's job.  It may use the workspace and only the workspace;
+ * adn_wpe_workspace_bytes reports 0 today (R, P, the factor and the taps of a row stay on chip), and workspace may then be NULL.
+ * Cost: one launch for all iterations, n_clips x ceil(n_bins / B) workgroups, B = 16 bins up to K = 20, 8 up to K = 28, 4 beyond;
+ * a clip's frames pass through LDS in chunks, so no limit on n_frames comes from LDS.  No atomics, no constant table (a capture
+ * may hold a first call); nothing blocks or allocates.
+ * Limits (ADN_ERR_INVALID before any launch): NULL or misaligned spec / spec_out / mag_out; n_clips, n_frames, n_bins >= 1;
+ * width >= n_frames with a mag_out; overlapping spec and spec_out; launch grid < 2^31 workgroups; the parameters as above.
+ * ADN_ERR_WORKSPACE: workspace_bytes below adn_wpe_workspace_bytes.  Element offsets are 64-bit.
+ * Not here: online / recursive WPE for streams; more than one channel; any tuning by ear. */
+typedef struct adn_wpe_params { int taps, delay, iterations; float loading, power_floor; } adn_wpe_params;
+ADN_API int adn_wpe_workspace_bytes(int n_clips, int n_frames, int n_bins, const adn_wpe_params *params, size_t *bytes);
+ADN_API int adn_wpe(const float *spec, int n_clips, int n_frames, int n_bins, const adn_wpe_params *params, void *workspace,
+                    size_t workspace_bytes, float *spec_out, float *mag_out, int width, void *stream);
 
 /* ---- environment switches -------------------------------------------------------------------------------------------------
  * Read ONCE, when a U-Net handle is created (never per call).  None is needed in production: the defaults are the measured best
