@@ -9,7 +9,8 @@ __all__ = ["UNet", "SpectrogramDataset", "WavToSpecDataset", "audio_to_magnitude
            "audio_to_spectrogram", "stft_magnitude", "per_clip_l1", "CombinedPerceptualLoss", "NoiseMixDataset",
            "resample_length", "mix_snr", "load_audio", "StreamResampler", "Denoiser", "StreamDenoiser", "StreamPool", "ReverbSettings",
            "snr", "si_sdr", "seg_snr", "stoi", "evaluate", "SpectralDenoiser", "SpectralParams",
-           "StreamSpectralDenoiser", "SpectralStreamPool", "spectral_gain_windows", "Dereverberator", "WpeParams"]
+           "StreamSpectralDenoiser", "SpectralStreamPool", "spectral_gain_windows", "Dereverberator", "WpeParams",
+           "WpeStreamParams", "wpe_online", "StreamDereverberator", "DereverbStreamPool"]
 # (resample / reverb themselves: audiodenoiser_amd.resample.resample, audiodenoiser_amd.reverb.reverb -- the modules own the names)
 
 
@@ -35,7 +36,7 @@ def __getattr__(name):
     if name in ("SpectralDenoiser", "SpectralParams", "StreamSpectralDenoiser", "SpectralStreamPool", "spectral_gain_windows"):
         import importlib
         return getattr(importlib.import_module(".baseline", __name__), name)
-    if name in ("Dereverberator", "WpeParams"):
+    if name in ("Dereverberator", "WpeParams", "WpeStreamParams", "wpe_online", "StreamDereverberator", "DereverbStreamPool"):
         import importlib
         return getattr(importlib.import_module(".dereverb", __name__), name)
     if name in ("StreamDenoiser", "StreamPool"):

@@ -104,6 +104,11 @@ def load() -> ctypes.CDLL:
         L.adn_spectral_gain_windows.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(SpectralParamsStruct), vp, ci, vp, vp]
         L.adn_wpe_workspace_bytes.argtypes = [ci, ci, ci, ctypes.POINTER(WpeParamsStruct), ctypes.POINTER(sz)]
         L.adn_wpe.argtypes = [vp, ci, ci, ci, ctypes.POINTER(WpeParamsStruct), vp, sz, vp, vp, ci, vp]
+        wsp = ctypes.POINTER(WpeStreamParamsStruct)
+        L.adn_wpe_stream_state_bytes.argtypes = [ci, ci, wsp, ctypes.POINTER(sz)]
+        L.adn_wpe_online.argtypes = [vp, ci, ci, ci, cl, wsp, vp, sz, ci, vp, vp, ci, ci, vp]
+        L.adn_wpe_stream.argtypes = [vp, sz, vp, ci, cl, ci, cl, ci, ci, ci, ci, ci, ci, wsp, vp, sz, vp]
+        L.adn_wpe_stream_pool.argtypes = [vp, sz, ci, ci, ci, ci, ci, ci, cl, vp, ci, vp, wsp, vp, sz, vp]
         for name in ("adn_device_count", "adn_prepare", "adn_unet_create", "adn_unet_create_ex", "adn_unet_create_general", "adn_unet_channels",
                      "adn_unet_set_batch_invariant", "adn_unet_destroy", "adn_unet_workspace_bytes", "adn_unet_forward", "adn_unet_forward_taps", "adn_unet_set_timing", "adn_unet_get_timing",
                      "adn_stft_n_frames", "adn_stft_mag", "adn_stft_mag_fit", "adn_quantize_pad", "adn_per_clip_l1",
@@ -119,7 +124,8 @@ def load() -> ctypes.CDLL:
                      "adn_resample_stream_plan", "adn_resample_stream_state_bytes", "adn_resample_stream",
                      "adn_stream_pool_rate_state_bytes", "adn_stream_pool_push_rate", "adn_stream_pool_emit_rate",
                      "adn_quality_workspace_bytes", "adn_quality", "adn_stoi_workspace_bytes", "adn_stoi",
-                     "adn_spectral_gain", "adn_spectral_gain_windows", "adn_wpe_workspace_bytes", "adn_wpe"):
+                     "adn_spectral_gain", "adn_spectral_gain_windows", "adn_wpe_workspace_bytes", "adn_wpe",
+                     "adn_wpe_stream_state_bytes", "adn_wpe_online", "adn_wpe_stream", "adn_wpe_stream_pool"):
             getattr(L, name).restype = ci
         _lib = L
         return L
@@ -134,6 +140,12 @@ class WpeParamsStruct(ctypes.Structure):
     """``adn_wpe_params`` of include/adn.h (the Python face is ``audiodenoiser_amd.dereverb.WpeParams``)."""
     _fields_ = [("taps", ctypes.c_int), ("delay", ctypes.c_int), ("iterations", ctypes.c_int), ("loading", ctypes.c_float),
                 ("power_floor", ctypes.c_float)]
+
+
+class WpeStreamParamsStruct(ctypes.Structure):
+    """``adn_wpe_stream_params`` of include/adn.h (the Python face is ``audiodenoiser_amd.dereverb.WpeStreamParams``)."""
+    _fields_ = [("taps", ctypes.c_int), ("delay", ctypes.c_int), ("forget", ctypes.c_float), ("loading", ctypes.c_float),
+                ("power_floor", ctypes.c_float), ("smooth", ctypes.c_float)]
 
 
 class SpectralRow(ctypes.Structure):
@@ -184,4 +196,5 @@ EXPORTED_SYMBOLS = (
     "adn_stream_pool_rate_state_bytes", "adn_stream_pool_push_rate", "adn_stream_pool_emit_rate",
     "adn_quality_workspace_bytes", "adn_quality", "adn_stoi_workspace_bytes", "adn_stoi",
     "adn_spectral_gain", "adn_spectral_gain_windows", "adn_wpe_workspace_bytes", "adn_wpe",
+    "adn_wpe_stream_state_bytes", "adn_wpe_online", "adn_wpe_stream", "adn_wpe_stream_pool",
 )

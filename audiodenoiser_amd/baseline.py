@@ -242,7 +242,7 @@ class StreamSpectralDenoiser(StreamDenoiser):
     def network(self, x):
         raise RuntimeError("StreamSpectralDenoiser: there is no network; the gain runs between analyze and emit (spectral_gain_windows)")
 
-    def _net(self, x: torch.Tensor, first_step: int, n_steps: int) -> torch.Tensor:
+    def _net(self, x: torch.Tensor, first_step: int, n_steps: int, final_length: int = -1) -> torch.Tensor:
         w, b = self.window_frames, self.block_frames
         return spectral_gain_windows(x, self._gain_state, w - b, b, n_steps, self.params, None, x)
 

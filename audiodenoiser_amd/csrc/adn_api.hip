@@ -892,6 +892,130 @@ int adn_stream_pool_emit(void *state, size_t state_bytes, int n_slots, int n_fft
     return ADN_OK;
 }
 
+/* ---- streaming dereverberation: recursive WPE (adn.h, "dereverb stream") ------------------------------------------- */
+// The parameters of a call (NULL = the defaults), refused outside their legal ranges; the message names the field.
+static int wpe_stream_consts(const char *who, const adn_wpe_stream_params *params, adn::WpeStreamConsts *k)
+{
+    const std::string w(who);
+    const adn_wpe_stream_params defaults = {20, 3, 0.99f, 300.f, 0.01f, 0.9f};
+    const adn_wpe_stream_params p = params ? *params : defaults;
+    if (p.taps < 1 || p.taps > 32) return fail(ADN_ERR_INVALID, w + ": need 1 <= taps <= 32");
+    if (p.delay < 1 || p.delay > 8) return fail(ADN_ERR_INVALID, w + ": need 1 <= delay <= 8");
+    // written so that a NaN fails every test
+    if (!(p.forget >= 0.95f && p.forget <= 1.f)) return fail(ADN_ERR_INVALID, w + ": need 0.95 <= forget <= 1");
+    if (!(p.loading >= 1.f && p.loading <= 1e6f)) return fail(ADN_ERR_INVALID, w + ": need 1 <= loading <= 1e6");
+    if (!(p.power_floor > 0.f && p.power_floor <= 1.f)) return fail(ADN_ERR_INVALID, w + ": need 0 < power_floor <= 1");
+    if (!(p.smooth >= 0.f && p.smooth < 1.f)) return fail(ADN_ERR_INVALID, w + ": need 0 <= smooth < 1");
+    k->K = p.taps;
+    k->D = p.delay;
+    k->alpha = p.forget;
+    k->p0 = 1.f / p.loading;
+    k->rho = p.power_floor;
+    k->beta = p.smooth;
+    k->one_minus_beta = 1.f - p.smooth;
+    return ADN_OK;
+}
+
+// The WPE state of a call: n_slots x n_bins records, 8-byte aligned, at least adn_wpe_stream_state_bytes.
+static int wpe_stream_state(const char *who, const void *wstate, size_t wstate_bytes, int n_slots, int n_bins, const adn::WpeStreamConsts &k)
+{
+    const std::string w(who);
+    if (!wstate) return fail(ADN_ERR_INVALID, w + ": null pointer (the WPE state)");
+    if (n_slots < 1 || n_slots > (1 << 20) || n_bins < 1 || n_bins > (1 << 20))
+        return fail(ADN_ERR_INVALID, w + ": need 1 <= n_slots <= 2^20 and 1 <= n_bins <= 2^20");
+    const size_t need = (size_t)n_slots * (size_t)n_bins * (size_t)adn::wpe_stream_record_floats(k.K, k.D) * sizeof(float);
+    if (wstate_bytes < need) return fail(ADN_ERR_WORKSPACE, w + ": the WPE state is smaller than adn_wpe_stream_state_bytes");
+    if (!aligned_to(wstate, 8)) return fail(ADN_ERR_INVALID, w + ": the WPE state must be 8-byte aligned");
+    return ADN_OK;
+}
+
+int adn_wpe_stream_state_bytes(int n_slots, int n_bins, const adn_wpe_stream_params *params, size_t *bytes)
+{
+    adn::WpeStreamConsts k;
+    if (!bytes) return fail(ADN_ERR_INVALID, "adn_wpe_stream_state_bytes: null pointer");
+    if (n_slots < 1 || n_slots > (1 << 20) || n_bins < 1 || n_bins > (1 << 20))
+        return fail(ADN_ERR_INVALID, "adn_wpe_stream_state_bytes: need 1 <= n_slots <= 2^20 and 1 <= n_bins <= 2^20");
+    const int rc = wpe_stream_consts("adn_wpe_stream_state_bytes", params, &k);
+    if (rc != ADN_OK) return rc;
+    *bytes = (size_t)n_slots * (size_t)n_bins * (size_t)adn::wpe_stream_record_floats(k.K, k.D) * sizeof(float);
+    return ADN_OK;
+}
+
+int adn_wpe_online(const float *spec, int n_rows, int n_frames, int n_bins, long first_frame, const adn_wpe_stream_params *params,
+                   void *state, size_t state_bytes, int n_slots, float *spec_out, float *mag_out, int width, int col0, void *stream)
+{
+    adn::WpeStreamConsts k;
+    if (!spec || !spec_out) return fail(ADN_ERR_INVALID, "adn_wpe_online: null pointer (spec, spec_out)");
+    if (n_rows < 1 || n_frames < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, "adn_wpe_online: n_rows, n_frames and n_bins must be >= 1");
+    if (first_frame < 0 || first_frame + n_frames >= (1L << 31))
+        return fail(ADN_ERR_INVALID, "adn_wpe_online: need first_frame >= 0 and first_frame + n_frames < 2^31");
+    int rc = wpe_stream_consts("adn_wpe_online", params, &k);
+    if (rc != ADN_OK) return rc;
+    rc = wpe_stream_state("adn_wpe_online", state, state_bytes, n_slots, n_bins, k);
+    if (rc != ADN_OK) return rc;
+    if (n_rows > n_slots) return fail(ADN_ERR_INVALID, "adn_wpe_online: row i uses slot i: need n_rows <= n_slots");
+    if (mag_out && (col0 < 0 || width < 1 || (long)col0 + n_frames > width))
+        return fail(ADN_ERR_INVALID, "adn_wpe_online: need col0 >= 0 and col0 + n_frames <= width");
+    if (!aligned_to(spec, 8) || !aligned_to(spec_out, 8) || !aligned_to(mag_out, 4))
+        return fail(ADN_ERR_INVALID, "adn_wpe_online: spec and spec_out must be 8-byte aligned, mag_out 4-byte aligned");
+    const char *a = reinterpret_cast<const char *>(spec), *b = reinterpret_cast<const char *>(spec_out);
+    const size_t span = (size_t)n_rows * (size_t)n_frames * (size_t)n_bins * 2 * sizeof(float);
+    if (a < b + span && b < a + span) return fail(ADN_ERR_INVALID, "adn_wpe_online: spec and spec_out may not overlap");
+    if (adn::wpe_stream_grid(n_rows, n_bins) > 0x7fffffffL)
+        return fail(ADN_ERR_INVALID, "adn_wpe_online: grid too large (n_rows x ceil(n_bins / 8) >= 2^31)");
+    ADN_LAUNCH(adn::launch_wpe_online(spec, n_rows, n_frames, n_bins, (int)first_frame, k, static_cast<float *>(state), spec_out, mag_out,
+                                      width, col0, static_cast<hipStream_t>(stream)), "adn_wpe_online");
+    return ADN_OK;
+}
+
+int adn_wpe_stream(void *sstate, size_t sstate_bytes, float *y, int n_streams, long first_step, int n_steps,
+                   long final_length, int n_fft, int hop, int window, int block, int lookahead, int max_steps,
+                   const adn_wpe_stream_params *params, void *wpe_state, size_t wpe_state_bytes, void *stream)
+{
+    adn::StreamGeom g;
+    adn::StreamCall c;
+    adn::WpeStreamConsts k;
+    int rc = stream_state("adn_wpe_stream", sstate, sstate_bytes, n_streams, n_fft, hop, window, block, lookahead, max_steps, &g);
+    if (rc != ADN_OK) return rc;
+    if (lookahead != 0) return fail(ADN_ERR_INVALID, "adn_wpe_stream: the operator is causal: lookahead must be 0");
+    if (!y) return fail(ADN_ERR_INVALID, "adn_wpe_stream: null pointer");
+    if (!aligned_to(y, 4)) return fail(ADN_ERR_INVALID, "adn_wpe_stream: y must be 4-byte aligned");
+    rc = stream_call("adn_wpe_stream", g, first_step, n_steps, final_length, &c);
+    if (rc != ADN_OK) return rc;
+    rc = wpe_stream_consts("adn_wpe_stream", params, &k);
+    if (rc != ADN_OK) return rc;
+    rc = wpe_stream_state("adn_wpe_stream", wpe_state, wpe_state_bytes, n_streams, n_fft / 2 + 1, k);
+    if (rc != ADN_OK) return rc;
+    ADN_LAUNCH(adn::launch_wpe_stream(static_cast<float *>(sstate), y, n_streams, g, c, k, static_cast<float *>(wpe_state),
+                                      static_cast<hipStream_t>(stream)), "adn_wpe_stream");
+    return ADN_OK;
+}
+
+int adn_wpe_stream_pool(void *pstate, size_t pstate_bytes, int n_slots, int n_fft, int hop, int window, int block,
+                        int lookahead, long ring_samples, const adn_stream_pool_row *rows, int n_rows, float *y,
+                        const adn_wpe_stream_params *params, void *wpe_state, size_t wpe_state_bytes, void *stream)
+{
+    PoolState p;
+    adn::StreamPoolRows t = {};
+    adn::WpeStreamConsts k;
+    int max_new, max_span;
+    long max_out;
+    int rc = pool_state("adn_wpe_stream_pool", pstate, pstate_bytes, n_slots, n_fft, hop, window, block, lookahead, ring_samples, &p);
+    if (rc != ADN_OK) return rc;
+    if (lookahead != 0) return fail(ADN_ERR_INVALID, "adn_wpe_stream_pool: the operator is causal: lookahead must be 0");
+    if (!y) return fail(ADN_ERR_INVALID, "adn_wpe_stream_pool: null pointer");
+    if (!aligned_to(y, 4)) return fail(ADN_ERR_INVALID, "adn_wpe_stream_pool: y must be 4-byte aligned");
+    rc = pool_rows("adn_wpe_stream_pool", p, n_slots, rows, n_rows, &t, &max_new, &max_span, &max_out);
+    if (rc != ADN_OK) return rc;
+    rc = wpe_stream_consts("adn_wpe_stream_pool", params, &k);
+    if (rc != ADN_OK) return rc;
+    rc = wpe_stream_state("adn_wpe_stream_pool", wpe_state, wpe_state_bytes, n_slots, n_fft / 2 + 1, k);
+    if (rc != ADN_OK) return rc;
+    ADN_LAUNCH(adn::launch_wpe_stream_pool(static_cast<float *>(pstate), y, p.g, t, k, static_cast<float *>(wpe_state),
+                                           static_cast<hipStream_t>(stream)), "adn_wpe_stream_pool");
+    return ADN_OK;
+}
+
 static const char *resample_stream_text = ": rates must be >= 1 with max(up, down) <= 4096 after dividing by their gcd, and at most "
                                           "16384 carried samples (2 floor(half / up) + ceil(down / up) + 1)";
 

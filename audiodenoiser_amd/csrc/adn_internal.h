@@ -553,6 +553,24 @@ hipError_t launch_stream_windows(const float *state, int n_streams, const Stream
                                  hipStream_t st);
 hipError_t launch_stream_emit(const float *y, int n_streams, const StreamGeom &g, const StreamCall &c, float *state, float *audio,
                               long out_stride, hipStream_t st);
+// Streaming dereverberation (dereverb_stream_kernels.hip; adn.h, "dereverb stream"): one RLS update per frame on every row.
+// WpeStreamConsts: the parameters and the two constants derived from them once per call on the host, in fp32: p0 = 1 / loading,
+// 1 - smooth.  wstate: wpe_stream_record_floats(K, D) floats per (slot, bin), [slot][bin] consecutive; a row that starts at frame
+// 0 reads none of it.  The three launches differ in where a row's frames are: frame-major spectrograms (row i = slot i, frames
+// first_frame .. first_frame + T - 1); the X ring of a lockstep stream state (frames f_first .. f_last of `call`, in place, M_t
+// into columns [W - B, W) of y); the same for the rows of a pool.  wpe_stream_grid: the workgroups of a launch.
+struct WpeStreamConsts {
+    int K, D;
+    float alpha, p0, rho, beta, one_minus_beta;
+};
+long wpe_stream_record_floats(int K, int D);
+long wpe_stream_grid(long n_rows, int F);
+hipError_t launch_wpe_online(const void *spec, int n_rows, int T, int F, int first_frame, const WpeStreamConsts &c, float *wstate,
+                             void *spec_out, float *mag_out, int width, int col0, hipStream_t st);
+hipError_t launch_wpe_stream(float *state, float *y, int n_streams, const StreamGeom &g, const StreamCall &call,
+                             const WpeStreamConsts &c, float *wstate, hipStream_t st);
+hipError_t launch_wpe_stream_pool(float *state, float *y, const StreamGeom &g, const StreamPoolRows &rows, const WpeStreamConsts &c,
+                                  float *wstate, hipStream_t st);
 hipError_t launch_quantize_pad(const float *in, int n, int h, int w, float *out, int H, int W, hipStream_t st);
 hipError_t launch_per_clip_l1(const float *a, const float *b, int n_clips, long elems, float *out, hipStream_t st);
 // Polyphase resampler and SNR mixer (resample_kernels.hip).  resample_ratio: up / down of a rate pair, false outside the limits

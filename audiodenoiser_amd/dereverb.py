@@ -6,7 +6,12 @@
     dr.denoise_file("room.wav", "dry.wav")
     Dereverberator(gain=True)                          # WPE, then the Wiener gain of the spectral baseline on its result
 
+    live = StreamDereverberator(n_streams=2)           # audio that is still arriving: recursive WPE, one update per frame
+    out = live.push(block); ...; out = live.flush()    # the surface of StreamDenoiser; DereverbStreamPool: that of StreamPool
+    d, mag, state = wpe_online(spec)                   # the recursion on a spectrogram; pass state and first_frame to go on
+
     python -m audiodenoiser_amd.dereverb IN OUT [--reference CLEAN] [--taps K] [--delay D] [--iterations I] [--gain]
+    python -m audiodenoiser_amd.dereverb IN OUT --live [--chunk N] [--block B] [--forget A] [--gain] [--reference CLEAN]
 
 The operator is DEFINED in ``include/adn.h`` ("dereverb"; float64 restatement: ``tests/dereverb_ref.py``) and is unpinned against
 any package: single-channel WPE, delayed linear prediction per frequency bin with the variance re-estimated from the last result
@@ -21,8 +26,16 @@ on the ``reverb`` noise type has to beat in the ``--reference`` report.  ``Derev
 
 ``denoise``, ``denoise_file``, the rate handling and the every-channel-a-clip rule are ``Denoiser``'s, unchanged.
 
-What is NOT here: online / recursive WPE for streams, more than one channel, any tuning of the defaults by ear.  There is no CPU
-path.
+The streaming form is a different algorithm with its own kernel, DEFINED in ``include/adn.h`` ("dereverb stream"; float64
+restatement: ``tests/dereverb_stream_ref.py``; ``csrc/dereverb_stream_kernels.hip``): recursive least squares per (stream, bin), a
+K x K inverse correlation matrix and K taps carried on the device and updated once per frame.  ``StreamDereverberator`` is
+``StreamDenoiser`` and ``DereverbStreamPool`` is ``StreamPool`` with ``adn_wpe_stream`` / ``adn_wpe_stream_pool`` in the network's
+place, exactly as ``StreamSpectralDenoiser`` / ``SpectralStreamPool`` carry the spectral gain; ``gain=True`` runs that gain on the
+same columns afterwards, the streaming form of the cascade.  A row that starts at frame 0 starts fresh whatever the WPE state
+holds, so there is nothing to reset.
+
+What is NOT here: more than one channel, look-ahead or iterated online variants, any tuning of the defaults by ear.  There is no
+CPU path.
 """
 from __future__ import annotations
 
@@ -34,11 +47,13 @@ import os
 import torch
 
 from . import _lib
-from .baseline import SpectralParams, spectral_gain
+from .baseline import SPECTRAL_MAX_ROWS, SpectralParams, _spectral_device, spectral_gain, spectral_gain_windows
 from .denoise import Denoiser, _report, _stream
 from .griffin_lim import stft_complex
+from .stream import POOL_MAX_ROWS, PoolBook, StreamDenoiser, StreamPool, _check_stream_args
 
-__all__ = ["WpeParams", "wpe", "Dereverberator"]
+__all__ = ["WpeParams", "wpe", "Dereverberator", "WpeStreamParams", "wpe_online", "wpe_stream_state_bytes", "StreamDereverberator",
+           "DereverbStreamPool"]
 
 
 @dataclasses.dataclass(frozen=True)
@@ -146,6 +161,207 @@ class Dereverberator(Denoiser):
         return out
 
 
+@dataclasses.dataclass(frozen=True)
+class WpeStreamParams:
+    """``adn_wpe_stream_params`` of ``include/adn.h`` ("dereverb stream") with its defaults and its legal ranges."""
+    taps: int = 20
+    delay: int = 3
+    forget: float = 0.99
+    loading: float = 300.0
+    power_floor: float = 0.01
+    smooth: float = 0.9
+
+    def __post_init__(self):
+        for name, lo, hi in (("taps", 1, 32), ("delay", 1, 8)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError(f"WpeStreamParams: need an integer {lo} <= {name} <= {hi}")
+        # the ranges hold for the fp32 values the library sees; a NaN fails every comparison
+        f32 = {name: ctypes.c_float(float(getattr(self, name))).value for name in ("forget", "loading", "power_floor", "smooth")}
+        if not 0.95 <= float(self.forget) <= 1.0 or not ctypes.c_float(0.95).value <= f32["forget"]:
+            raise ValueError("WpeStreamParams: need 0.95 <= forget <= 1")
+        if not 1.0 <= float(self.loading) <= 1e6:
+            raise ValueError("WpeStreamParams: need 1 <= loading <= 1e6")
+        if not 0.0 < float(self.power_floor) <= 1.0 or not f32["power_floor"] > 0.0:
+            raise ValueError("WpeStreamParams: need 0 < power_floor <= 1")
+        if not 0.0 <= float(self.smooth) < 1.0 or not f32["smooth"] < 1.0:
+            raise ValueError("WpeStreamParams: need 0 <= smooth < 1")
+
+    def to_struct(self) -> "_lib.WpeStreamParamsStruct":
+        return _lib.WpeStreamParamsStruct(int(self.taps), int(self.delay), float(self.forget), float(self.loading),
+                                          float(self.power_floor), float(self.smooth))
+
+
+def _stream_params(who, params):
+    if params is not None and not isinstance(params, WpeStreamParams):
+        raise TypeError(f"{who}: params must be a WpeStreamParams")
+    return ctypes.byref(params.to_struct()) if params is not None else None
+
+
+def wpe_stream_state_bytes(n_slots: int, n_bins: int, params: WpeStreamParams = None) -> int:
+    """``adn_wpe_stream_state_bytes``: the bytes of the opaque WPE state of ``n_slots`` rows of ``n_bins`` bins (no device needed)."""
+    need = ctypes.c_size_t(0)
+    _lib.check(_lib.load().adn_wpe_stream_state_bytes(n_slots, n_bins, _stream_params("wpe_stream_state_bytes", params),
+                                                      ctypes.byref(need)), "adn_wpe_stream_state_bytes")
+    return int(need.value)
+
+
+def wpe_online(spec: torch.Tensor, state: torch.Tensor = None, first_frame: int = 0, params: WpeStreamParams = None,
+               mag_out: torch.Tensor = None, col0: int = 0):
+    """``adn_wpe_online`` on the current stream.  ``spec``: complex64 ``(n_rows, T, F)`` on a ROCm device, the frames
+    ``first_frame ... first_frame + T - 1`` of every row.  ``state``: the uint8 tensor an earlier call returned for the frames before
+    them (None allocates one; with ``first_frame = 0`` every row starts fresh whatever it holds); it is updated IN PLACE.
+    ``mag_out``: float32 ``(n_rows, 1, F, width)`` whose columns ``[col0, col0 + T)`` are written and nothing else; None allocates
+    ``(n_rows, 1, F, T)``.  Returns ``(d, mag_out, state)``, ``d`` a new complex64 tensor of ``spec``'s shape."""
+    if not isinstance(spec, torch.Tensor) or not spec.is_cuda or spec.dtype != torch.complex64 or spec.dim() != 3:
+        raise ValueError("wpe_online: expected a (n_rows, n_frames, n_bins) complex64 tensor on a ROCm device")
+    p = _stream_params("wpe_online", params)
+    n, t, f = spec.shape
+    if n < 1 or t < 1 or f < 1:
+        raise ValueError("wpe_online: need at least one row, one frame and one bin")
+    if not (isinstance(first_frame, int) and first_frame >= 0 and isinstance(col0, int) and col0 >= 0):
+        raise ValueError("wpe_online: need integers first_frame >= 0 and col0 >= 0")
+    dev = spec.device
+    need = wpe_stream_state_bytes(n, f, params)
+    if state is None:
+        if first_frame != 0:
+            raise ValueError("wpe_online: first_frame > 0 continues a row: pass the state of the call before")
+        state = torch.empty((need,), dtype=torch.uint8, device=dev)
+    elif (not isinstance(state, torch.Tensor) or not state.is_cuda or state.device != dev or state.dtype != torch.uint8
+          or state.dim() != 1 or state.numel() < need or not state.is_contiguous()):
+        raise ValueError("wpe_online: state must be a contiguous uint8 tensor of at least wpe_stream_state_bytes on spec's device")
+    s = torch.view_as_real(spec.contiguous())
+    if mag_out is None:
+        if col0 != 0:
+            raise ValueError("wpe_online: col0 needs a mag_out buffer")
+        mag_out = torch.empty((n, 1, f, t), dtype=torch.float32, device=dev)
+    elif (not isinstance(mag_out, torch.Tensor) or not mag_out.is_cuda or mag_out.device != dev or mag_out.dtype != torch.float32
+          or mag_out.dim() != 4 or tuple(mag_out.shape[:3]) != (n, 1, f) or not mag_out.is_contiguous()):
+        raise ValueError("wpe_online: mag_out must be a contiguous (n_rows, 1, n_bins, width) float32 tensor on spec's device")
+    out = torch.empty((n, t, f, 2), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().adn_wpe_online(s.data_ptr(), n, t, f, first_frame, p, state.data_ptr(), state.numel(), n,
+                                              out.data_ptr(), mag_out.data_ptr(), int(mag_out.shape[3]), col0, _stream(dev)),
+                   "adn_wpe_online")
+    return torch.view_as_complex(out), mag_out, state
+
+
+class StreamDereverberator(StreamDenoiser):
+    """``StreamDenoiser`` with recursive WPE in the network's place: no model, the phase of the dereverberated spectrum, the same
+    surface -- ``push``, ``flush``, ``reset``, ``received``, ``emitted``, ``latency_samples``, ``analyze``, ``emit``, ``input_rate``.
+
+    The operator is causal, so ``lookahead_frames`` is 0 and ``window_frames = max(16, block_frames)`` is only the carrier the
+    stream geometry needs: each run of steps calls ``adn_wpe_stream`` in place on the analysed windows -- ``d`` into the frames the
+    steps emit, ``|d|`` into the ``block_frames`` columns ``adn_stream_emit`` reads -- and with ``gain=True`` then
+    ``adn_spectral_gain_windows`` on the same columns (``gain_params``), whose three floats per bin live beside the WPE state.  The
+    WPE state needs no reset: a stream's frame 0 starts it afresh.  ``block_frames = 4``: as ``StreamSpectralDenoiser``."""
+
+    def __init__(self, device=None, n_streams: int = 1, sample_rate: int = 8000, n_fft: int = 512, hop_length: int = 128,
+                 block_frames: int = 4, params: WpeStreamParams = None, gain: bool = False, gain_params: SpectralParams = None,
+                 input_rate=None):
+        window = max(16, block_frames) if isinstance(block_frames, int) else 16
+        _check_stream_args("StreamDereverberator", n_streams, sample_rate, n_fft, hop_length, window, block_frames, 0, 64, input_rate)
+        _stream_params("StreamDereverberator", params)
+        dev = _spectral_device("StreamDereverberator", device, gain_params)
+        self.model = None
+        self.params = WpeStreamParams() if params is None else params
+        self.gain = bool(gain)
+        self.gain_params = SpectralParams() if gain_params is None else gain_params
+        f = n_fft // 2 + 1
+        self._wpe_state = torch.empty((wpe_stream_state_bytes(n_streams, f, self.params),), dtype=torch.uint8, device=dev)
+        self._gain_state = torch.empty((n_streams, 3, f), dtype=torch.float32, device=dev)
+        self._setup(dev, n_streams, sample_rate, n_fft, hop_length, window, block_frames, 0, 64, input_rate)
+
+    def reset(self):
+        """Forget the running stream, the gain's noise estimate included: the object is ready for a new one."""
+        super().reset()
+        self._gain_state.fill_(-1.0)
+
+    def network(self, x):
+        raise RuntimeError("StreamDereverberator: there is no network; WPE runs between analyze and emit (adn_wpe_stream)")
+
+    def _net(self, x: torch.Tensor, first_step: int, n_steps: int, final_length: int = -1) -> torch.Tensor:
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().adn_wpe_stream(self._state.data_ptr(), self._state.numel(), x.data_ptr(), self.n_streams, first_step,
+                                                  n_steps, final_length, *self._plan, self.max_steps,
+                                                  ctypes.byref(self.params.to_struct()), self._wpe_state.data_ptr(),
+                                                  self._wpe_state.numel(), _stream(self.device)), "adn_wpe_stream")
+        if self.gain:
+            w, b = self.window_frames, self.block_frames
+            spectral_gain_windows(x, self._gain_state, w - b, b, n_steps, self.gain_params, None, x)
+        return x
+
+
+class DereverbStreamPool(StreamPool):
+    """``StreamPool`` with recursive WPE in the network's place: ``open``, ``push``, ``push_many``, ``close``, ``step``, ``drain``,
+    ``room``, ``received`` and the rates are the parent's.  A tick calls ``adn_wpe_stream_pool`` once per group of up to 256 rows,
+    in place on the analysed windows (and with ``gain=True`` ``adn_spectral_gain_windows`` with ``rows = (slot, step == 0)``).  A
+    stream's frame 0 starts its slot afresh, so a slot is reusable without a reset.  Each stream is, bit for bit, what a solo
+    ``StreamDereverberator`` (at its ``input_rate``) returns for the same samples."""
+
+    def __init__(self, device=None, max_streams: int = 64, backlog_steps: int = 4, sample_rate: int = 8000, n_fft: int = 512,
+                 hop_length: int = 128, block_frames: int = 4, params: WpeStreamParams = None, gain: bool = False,
+                 gain_params: SpectralParams = None, input_rates=None):
+        window = max(16, block_frames) if isinstance(block_frames, int) else 16
+        self.book = PoolBook(max_streams, backlog_steps, n_fft, hop_length, window, block_frames, 0, input_rates, sample_rate)
+        _stream_params("DereverbStreamPool", params)
+        dev = _spectral_device("DereverbStreamPool", device, gain_params)
+        self.model, self.batch_windows = None, POOL_MAX_ROWS
+        self.params = WpeStreamParams() if params is None else params
+        self.gain = bool(gain)
+        self.gain_params = SpectralParams() if gain_params is None else gain_params
+        f = n_fft // 2 + 1
+        self._wpe_state = torch.empty((wpe_stream_state_bytes(max_streams, f, self.params),), dtype=torch.uint8, device=dev)
+        self._gain_state = torch.empty((max_streams, 3, f), dtype=torch.float32, device=dev)
+        self._setup(dev)
+
+    def reset(self):
+        """Forget every stream, the gain's noise estimates included: all slots are free."""
+        super().reset()
+        self._gain_state.fill_(-1.0)
+
+    def network(self, x):
+        raise RuntimeError("DereverbStreamPool: there is no network; WPE runs between analyze and emit (adn_wpe_stream_pool)")
+
+    def _net(self, x: torch.Tensor, rows) -> torch.Tensor:
+        w, b = self.book.window_frames, self.book.block_frames
+        L, p = _lib.load(), ctypes.byref(self.params.to_struct())
+        for i in range(0, len(rows), POOL_MAX_ROWS):
+            part, group = x[i:i + POOL_MAX_ROWS], rows[i:i + POOL_MAX_ROWS]
+            with torch.cuda.device(self.device):
+                _lib.check(L.adn_wpe_stream_pool(self._state.data_ptr(), self._state.numel(), *self._args, self._rows(group), len(group),
+                                                 part.data_ptr(), p, self._wpe_state.data_ptr(), self._wpe_state.numel(),
+                                                 _stream(self.device)), "adn_wpe_stream_pool")
+            if self.gain:
+                for j in range(0, len(group), SPECTRAL_MAX_ROWS):
+                    sub = part[j:j + SPECTRAL_MAX_ROWS]
+                    spectral_gain_windows(sub, self._gain_state, w - b, b, 1, self.gain_params,
+                                          [(slot, step == 0) for slot, step, _ in group[j:j + SPECTRAL_MAX_ROWS]], sub)
+        return x
+
+
+def _live(args) -> int:
+    """``--live``: the file pushed through ``StreamDereverberator`` at its own rate, ``--chunk`` samples at a time."""
+    import numpy as np
+
+    from .wav import read_wav, write_wav
+    audio, rate = read_wav(args.src, mono=False)             # (L, channels): every channel is a stream
+    dev = _lib.staging_device()
+    x = torch.from_numpy(np.ascontiguousarray(audio.T, dtype=np.float32)).to(dev)
+    params = WpeStreamParams(taps=args.taps, delay=args.delay, forget=args.forget)
+    sd = StreamDereverberator(dev, n_streams=x.shape[0], block_frames=args.block, params=params, gain=args.gain, input_rate=int(rate))
+    outs = [sd.push(x[:, i:i + args.chunk]) for i in range(0, x.shape[1], args.chunk)]
+    latency = sd.latency_input_samples
+    outs.append(sd.flush())
+    out = torch.cat(outs, dim=1)
+    write_wav(args.dst, np.ascontiguousarray(out.cpu().numpy().T), rate)
+    print(f"{args.src} -> {args.dst}: {x.shape[1]} samples at {rate} Hz in pushes of {args.chunk} at its own rate, "
+          f"latency {latency} samples")
+    if args.reference is not None:
+        print(_report(args.src, args.dst, args.reference))
+    return 0
+
+
 def main(argv=None) -> int:
     import argparse
     ap = argparse.ArgumentParser(prog="python -m audiodenoiser_amd.dereverb",
@@ -158,7 +374,21 @@ def main(argv=None) -> int:
     ap.add_argument("--delay", type=int, default=WpeParams.delay, help="prediction delay D in frames, 1 ... 8")
     ap.add_argument("--iterations", type=int, default=WpeParams.iterations, help="iterations I, 1 ... 8")
     ap.add_argument("--gain", action="store_true", help="run the spectral baseline's Wiener gain on the result of WPE")
+    ap.add_argument("--live", action="store_true",
+                    help="push the file (not a folder) through the streaming form (recursive WPE) at its own rate, as a live feed arrives")
+    ap.add_argument("--chunk", type=int, default=1024, help="with --live: samples per push, at the file's rate")
+    ap.add_argument("--block", type=int, default=4, help="with --live: frames per step (latency (block - 1) hop + n_fft samples)")
+    ap.add_argument("--forget", type=float, default=WpeStreamParams.forget, help="with --live: forgetting factor, 0.95 ... 1")
     args = ap.parse_args(argv)
+    if args.live:
+        if args.chunk < 1 or args.block < 1:
+            ap.error("--chunk and --block must be >= 1")
+        if os.path.isdir(args.src):
+            ap.error("--live takes one wav file")
+        try:
+            return _live(args)
+        except ValueError as exc:
+            ap.error(str(exc))
     try:
         params = WpeParams(taps=args.taps, delay=args.delay, iterations=args.iterations)
     except ValueError as exc:

@@ -240,9 +240,9 @@ class StreamDenoiser:
         """The U-Net over ``batch_windows`` windows at a time, into slices of one output buffer (as ``Denoiser.network``)."""
         return _network(self.model, x, self.batch_windows, "StreamDenoiser")
 
-    def _net(self, x: torch.Tensor, first_step: int, n_steps: int) -> torch.Tensor:
-        """What stands between ``analyze`` and ``emit`` for steps ``first_step ..`` (``x``: a stream's ``n_steps`` steps consecutive):
-        here the network, which needs neither number."""
+    def _net(self, x: torch.Tensor, first_step: int, n_steps: int, final_length: int = -1) -> torch.Tensor:
+        """What stands between ``analyze`` and ``emit`` for steps ``first_step ..`` of a stream that runs (``final_length`` -1) or has
+        ended at that length (``x``: a stream's ``n_steps`` steps consecutive): here the network, which needs none of the numbers."""
         return self.network(x)
 
     def emit_count(self, first_step: int, n_steps: int, final_length: int = -1) -> int:
@@ -264,7 +264,7 @@ class StreamDenoiser:
         """Steps ``_done .. _done + n_steps - 1`` on the pending samples; what they bring leaves the pending buffer."""
         first = self._done
         x = self.analyze(self._pend, self._cap, first, n_steps, final_length)
-        out = self.emit(self._net(x, first, n_steps), first, n_steps, final_length)
+        out = self.emit(self._net(x, first, n_steps, final_length), first, n_steps, final_length)
         end = self._end_of(first + n_steps - 1)
         used = min(max(end - self._base, 0), self._fill)
         rest = self._fill - used

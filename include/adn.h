@@ -33,7 +33,7 @@
 
 #include <stddef.h>
 
-/* The 64 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 68 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -688,11 +688,103 @@ ADN_API int adn_spectral_gain_windows(const float *windows, float *y, int n_rows
  * Limits (ADN_ERR_INVALID before any launch): NULL or misaligned spec / spec_out / mag_out; n_clips, n_frames, n_bins >= 1;
  * width >= n_frames with a mag_out; overlapping spec and spec_out; launch grid < 2^31 workgroups; the parameters as above.
  * ADN_ERR_WORKSPACE: workspace_bytes below adn_wpe_workspace_bytes.  Element offsets are 64-bit.
- * Not here: online / recursive WPE for streams; more than one channel; any tuning by ear. */
+ * For audio that is still arriving, online / recursive WPE: the next section, "dereverb stream".
+ * Not here: more than one channel; any tuning by ear. */
 typedef struct adn_wpe_params { int taps, delay, iterations; float loading, power_floor; } adn_wpe_params;
 ADN_API int adn_wpe_workspace_bytes(int n_clips, int n_frames, int n_bins, const adn_wpe_params *params, size_t *bytes);
 ADN_API int adn_wpe(const float *spec, int n_clips, int n_frames, int n_bins, const adn_wpe_params *params, void *workspace,
                     size_t workspace_bytes, float *spec_out, float *mag_out, int width, void *stream);
+
+/* ---- dereverb stream: recursive WPE, one update per frame, for audio that is still arriving -----------------------------------------
+ * No reference counterpart and no checkpoint.  The library DEFINES the operator below (float64 restatement:
+ * tests/dereverb_stream_ref.py); it is UNPINNED against any package, like its offline sibling "dereverb".  It is a different
+ * algorithm from that one, not a streaming evaluation of it: recursive least squares per (stream, bin) row -- a K x K inverse
+ * correlation matrix P and K taps g are carried and updated once per frame, the variance is the a-priori error's own power with a
+ * floor that follows the row's running power.  It is causal: d_t depends on X_0 ... X_t only.
+ * Not validated: the defaults are the values of the host prototype; they were not tuned by ear.  They differ on purpose from the
+ * offline loading and power_floor, whose meanings are different.
+ *
+ * Every (stream, bin) row is independent.  X_t are the row's complex values, t = 0, 1, ..., and X_t = 0 for t < 0.  In fp32:
+ *   first frame (t = 0):  g = 0 (K taps),  P = (1 / delta) I (K x K),  s_0 = p_0
+ *   p_t    = fmaf(re, re, im * im)
+ *   s_t    = beta s_{t-1} + (1 - beta) p_t                      (t > 0)
+ *   phi_t  = max(rho s_t, 1e-30)
+ *   x~_j   = X_{t-D-j},  j = 0 ... K-1                          (raw inputs, never outputs)
+ *   e_t    = X_t - sum_j conj(g_j) x~_j                         (the a-priori error = the OUTPUT d_t; j ascending)
+ *   lam_t  = max(|e_t|^2, phi_t)                                (|.|^2 as p_t)
+ *   u_j    = sum_k P_jk x~_k                                    (k ascending)
+ *   q      = sum_j Re(conj(x~_j) u_j)                           (j ascending)
+ *   den    = alpha lam_t + q
+ *   k_j    = u_j / den
+ *   P_jk  <- (P_jk - k_j conj(u_k)) / alpha   for j >= k;  Im P_jj := 0;  P_kj := conj(P_jk)
+ *   g_j   <- g_j + k_j conj(e_t)
+ *   M_t    = sqrtf(fmaf(e.re, e.re, e.im * e.im))               (the optional magnitude)
+ * The Hermitian update is part of the DEFINITION: only the lower triangle is computed, the upper one is its conjugate.  The plain
+ * update P <- (P - k u^H) / alpha loses the symmetry to rounding and diverges within a few hundred frames, in float64 as well.
+ * Arithmetic: a complex multiply-add is two fmaf per component, the real-part product first (acc.re = fmaf(-+a.im b.im,
+ * fmaf(a.re, b.re, acc.re)), acc.im = fmaf(a.im b.re, fmaf(+-a.re b.im, acc.im))); the sums of e_t, u_j and q start at +0, and
+ * e_t is X_t minus the finished sum; s_t is two products and their sum, den a product and a sum, each rounded; the divisions by
+ * den and by alpha are divisions, componentwise and correctly rounded, as is the square root.  max(x, c) is `x < c ? c : x`: a
+ * NaN x stays NaN.  1 / delta and 1 - beta are computed once, in fp32.
+ * The recursion is exact RLS: with the lam_t it produced, g after T frames solves
+ *   (alpha^T delta I + sum_t alpha^(T-1-t) x~_t x~_t^H / lam_t) g = sum_t alpha^(T-1-t) x~_t conj(X_t) / lam_t;
+ * with alpha = 1 that is the growing-window solution (tests/test_dereverb_stream_host.py, to 1e-9 in float64).
+ * Parameters (adn_wpe_stream_params; NULL = the defaults): taps K 20, delay D 3, forget alpha 0.99, loading delta 300,
+ * power_floor rho 0.01, smooth beta 0.9.  delta is dimensionless (x~ x~^H / lam is); it is the inverse of P's first diagonal.
+ * Legal (ADN_ERR_INVALID otherwise, before any launch, the message names the field; a NaN is illegal): 1 <= taps <= 32;
+ * 1 <= delay <= 8; 0.95 <= forget <= 1; 1 <= loading <= 1e6; 0 < power_floor <= 1; 0 <= smooth < 1.
+ * Consequences: the first D frames of a row come back bit for bit (no tap has a frame: e_t = X_t - (+0)); an all-zero row gives
+ * zeros; a non-finite value is confined to its own (stream, bin) row, which stays poisoned from then on.
+ * Not claimed: a row that is exactly zero for very long with alpha < 1 grows P by 1 / alpha per frame (the wind-up of every
+ * exponentially forgetting RLS) and overflows fp32 after about ln(3e38 delta) / -ln(alpha) frames (9400 at the defaults).
+ *
+ * What is pinned.  The result is bounded against the float64 restatement (tests/test_gpu_dereverb_stream.py: per row
+ * max |d - d64| <= 4 FLOOR max |d64|, FLOOR the error of the same statements run in fp32 on the host); it is NOT pinned bit for bit
+ * to numpy.  Pinned bit for bit: two calls give the same result; cutting a row's frames into calls (the carried state) changes
+ * nothing; a row gives the same bits alone or in any batch, in whatever slot; a bin gives the same bits whichever other bins share
+ * the call; a stream of the pool equals the same stream in lockstep.  Deterministic: no atomics, no reduction across lanes.
+ *
+ * State (adn_wpe_stream_state_bytes(n_slots, n_bins, params), caller-owned, opaque, 8-byte aligned, its size depends on taps and
+ * delay): per (slot, bin) the taps g, the full P, s, and a ring of the last D + K raw frames indexed by the frame number -- the
+ * history lives here, not in a stream's X ring, which is overwritten with d.  A ROW WHOSE FIRST FRAME OF THE CALL IS FRAME 0
+ * STARTS FRESH whatever the state holds: there is no reset call, no sentinel and no flag; the state may be handed over holding
+ * anything, and a pool slot is reused without a reset.  Any other call continues the row at the frame after its last one; the
+ * frames of a row go in order.  The state is read and written by the lanes that own the row.
+ *
+ * Three entry points, one step function, three places the frames come from:
+ *   adn_wpe_online: spec and spec_out are frame-major (n_rows, n_frames, n_bins, 2) fp32 as adn_stft_complex writes it, 8-byte
+ *     aligned, and may not overlap; they hold the frames first_frame ... first_frame + n_frames - 1 of every row.  Row i uses slot
+ *     i of the state.  mag_out may be NULL; otherwise (n_rows, 1, n_bins, width) fp32, the network-output layout: the call writes
+ *     columns [col0, col0 + n_frames) of it, all of spec_out, the state of its rows, and not one byte else.
+ *   adn_wpe_stream: between adn_stream_analyze and adn_stream_emit of the same steps (the geometry arguments are theirs; lookahead
+ *     must be 0, the operator is causal).  It reads the frames f_first ... f_last the steps emit from the X ring of stream_state,
+ *     writes d_t back into the same ring cells, and M_t into columns [window - block, window) of y, the (n_streams * n_steps, 1, F,
+ *     window) windows buffer adn_stream_analyze wrote -- no other byte of it, and nothing for the frames at and past the end of a
+ *     finished stream.  adn_stream_emit then does what it always does, magnitude from y and phase from the X ring: the inverse STFT
+ *     of |d| with the phase of d, the rule Dereverberator uses offline.  Stream i uses slot i of wpe_state (n_streams slots).
+ *   adn_wpe_stream_pool: the same between adn_stream_pool_analyze and adn_stream_pool_emit, for their rows (slot, step,
+ *     final_length), handed to the kernel by value; y is the (n_rows, 1, F, window) buffer.  wpe_state has n_slots slots.
+ * Cost: one launch, n_rows x ceil(n_bins / 8) workgroups of 8 rows; no workspace, no atomics, no constant table (a capture may
+ * hold a first call); nothing blocks or allocates.  A call's time is the per-frame chain of a workgroup (measured: 8 us a frame),
+ * not the state's bytes (0.17 of their bound at 256 feeds): profiles/bench_dereverb_stream.md.
+ * Limits (ADN_ERR_INVALID before any launch): NULL or misaligned pointers; every count >= 1; n_slots, n_bins <= 2^20;
+ * first_frame >= 0, first_frame + n_frames < 2^31; n_rows <= n_slots; col0 >= 0 and col0 + n_frames <= width with a mag_out;
+ * overlapping spec and spec_out; lookahead != 0; everything adn_stream_emit / adn_stream_pool_emit refuse about the geometry, the
+ * steps and the rows (more than ADN_STREAM_POOL_MAX_ROWS rows, a slot out of range or named twice); launch grid < 2^31 workgroups;
+ * the parameters as above.  ADN_ERR_WORKSPACE: a state below its size function's bytes.  Element offsets are 64-bit.
+ * adn_wpe_stream_state_bytes is host-only (no device needed).
+ * Not here: more than one channel; look-ahead or iterated online variants; any tuning by ear. */
+typedef struct adn_wpe_stream_params { int taps, delay; float forget, loading, power_floor, smooth; } adn_wpe_stream_params;
+ADN_API int adn_wpe_stream_state_bytes(int n_slots, int n_bins, const adn_wpe_stream_params *params, size_t *bytes);
+ADN_API int adn_wpe_online(const float *spec, int n_rows, int n_frames, int n_bins, long first_frame,
+                           const adn_wpe_stream_params *params, void *state, size_t state_bytes, int n_slots, float *spec_out,
+                           float *mag_out, int width, int col0, void *stream);
+ADN_API int adn_wpe_stream(void *stream_state, size_t stream_state_bytes, float *y, int n_streams, long first_step, int n_steps,
+                           long final_length, int n_fft, int hop, int window, int block, int lookahead, int max_steps,
+                           const adn_wpe_stream_params *params, void *wpe_state, size_t wpe_state_bytes, void *stream);
+ADN_API int adn_wpe_stream_pool(void *pool_state, size_t pool_state_bytes, int n_slots, int n_fft, int hop, int window, int block,
+                                int lookahead, long ring_samples, const adn_stream_pool_row *rows, int n_rows, float *y,
+                                const adn_wpe_stream_params *params, void *wpe_state, size_t wpe_state_bytes, void *stream);
 
 /* ---- environment switches -------------------------------------------------------------------------------------------------
  * Read ONCE, when a U-Net handle is created (never per call).  None is needed in production: the defaults are the measured best
