@@ -90,8 +90,9 @@ struct adn_unet {
     // whatever batch it is computed in.
     bool allow_split = false;
     // fp32 transposed convolutions on the bf16 matrix cores through a three-term split of both operands (six products, fp32
-    // accumulation; conv_dma<..., SPLIT>): fp32-level accuracy at 3/8 of the exact-fp32 matrix time.  ADN_CONVT_SPLIT=0 when the
-    // handle is created keeps the exact-fp32 MFMA form.
+    // accumulation; conv_dma<..., SPLIT>): the accuracy of an fp32 accumulation chain -- twelve roundings per 16 channels against the
+    // exact-fp32 MFMA's sixteen, a block with them within 1.1 x of its fp32 floor (profiles/f32_blocks.md) -- at 3/8 of the exact-fp32
+    // matrix time.  ADN_CONVT_SPLIT=0 when the handle is created keeps the exact-fp32 MFMA form.
     bool convt_split = true;
     // Small grids (one or a few clips): a 3x3 layer whose F(4x4,3x3) launch would be fewer than `auto_grid` workgroups (2 per CU)
     // runs on the finer-grained F(2x2,3x3) kernel instead, cut along K where even that grid cannot fill the chip

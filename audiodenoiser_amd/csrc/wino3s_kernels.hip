@@ -11,6 +11,13 @@
 // the 6x6 transform domain (i: vertical).  Stages 1 and 3 are memory-bound: one thread per (row, half channel block) holds the
 // 36 values of four channels as 16-byte vectors, so a wave reads / writes V and M in 1 KB runs.
 // A row of the GEMM is one tile: a non-finite input pixel reaches the tiles whose 6x6 patch holds it and no other.
+//
+// Numerics (tests/test_gpu_f32_blocks.py, profiles/f32_blocks.md): the split is exact, so what the form adds to F(4x4,3x3) in fp32
+// is the roundings of its accumulator alone -- twelve per 16 channels (six products, and the bf16 instruction rounds after each 8
+// of its 16 terms) where the exact-fp32 MFMA rounds sixteen times.  A block that runs the form sits ON the floor of that
+// arithmetic restated in another order (E rms 7 - 35 fp32 ulps of the block's rms against floors of 8 - 38, 0.73 - 1.09 of the
+// floor; the one-launch F(4x4) kernel: 7 - 48), and every product is needed: with one of the three second-order products missing a
+// block lands 1.4 - 4 x outside the bound of twice the floor.
 #include "adn_internal.h"
 
 namespace adn {
