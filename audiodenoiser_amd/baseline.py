@@ -44,9 +44,10 @@ import os
 import torch
 
 from . import _lib
-from .denoise import Denoiser, _report, _stream
+from ._host import check_stft_plan, current_stream, rocm_device, run_files, run_live
+from .denoise import Denoiser
 from .griffin_lim import stft_complex
-from .stream import PoolBook, StreamDenoiser, StreamPool, _check_stream_args
+from .stream import PoolBook, StreamDenoiser, StreamPool, _check_stream_args, causal_carrier
 
 __all__ = ["SpectralParams", "spectral_gain", "SpectralDenoiser", "spectral_gain_windows", "StreamSpectralDenoiser",
            "SpectralStreamPool"]
@@ -112,9 +113,16 @@ def spectral_gain(spec: torch.Tensor, params: SpectralParams = None, state: torc
     p = ctypes.byref(params.to_struct()) if params is not None else None
     with torch.cuda.device(dev):
         _lib.check(_lib.load().adn_spectral_gain(s.data_ptr(), n, t, f, p, state.data_ptr() if state is not None else None,
-                                                 new_state.data_ptr(), out.data_ptr(), int(out.shape[3]), int(col0), _stream(dev)),
+                                                 new_state.data_ptr(), out.data_ptr(), int(out.shape[3]), int(col0), current_stream(dev)),
                    "adn_spectral_gain")
     return out, new_state
+
+
+def _spectral_params(who, params, name: str = "params") -> SpectralParams:
+    """The ``params`` argument of a class: a ``SpectralParams``, None for the defaults."""
+    if params is not None and not isinstance(params, SpectralParams):
+        raise TypeError(f"{who}: {name} must be a SpectralParams")
+    return SpectralParams() if params is None else params
 
 
 class SpectralDenoiser(Denoiser):
@@ -122,25 +130,10 @@ class SpectralDenoiser(Denoiser):
 
     def __init__(self, device=None, sample_rate: int = 8000, n_fft: int = 512, hop_length: int = 128,
                  params: SpectralParams = None):
-        if not (isinstance(n_fft, int) and 64 <= n_fft <= 4096 and n_fft & (n_fft - 1) == 0):
-            raise ValueError("SpectralDenoiser: n_fft must be a power of two in [64, 4096]")
-        if not (isinstance(hop_length, int) and 1 <= hop_length <= n_fft // 4):
-            raise ValueError("SpectralDenoiser: need 1 <= hop_length <= n_fft / 4 (the inverse transform of the whole input length "
-                             "divides by a window sum-of-squares that falls to 2e-8 at n_fft / 2)")
-        if not (isinstance(sample_rate, int) and sample_rate >= 1):
-            raise ValueError("SpectralDenoiser: sample_rate must be >= 1")
-        if params is not None and not isinstance(params, SpectralParams):
-            raise TypeError("SpectralDenoiser: params must be a SpectralParams")
-        dev = _lib.staging_device() if device is None else torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("SpectralDenoiser: the device must be a ROCm device; there is no CPU path")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.model, self.device = None, dev
-        self.sample_rate, self.n_fft, self.hop_length = sample_rate, n_fft, hop_length
-        self.params = SpectralParams() if params is None else params
-        self.phase = "noisy"
-        self.n_bins = n_fft // 2 + 1
+        check_stft_plan("SpectralDenoiser", n_fft, hop_length, sample_rate)
+        self.params = _spectral_params("SpectralDenoiser", params)
+        self.model = None
+        self._setup(rocm_device("SpectralDenoiser", device), sample_rate, n_fft, hop_length, "noisy")
 
     def gain(self, spec: torch.Tensor) -> torch.Tensor:
         """complex64 ``(n_clips, T, F)`` -> the magnitudes ``(n_clips, 1, F, max(T, 16))`` that ``adn_denoise_resynth`` reads as
@@ -151,16 +144,9 @@ class SpectralDenoiser(Denoiser):
 
     def _core(self, x: torch.Tensor, rand) -> torch.Tensor:
         """``x`` (n_clips, L) at the working rate -> (n_clips, L)."""
-        n, length = x.shape
         spec = stft_complex(x, self.n_fft, self.hop_length)
         y = self.gain(spec)
-        out = torch.empty((n, length), dtype=torch.float32, device=x.device)
-        s = torch.view_as_real(spec)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().adn_denoise_resynth(y.data_ptr(), s.data_ptr(), n, length, self.n_fft, self.hop_length,
-                                                       int(y.shape[3]), 0, out.data_ptr(), _stream(x.device)),
-                       "adn_denoise_resynth")
-        return out
+        return self._resynth(y, spec, x.shape[1], int(y.shape[3]), 0)
 
 
 def spectral_gain_windows(windows: torch.Tensor, state: torch.Tensor, col0: int, n_cols: int, n_steps: int = 1,
@@ -198,20 +184,24 @@ def spectral_gain_windows(windows: torch.Tensor, state: torch.Tensor, col0: int,
     p = ctypes.byref(params.to_struct()) if params is not None else None
     with torch.cuda.device(dev):
         _lib.check(_lib.load().adn_spectral_gain_windows(windows.data_ptr(), out.data_ptr(), n_rows, n_steps, f, w, col0, n_cols, p,
-                                                         state.data_ptr(), int(state.shape[0]), table, _stream(dev)),
+                                                         state.data_ptr(), int(state.shape[0]), table, current_stream(dev)),
                    "adn_spectral_gain_windows")
     return out
 
 
-def _spectral_device(who, device, params):
-    if params is not None and not isinstance(params, SpectralParams):
-        raise TypeError(f"{who}: params must be a SpectralParams")
-    dev = _lib.staging_device() if device is None else torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"{who}: the device must be a ROCm device; there is no CPU path")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return dev
+def _gain_kept_columns(windows: torch.Tensor, rows, n_steps: int, state: torch.Tensor, plan, params: SpectralParams) -> torch.Tensor:
+    """The gain as a stream class runs it between ``analyze`` and ``emit``: in place on the ``block_frames`` columns a step keeps
+    (``plan``: the stream plan, ``(n_fft, hop, W, B, A)``).  ``rows=None``: a lockstep object's ``n_steps`` steps per stream, row i
+    on slot i.  Otherwise a pool tick's rows ``(slot, step, final_length)``, one step each, ``SPECTRAL_MAX_ROWS`` a call, a stream's
+    step 0 starting its slot afresh."""
+    w, b = plan[2], plan[3]
+    if rows is None:
+        return spectral_gain_windows(windows, state, w - b, b, n_steps, params, None, windows)
+    for i in range(0, len(rows), SPECTRAL_MAX_ROWS):
+        part = windows[i:i + SPECTRAL_MAX_ROWS]
+        spectral_gain_windows(part, state, w - b, b, 1, params, [(slot, step == 0) for slot, step, _ in rows[i:i + SPECTRAL_MAX_ROWS]],
+                              part)
+    return windows
 
 
 class StreamSpectralDenoiser(StreamDenoiser):
@@ -226,13 +216,14 @@ class StreamSpectralDenoiser(StreamDenoiser):
 
     def __init__(self, device=None, n_streams: int = 1, sample_rate: int = 8000, n_fft: int = 512, hop_length: int = 128,
                  block_frames: int = 4, params: SpectralParams = None, input_rate=None):
-        window = max(16, block_frames) if isinstance(block_frames, int) else 16
-        _check_stream_args("StreamSpectralDenoiser", n_streams, sample_rate, n_fft, hop_length, window, block_frames, 0, 64, input_rate)
-        dev = _spectral_device("StreamSpectralDenoiser", device, params)
+        window, ahead, batch = causal_carrier(block_frames)
+        _check_stream_args("StreamSpectralDenoiser", n_streams, sample_rate, n_fft, hop_length, window, block_frames, ahead, batch,
+                           input_rate)
+        self.params = _spectral_params("StreamSpectralDenoiser", params)
+        dev = rocm_device("StreamSpectralDenoiser", device)
         self.model = None
-        self.params = SpectralParams() if params is None else params
         self._gain_state = torch.empty((n_streams, 3, n_fft // 2 + 1), dtype=torch.float32, device=dev)
-        self._setup(dev, n_streams, sample_rate, n_fft, hop_length, window, block_frames, 0, 64, input_rate)
+        self._setup(dev, n_streams, sample_rate, n_fft, hop_length, window, block_frames, ahead, batch, input_rate)
 
     def reset(self):
         """Forget the running stream, the noise estimate included: the object is ready for a new one."""
@@ -243,8 +234,7 @@ class StreamSpectralDenoiser(StreamDenoiser):
         raise RuntimeError("StreamSpectralDenoiser: there is no network; the gain runs between analyze and emit (spectral_gain_windows)")
 
     def _net(self, x: torch.Tensor, first_step: int, n_steps: int, final_length: int = -1) -> torch.Tensor:
-        w, b = self.window_frames, self.block_frames
-        return spectral_gain_windows(x, self._gain_state, w - b, b, n_steps, self.params, None, x)
+        return _gain_kept_columns(x, None, n_steps, self._gain_state, self._plan, self.params)
 
 
 class SpectralStreamPool(StreamPool):
@@ -256,11 +246,11 @@ class SpectralStreamPool(StreamPool):
 
     def __init__(self, device=None, max_streams: int = 64, backlog_steps: int = 4, sample_rate: int = 8000, n_fft: int = 512,
                  hop_length: int = 128, block_frames: int = 4, params: SpectralParams = None, input_rates=None):
-        window = max(16, block_frames) if isinstance(block_frames, int) else 16
-        self.book = PoolBook(max_streams, backlog_steps, n_fft, hop_length, window, block_frames, 0, input_rates, sample_rate)
-        dev = _spectral_device("SpectralStreamPool", device, params)
+        window, ahead, _ = causal_carrier(block_frames)
+        self.book = PoolBook(max_streams, backlog_steps, n_fft, hop_length, window, block_frames, ahead, input_rates, sample_rate)
+        self.params = _spectral_params("SpectralStreamPool", params)
+        dev = rocm_device("SpectralStreamPool", device)
         self.model, self.batch_windows = None, SPECTRAL_MAX_ROWS
-        self.params = SpectralParams() if params is None else params
         self._gain_state = torch.empty((max_streams, 3, n_fft // 2 + 1), dtype=torch.float32, device=dev)
         self._setup(dev)
 
@@ -273,33 +263,7 @@ class SpectralStreamPool(StreamPool):
         raise RuntimeError("SpectralStreamPool: there is no network; the gain runs between analyze and emit (spectral_gain_windows)")
 
     def _net(self, x: torch.Tensor, rows) -> torch.Tensor:
-        w, b = self.book.window_frames, self.book.block_frames
-        for i in range(0, len(rows), SPECTRAL_MAX_ROWS):
-            part = x[i:i + SPECTRAL_MAX_ROWS]
-            spectral_gain_windows(part, self._gain_state, w - b, b, 1, self.params,
-                                  [(slot, step == 0) for slot, step, _ in rows[i:i + SPECTRAL_MAX_ROWS]], part)
-        return x
-
-
-def _live(args, params) -> int:
-    """``--live``: the file pushed through ``StreamSpectralDenoiser`` at its own rate, ``--chunk`` samples at a time."""
-    import numpy as np
-
-    from .wav import read_wav, write_wav
-    audio, rate = read_wav(args.src, mono=False)             # (L, channels): every channel is a stream
-    dev = _lib.staging_device()
-    x = torch.from_numpy(np.ascontiguousarray(audio.T, dtype=np.float32)).to(dev)
-    sd = StreamSpectralDenoiser(dev, n_streams=x.shape[0], block_frames=args.block, params=params, input_rate=int(rate))
-    outs = [sd.push(x[:, i:i + args.chunk]) for i in range(0, x.shape[1], args.chunk)]
-    latency = sd.latency_input_samples
-    outs.append(sd.flush())
-    out = torch.cat(outs, dim=1)
-    write_wav(args.dst, np.ascontiguousarray(out.cpu().numpy().T), rate)
-    print(f"{args.src} -> {args.dst}: {x.shape[1]} samples at {rate} Hz in pushes of {args.chunk} at its own rate, "
-          f"latency {latency} samples")
-    if args.reference is not None:
-        print(_report(args.src, args.dst, args.reference))
-    return 0
+        return _gain_kept_columns(x, rows, 1, self._gain_state, self.book.plan, self.params)
 
 
 def main(argv=None) -> int:
@@ -323,20 +287,11 @@ def main(argv=None) -> int:
             ap.error("--chunk and --block must be >= 1")
         if os.path.isdir(args.src):
             ap.error("--live takes one wav file")
-        return _live(args, params)
-    dn = SpectralDenoiser(params=params)
-    if os.path.isdir(args.src):
-        os.makedirs(args.dst, exist_ok=True)
-        jobs = [(os.path.join(args.src, f), os.path.join(args.dst, f)) for f in sorted(os.listdir(args.src)) if f.lower().endswith(".wav")]
-    else:
-        jobs = [(args.src, args.dst)]
-    for src, dst in jobs:
-        n, rate = dn.denoise_file(src, dst)
-        print(f"{src} -> {dst}: {n} samples at {rate} Hz")
-        if args.reference is not None:
-            ref = os.path.join(args.reference, os.path.basename(src)) if os.path.isdir(args.reference) else args.reference
-            print(_report(src, dst, ref))
-    return 0
+
+        def make(dev, n_streams, rate):
+            return StreamSpectralDenoiser(dev, n_streams=n_streams, block_frames=args.block, params=params, input_rate=rate)
+        return run_live(make, args.src, args.dst, args.chunk, args.reference)
+    return run_files(SpectralDenoiser(params=params), args.src, args.dst, args.reference)
 
 
 if __name__ == "__main__":

@@ -40,12 +40,12 @@ of scope.  There is no CPU path.
 from __future__ import annotations
 
 import ctypes
-import os
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._host import check_stft_plan, current_stream, model_device, run_files, stage, unet_windows
 from .griffin_lim import griffin_lim_reconstruction, stft_complex
 from .resample import _resample_device
 from .wav import read_wav, write_wav
@@ -61,18 +61,10 @@ def denoise_plan(n_frames: int, window_frames: int = 256, overlap_frames: int = 
     return int(k.value), int(w.value)
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 class Denoiser:
     def __init__(self, model, sample_rate: int = 8000, n_fft: int = 512, hop_length: int = 128, window_frames: int = 256,
                  overlap_frames: int = 32, phase: str = "noisy", batch_windows: int = 64, gl_iterations: int = 50):
-        if not (isinstance(n_fft, int) and 64 <= n_fft <= 4096 and n_fft & (n_fft - 1) == 0):
-            raise ValueError("Denoiser: n_fft must be a power of two in [64, 4096]")
-        if not (isinstance(hop_length, int) and 1 <= hop_length <= n_fft // 4):
-            raise ValueError("Denoiser: need 1 <= hop_length <= n_fft / 4 (the inverse transform of the whole input length divides "
-                             "by a window sum-of-squares that falls to 2e-8 at n_fft / 2)")
+        check_stft_plan("Denoiser", n_fft, hop_length, sample_rate)
         if not (isinstance(window_frames, int) and window_frames >= 16):
             raise ValueError("Denoiser: window_frames must be >= 16 (the network pools four times)")
         if not (isinstance(overlap_frames, int) and 0 <= overlap_frames <= window_frames // 2):
@@ -81,30 +73,35 @@ class Denoiser:
             raise ValueError("Denoiser: phase must be 'noisy' or 'griffin_lim'")
         if not (isinstance(batch_windows, int) and batch_windows >= 1):
             raise ValueError("Denoiser: batch_windows must be >= 1")
-        if not (isinstance(sample_rate, int) and sample_rate >= 1):
-            raise ValueError("Denoiser: sample_rate must be >= 1")
         if not (isinstance(gl_iterations, int) and gl_iterations >= 0):
             raise ValueError("Denoiser: gl_iterations must be >= 0")
-        from .model import UNet
-        if not isinstance(model, UNet) or model.in_channels != 1 or model.num_classes != 1:
-            raise ValueError("Denoiser: model must be an audiodenoiser_amd.model.UNet(1, 1)")
-        if model.training:
-            raise RuntimeError("Denoiser: the model is in train mode; call .eval() (the HIP forward is the eval forward)")
-        dev = next(model.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("Denoiser: the model must live on a ROCm device (model.to('cuda')); there is no CPU path")
-        self.model, self.device = model, dev
+        self.model = model
+        self._setup(model_device("Denoiser", model), sample_rate, n_fft, hop_length, phase, window_frames, overlap_frames,
+                    batch_windows, gl_iterations)
+
+    def _setup(self, dev, sample_rate, n_fft, hop_length, phase, window_frames=None, overlap_frames=None, batch_windows=None,
+               gl_iterations=None):
+        """Everything of the constructor that needs no model.  A subclass with an operator in the network's place has no window
+        plan: it leaves those four None, sets ``model = None``, and the building blocks below refuse."""
+        self.device = dev
         self.sample_rate, self.n_fft, self.hop_length = sample_rate, n_fft, hop_length
         self.window_frames, self.overlap_frames = window_frames, overlap_frames
         self.phase, self.batch_windows, self.gl_iterations = phase, batch_windows, gl_iterations
         self.n_bins = n_fft // 2 + 1
 
+    def _needs_network(self, what: str) -> None:
+        if self.model is None:
+            raise RuntimeError(f"{type(self).__name__}: there is no network; {what} belongs to the window plan around one "
+                               "(here _core runs the operator on the whole spectrogram)")
+
     # ------------------------------------------------------------------ building blocks (device tensors)
     def plan(self, n_frames: int):
+        self._needs_network("plan")
         return denoise_plan(n_frames, self.window_frames, self.overlap_frames)
 
     def windows(self, spec: torch.Tensor) -> torch.Tensor:
         """complex64 ``(n_clips, T, F)`` (``stft_complex``) -> network input ``(n_clips * K, 1, F, width)``."""
+        self._needs_network("windows")
         if not spec.is_cuda or spec.dtype != torch.complex64 or spec.dim() != 3:
             raise ValueError("Denoiser.windows: expected a (n_clips, n_frames, n_bins) complex64 tensor on a ROCm device")
         s = torch.view_as_real(spec.contiguous())
@@ -113,48 +110,40 @@ class Denoiser:
         out = torch.empty((n * k, 1, f, w), dtype=torch.float32, device=spec.device)
         with torch.cuda.device(spec.device):
             _lib.check(_lib.load().adn_denoise_windows(s.data_ptr(), n, t, f, self.window_frames, self.overlap_frames,
-                                                       out.data_ptr(), _stream(spec.device)), "adn_denoise_windows")
+                                                       out.data_ptr(), current_stream(spec.device)), "adn_denoise_windows")
         return out
 
     def network(self, x: torch.Tensor) -> torch.Tensor:
         """The U-Net over ``batch_windows`` windows at a time, into slices of one output buffer."""
-        x = x.contiguous()
-        nw, _, f, w = x.shape
-        dev = x.device
-        y = torch.empty_like(x)
-        m = self.model
-        if m.training:
-            raise RuntimeError("Denoiser: the model is in train mode; call .eval()")
-        L = _lib.load()
-        handle = m._ensure_handle(dev)
-        step, per = self.batch_windows, f * w * 4
-        with torch.cuda.device(dev):
-            for i in range(0, nw, step):
-                n = min(step, nw - i)
-                ws = m._workspace_for(n, f, w, dev)
-                _lib.check(L.adn_unet_forward(handle, x.data_ptr() + i * per, y.data_ptr() + i * per, n, f, w, ws.data_ptr(),
-                                              ws.numel(), _stream(dev)), "adn_unet_forward")
-        return y
+        self._needs_network("network")
+        return unet_windows("Denoiser", self.model, x, self.batch_windows)
 
     def stitch(self, y: torch.Tensor, n_clips: int, n_frames: int, clamp: bool) -> torch.Tensor:
         """Network output ``(n_clips * K, 1, F, width)`` -> ``(n_clips, F, n_frames)``, cross-faded (``adn_denoise_stitch``)."""
+        self._needs_network("stitch")
         y = y.contiguous()
         f = y.shape[2]
         out = torch.empty((n_clips, f, n_frames), dtype=torch.float32, device=y.device)
         with torch.cuda.device(y.device):
             _lib.check(_lib.load().adn_denoise_stitch(y.data_ptr(), n_clips, n_frames, f, self.window_frames, self.overlap_frames,
-                                                      int(bool(clamp)), out.data_ptr(), _stream(y.device)), "adn_denoise_stitch")
+                                                      int(bool(clamp)), out.data_ptr(), current_stream(y.device)), "adn_denoise_stitch")
         return out
 
     def resynth(self, y: torch.Tensor, spec: torch.Tensor, length: int) -> torch.Tensor:
         """Network output + the input's complex STFT -> audio ``(n_clips, length)`` (``adn_denoise_resynth``)."""
+        self._needs_network("resynth")
+        return self._resynth(y, spec, length, self.window_frames, self.overlap_frames)
+
+    def _resynth(self, y: torch.Tensor, spec: torch.Tensor, length: int, window_frames: int, overlap_frames: int) -> torch.Tensor:
+        """``adn_denoise_resynth`` under a window plan given by the caller: the object's, or, for a subclass whose operator wrote
+        one window per clip, ``(y.shape[3], 0)`` -- the plan's exact pass-through case, "a frame covered by one window is y itself"."""
         y = y.contiguous()
         s = torch.view_as_real(spec.contiguous())
         n = spec.shape[0]
         out = torch.empty((n, length), dtype=torch.float32, device=y.device)
         with torch.cuda.device(y.device):
             _lib.check(_lib.load().adn_denoise_resynth(y.data_ptr(), s.data_ptr(), n, length, self.n_fft, self.hop_length,
-                                                       self.window_frames, self.overlap_frames, out.data_ptr(), _stream(y.device)),
+                                                       window_frames, overlap_frames, out.data_ptr(), current_stream(y.device)),
                        "adn_denoise_resynth")
         return out
 
@@ -180,15 +169,7 @@ class Denoiser:
         numpy in -> numpy out, tensor on a ROCm device in -> tensor there out; everything between the input copy and the
         output copy runs on the device on the current stream.  ``rand`` (``(N, F, T)`` uniform [0, 1)) makes
         ``phase="griffin_lim"`` reproducible, as in ``griffin_lim_reconstruction``."""
-        is_np = not isinstance(audio, torch.Tensor)
-        if is_np:
-            a = torch.from_numpy(np.ascontiguousarray(audio, dtype=np.float32)).to(self.device)
-        else:
-            a = audio
-            if not a.is_cuda:
-                raise RuntimeError("Denoiser.denoise: a tensor must live on a ROCm device (no CPU path); pass numpy to have it staged")
-            if a.dtype != torch.float32:
-                raise TypeError("Denoiser.denoise: expected float32 audio")
+        a, is_np = stage("Denoiser.denoise", audio, self.device)
         single = a.dim() == 1
         x = (a[None] if single else a).contiguous()
         if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
@@ -212,12 +193,8 @@ class Denoiser:
         """Magnitudes ``(F, T)`` or ``(N, F, T)`` of any ``T >= 1`` -> the stitched network output of the same shape (no clamp):
         the reference's ``test.py:100-114`` for spectrograms longer than the network's window.  For ``16 <= T <= window_frames``
         it is ``model(mag[:, None])[:, 0]`` bit for bit."""
-        is_np = not isinstance(mag, torch.Tensor)
-        m = torch.from_numpy(np.ascontiguousarray(mag, dtype=np.float32)).to(self.device) if is_np else mag
-        if not m.is_cuda:
-            raise RuntimeError("Denoiser.denoise_spectrogram: a tensor must live on a ROCm device (no CPU path)")
-        if m.dtype != torch.float32:
-            raise TypeError("Denoiser.denoise_spectrogram: expected float32 magnitudes")
+        self._needs_network("denoise_spectrogram")
+        m, is_np = stage("Denoiser.denoise_spectrogram", mag, self.device, "magnitudes")
         single = m.dim() == 2
         m = (m[None] if single else m).contiguous()
         if m.dim() != 3 or m.shape[1] < 16 or m.shape[2] < 1:
@@ -256,23 +233,6 @@ def _load_model(path, dtype, device):
     return model.to(device).eval().set_compute_dtype(dtype)
 
 
-def _report(src, dst, ref_path) -> str:
-    """One JSON line: the four metrics of the noisy input and of the denoised output against the clean reference, at the
-    file's rate, each pair cut to the shorter of the two (mono mixes)."""
-    import json
-    from .metrics import evaluate
-    ref, ref_rate = read_wav(ref_path, mono=True)
-    row = {"file": src, "reference": ref_path, "sample_rate": int(ref_rate)}
-    for key, path in (("noisy", src), ("denoised", dst)):
-        audio, rate = read_wav(path, mono=True)
-        if rate != ref_rate:
-            raise ValueError(f"--reference: {ref_path} is at {ref_rate} Hz, {path} at {rate} Hz")
-        n = min(len(audio), len(ref))
-        m = evaluate(audio[:n], ref[:n], sr=int(rate))
-        row[key] = {k: float(v[0]) for k, v in m.items()}
-    return json.dumps(row)
-
-
 def main(argv=None) -> int:
     import argparse
     ap = argparse.ArgumentParser(prog="python -m audiodenoiser_amd.denoise", description="Denoise a wav file or a folder of wav files.")
@@ -288,18 +248,7 @@ def main(argv=None) -> int:
     args = ap.parse_args(argv)
     dev = _lib.staging_device()
     dn = Denoiser(_load_model(args.model, args.dtype, dev), window_frames=args.window, overlap_frames=args.overlap, phase=args.phase)
-    if os.path.isdir(args.src):
-        os.makedirs(args.dst, exist_ok=True)
-        jobs = [(os.path.join(args.src, f), os.path.join(args.dst, f)) for f in sorted(os.listdir(args.src)) if f.lower().endswith(".wav")]
-    else:
-        jobs = [(args.src, args.dst)]
-    for src, dst in jobs:
-        n, rate = dn.denoise_file(src, dst)
-        print(f"{src} -> {dst}: {n} samples at {rate} Hz")
-        if args.reference is not None:
-            ref = os.path.join(args.reference, os.path.basename(src)) if os.path.isdir(args.reference) else args.reference
-            print(_report(src, dst, ref))
-    return 0
+    return run_files(dn, args.src, args.dst, args.reference)
 
 
 if __name__ == "__main__":

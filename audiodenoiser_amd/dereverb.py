@@ -47,10 +47,11 @@ import os
 import torch
 
 from . import _lib
-from .baseline import SPECTRAL_MAX_ROWS, SpectralParams, _spectral_device, spectral_gain, spectral_gain_windows
-from .denoise import Denoiser, _report, _stream
+from ._host import check_stft_plan, current_stream, rocm_device, run_files, run_live
+from .baseline import SpectralParams, _gain_kept_columns, _spectral_params, spectral_gain
+from .denoise import Denoiser
 from .griffin_lim import stft_complex
-from .stream import POOL_MAX_ROWS, PoolBook, StreamDenoiser, StreamPool, _check_stream_args
+from .stream import POOL_MAX_ROWS, PoolBook, StreamDenoiser, StreamPool, _check_stream_args, causal_carrier
 
 __all__ = ["WpeParams", "wpe", "Dereverberator", "WpeStreamParams", "wpe_online", "wpe_stream_state_bytes", "StreamDereverberator",
            "DereverbStreamPool"]
@@ -109,7 +110,7 @@ def wpe(spec: torch.Tensor, params: WpeParams = None, mag_out: torch.Tensor = No
     ws = torch.empty((need.value,), dtype=torch.uint8, device=dev) if need.value else None
     with torch.cuda.device(dev):
         _lib.check(L.adn_wpe(s.data_ptr(), n, t, f, p, ws.data_ptr() if ws is not None else None, need.value, out.data_ptr(),
-                             mag_out.data_ptr(), int(mag_out.shape[3]), _stream(dev)), "adn_wpe")
+                             mag_out.data_ptr(), int(mag_out.shape[3]), current_stream(dev)), "adn_wpe")
     return torch.view_as_complex(out), mag_out
 
 
@@ -119,29 +120,14 @@ class Dereverberator(Denoiser):
 
     def __init__(self, device=None, sample_rate: int = 8000, n_fft: int = 512, hop_length: int = 128, params: WpeParams = None,
                  gain: bool = False, gain_params: SpectralParams = None):
-        if not (isinstance(n_fft, int) and 64 <= n_fft <= 4096 and n_fft & (n_fft - 1) == 0):
-            raise ValueError("Dereverberator: n_fft must be a power of two in [64, 4096]")
-        if not (isinstance(hop_length, int) and 1 <= hop_length <= n_fft // 4):
-            raise ValueError("Dereverberator: need 1 <= hop_length <= n_fft / 4 (the inverse transform of the whole input length "
-                             "divides by a window sum-of-squares that falls to 2e-8 at n_fft / 2)")
-        if not (isinstance(sample_rate, int) and sample_rate >= 1):
-            raise ValueError("Dereverberator: sample_rate must be >= 1")
+        check_stft_plan("Dereverberator", n_fft, hop_length, sample_rate)
         if params is not None and not isinstance(params, WpeParams):
             raise TypeError("Dereverberator: params must be a WpeParams")
-        if gain_params is not None and not isinstance(gain_params, SpectralParams):
-            raise TypeError("Dereverberator: gain_params must be a SpectralParams")
-        dev = _lib.staging_device() if device is None else torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("Dereverberator: the device must be a ROCm device; there is no CPU path")
-        if dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        self.model, self.device = None, dev
-        self.sample_rate, self.n_fft, self.hop_length = sample_rate, n_fft, hop_length
         self.params = WpeParams() if params is None else params
         self.gain = bool(gain)
-        self.gain_params = SpectralParams() if gain_params is None else gain_params
-        self.phase = "dereverberated"
-        self.n_bins = n_fft // 2 + 1
+        self.gain_params = _spectral_params("Dereverberator", gain_params, "gain_params")
+        self.model = None
+        self._setup(rocm_device("Dereverberator", device), sample_rate, n_fft, hop_length, "dereverberated")
 
     def _core(self, x: torch.Tensor, rand) -> torch.Tensor:
         """``x`` (n_clips, L) at the working rate -> (n_clips, L)."""
@@ -152,13 +138,7 @@ class Dereverberator(Denoiser):
         d, _ = wpe(spec, self.params, y)
         if self.gain:
             spectral_gain(d, self.gain_params, None, y, 0)
-        out = torch.empty((n, length), dtype=torch.float32, device=x.device)
-        s = torch.view_as_real(d)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().adn_denoise_resynth(y.data_ptr(), s.data_ptr(), n, length, self.n_fft, self.hop_length,
-                                                       int(y.shape[3]), 0, out.data_ptr(), _stream(x.device)),
-                       "adn_denoise_resynth")
-        return out
+        return self._resynth(y, d, length, int(y.shape[3]), 0)
 
 
 @dataclasses.dataclass(frozen=True)
@@ -241,9 +221,49 @@ def wpe_online(spec: torch.Tensor, state: torch.Tensor = None, first_frame: int 
     out = torch.empty((n, t, f, 2), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.load().adn_wpe_online(s.data_ptr(), n, t, f, first_frame, p, state.data_ptr(), state.numel(), n,
-                                              out.data_ptr(), mag_out.data_ptr(), int(mag_out.shape[3]), col0, _stream(dev)),
+                                              out.data_ptr(), mag_out.data_ptr(), int(mag_out.shape[3]), col0, current_stream(dev)),
                    "adn_wpe_online")
     return torch.view_as_complex(out), mag_out, state
+
+
+def _wpe_setup(sd, who, device, n_slots, n_fft, params, gain, gain_params):
+    """What both stream classes carry for the operator, ``n_slots`` rows of it: the parameters, the WPE state and the gain's three
+    floats per bin, on the device this returns.  Refuses parameter types before it looks at the device."""
+    _stream_params(who, params)
+    sd.gain_params = _spectral_params(who, gain_params, "gain_params")
+    dev = rocm_device(who, device)
+    sd.model = None
+    sd.params = WpeStreamParams() if params is None else params
+    sd.gain = bool(gain)
+    f = n_fft // 2 + 1
+    sd._wpe_state = torch.empty((wpe_stream_state_bytes(n_slots, f, sd.params),), dtype=torch.uint8, device=dev)
+    sd._gain_state = torch.empty((n_slots, 3, f), dtype=torch.float32, device=dev)
+    return dev
+
+
+def _wpe_then_gain(sd, x: torch.Tensor, rows, n_steps: int, first_step: int = 0, final_length: int = -1) -> torch.Tensor:
+    """The operator of both stream classes between ``analyze`` and ``emit``, in place on the analysed windows ``x``; every state
+    is read from ``sd`` when it runs.  ``rows=None``: the lockstep object's steps ``first_step ..``, ``n_steps`` per stream
+    (``adn_wpe_stream``).  Otherwise a pool tick's rows ``(slot, step, final_length)``, one step each, ``POOL_MAX_ROWS`` a call
+    (``adn_wpe_stream_pool``).  With ``sd.gain`` the spectral gain follows each call on the columns it wrote."""
+    L = _lib.load()
+    state = (sd._state.data_ptr(), sd._state.numel())
+    wpe_args = (ctypes.byref(sd.params.to_struct()), sd._wpe_state.data_ptr(), sd._wpe_state.numel(), current_stream(sd.device))
+    if rows is None:
+        plan, groups = sd._plan, [(x, None)]
+    else:
+        plan, groups = sd.book.plan, [(x[i:i + POOL_MAX_ROWS], rows[i:i + POOL_MAX_ROWS]) for i in range(0, len(rows), POOL_MAX_ROWS)]
+    for part, group in groups:
+        with torch.cuda.device(sd.device):
+            if group is None:
+                _lib.check(L.adn_wpe_stream(*state, part.data_ptr(), sd.n_streams, first_step, n_steps, final_length, *plan,
+                                            sd.max_steps, *wpe_args), "adn_wpe_stream")
+            else:
+                _lib.check(L.adn_wpe_stream_pool(*state, *sd._args, sd._rows(group), len(group), part.data_ptr(), *wpe_args),
+                           "adn_wpe_stream_pool")
+        if sd.gain:
+            _gain_kept_columns(part, group, n_steps, sd._gain_state, plan, sd.gain_params)
+    return x
 
 
 class StreamDereverberator(StreamDenoiser):
@@ -259,18 +279,11 @@ class StreamDereverberator(StreamDenoiser):
     def __init__(self, device=None, n_streams: int = 1, sample_rate: int = 8000, n_fft: int = 512, hop_length: int = 128,
                  block_frames: int = 4, params: WpeStreamParams = None, gain: bool = False, gain_params: SpectralParams = None,
                  input_rate=None):
-        window = max(16, block_frames) if isinstance(block_frames, int) else 16
-        _check_stream_args("StreamDereverberator", n_streams, sample_rate, n_fft, hop_length, window, block_frames, 0, 64, input_rate)
-        _stream_params("StreamDereverberator", params)
-        dev = _spectral_device("StreamDereverberator", device, gain_params)
-        self.model = None
-        self.params = WpeStreamParams() if params is None else params
-        self.gain = bool(gain)
-        self.gain_params = SpectralParams() if gain_params is None else gain_params
-        f = n_fft // 2 + 1
-        self._wpe_state = torch.empty((wpe_stream_state_bytes(n_streams, f, self.params),), dtype=torch.uint8, device=dev)
-        self._gain_state = torch.empty((n_streams, 3, f), dtype=torch.float32, device=dev)
-        self._setup(dev, n_streams, sample_rate, n_fft, hop_length, window, block_frames, 0, 64, input_rate)
+        window, ahead, batch = causal_carrier(block_frames)
+        _check_stream_args("StreamDereverberator", n_streams, sample_rate, n_fft, hop_length, window, block_frames, ahead, batch,
+                           input_rate)
+        dev = _wpe_setup(self, "StreamDereverberator", device, n_streams, n_fft, params, gain, gain_params)
+        self._setup(dev, n_streams, sample_rate, n_fft, hop_length, window, block_frames, ahead, batch, input_rate)
 
     def reset(self):
         """Forget the running stream, the gain's noise estimate included: the object is ready for a new one."""
@@ -281,15 +294,7 @@ class StreamDereverberator(StreamDenoiser):
         raise RuntimeError("StreamDereverberator: there is no network; WPE runs between analyze and emit (adn_wpe_stream)")
 
     def _net(self, x: torch.Tensor, first_step: int, n_steps: int, final_length: int = -1) -> torch.Tensor:
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().adn_wpe_stream(self._state.data_ptr(), self._state.numel(), x.data_ptr(), self.n_streams, first_step,
-                                                  n_steps, final_length, *self._plan, self.max_steps,
-                                                  ctypes.byref(self.params.to_struct()), self._wpe_state.data_ptr(),
-                                                  self._wpe_state.numel(), _stream(self.device)), "adn_wpe_stream")
-        if self.gain:
-            w, b = self.window_frames, self.block_frames
-            spectral_gain_windows(x, self._gain_state, w - b, b, n_steps, self.gain_params, None, x)
-        return x
+        return _wpe_then_gain(self, x, None, n_steps, first_step, final_length)
 
 
 class DereverbStreamPool(StreamPool):
@@ -302,17 +307,10 @@ class DereverbStreamPool(StreamPool):
     def __init__(self, device=None, max_streams: int = 64, backlog_steps: int = 4, sample_rate: int = 8000, n_fft: int = 512,
                  hop_length: int = 128, block_frames: int = 4, params: WpeStreamParams = None, gain: bool = False,
                  gain_params: SpectralParams = None, input_rates=None):
-        window = max(16, block_frames) if isinstance(block_frames, int) else 16
-        self.book = PoolBook(max_streams, backlog_steps, n_fft, hop_length, window, block_frames, 0, input_rates, sample_rate)
-        _stream_params("DereverbStreamPool", params)
-        dev = _spectral_device("DereverbStreamPool", device, gain_params)
-        self.model, self.batch_windows = None, POOL_MAX_ROWS
-        self.params = WpeStreamParams() if params is None else params
-        self.gain = bool(gain)
-        self.gain_params = SpectralParams() if gain_params is None else gain_params
-        f = n_fft // 2 + 1
-        self._wpe_state = torch.empty((wpe_stream_state_bytes(max_streams, f, self.params),), dtype=torch.uint8, device=dev)
-        self._gain_state = torch.empty((max_streams, 3, f), dtype=torch.float32, device=dev)
+        window, ahead, _ = causal_carrier(block_frames)
+        self.book = PoolBook(max_streams, backlog_steps, n_fft, hop_length, window, block_frames, ahead, input_rates, sample_rate)
+        dev = _wpe_setup(self, "DereverbStreamPool", device, max_streams, n_fft, params, gain, gain_params)
+        self.batch_windows = POOL_MAX_ROWS
         self._setup(dev)
 
     def reset(self):
@@ -324,42 +322,7 @@ class DereverbStreamPool(StreamPool):
         raise RuntimeError("DereverbStreamPool: there is no network; WPE runs between analyze and emit (adn_wpe_stream_pool)")
 
     def _net(self, x: torch.Tensor, rows) -> torch.Tensor:
-        w, b = self.book.window_frames, self.book.block_frames
-        L, p = _lib.load(), ctypes.byref(self.params.to_struct())
-        for i in range(0, len(rows), POOL_MAX_ROWS):
-            part, group = x[i:i + POOL_MAX_ROWS], rows[i:i + POOL_MAX_ROWS]
-            with torch.cuda.device(self.device):
-                _lib.check(L.adn_wpe_stream_pool(self._state.data_ptr(), self._state.numel(), *self._args, self._rows(group), len(group),
-                                                 part.data_ptr(), p, self._wpe_state.data_ptr(), self._wpe_state.numel(),
-                                                 _stream(self.device)), "adn_wpe_stream_pool")
-            if self.gain:
-                for j in range(0, len(group), SPECTRAL_MAX_ROWS):
-                    sub = part[j:j + SPECTRAL_MAX_ROWS]
-                    spectral_gain_windows(sub, self._gain_state, w - b, b, 1, self.gain_params,
-                                          [(slot, step == 0) for slot, step, _ in group[j:j + SPECTRAL_MAX_ROWS]], sub)
-        return x
-
-
-def _live(args) -> int:
-    """``--live``: the file pushed through ``StreamDereverberator`` at its own rate, ``--chunk`` samples at a time."""
-    import numpy as np
-
-    from .wav import read_wav, write_wav
-    audio, rate = read_wav(args.src, mono=False)             # (L, channels): every channel is a stream
-    dev = _lib.staging_device()
-    x = torch.from_numpy(np.ascontiguousarray(audio.T, dtype=np.float32)).to(dev)
-    params = WpeStreamParams(taps=args.taps, delay=args.delay, forget=args.forget)
-    sd = StreamDereverberator(dev, n_streams=x.shape[0], block_frames=args.block, params=params, gain=args.gain, input_rate=int(rate))
-    outs = [sd.push(x[:, i:i + args.chunk]) for i in range(0, x.shape[1], args.chunk)]
-    latency = sd.latency_input_samples
-    outs.append(sd.flush())
-    out = torch.cat(outs, dim=1)
-    write_wav(args.dst, np.ascontiguousarray(out.cpu().numpy().T), rate)
-    print(f"{args.src} -> {args.dst}: {x.shape[1]} samples at {rate} Hz in pushes of {args.chunk} at its own rate, "
-          f"latency {latency} samples")
-    if args.reference is not None:
-        print(_report(args.src, args.dst, args.reference))
-    return 0
+        return _wpe_then_gain(self, x, rows, 1)
 
 
 def main(argv=None) -> int:
@@ -385,27 +348,19 @@ def main(argv=None) -> int:
             ap.error("--chunk and --block must be >= 1")
         if os.path.isdir(args.src):
             ap.error("--live takes one wav file")
+
+        def make(dev, n_streams, rate):
+            params = WpeStreamParams(taps=args.taps, delay=args.delay, forget=args.forget)
+            return StreamDereverberator(dev, n_streams=n_streams, block_frames=args.block, params=params, gain=args.gain, input_rate=rate)
         try:
-            return _live(args)
+            return run_live(make, args.src, args.dst, args.chunk, args.reference)
         except ValueError as exc:
             ap.error(str(exc))
     try:
         params = WpeParams(taps=args.taps, delay=args.delay, iterations=args.iterations)
     except ValueError as exc:
         ap.error(str(exc))
-    dn = Dereverberator(params=params, gain=args.gain)
-    if os.path.isdir(args.src):
-        os.makedirs(args.dst, exist_ok=True)
-        jobs = [(os.path.join(args.src, f), os.path.join(args.dst, f)) for f in sorted(os.listdir(args.src)) if f.lower().endswith(".wav")]
-    else:
-        jobs = [(args.src, args.dst)]
-    for src, dst in jobs:
-        n, rate = dn.denoise_file(src, dst)
-        print(f"{src} -> {dst}: {n} samples at {rate} Hz")
-        if args.reference is not None:
-            ref = os.path.join(args.reference, os.path.basename(src)) if os.path.isdir(args.reference) else args.reference
-            print(_report(src, dst, ref))
-    return 0
+    return run_files(Dereverberator(params=params, gain=args.gain), args.src, args.dst, args.reference)
 
 
 if __name__ == "__main__":

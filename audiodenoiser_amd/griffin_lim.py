@@ -16,12 +16,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._host import current_stream as _stream
 
 __all__ = ["griffin_lim_reconstruction", "istft", "stft_complex"]
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def griffin_lim_reconstruction(magnitude_spectrogram, n_fft, hop_length, iterations=50, rand=None, device=None):

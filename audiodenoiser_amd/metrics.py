@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._host import current_stream, stage
 from .resample import _resample_device, resample_length
 
 __all__ = ["snr", "si_sdr", "seg_snr", "stoi", "evaluate", "STOI_RATE"]
@@ -35,14 +36,9 @@ STOI_RATE = 10000
 
 def _pair(est, ref, what):
     """-> (est, ref) as contiguous (N, L) float32 tensors on one ROCm device, and whether the caller passed single clips."""
-    def one(a):
-        if isinstance(a, torch.Tensor):
-            if not a.is_cuda:
-                raise RuntimeError(f"{what}: a tensor must live on a ROCm device (no CPU path); pass numpy to have it staged")
-            if a.dtype != torch.float32:
-                raise TypeError(f"{what}: expected float32 audio")
-            return a
-        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(_lib.staging_device())
+    def one(a):                                            # the staging device is asked for only when there is numpy to stage
+        x, was_numpy = stage(what, a, None)
+        return x.to(_lib.staging_device()) if was_numpy else x
     e, r = one(est), one(ref)
     if e.shape != r.shape or e.dim() not in (1, 2) or e.device != r.device:
         raise ValueError(f"{what}: est and ref must have one shape, (L,) or (N, L), on one device")
@@ -75,7 +71,7 @@ def _quality(e, r, lens, seg_frame):
     ld = None if lens is None else torch.from_numpy(lens).to(e.device)
     with torch.cuda.device(e.device):
         _lib.check(lib.adn_quality(e.data_ptr(), r.data_ptr(), None if ld is None else ld.data_ptr(), n, length, int(seg_frame),
-                                   ws.data_ptr(), ws.numel(), out.data_ptr(), torch.cuda.current_stream(e.device).cuda_stream),
+                                   ws.data_ptr(), ws.numel(), out.data_ptr(), current_stream(e.device)),
                    "adn_quality")
     return out
 
@@ -91,7 +87,7 @@ def _stoi_10k(e, r, lens):
     ld = None if lens is None else torch.from_numpy(lens).to(e.device)
     with torch.cuda.device(e.device):
         _lib.check(lib.adn_stoi(e.data_ptr(), r.data_ptr(), None if ld is None else ld.data_ptr(), n, length, ws.data_ptr(),
-                                ws.numel(), out.data_ptr(), torch.cuda.current_stream(e.device).cuda_stream), "adn_stoi")
+                                ws.numel(), out.data_ptr(), current_stream(e.device)), "adn_stoi")
     return out
 
 

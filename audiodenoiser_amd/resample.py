@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._host import current_stream, stage
 from .wav import read_wav
 
 __all__ = ["resample_length", "resample", "prepare_resample", "mix_snr", "load_audio", "StreamResampler", "resample_stream_plan"]
@@ -59,7 +60,7 @@ def _resample_device(audio: torch.Tensor, orig_sr: int, target_sr: int) -> torch
         raise ValueError("resample: empty batch")
     m = resample_length(length, orig_sr, target_sr)
     out = torch.empty((n_clips, m), dtype=torch.float32, device=a.device)
-    stream = torch.cuda.current_stream(a.device).cuda_stream
+    stream = current_stream(a.device)
     with torch.cuda.device(a.device):
         _lib.check(_lib.load().adn_resample(a.data_ptr(), n_clips, length, int(orig_sr), int(target_sr), out.data_ptr(), stream),
                    "adn_resample")
@@ -120,20 +121,10 @@ class StreamResampler:
         self._received = self._emitted = self._calls = 0
 
     def _to_device(self, block) -> torch.Tensor:
-        self._numpy = not isinstance(block, torch.Tensor)
-        if self._numpy:
-            if self._device is None:
-                self._device = _lib.staging_device()
-            x = torch.from_numpy(np.ascontiguousarray(block, dtype=np.float32)).to(self._device)
-        else:
-            x = block
-            if not x.is_cuda:
-                raise RuntimeError("StreamResampler.push: a tensor must live on a ROCm device (no CPU path); pass numpy to have it staged")
-            if x.dtype != torch.float32:
-                raise TypeError("StreamResampler.push: expected float32 audio")
-            if self._device is None:
-                self._device = x.device
-            x = x.to(self._device)
+        x, self._numpy = stage("StreamResampler.push", block, None)
+        if self._device is None:               # the first block names the device: its own, or the staging device for numpy
+            self._device = _lib.staging_device() if self._numpy else x.device
+        x = x.to(self._device)
         if x.dim() == 1:
             x = x[None]
         if x.dim() != 2 or x.shape[0] != self.n_streams:
@@ -153,7 +144,7 @@ class StreamResampler:
                                                        x.stride(0) if n_new else 0, self.n_streams, self._calls, self._received, n_new,
                                                        1 if final else 0, self.orig_sr, self.target_sr,
                                                        out.data_ptr() if out.shape[1] else None, out.shape[1],
-                                                       torch.cuda.current_stream(dev).cuda_stream), "adn_resample_stream")
+                                                       current_stream(dev)), "adn_resample_stream")
         self._received += n_new
         self._emitted = total
         self._calls += 1
@@ -203,7 +194,7 @@ def _mix_device(clean: torch.Tensor, noise: torch.Tensor, snr_db: float) -> torc
     _lib.check(lib.adn_mix_snr_workspace_bytes(n_clips, length, ctypes.byref(need)), "adn_mix_snr_workspace_bytes")
     ws = torch.empty((max(1, (need.value + 3) // 4),), dtype=torch.float32, device=c.device)
     out = torch.empty_like(c)
-    stream = torch.cuda.current_stream(c.device).cuda_stream
+    stream = current_stream(c.device)
     with torch.cuda.device(c.device):
         _lib.check(lib.adn_mix_snr(c.data_ptr(), n.data_ptr(), n_clips, length, float(snr_db), ws.data_ptr(), ws.numel() * 4,
                                    out.data_ptr(), stream), "adn_mix_snr")

@@ -157,3 +157,31 @@ def test_illegal_parameters_and_shapes_are_refused():
                dict(t=1 << 30, width=1 << 30, col0=1 << 30), dict(spec=p + 4), dict(out=p + 2), dict(s_in=p + 1), dict(s_out=p + 3),
                dict(n=1 << 30, f=65, t=1, width=1)):
         assert call(**kw) == 1 and L.adn_last_error().startswith(b"adn_spectral_gain"), kw
+
+
+def _host_classes():
+    """(class, the name its refusals carry, how to construct it without a device): the three classes that take a model get a CPU
+    ``UNet(1, 1).eval()``, the six that take a device get ``"cpu"``."""
+    from audiodenoiser_amd import Denoiser, StreamDenoiser, StreamPool, baseline, dereverb
+    from audiodenoiser_amd.model import UNet
+    net = UNet(1, 1).eval()
+    return [(Denoiser, "Denoiser", net), (StreamDenoiser, "StreamDenoiser", net), (StreamPool, "StreamPool", net),
+            (baseline.SpectralDenoiser, "SpectralDenoiser", "cpu"), (dereverb.Dereverberator, "Dereverberator", "cpu"),
+            (baseline.StreamSpectralDenoiser, "StreamSpectralDenoiser", "cpu"),
+            (dereverb.StreamDereverberator, "StreamDereverberator", "cpu"),
+            (baseline.SpectralStreamPool, "StreamPool", "cpu"), (dereverb.DereverbStreamPool, "StreamPool", "cpu")]
+
+
+def test_every_class_refuses_the_stft_plan_by_name_before_it_looks_at_the_device():
+    """One check (``_host.check_stft_plan``) behind every class, the three with a model and the six without: an illegal transform is
+    a ValueError that names the class (``StreamPool`` for the three pools), raised although the model / device given is a CPU one
+    -- which alone would be a RuntimeError."""
+    for cls, who, first in _host_classes():
+        with pytest.raises(RuntimeError, match="no CPU path"):
+            cls(first)                                      # legal plan: the device is what is refused
+        for kw in (dict(n_fft=500), dict(n_fft=32), dict(n_fft=512, hop_length=512 // 4 + 1), dict(n_fft=64, hop_length=64 // 4 + 1),
+                   dict(sample_rate=0)):
+            with pytest.raises(ValueError, match=rf"^{who}: ") as exc:
+                cls(first, **kw)
+            word = "sample_rate" if "sample_rate" in kw else "hop_length" if "hop_length" in kw else "power of two in [64, 4096]"
+            assert word in str(exc.value), (cls.__name__, kw, str(exc.value))

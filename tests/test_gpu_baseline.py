@@ -295,3 +295,20 @@ def test_refusals_leave_out_untouched(dev):
     with pytest.raises(ValueError):
         from audiodenoiser_amd.baseline import spectral_gain
         spectral_gain(spec.cpu())
+
+
+# ---- the building blocks of the window plan, which this class does not have ---------------------------------------------------------
+def test_the_network_s_building_blocks_refuse_and_leave_the_object_usable(dev):
+    """No model and no window plan: what ``Denoiser`` builds around its network says so (a ``RuntimeError``, the stream variants'
+    sentence) before it looks at its argument, and the object denoises afterwards as before."""
+    from audiodenoiser_amd.baseline import SpectralDenoiser
+    dn = SpectralDenoiser(dev)
+    y = torch.zeros((1, 1, 33, 16), device=dev)
+    spec = torch.zeros((1, 3, 33), dtype=torch.complex64, device=dev)
+    for call in (lambda: dn.network(y), lambda: dn.windows(spec), lambda: dn.plan(40),
+                 lambda: dn.denoise_spectrogram(torch.zeros((33, 16), device=dev)), lambda: dn.stitch(y, 1, 16, False),
+                 lambda: dn.resynth(y, spec, 600)):
+        with pytest.raises(RuntimeError, match=r"^SpectralDenoiser: there is no network"):
+            call()
+    out = dn.denoise(bc.white_mix(600, 8.0, 5)[0].astype(np.float32))
+    assert out.shape == (600,) and out.dtype == np.float32 and np.isfinite(out).all()

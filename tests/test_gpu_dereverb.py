@@ -330,3 +330,22 @@ def test_si_sdr_on_the_reverberant_clip(dev):
           f"(the restatement's: {r_in:.2f}, {r_wpe:.2f}, {r_wiener:.2f}, {r_cascade:.2f})")
     assert r_wpe - r_in >= 2.0 and after - before >= 0.5 * (r_wpe - r_in)
     assert r_cascade - r_wiener >= 1.0 and cascade - wiener >= 0.5 * (r_cascade - r_wiener)
+
+
+# ---- the building blocks of the window plan, which this class does not have ---------------------------------------------------------
+@pytest.mark.parametrize("gain", (False, True))
+def test_the_network_s_building_blocks_refuse_and_leave_the_object_usable(dev, gain):
+    """No model and no window plan: what ``Denoiser`` builds around its network says so (a ``RuntimeError``, the stream variants'
+    sentence) before it looks at its argument, and the object dereverberates afterwards as before."""
+    from audiodenoiser_amd.dereverb import Dereverberator
+    dn = Dereverberator(dev, gain=gain)
+    y = torch.zeros((1, 1, 33, 16), device=dev)
+    spec = torch.zeros((1, 3, 33), dtype=torch.complex64, device=dev)
+    for call in (lambda: dn.network(y), lambda: dn.windows(spec), lambda: dn.plan(40),
+                 lambda: dn.denoise_spectrogram(torch.zeros((33, 16), device=dev)), lambda: dn.stitch(y, 1, 16, False),
+                 lambda: dn.resynth(y, spec, 600)):
+        with pytest.raises(RuntimeError, match=r"^Dereverberator: there is no network"):
+            call()
+    clip = np.random.default_rng(600).uniform(-0.5, 0.5, 600).astype(np.float32)
+    out = dn.denoise(clip)
+    assert out.shape == (600,) and out.dtype == np.float32 and np.isfinite(out).all()

@@ -19,7 +19,14 @@ and the CUs, and `more_items_than_8_per_cu` says whether the items exceed even 8
 registers allow 3): then some workgroup must walk from one clip into the next.  Not covered here: fitted windows wider than
 96 frames and the reference's 513 x 256 at scale -- tests/test_gpu_parity.py has those.  A digest only says that a value has
 not moved: whether resynth and the stream kernels are RIGHT at n_fft 2048 and 4096, and at every other size, is checked against
-float64 by tests/test_gpu_spectral_grid.py."""
+float64 by tests/test_gpu_spectral_grid.py.
+
+At n_fft 64 and 512 the classes with an operator in the network's place follow (`operators`): SpectralDenoiser, Dereverberator,
+their lockstep stream forms at the working rate and at 48 kHz, and their pools with streams at 8, 48 and 16 kHz driven through
+push_many / step / close -- block_frames 8, pushes of 1, 3, 8, 2 hops in turn.  Those lines use public names only, so the script
+also compares two versions of the PYTHON layer over one library: import the other commit's package first and run this file in
+that process (`runpy.run_path`; a package already imported wins over the path added below), ADN_LIBADN_PATH naming the one
+built library."""
 import hashlib
 import os
 import sys
@@ -154,6 +161,78 @@ def stream(model, n_fft):
     say(f"stream_pool n_fft={n_fft} hop={hop} lengths={lengths} W={W} B={B} A={A} slots=3", *outs)
 
 
+def pieces(total, unit):
+    """Cuts of ``total`` samples into pushes of 1, 3, 8, 2, 1, 3, ... ``unit``s; the last takes what is left."""
+    pos, k = 0, 0
+    while pos < total:
+        m = min((1, 3, 8, 2)[k % 4] * unit, total - pos)
+        yield pos, m
+        pos, k = pos + m, k + 1
+
+
+def lockstep(cls, tag, a, hop, rate, **kw):
+    """A lockstep stream class without a network: every channel of ``a`` a stream, fed at ``rate`` (None: the working rate)."""
+    sd = cls(DEV, n_streams=a.shape[0], n_fft=4 * hop, hop_length=hop, block_frames=B, input_rate=rate, **kw)
+    outs = [sd.push(a[:, pos:pos + m]) for pos, m in pieces(a.shape[1], hop * (rate or 8000) // 8000)]
+    outs.append(sd.flush())
+    out = torch.cat(outs, dim=1)
+    assert out.shape == a.shape, (out.shape, a.shape)
+    say(f"{tag} streams={a.shape[0]} L={a.shape[1]} B={B} input_rate={rate}", out)
+
+
+def pooled(cls, tag, feeds, hop, **kw):
+    """A pool class without a network: ``feeds`` = ``(rate, samples)`` per stream, all opened at once, each pushed in its own
+    pieces through ``push_many`` as far as its room allows, closed when it has sent everything; one ``step`` per round."""
+    rates = [r for r, _ in feeds]
+    pool = cls(DEV, max_streams=len(feeds), n_fft=4 * hop, hop_length=hop, block_frames=B, input_rates=rates, **kw)
+    sids = [pool.open(input_rate=r) for r in rates]
+    cuts = [pieces(x.shape[0], hop * r // 8000) for r, x in feeds]
+    sent, got, waiting = [0] * len(feeds), {s: [] for s in sids}, {}
+    for _ in range(1000):
+        blocks = {}
+        for i, (r, x) in enumerate(feeds):
+            if i not in waiting and sent[i] < x.shape[0]:
+                waiting[i] = next(cuts[i])[1]
+            if i in waiting and waiting[i] <= pool.room(sids[i]):
+                blocks[sids[i]] = x[sent[i]:sent[i] + waiting[i]]
+                sent[i] += waiting.pop(i)
+        pool.push_many(blocks)
+        for i, (r, x) in enumerate(feeds):
+            if sids[i] in blocks and sent[i] == x.shape[0]:
+                pool.close(sids[i])
+        ran = pool.step()
+        for sid, samples, _ in ran:
+            got[sid].append(samples)
+        if not ran and not blocks:
+            break
+    outs = [torch.cat(got[s]) if got[s] else torch.empty(0, device=DEV) for s in sids]
+    assert [o.shape[0] for o in outs] == [x.shape[0] for _, x in feeds], [o.shape[0] for o in outs]
+    say(f"{tag} rates={tuple(rates)} lengths={tuple(x.shape[0] for _, x in feeds)} B={B}", *outs)
+
+
+def operators(n_fft):
+    """The classes with an operator in the network's place, through their public surface alone: offline, lockstep at the working
+    rate and at 48 kHz, pooled with streams at 8, 48 and 16 kHz.  3 channels of 4 n_fft + 37 samples at the working rate; a feed
+    at another rate is that many times longer, so that it brings as many steps."""
+    from audiodenoiser_amd.baseline import SpectralDenoiser, SpectralStreamPool, StreamSpectralDenoiser
+    from audiodenoiser_amd.dereverb import DereverbStreamPool, Dereverberator, StreamDereverberator
+    hop, length = n_fft // 4, 4 * n_fft + 37
+    tag = f"n_fft={n_fft} hop={hop}"
+    a = audio(3000 + n_fft, 3, 6 * length)
+    say(f"SpectralDenoiser {tag} L={length}", SpectralDenoiser(DEV, n_fft=n_fft, hop_length=hop).denoise(a[:, :length]))
+    for rate in (None, 48000):
+        lockstep(StreamSpectralDenoiser, f"StreamSpectralDenoiser {tag}", a[:, :length * (rate or 8000) // 8000], hop, rate)
+    feeds = [(r, a[i, :length * r // 8000].contiguous()) for i, r in enumerate((8000, 48000, 16000))]
+    pooled(SpectralStreamPool, f"SpectralStreamPool {tag}", feeds, hop)
+    for gain in (False, True):
+        say(f"Dereverberator {tag} L={length} gain={int(gain)}",
+            Dereverberator(DEV, n_fft=n_fft, hop_length=hop, gain=gain).denoise(a[:, :length]))
+        for rate in (None, 48000):
+            lockstep(StreamDereverberator, f"StreamDereverberator {tag} gain={int(gain)}", a[:, :length * (rate or 8000) // 8000], hop,
+                     rate, gain=gain)
+        pooled(DereverbStreamPool, f"DereverbStreamPool {tag} gain={int(gain)}", feeds, hop, gain=gain)
+
+
 def main():
     model = UNet(1, 1).eval().to(DEV)              # the classes ask for one; fake_network runs in its place
     with torch.no_grad():
@@ -161,6 +240,8 @@ def main():
             transforms(n_fft)
             denoiser(model, n_fft)
             stream(model, n_fft)
+            if n_fft in (64, 512):
+                operators(n_fft)
 
 
 if __name__ == "__main__":
