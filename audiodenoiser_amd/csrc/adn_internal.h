@@ -200,7 +200,8 @@ struct ConvArgs {
     FastDiv fdGc, fdNcg, fdTx, fdTy;   // wino4_conv_f32 only: the divisors of its tile decode (fdGc.d == 0: plain division)
     int nwg_total;         // wino4_conv_f32 only: logical workgroup ids (= tiles incl. supertile padding) of the launch
     int split;             // fp32 transposed convolution only: 1 = weights are three bf16 planes (pack_convt_split), the contraction
-                           // runs as six bf16 MFMA products per term pair with fp32 accumulation (conv_dma<..., SPLIT>)
+                           // runs as six bf16 MFMA products per term pair with fp32 accumulation (conv_dma<..., SPLIT>);
+                           // 1 + SplitTile (below): planes packed for that workgroup tile, nct = 4 Cout / its columns (no K split)
     // split-K (small batches; F(2x2,3x3) kernel, and the fp32 transposed convolutions with `out` = the partial buffer -- see
     // conv_dma's KSPLIT): `ksplit` workgroups share one output tile, each sums a slice
     // of nchunk/ksplit chunks and writes raw partial sums to `partial` [split][N][H][W][Cout]; a second launch adds
@@ -379,14 +380,21 @@ struct Wino3sGeom {
     int tilesY, tilesX;        // 4x4 output tiles of one image
     long rows;                 // N * tilesY * tilesX
     size_t v_bytes, m_bytes;   // of V and M
-    long gemm_grid;            // workgroups of stage 2
+    long gemm_grid;            // workgroups of stage 2 on 128-column tiles: the measure choose_conv3 (unet.hip) compares with its
+                               // threshold whatever tile the layer's launch has (a 256-column launch has half as many)
 };
+// Workgroup tile of stage 2: 128 rows x 128 columns (4 waves, three workgroups per CU), or 128 rows x 256 columns (two workgroups per
+// CU; Cout % 256 == 0) with 4 waves of 64 x 128 each or 8 waves of 64 x 64 each.  A wider tile stages 0.8x the bytes per MFMA and has
+// half the barriers; an output element sees the same chunks and products in the same order in all three, so the results are
+// bit-identical.  U is packed per column tile (pack_wino4_split), so a layer's planes fix its tile width.
+enum SplitTile { SPLIT_BN128 = 0, SPLIT_BN256 = 1, SPLIT_BN256W8 = 2 };
+inline int split_tile_bn(SplitTile t) { return t == SPLIT_BN128 ? 128 : 256; }
 bool wino3s_applicable(ConvKind kind, const ConvArgs &a);
 Wino3sGeom wino3s_geom(const ConvArgs &a);
-// a.wpk = the U planes; V, M: wino3s_geom's bytes, 16-byte aligned, disjoint from the layer's tensors
-hipError_t launch_wino3s_conv(ConvKind kind, const ConvArgs &a, float *V, float *M, hipStream_t st);
+// a.wpk = the U planes packed for `tile`; V, M: wino3s_geom's bytes, 16-byte aligned, disjoint from the layer's tensors
+hipError_t launch_wino3s_conv(ConvKind kind, const ConvArgs &a, float *V, float *M, SplitTile tile, hipStream_t st);
 // stage 2 alone (conv_kernels.hip)
-hipError_t launch_wino_gemm(const float *V, const void *U, float *M, long rows, int Cin, int Cout, hipStream_t st);
+hipError_t launch_wino_gemm(const float *V, const void *U, float *M, long rows, int Cin, int Cout, SplitTile tile, hipStream_t st);
 
 // fp16 3x3 layers on v_mfma_f32_16x16x32_f16 (conv16_kernels.hip): 32 x 16-pixel tiles x 64 couts, 32-channel chunks (ConvArgs::
 // nchunk0 / nchunk count those), persistent workgroups, weights from ConvArgs::wpk in pack_conv16 layout; `resident`: the whole

@@ -375,27 +375,39 @@ __device__ __forceinline__ void conv_epilogue_staged(const ConvArgs &p, f32x16 (
     // ---- phase 2: 16-byte pieces, LDS -> global ----
     T *outp = static_cast<T *>(p.out);
     if constexpr (EPI == CONVT2X2) {
-        // The workgroup's 128 columns are (dj = 0, 1) x 64 channels of one di (convt_column): for each channel block of those
+        // Every 128 columns of the workgroup are (dj = 0, 1) x 64 channels of one di (convt_column): for each channel block of those
         // 64 channels and each tile row, the 16 input pixels x 2 dj x one block are ONE 1 KB run of the output row 2*gy + di:
-        // 64 lanes x 16 bytes, lane = (gx, dj, half block).
-        static_assert(BN == 128 && NT % 64 == 0, "transposed-convolution epilogue: 128 columns per workgroup");
+        // 64 lanes x 16 bytes, lane = (gx, dj, half block).  A 256-column workgroup holds two such groups, neighbours in
+        // convt_column's order: two channel groups of one di, or (Cout = 64) both di of the one channel group.
+        static_assert((BN == 128 || BN == 256) && NT % 64 == 0, "transposed-convolution epilogue: 128 or 256 columns per workgroup");
         constexpr int BE = ACT_BLOCK<T>, NBLK = 64 / BE;                         // elements per block, blocks per 64 channels
+        constexpr int NSUB = BN / 128;                                           // groups of 128 columns
         const int Ho = 2 * p.H, Wo = 2 * p.W;
-        const int ncg = p.Cout >> 6, di = ct / ncg, cg = ct - di * ncg;
+        const int ncg = p.Cout >> 6;
+        int di[NSUB], cg[NSUB];
+#pragma unroll
+        for (int sub = 0; sub < NSUB; ++sub) {
+            di[sub] = (ct * NSUB + sub) / ncg;
+            cg[sub] = (ct * NSUB + sub) - di[sub] * ncg;
+        }
         const size_t bstr = (size_t)Ho * Wo * BE;                                // elements between channel blocks
-        T *ob = outp + (size_t)n * Ho * Wo * p.Cout + (size_t)(NBLK * cg) * bstr;
+        T *ob[NSUB];
+#pragma unroll
+        for (int sub = 0; sub < NSUB; ++sub) ob[sub] = outp + (size_t)n * Ho * Wo * p.Cout + (size_t)(NBLK * cg[sub]) * bstr;
         const int gxl = lane >> 2, dj = (lane >> 1) & 1, half = lane & 1;
         const int gx = tx * TW + gxl;
         constexpr int THH = TH / HALVES;                                         // tile rows per staging pass
 #pragma unroll
-        for (int it = 0; it < NBLK * THH / (NT / 64); ++it) {
-            const int run = it * (NT / 64) + wave;                               // (channel block, tile row of this pass)
-            const int b8 = run / THH, py = run - b8 * THH;
-            const int gy = ty * TH + hf * THH + py;
-            const piece_t val = *reinterpret_cast<const piece_t *>(stage + (py * TW + gxl) * RS + dj * 64 + b8 * BE + half * EPP);
-            if (gy < p.H && gx < p.W)
-                *reinterpret_cast<piece_t *>(ob + b8 * bstr + ((size_t)(2 * gy + di) * Wo + 2 * gx + dj) * BE + half * EPP) = val;
-        }
+        for (int sub = 0; sub < NSUB; ++sub)
+#pragma unroll
+            for (int it = 0; it < NBLK * THH / (NT / 64); ++it) {
+                const int run = it * (NT / 64) + wave;                           // (channel block, tile row of this pass)
+                const int b8 = run / THH, py = run - b8 * THH;
+                const int gy = ty * TH + hf * THH + py;
+                const piece_t val = *reinterpret_cast<const piece_t *>(stage + (py * TW + gxl) * RS + dj * 64 + b8 * BE + half * EPP + sub * 128);
+                if (gy < p.H && gx < p.W)
+                    *reinterpret_cast<piece_t *>(ob[sub] + b8 * bstr + ((size_t)(2 * gy + di[sub]) * Wo + 2 * gx + dj) * BE + half * EPP) = val;
+            }
         if (HALVES > 1 && hf + 1 < HALVES) __syncthreads();                      // the stores of this half have read the tile
     } else if constexpr (EPI == WINO_GEMM) {
         // Raw sums M[position n][cout block][row][8]: lane = (row, half block), so a wave stores 32 rows x 32 bytes = one 1 KB run
@@ -1031,8 +1043,12 @@ hipError_t launch_conv_mfma_t(ConvKind kind, const ConvArgs &a, hipStream_t st)
         if (kind == CONV3X3_RELU_DOT) return hipErrorInvalidValue;     // fp32: only the Winograd kernel fuses the last layer
         if (kind == CONVT2X2) {
             // a.split: weights packed as three bf16 planes (pack_convt_split): the split-bf16 form on the bf16 matrix cores
+            if (a.split > 1 && a.ksplit > 1) return hipErrorInvalidValue;     // K-split slices run on 128-column planes
             if (a.split && a.ksplit > 1) return launch_dma_cfg<T, 8, 128, 2, 2, 1, CONVT_KG, CONVT2X2, 3, 1, 1>(a, st);
             if (a.ksplit > 1) return hipErrorInvalidValue;       // the K split exists for the split-bf16 form only
+            // (a.split = 1 + SplitTile: the workgroup tile the planes are packed for and a.nct counts)
+            if (a.split == 1 + SPLIT_BN256) return launch_dma_cfg<T, 8, 256, 2, 2, 1, CONVT_KG, CONVT2X2, 2, 1>(a, st);
+            if (a.split == 1 + SPLIT_BN256W8) return launch_dma_cfg<T, 8, 256, 2, 4, 1, CONVT_KG, CONVT2X2, 2, 1>(a, st);
             if (a.split) return launch_dma_cfg<T, 8, 128, 2, 2, 1, CONVT_KG, CONVT2X2, 3, 1>(a, st);
             return launch_dma_cfg<T, 8, 128, 2, 2, 1, CONVT_KG, CONVT2X2, CONVT_WPE>(a, st);
         }
@@ -1072,12 +1088,15 @@ hipError_t launch_conv_mfma(ConvKind kind, const ConvArgs &a, bool f16, hipStrea
 }
 
 // Stage 2 of the three-stage F(4x4,3x3) form: M[pos][Cout/8][row][8] = sum over cin of V[pos][Cin/8][row][8] * U_pos, 36 positions
-// as the "clips" of one conv_dma<..., SPLIT> launch with 128-row x 128-column tiles.  Workgroup ids run column tile first, then
-// row tile, then position: the workgroups that share an XCD (xcd_remap) work on neighbouring row tiles of one position.
-hipError_t launch_wino_gemm(const float *V, const void *U, float *M, long rows, int Cin, int Cout, hipStream_t st)
+// as the "clips" of one conv_dma<..., SPLIT> launch with 128-row tiles of 128 or 256 columns (SplitTile, adn_internal.h; U packed
+// for that width).  Workgroup ids run column tile first, then row tile, then position: the workgroups that share an XCD (xcd_remap)
+// work on neighbouring row tiles of one position.  The 256-column forms hold 69.6 KB of LDS (two per CU; launch_dma_cfg opts in)
+// and stage the tile for the store in two halves of 66.5 KB.
+hipError_t launch_wino_gemm(const float *V, const void *U, float *M, long rows, int Cin, int Cout, SplitTile tile, hipStream_t st)
 {
+    const int BN = split_tile_bn(tile);
     // (a chunk of V -- two channel blocks of all rows -- must stay inside the 4 GB of a buffer descriptor)
-    if (!V || !U || !M || rows < 1 || rows >= (1L << 25) || Cin < 16 || (Cin & 15) || Cout < 128 || (Cout & 127)) return hipErrorInvalidValue;
+    if (!V || !U || !M || rows < 1 || rows >= (1L << 25) || Cin < 16 || (Cin & 15) || Cout < BN || Cout % BN) return hipErrorInvalidValue;
     ConvArgs a{};
     a.N = 36;
     a.W = TW;
@@ -1093,7 +1112,9 @@ hipError_t launch_wino_gemm(const float *V, const void *U, float *M, long rows, 
     a.split = 1;
     a.tilesY = (a.H + 7) / 8;
     a.tilesX = 1;
-    a.nct = Cout / 128;
+    a.nct = Cout / BN;
+    if (tile == SPLIT_BN256) return launch_dma_cfg<float, 8, 256, 2, 2, 1, CONVT_KG, WINO_GEMM, 2, 1>(a, st);
+    if (tile == SPLIT_BN256W8) return launch_dma_cfg<float, 8, 256, 2, 4, 1, CONVT_KG, WINO_GEMM, 2, 1>(a, st);
     return launch_dma_cfg<float, 8, 128, 2, 2, 1, CONVT_KG, WINO_GEMM, 3, 1>(a, st);
 }
 

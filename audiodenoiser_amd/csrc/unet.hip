@@ -60,8 +60,11 @@ struct LayerWeights {
     size_t w_off, b_off;   // the form the path's own kernel reads, and the bias per GEMM column
     size_t w4_off;         // 3x3, fp32 Winograd path: F(4x4,3x3) pack of the same weights
     size_t w3_off;         // 3x3 at levels 3 and 4 from 512 input channels on, fp32 Winograd path: U as three bf16 planes (pack_wino4_split)
+    adn::SplitTile w3_tile;  // ... packed once, for this workgroup tile of the GEMM stage (split_tile); transposed convolutions: of wt_off
     size_t w16_off;        // fp16 path: pack_conv16 / pack_convt16 form (16x16x32 MFMA kernels)
     size_t braw_off;       // transposed convolution: the Cout biases as they are (convt16_f16; the K-split reduce launch)
+    size_t wt_off;         // fp32 split-bf16 transposed convolution on a 256-column tile (w3_tile): the planes packed for it, beside
+                           // the 128-column planes at w_off that its K-split launches at small batches keep reading (17 MB in all)
 };
 
 }  // namespace
@@ -116,8 +119,20 @@ struct adn_unet {
     // workgroups, or the handle is pinned (choose_conv3), 2 = wherever they fit (tests).  ADN_WINO_GEMM when the handle is created.
     // gemm_grid: two rounds of three workgroups per CU (batch 11 of 513x256 at level 3, 21 at level 4).  Measured per layer at batch
     // 4 ... 32 (profiles/wino_gemm_ab.md) the form also wins from 576 workgroups on; the whole suite has only been run with 1536.
+    // The threshold counts 128-column workgroups whatever tile a layer runs (Wino3sGeom::gemm_grid): a 256-column launch of the
+    // same layer has half as many at two per CU, i.e. 768 of its own = one and a half of its rounds.  Two of its rounds (1 024)
+    // would move the first batch of 513x256 that takes the form from 11 to 15 at level 3 and from 21 to 29 at level 4; the set of
+    // batches that take the form does not depend on the tile.
     int wino_gemm = 1;
     long gemm_grid = 1536;
+    // Workgroup tile of the GEMM stage (ADN_SPLIT_BN when the handle is created): -1 = per layer by measurement (split_tile below),
+    // else an adn::SplitTile for every layer whose Cout % 256 == 0.
+    int split_bn = -1;
+    // A transposed convolution keeps both packings (LayerWeights::wt_off), so its tile is chosen per launch: 256 columns from two
+    // rounds of two workgroups per CU on (1 024 of them = 2 048 of the 128-column launch), below that 128 columns -- a small grid
+    // of tiles twice as large leaves CUs idle (pinned handle, one clip of 513x256: 1.46 -> 1.55 ms per forward with wide tiles
+    // everywhere).
+    long convt_wide_grid = 2048;
 };
 
 namespace {
@@ -318,28 +333,29 @@ inline void split3_host(float v, uint16_t (&t)[3])
 }
 
 // U for the three-stage form (wino3s_kernels.hip): the fp32 values of wino4_u split into three bf16 planes and packed per
-// transform-domain position as the GEMM slabs of conv_dma<..., SPLIT, WINO_GEMM>: [pos = 6x + v][column tile of 128 couts][chunk of
-// 16 channels][plane][half h][cout n][8 bf16], element kk of half h = input channel chunk*16 + 8h + kk.
-void pack_wino4_split(const float *w /*(Cout,Cin,3,3)*/, const std::vector<float> &scale, int Cin, int Cout, uint16_t *dst)
+// transform-domain position as the GEMM slabs of conv_dma<..., SPLIT, WINO_GEMM>: [pos = 6x + v][column tile of BN couts][chunk of
+// 16 channels][plane][half h][cout n][8 bf16], element kk of half h = input channel chunk*16 + 8h + kk.  BN = 128 or 256: the
+// columns of the workgroup tile the layer's GEMM launches run (adn::SplitTile).
+void pack_wino4_split(const float *w /*(Cout,Cin,3,3)*/, const std::vector<float> &scale, int Cin, int Cout, int BN, uint16_t *dst)
 {
-    const int nct = Cout / 128, nchunk = Cin / 16;
+    const int nct = Cout / BN, nchunk = Cin / 16;
     for (int co = 0; co < Cout; ++co)
         for (int ci = 0; ci < Cin; ++ci) {
             float U[36];
             wino4_u(w + ((size_t)co * Cin + ci) * 9, scale[co], U);
-            const int ct = co / 128, n = co % 128, ch = ci / 16, hh = (ci % 16) / 8, kk = ci % 8;
+            const int ct = co / BN, n = co % BN, ch = ci / 16, hh = (ci % 16) / 8, kk = ci % 8;
             for (int pos = 0; pos < 36; ++pos) {
                 uint16_t t[3];
                 split3_host(U[pos], t);
-                uint16_t *slab = dst + (((size_t)pos * nct + ct) * nchunk + ch) * (3 * 2 * 128 * 8);
-                for (int plane = 0; plane < 3; ++plane) slab[((plane * 2 + hh) * 128 + n) * 8 + kk] = t[plane];
+                uint16_t *slab = dst + (((size_t)pos * nct + ct) * nchunk + ch) * ((size_t)3 * 2 * BN * 8);
+                for (int plane = 0; plane < 3; ++plane) slab[((plane * 2 + hh) * BN + n) * 8 + kk] = t[plane];
             }
         }
 }
 
-void pack_convt_split(const float *w /*(Cin,Cout,2,2)*/, int Cin, int Cout, uint16_t *dst)
+void pack_convt_split(const float *w /*(Cin,Cout,2,2)*/, int Cin, int Cout, int BN /*columns of the workgroup tile: 128 | 256*/, uint16_t *dst)
 {
-    const int BN = 128, KC = 16;
+    const int KC = 16;
     const int ncol = 4 * Cout, nct = ncol / BN, nchunk = Cin / KC;
     size_t o = 0;
     for (int ct = 0; ct < nct; ++ct)
@@ -493,6 +509,7 @@ enum Conv3Kernel {
 // the layer's tensors in the first buffer and M in the second (forward_impl).  U == nullptr: the layer has no such form.
 struct WinoScratch {
     const void *U = nullptr;
+    adn::SplitTile tile = adn::SPLIT_BN128;      // the workgroup tile U is packed for
     float *V = nullptr, *M = nullptr;
     size_t v_bytes = 0, m_bytes = 0;
 };
@@ -605,7 +622,7 @@ hipError_t launch_conv3_kernels(const adn_unet *h, adn::ConvKind kind, const Con
     switch (c.kernel) {
     case WINO3S:
         a.wpk = sc.U;
-        return adn::launch_wino3s_conv(kind, a, sc.V, sc.M, st);
+        return adn::launch_wino3s_conv(kind, a, sc.V, sc.M, sc.tile, st);
     case CONV16:
         a.wpk = a.wpk4;
         a.nchunk0 = a.s0.C / 32;                         // conv16_f16 walks K in chunks of 32 channels
@@ -698,6 +715,13 @@ hipError_t launch_convt_kernels(const adn_unet *h, const LayerWeights &L, const 
         if (e != hipSuccess) return e;
         return adn::launch_convt_reduce(partial, h->dev + L.braw_off, out, c.ksplit, a.N, 2 * a.H, 2 * a.W, a.Cout, st);
     }
+    // The layer's wide tile (its own planes, half the column tiles) where the launch fills the chip with it, or the switch names it;
+    // the bits are those of the 128-column tile, so a pinned handle may choose by the batch as well.
+    if (a.split && L.wt_off && (h->split_bn >= 0 || adn::conv_workgroups(a) >= h->convt_wide_grid)) {
+        a.split = 1 + L.w3_tile;
+        a.wpk = h->dev + L.wt_off;
+        a.nct /= 2;
+    }
     return adn::launch_conv_mfma(adn::CONVT2X2, a, h->f16, st);
 }
 
@@ -759,6 +783,7 @@ int forward_impl(adn_unet *h, const float *x, float *y, int N, int F, int T, voi
         const size_t front = (size_t)N * p.H[d.level] * p.W[d.level] * std::max(std::max(d.C0, d.C1), d.Cout) * sizeof(float);
         if (front >= full) return sc;
         sc.U = h->dev + h->lw[li].w3_off;
+        sc.tile = h->lw[li].w3_tile;
         sc.V = reinterpret_cast<float *>(static_cast<char *>(tA) + front);
         sc.M = reinterpret_cast<float *>(static_cast<char *>(tB) + front);
         sc.v_bytes = sc.m_bytes = full - front;
@@ -894,10 +919,25 @@ void read_switches(adn_unet &h)
     if (const char *ag = std::getenv("ADN_AUTO_GRID64")) h.auto_grid64 = std::atol(ag);
     if (h.f16) h.convt_split = false;
     if (const char *wg = std::getenv("ADN_WINO_GEMM")) h.wino_gemm = std::atoi(wg) == 2 ? 2 : std::atoi(wg) != 0;
+    if (const char *sb = std::getenv("ADN_SPLIT_BN"))
+        h.split_bn = !std::strcmp(sb, "128") ? adn::SPLIT_BN128 : !std::strcmp(sb, "256") ? adn::SPLIT_BN256 : !std::strcmp(sb, "256w8") ? adn::SPLIT_BN256W8 : -2;
     if (const char *wt = std::getenv("ADN_WINO_TILE")) {
         h.use_wino4 = std::atoi(wt) != 2;
         h.force_wino4 = std::atoi(wt) == 4;
     }
+}
+
+// Workgroup tile of a split-bf16 GEMM -- the GEMM stage of the three-stage form, a transposed convolution (4 Cout columns) -- for
+// layer `d`: the handle's switch where the layer has whole 256-column tiles, else the measured default
+// (profiles/split_gemm_tile_ab.md).
+adn::SplitTile split_tile(const adn_unet &h, const LayerDesc &d)
+{
+    if ((d.kind == CONVT ? 4 * d.Cout : d.Cout) % 256) return adn::SPLIT_BN128;
+    if (h.split_bn >= 0) return static_cast<adn::SplitTile>(h.split_bn);
+    // Measured at batch 64 x 513x256, interleaved with the 128-column library: 256 columns on 4 waves is faster in every pair, by
+    // more than the 128-column spread, for the five GEMM stages (6 - 9 %) and for up1 ... up3 (13, 11, 3 %); up4's transposed
+    // convolution (8 chunks, 256 columns in all) is inside the spread and stays; the 8-wave form gains 1 - 3 % and is nowhere ahead.
+    return d.kind == CONVT && d.Cout < 128 ? adn::SPLIT_BN128 : adn::SPLIT_BN256;
 }
 
 // Folds BatchNorm and packs every tensor of the state_dict walk (adn.h) into `host` in the forms the handle's kernels read; the
@@ -938,7 +978,12 @@ void pack_weights(adn_unet &h, const float *const *t, std::vector<float> &host)
                 }
             } else if (h.convt_split) {
                 L.w_off = reserve(3 * n16);                                      // three bf16 planes
-                pack_convt_split(t[ti], Cin, Cout, reinterpret_cast<uint16_t *>(host.data() + L.w_off));
+                pack_convt_split(t[ti], Cin, Cout, 128, reinterpret_cast<uint16_t *>(host.data() + L.w_off));
+                L.w3_tile = split_tile(h, d);
+                if (L.w3_tile != adn::SPLIT_BN128) {
+                    L.wt_off = reserve(3 * n16);
+                    pack_convt_split(t[ti], Cin, Cout, adn::split_tile_bn(L.w3_tile), reinterpret_cast<uint16_t *>(host.data() + L.wt_off));
+                }
                 L.braw_off = reserve(Cout);
                 std::memcpy(host.data() + L.braw_off, t[ti + 1], sizeof(float) * Cout);
             } else {
@@ -970,7 +1015,8 @@ void pack_weights(adn_unet &h, const float *const *t, std::vector<float> &host)
                 // inside the run-to-run spread; profiles/wino_gemm_ab.md)
                 if (h.wino_gemm && d.level >= 3 && Cin >= 512 && Cin % 16 == 0 && Cout % 128 == 0) {
                     L.w3_off = reserve((size_t)36 * Cin * Cout * 3 / 2);
-                    pack_wino4_split(t[ti], scale, Cin, Cout, reinterpret_cast<uint16_t *>(host.data() + L.w3_off));
+                    L.w3_tile = split_tile(h, d);
+                    pack_wino4_split(t[ti], scale, Cin, Cout, adn::split_tile_bn(L.w3_tile), reinterpret_cast<uint16_t *>(host.data() + L.w3_off));
                 }
             }
         } else if (h.f16) {
@@ -1047,6 +1093,8 @@ int adn_unet_create_general(adn_unet **handle, int device, const float *const *t
     h->n_classes = num_classes;
     h->f16 = dtype == ADN_DTYPE_F16;
     read_switches(*h);
+    // (a tile the library does not have is refused: the planes are packed for it, so a misspelt width must not pass for the default)
+    if (h->split_bn < -1) return fail(ADN_ERR_INVALID, "adn_unet_create: ADN_SPLIT_BN must be 128, 256 or 256w8");
     std::vector<float> host;
     pack_weights(*h, t, host);
     h->dev_floats = host.size();

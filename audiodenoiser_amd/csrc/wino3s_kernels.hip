@@ -3,7 +3,7 @@
 // wino4_conv_f32 (wino4_kernels.hip) keeps V = B^T d B and M = sum V .* U on chip, which binds its matrix stage to a 32-cout
 // tile and to the exact-fp32 MFMA.  Here the same products run on the bf16 matrix cores through the three-term split of the
 // transposed convolutions (conv_dma<..., SPLIT, WINO_GEMM>, conv_kernels.hip), whose 128 x 128 tile pays for the split of an
-// activation 128 columns wide -- at the price of V and M in memory, 2.25x the layer's input and output:
+// activation 128 columns wide (or 256: SplitTile, adn_internal.h) -- at the price of V and M in memory, 2.25x the layer's input and output:
 //   stage 1  wino3s_input_kernel    C8 activations (virtual pad + cat of two sources) -> V[pos][Cin/8][row][8]
 //   stage 2  launch_wino_gemm       M_pos = V_pos U_pos, 36 GEMMs in one launch      -> M[pos][Cout/8][row][8]
 //   stage 3  wino3s_output_kernel   A^T M A + bias, ReLU (+ 2x2 max-pool)             -> C8 output (+ pooled tensor)
@@ -144,7 +144,7 @@ Wino3sGeom wino3s_geom(const ConvArgs &a)
     return g;
 }
 
-hipError_t launch_wino3s_conv(ConvKind kind, const ConvArgs &a, float *V, float *M, hipStream_t st)
+hipError_t launch_wino3s_conv(ConvKind kind, const ConvArgs &a, float *V, float *M, SplitTile tile, hipStream_t st)
 {
     if (!wino3s_applicable(kind, a) || !V || !M || !a.wpk || !a.bias || !a.out) return hipErrorInvalidValue;
     const Wino3sGeom g = wino3s_geom(a);
@@ -153,7 +153,7 @@ hipError_t launch_wino3s_conv(ConvKind kind, const ConvArgs &a, float *V, float 
     hipLaunchKernelGGL(wino3s_input_kernel, dim3((unsigned)bx, (unsigned)(Cin / 8)), dim3(NT), 0, st, a, V, g.tilesY, g.tilesX, g.rows);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    e = launch_wino_gemm(V, a.wpk, M, g.rows, Cin, a.Cout, st);
+    e = launch_wino_gemm(V, a.wpk, M, g.rows, Cin, a.Cout, tile, st);
     if (e != hipSuccess) return e;
     if (kind == CONV3X3_RELU_POOL)
         hipLaunchKernelGGL(wino3s_output_kernel<true>, dim3((unsigned)bx, (unsigned)(a.Cout / 8)), dim3(NT), 0, st, a, M, g.tilesY,

@@ -800,6 +800,9 @@ ADN_API int adn_wpe_stream_pool(void *pool_state, size_t pool_state_bytes, int n
  *   ADN_WINO_GEMM=0 | 2      fp32 3x3 layers at the two deepest levels as input transform + 36 split-bf16 GEMMs + output transform
  *                            (csrc/wino3s_kernels.hip): never | wherever its buffers fit the workspace (default 1: where they fit
  *                            and the GEMM launch fills the chip, or the handle is pinned)
+ *   ADN_SPLIT_BN=128 | 256 | 256w8   the GEMM stage of that form on workgroup tiles of 128 rows x 128 columns | x 256 columns, 4 waves |
+ *                            x 256 columns, 8 waves, for every layer with Cout % 256 == 0 (default: per layer, as measured;
+ *                            bit-identical results; another value is refused when the handle is created)
  *   ADN_F16_CONV=32         fp16 3x3 layers on conv_dma<_Float16> (32x32x16 MFMA) instead of conv16_f16 (16x16x32)
  *   ADN_F16_FIRST=0          fp16: Conv2d(1 -> 64) as its own launch instead of fused into down1's second convolution
  *   ADN_F16_CONVT=dma        fp16 transposed convolutions on conv_dma<_Float16> (32x32x16 MFMA, LDS-staged stores) instead of convt16_f16
