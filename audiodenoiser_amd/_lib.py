@@ -104,6 +104,8 @@ def load() -> ctypes.CDLL:
         L.adn_spectral_gain_windows.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, ctypes.POINTER(SpectralParamsStruct), vp, ci, vp, vp]
         L.adn_wpe_workspace_bytes.argtypes = [ci, ci, ci, ctypes.POINTER(WpeParamsStruct), ctypes.POINTER(sz)]
         L.adn_wpe.argtypes = [vp, ci, ci, ci, ctypes.POINTER(WpeParamsStruct), vp, sz, vp, vp, ci, vp]
+        L.adn_wpe_mc_workspace_bytes.argtypes = [ci, ci, ci, ci, ctypes.POINTER(WpeParamsStruct), ctypes.POINTER(sz)]
+        L.adn_wpe_mc.argtypes = [vp, ci, ci, ci, ci, ctypes.POINTER(WpeParamsStruct), vp, sz, vp, vp, ci, vp]
         wsp = ctypes.POINTER(WpeStreamParamsStruct)
         L.adn_wpe_stream_state_bytes.argtypes = [ci, ci, wsp, ctypes.POINTER(sz)]
         L.adn_wpe_online.argtypes = [vp, ci, ci, ci, cl, wsp, vp, sz, ci, vp, vp, ci, ci, vp]
@@ -125,6 +127,7 @@ def load() -> ctypes.CDLL:
                      "adn_stream_pool_rate_state_bytes", "adn_stream_pool_push_rate", "adn_stream_pool_emit_rate",
                      "adn_quality_workspace_bytes", "adn_quality", "adn_stoi_workspace_bytes", "adn_stoi",
                      "adn_spectral_gain", "adn_spectral_gain_windows", "adn_wpe_workspace_bytes", "adn_wpe",
+                     "adn_wpe_mc_workspace_bytes", "adn_wpe_mc",
                      "adn_wpe_stream_state_bytes", "adn_wpe_online", "adn_wpe_stream", "adn_wpe_stream_pool"):
             getattr(L, name).restype = ci
         _lib = L
@@ -196,5 +199,6 @@ EXPORTED_SYMBOLS = (
     "adn_stream_pool_rate_state_bytes", "adn_stream_pool_push_rate", "adn_stream_pool_emit_rate",
     "adn_quality_workspace_bytes", "adn_quality", "adn_stoi_workspace_bytes", "adn_stoi",
     "adn_spectral_gain", "adn_spectral_gain_windows", "adn_wpe_workspace_bytes", "adn_wpe",
+    "adn_wpe_mc_workspace_bytes", "adn_wpe_mc",
     "adn_wpe_stream_state_bytes", "adn_wpe_online", "adn_wpe_stream", "adn_wpe_stream_pool",
 )

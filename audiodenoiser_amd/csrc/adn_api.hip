@@ -622,6 +622,58 @@ int adn_wpe(const float *spec, int n_clips, int n_frames, int n_bins, const adn_
     return ADN_OK;
 }
 
+/* ---- multichannel dereverberation: joint WPE of a recording's channels (adn.h, "dereverb multichannel") ---------------- */
+// The shape and the parameters of a call: NULL = the defaults of "dereverb" with taps = 32 / channels.
+static int wpe_mc_shape(const char *who, int n_groups, int channels, int n_frames, int n_bins, const adn_wpe_params *params,
+                        adn::WpeConsts *k)
+{
+    const std::string w(who);
+    if (n_groups < 1 || n_frames < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, w + ": n_groups, n_frames and n_bins must be >= 1");
+    if (channels < 1 || channels > 8) return fail(ADN_ERR_INVALID, w + ": need 1 <= channels <= 8");
+    if ((long)n_groups * channels > 0x7fffffffL) return fail(ADN_ERR_INVALID, w + ": need n_groups * channels < 2^31");
+    const adn_wpe_params defaults = {32 / channels, 3, 3, 1e-3f, 1e-3f};
+    const int rc = wpe_consts(who, params ? params : &defaults, k);
+    if (rc != ADN_OK) return rc;
+    if (channels * k->K > 32) return fail(ADN_ERR_INVALID, w + ": need channels * taps <= 32");
+    const long grid = channels == 1 ? adn::wpe_grid(n_groups, n_bins, k->K) : adn::wpe_mc_grid(n_groups, channels, n_bins, k->K);
+    if (grid > 0x7fffffffL) return fail(ADN_ERR_INVALID, w + ": grid too large (n_groups x ceil(n_bins / bins per workgroup) >= 2^31)");
+    return ADN_OK;
+}
+
+int adn_wpe_mc_workspace_bytes(int n_groups, int channels, int n_frames, int n_bins, const adn_wpe_params *params, size_t *bytes)
+{
+    adn::WpeConsts k;
+    if (!bytes) return fail(ADN_ERR_INVALID, "adn_wpe_mc_workspace_bytes: null pointer");
+    const int rc = wpe_mc_shape("adn_wpe_mc_workspace_bytes", n_groups, channels, n_frames, n_bins, params, &k);
+    if (rc != ADN_OK) return rc;
+    *bytes = 0;                                          // R, P, the factor and the taps of a (group, bin) never leave the chip
+    return ADN_OK;
+}
+
+int adn_wpe_mc(const float *spec, int n_groups, int channels, int n_frames, int n_bins, const adn_wpe_params *params, void *workspace,
+               size_t workspace_bytes, float *spec_out, float *mag_out, int width, void *stream)
+{
+    adn::WpeConsts k;
+    if (!spec || !spec_out) return fail(ADN_ERR_INVALID, "adn_wpe_mc: null pointer (spec, spec_out)");
+    const int rc = wpe_mc_shape("adn_wpe_mc", n_groups, channels, n_frames, n_bins, params, &k);
+    if (rc != ADN_OK) return rc;
+    if (mag_out && width < n_frames) return fail(ADN_ERR_INVALID, "adn_wpe_mc: need width >= n_frames");
+    if (!aligned_to(spec, 8) || !aligned_to(spec_out, 8) || !aligned_to(mag_out, 4))
+        return fail(ADN_ERR_INVALID, "adn_wpe_mc: spec and spec_out must be 8-byte aligned, mag_out 4-byte aligned");
+    const size_t need = 0;                               // adn_wpe_mc_workspace_bytes
+    if (workspace_bytes < need || (need && !workspace))
+        return fail(ADN_ERR_WORKSPACE, "adn_wpe_mc: workspace smaller than adn_wpe_mc_workspace_bytes");
+    const char *a = reinterpret_cast<const char *>(spec), *b = reinterpret_cast<const char *>(spec_out);
+    const size_t span = (size_t)n_groups * (size_t)channels * (size_t)n_frames * (size_t)n_bins * 2 * sizeof(float);
+    if (a < b + span && b < a + span) return fail(ADN_ERR_INVALID, "adn_wpe_mc: spec and spec_out may not overlap");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (channels == 1)                                   // every statement reduces to "dereverb": the same kernel, the same bits
+        ADN_LAUNCH(adn::launch_wpe(spec, n_groups, n_frames, n_bins, k, spec_out, mag_out, width, st), "adn_wpe_mc");
+    else
+        ADN_LAUNCH(adn::launch_wpe_mc(spec, n_groups, channels, n_frames, n_bins, k, spec_out, mag_out, width, st), "adn_wpe_mc");
+    return ADN_OK;
+}
+
 /* ---- streaming denoiser: plan, state, analysis, emit (adn.h, "stream") ------------------------------------------- */
 static const char *stream_plan_text = ": need a power-of-two n_fft in [64, 4096], 1 <= hop <= n_fft / 4, window >= 16, block >= 1, "
                                       "lookahead >= 0, block + lookahead <= window, n_streams >= 1 and 1 <= max_steps <= 65536";

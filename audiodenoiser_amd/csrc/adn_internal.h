@@ -478,6 +478,12 @@ struct WpeConsts {
 long wpe_grid(int n_clips, int F, int K);
 hipError_t launch_wpe(const void *spec, int n_clips, int T, int F, const WpeConsts &k, void *spec_out, float *mag_out, int width,
                       hipStream_t st);
+// Multichannel dereverberation (dereverb_mc_kernels.hip; adn.h, "dereverb multichannel"): the same iterations on the N = C K
+// stacked past frames of the C consecutive clips of a group, 2 <= C <= 8 and C K <= 32 (C = 1 is launch_wpe), one launch, no
+// workspace.  The layouts are launch_wpe's with n_groups * C clips.  wpe_mc_grid: n_groups x ceil(F / (256 / lanes per bin)).
+long wpe_mc_grid(int n_groups, int C, int F, int K);
+hipError_t launch_wpe_mc(const void *spec, int n_groups, int C, int T, int F, const WpeConsts &k, void *spec_out, float *mag_out,
+                         int width, hipStream_t st);
 // Streaming denoiser (stream_kernels.hip; adn.h, "stream").  StreamGeom: the plan and the layout of the state buffer of one batch
 // of streams, in floats (sections X, mag, hist, tail; `total` floats in all); stream_geom is false outside the limits of adn.h.
 // StreamCall: what one call of n_steps steps from step `first` covers, derived from the step index alone (stream_call):

@@ -31,6 +31,7 @@
 // correlation (the 4 x 4 blocks compute 4 T 16 nb (nb + 1) / 2, 1.04 x that at K = 20) and 4 T K for the filter, the solve K^3 / 6.
 // Measured times: profiles/bench_dereverb.md.
 #include "adn_internal.h"
+#include "wpe_solve.h"                               // max_keep_nan, wpe_solve: shared with dereverb_mc_kernels.hip
 
 namespace adn {
 namespace {
@@ -41,9 +42,6 @@ constexpr int WPE_HMAX = 8 + 32 - 1;                 // most history frames: D +
 
 // lanes that share a row: the smallest of 16, 32, 64 that holds the nb (nb + 1) / 2 blocks of its lower triangle
 inline int wpe_lanes_per_bin(int K) { return K <= 20 ? 16 : K <= 28 ? 32 : 64; }
-
-// max(x, c) of adn.h: a NaN x stays NaN
-__device__ __forceinline__ float max_keep_nan(float x, float c) { return x < c ? c : x; }
 
 // d_t = X_t - sum_j conj(g_j) X_{t-D-j}, j ascending over the n taps whose frame exists (adn.h, "dereverb").  xs points at X_t of
 // the row in the staged chunk, earlier frames `pitch` cells before each other.
@@ -58,72 +56,6 @@ __device__ __forceinline__ float2 wpe_filter(const float2 *xs, int pitch, const 
         d.y = fmaf(c.y, x.x, fmaf(-c.x, x.y, d.y));
     }
     return d;
-}
-
-// The solve of one row by its group of LPB lanes (lane gl): A (packed lower triangle, row r at r (r + 1) / 2) holds R, g holds P;
-// on return g holds the taps.  The loops are uniform over the workgroup, the barriers are the workgroup's.
-template <int LPB>
-__device__ __forceinline__ void wpe_solve(float2 *A, float2 *g, int K, float loading, int gl)
-{
-#pragma clang fp contract(off)
-    if (gl == 0) {                                   // A = R + (loading tr(R) / K + 1e-30) I; the diagonal is real
-        float tr = 0.f;
-        for (int j = 0; j < K; ++j) tr += A[j * (j + 1) / 2 + j].x;
-        const float eps = (loading * tr) / (float)K + 1e-30f;
-        for (int j = 0; j < K; ++j) {
-            float2 &a = A[j * (j + 1) / 2 + j];
-            a.x = a.x + eps;
-            a.y = 0.f;
-        }
-    }
-    __syncthreads();
-    for (int c = 0; c < K; ++c) {                    // A = L L^H, column after column, L in A's place
-        const float2 *rc = A + c * (c + 1) / 2;
-        if (gl == 0) {
-            float s = rc[c].x;
-            for (int k = 0; k < c; ++k) {
-                s = fmaf(-rc[k].x, rc[k].x, s);
-                s = fmaf(-rc[k].y, rc[k].y, s);
-            }
-            A[c * (c + 1) / 2 + c].x = sqrtf(s);
-        }
-        __syncthreads();
-        const float lcc = rc[c].x;
-        for (int r = c + 1 + gl; r < K; r += LPB) {
-            float2 *rr = A + r * (r + 1) / 2;
-            float2 v = rr[c];
-            for (int k = 0; k < c; ++k) {            // v -= L_rk conj(L_ck)
-                const float2 a = rr[k], b = rc[k];
-                v.x = fmaf(-a.y, b.y, fmaf(-a.x, b.x, v.x));
-                v.y = fmaf(a.x, b.y, fmaf(-a.y, b.x, v.y));
-            }
-            rr[c] = make_float2(v.x / lcc, v.y / lcc);
-        }
-        __syncthreads();
-    }
-    if (gl == 0) {
-        for (int r = 0; r < K; ++r) {                // L y = P
-            const float2 *rr = A + r * (r + 1) / 2;
-            float2 v = g[r];
-            for (int k = 0; k < r; ++k) {            // v -= L_rk y_k
-                const float2 a = rr[k], y = g[k];
-                v.x = fmaf(a.y, y.y, fmaf(-a.x, y.x, v.x));
-                v.y = fmaf(-a.y, y.x, fmaf(-a.x, y.y, v.y));
-            }
-            g[r] = make_float2(v.x / rr[r].x, v.y / rr[r].x);
-        }
-        for (int r = K - 1; r >= 0; --r) {           // L^H g = y
-            float2 v = g[r];
-            for (int k = K - 1; k > r; --k) {        // v -= conj(L_kr) g_k
-                const float2 a = A[k * (k + 1) / 2 + r], y = g[k];
-                v.x = fmaf(-a.y, y.y, fmaf(-a.x, y.x, v.x));
-                v.y = fmaf(a.y, y.x, fmaf(-a.x, y.y, v.y));
-            }
-            const float lrr = A[r * (r + 1) / 2 + r].x;
-            g[r] = make_float2(v.x / lrr, v.y / lrr);
-        }
-    }
-    __syncthreads();
 }
 
 template <int LPB>

@@ -40,6 +40,7 @@ of scope.  There is no CPU path.
 from __future__ import annotations
 
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -164,6 +165,10 @@ class Denoiser:
         return out
 
     # ------------------------------------------------------------------ public surface
+    # A subclass whose operator treats the channels of a recording jointly sets this: ``denoise`` then takes (C, L) as ONE recording
+    # of C channels and (N, C, L) as a batch of recordings, and calls ``_core(x, rand, channels=C)`` on the (N C, L) rows.
+    joint_channels = False
+
     def denoise(self, audio, sr=None, rand=None):
         """``audio`` (L,) or (N, L) float32 at rate ``sr`` (default: the working rate) -> the same shape at the same rate.
         numpy in -> numpy out, tensor on a ROCm device in -> tensor there out; everything between the input copy and the
@@ -172,12 +177,17 @@ class Denoiser:
         a, is_np = stage("Denoiser.denoise", audio, self.device)
         single = a.dim() == 1
         x = (a[None] if single else a).contiguous()
+        shape, core = x.shape, self._core
+        if self.joint_channels:
+            if x.dim() not in (2, 3) or min(shape) < 1:
+                raise ValueError("Denoiser.denoise: joint channels: audio must be (L,), (C, L) or (N, C, L) with at least one sample")
+            x, core = x.reshape(-1, shape[-1]), functools.partial(self._core, channels=int(shape[-2]))
         if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
             raise ValueError("Denoiser.denoise: audio must be (L,) or (N, L) with at least one sample")
         rate = self.sample_rate if sr is None else int(sr)
         length = x.shape[1]
         if rate != self.sample_rate:
-            low = self._core(_resample_device(x, rate, self.sample_rate), rand)
+            low = core(_resample_device(x, rate, self.sample_rate), rand)
             up = _resample_device(low, self.sample_rate, rate)
             if up.shape[1] >= length:
                 out = up[:, :length].contiguous()
@@ -185,7 +195,8 @@ class Denoiser:
                 out = torch.zeros_like(x)
                 out[:, :up.shape[1]] = up
         else:
-            out = self._core(x, rand)
+            out = core(x, rand)
+        out = out.reshape(shape)
         out = out[0] if single else out
         return out.cpu().numpy() if is_np else out
 

@@ -5,12 +5,13 @@
     dry = dr.denoise(reverberant, sr=44100)            # (L,) or (N, L); numpy -> numpy, device tensor -> device tensor
     dr.denoise_file("room.wav", "dry.wav")
     Dereverberator(gain=True)                          # WPE, then the Wiener gain of the spectral baseline on its result
+    Dereverberator(channels="joint")                   # (C, L) is ONE recording of C microphones, (N, C, L) a batch of them
 
     live = StreamDereverberator(n_streams=2)           # audio that is still arriving: recursive WPE, one update per frame
     out = live.push(block); ...; out = live.flush()    # the surface of StreamDenoiser; DereverbStreamPool: that of StreamPool
     d, mag, state = wpe_online(spec)                   # the recursion on a spectrogram; pass state and first_frame to go on
 
-    python -m audiodenoiser_amd.dereverb IN OUT [--reference CLEAN] [--taps K] [--delay D] [--iterations I] [--gain]
+    python -m audiodenoiser_amd.dereverb IN OUT [--reference CLEAN] [--taps K] [--delay D] [--iterations I] [--gain] [--joint]
     python -m audiodenoiser_amd.dereverb IN OUT --live [--chunk N] [--block B] [--forget A] [--gain] [--reference CLEAN]
 
 The operator is DEFINED in ``include/adn.h`` ("dereverb"; float64 restatement: ``tests/dereverb_ref.py``) and is unpinned against
@@ -26,6 +27,14 @@ on the ``reverb`` noise type has to beat in the ``--reference`` report.  ``Derev
 
 ``denoise``, ``denoise_file``, the rate handling and the every-channel-a-clip rule are ``Denoiser``'s, unchanged.
 
+``channels="joint"`` replaces that rule: the channels of a recording are dereverberated together by ``adn_wpe_mc``
+(``csrc/dereverb_mc_kernels.hip``), DEFINED in ``include/adn.h`` ("dereverb multichannel"; float64 restatement:
+``tests/dereverb_mc_ref.py``) and unpinned against any package like its sibling: every channel's late reverberation is predicted
+from the past frames of all channels, ``taps`` per channel, ``channels * taps <= 32``.  A ``(C, L)`` input is one recording of
+``C <= 8`` channels, ``(N, C, L)`` a batch of recordings, ``denoise_file`` takes the wav's channels as one recording, and
+``params=None`` takes ``taps = 32 // C`` -- a design value from the host figures in ``profiles/bench_dereverb_mc.md``, not tuned
+by ear.  A mono input is the single-channel path.  ``wpe_joint`` is the operator on spectrograms.
+
 The streaming form is a different algorithm with its own kernel, DEFINED in ``include/adn.h`` ("dereverb stream"; float64
 restatement: ``tests/dereverb_stream_ref.py``; ``csrc/dereverb_stream_kernels.hip``): recursive least squares per (stream, bin), a
 K x K inverse correlation matrix and K taps carried on the device and updated once per frame.  ``StreamDereverberator`` is
@@ -34,8 +43,8 @@ place, exactly as ``StreamSpectralDenoiser`` / ``SpectralStreamPool`` carry the 
 same columns afterwards, the streaming form of the cascade.  A row that starts at frame 0 starts fresh whatever the WPE state
 holds, so there is nothing to reset.
 
-What is NOT here: more than one channel, look-ahead or iterated online variants, any tuning of the defaults by ear.  There is no
-CPU path.
+What is NOT here: more than one channel in the streaming classes (they stay single-channel), look-ahead or iterated online
+variants, beamforming, any tuning of the defaults by ear.  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -53,7 +62,7 @@ from .denoise import Denoiser
 from .griffin_lim import stft_complex
 from .stream import POOL_MAX_ROWS, PoolBook, StreamDenoiser, StreamPool, _check_stream_args, causal_carrier
 
-__all__ = ["WpeParams", "wpe", "Dereverberator", "WpeStreamParams", "wpe_online", "wpe_stream_state_bytes", "StreamDereverberator",
+__all__ = ["WpeParams", "wpe", "wpe_joint", "Dereverberator", "WpeStreamParams", "wpe_online", "wpe_stream_state_bytes", "StreamDereverberator",
            "DereverbStreamPool"]
 
 
@@ -83,59 +92,107 @@ class WpeParams:
         return _lib.WpeParamsStruct(int(self.taps), int(self.delay), int(self.iterations), float(self.loading), float(self.power_floor))
 
 
-def wpe(spec: torch.Tensor, params: WpeParams = None, mag_out: torch.Tensor = None):
-    """``adn_wpe`` on the current stream.  ``spec``: complex64 ``(n_clips, T, F)`` on a ROCm device (``stft_complex``).
-    ``mag_out``: float32 ``(n_clips, 1, F, width)``, ``width >= T``, whose columns ``[0, T)`` are written and nothing else; None
-    allocates ``(n_clips, 1, F, T)``.  The workspace is allocated here.  Returns ``(spec_out, mag_out)``, ``spec_out`` a new
-    complex64 tensor of ``spec``'s shape."""
+def _wpe(who, spec, channels, params, mag_out):
+    """``adn_wpe`` (``channels=None``) or ``adn_wpe_mc`` on the current stream, the workspace allocated here."""
     if not isinstance(spec, torch.Tensor) or not spec.is_cuda or spec.dtype != torch.complex64 or spec.dim() != 3:
-        raise ValueError("wpe: expected a (n_clips, n_frames, n_bins) complex64 tensor on a ROCm device")
-    if params is not None and not isinstance(params, WpeParams):
-        raise TypeError("wpe: params must be a WpeParams")
+        raise ValueError(f"{who}: expected a (n_clips, n_frames, n_bins) complex64 tensor on a ROCm device")
     n, t, f = spec.shape
     if n < 1 or t < 1 or f < 1:
-        raise ValueError("wpe: need at least one clip, one frame and one bin")
+        raise ValueError(f"{who}: need at least one clip, one frame and one bin")
     dev = spec.device
     s = torch.view_as_real(spec.contiguous())
     if mag_out is None:
         mag_out = torch.empty((n, 1, f, t), dtype=torch.float32, device=dev)
     elif (not isinstance(mag_out, torch.Tensor) or not mag_out.is_cuda or mag_out.device != dev or mag_out.dtype != torch.float32
           or mag_out.dim() != 4 or tuple(mag_out.shape[:3]) != (n, 1, f) or not mag_out.is_contiguous()):
-        raise ValueError("wpe: mag_out must be a contiguous (n_clips, 1, n_bins, width) float32 tensor on spec's device")
+        raise ValueError(f"{who}: mag_out must be a contiguous (n_clips, 1, n_bins, width) float32 tensor on spec's device")
     out = torch.empty((n, t, f, 2), dtype=torch.float32, device=dev)
     p = ctypes.byref(params.to_struct()) if params is not None else None
     L = _lib.load()
+    size, run, shape = ((L.adn_wpe_workspace_bytes, L.adn_wpe, (n, t, f)) if channels is None else
+                        (L.adn_wpe_mc_workspace_bytes, L.adn_wpe_mc, (n // channels, channels, t, f)))
     need = ctypes.c_size_t(0)
-    _lib.check(L.adn_wpe_workspace_bytes(n, t, f, p, ctypes.byref(need)), "adn_wpe_workspace_bytes")
+    _lib.check(size(*shape, p, ctypes.byref(need)), size.__name__)
     ws = torch.empty((need.value,), dtype=torch.uint8, device=dev) if need.value else None
     with torch.cuda.device(dev):
-        _lib.check(L.adn_wpe(s.data_ptr(), n, t, f, p, ws.data_ptr() if ws is not None else None, need.value, out.data_ptr(),
-                             mag_out.data_ptr(), int(mag_out.shape[3]), current_stream(dev)), "adn_wpe")
+        _lib.check(run(s.data_ptr(), *shape, p, ws.data_ptr() if ws is not None else None, need.value, out.data_ptr(),
+                       mag_out.data_ptr(), int(mag_out.shape[3]), current_stream(dev)), run.__name__)
     return torch.view_as_complex(out), mag_out
+
+
+def wpe(spec: torch.Tensor, params: WpeParams = None, mag_out: torch.Tensor = None):
+    """``adn_wpe`` on the current stream.  ``spec``: complex64 ``(n_clips, T, F)`` on a ROCm device (``stft_complex``).
+    ``mag_out``: float32 ``(n_clips, 1, F, width)``, ``width >= T``, whose columns ``[0, T)`` are written and nothing else; None
+    allocates ``(n_clips, 1, F, T)``.  The workspace is allocated here.  Returns ``(spec_out, mag_out)``, ``spec_out`` a new
+    complex64 tensor of ``spec``'s shape."""
+    if params is not None and not isinstance(params, WpeParams):
+        raise TypeError("wpe: params must be a WpeParams")
+    return _wpe("wpe", spec, None, params, mag_out)
+
+
+def _joint_params(who, params, channels):
+    """The parameters of a joint call on ``channels`` channels: ``params``, or the defaults with ``taps = 32 // channels``.
+    ValueError for a channel count outside 1 ... 8 and for ``channels * taps > 32``, before anything looks at a device."""
+    if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= 8:
+        raise ValueError(f"{who}: need an integer 1 <= channels <= 8")
+    if params is None:
+        return WpeParams(taps=32 // channels)
+    if not isinstance(params, WpeParams):
+        raise TypeError(f"{who}: params must be a WpeParams")
+    if channels * params.taps > 32:
+        raise ValueError(f"{who}: need channels * taps <= 32 (channels {channels}, taps {params.taps})")
+    return params
+
+
+def wpe_joint(spec: torch.Tensor, channels: int, params: WpeParams = None, mag_out: torch.Tensor = None):
+    """``adn_wpe_mc`` on the current stream: ``wpe`` with the leading dimension ``n_groups * channels``, the ``channels`` channels
+    of a recording consecutive clips (``stft_complex`` of an ``(n_groups * channels, L)`` batch), dereverberated jointly.
+    ``params=None``: the defaults with ``taps = 32 // channels``.  ValueError if the leading dimension is no multiple of
+    ``channels`` or ``channels * taps > 32``.  ``channels = 1`` returns ``wpe``'s bits."""
+    params = _joint_params("wpe_joint", params, channels)
+    if isinstance(spec, torch.Tensor) and spec.dim() == 3 and spec.shape[0] % channels:
+        raise ValueError(f"wpe_joint: the leading dimension {spec.shape[0]} is not a multiple of channels = {channels}")
+    return _wpe("wpe_joint", spec, channels, params, mag_out)
 
 
 class Dereverberator(Denoiser):
     """``Denoiser`` with WPE in the network's place: no model, the phase of the dereverberated spectrum.  ``gain=True`` runs the
-    spectral baseline's Wiener gain (``gain_params``) on the result of WPE: the cascade."""
+    spectral baseline's Wiener gain (``gain_params``) on the result of WPE: the cascade.
+
+    ``channels="separate"`` (default): every channel a clip of its own, ``Denoiser``'s rule.  ``channels="joint"``: the channels
+    of a recording are dereverberated together (``wpe_joint``): ``(C, L)`` is one recording of ``C <= 8`` channels, ``(N, C, L)``
+    a batch, ``denoise_file`` takes the wav's channels as one recording; ``params=None`` then takes ``taps = 32 // C``, and a
+    ``params`` with ``C * taps > 32`` is a ValueError of the call.  A mono input is the single-channel path; the gain runs per
+    channel on the joint result."""
 
     def __init__(self, device=None, sample_rate: int = 8000, n_fft: int = 512, hop_length: int = 128, params: WpeParams = None,
-                 gain: bool = False, gain_params: SpectralParams = None):
+                 gain: bool = False, gain_params: SpectralParams = None, channels: str = "separate"):
         check_stft_plan("Dereverberator", n_fft, hop_length, sample_rate)
         if params is not None and not isinstance(params, WpeParams):
             raise TypeError("Dereverberator: params must be a WpeParams")
+        if channels not in ("separate", "joint"):
+            raise ValueError("Dereverberator: channels must be 'separate' or 'joint'")
         self.params = WpeParams() if params is None else params
+        self.channels = channels
+        self.joint_channels = channels == "joint"            # Denoiser.denoise: (C, L) is one recording, _core is told C
+        self._default_taps = params is None                  # joint: taps = 32 // C
         self.gain = bool(gain)
         self.gain_params = _spectral_params("Dereverberator", gain_params, "gain_params")
         self.model = None
         self._setup(rocm_device("Dereverberator", device), sample_rate, n_fft, hop_length, "dereverberated")
 
-    def _core(self, x: torch.Tensor, rand) -> torch.Tensor:
-        """``x`` (n_clips, L) at the working rate -> (n_clips, L)."""
+    def _core(self, x: torch.Tensor, rand, channels: int = 1) -> torch.Tensor:
+        """``x`` (n_clips, L) at the working rate -> (n_clips, L); ``channels`` consecutive clips are one recording."""
         n, length = x.shape
+        joint = None
+        if channels != 1:
+            joint = _joint_params("Dereverberator", None if self._default_taps else self.params, channels)
+            if self._default_taps:
+                joint = dataclasses.replace(self.params, taps=joint.taps)
         spec = stft_complex(x, self.n_fft, self.hop_length)
         t, f = spec.shape[1], spec.shape[2]
         y = torch.zeros((n, 1, f, max(t, 16)), dtype=torch.float32, device=x.device)
-        d, _ = wpe(spec, self.params, y)
+        d, _ = wpe(spec, self.params, y) if joint is None else wpe_joint(spec, channels, joint, y)
         if self.gain:
             spectral_gain(d, self.gain_params, None, y, 0)
         return self._resynth(y, d, length, int(y.shape[3]), 0)
@@ -333,34 +390,46 @@ def main(argv=None) -> int:
     ap.add_argument("dst", metavar="OUT", help="the wav file to write, or the folder to write into")
     ap.add_argument("--reference", metavar="CLEAN", default=None,
                     help="the dry wav of IN (or a folder with IN's file names): print one JSON line of metrics per file")
-    ap.add_argument("--taps", type=int, default=WpeParams.taps, help="prediction taps K, 1 ... 32")
+    ap.add_argument("--taps", type=int, default=None,
+                    help=f"prediction taps K, 1 ... 32 (default {WpeParams.taps}; with --joint 32 // channels, per channel)")
     ap.add_argument("--delay", type=int, default=WpeParams.delay, help="prediction delay D in frames, 1 ... 8")
     ap.add_argument("--iterations", type=int, default=WpeParams.iterations, help="iterations I, 1 ... 8")
     ap.add_argument("--gain", action="store_true", help="run the spectral baseline's Wiener gain on the result of WPE")
+    ap.add_argument("--joint", action="store_true",
+                    help="dereverberate the channels of a file together (multichannel WPE, channels * taps <= 32), not one by one")
     ap.add_argument("--live", action="store_true",
                     help="push the file (not a folder) through the streaming form (recursive WPE) at its own rate, as a live feed arrives")
     ap.add_argument("--chunk", type=int, default=1024, help="with --live: samples per push, at the file's rate")
     ap.add_argument("--block", type=int, default=4, help="with --live: frames per step (latency (block - 1) hop + n_fft samples)")
     ap.add_argument("--forget", type=float, default=WpeStreamParams.forget, help="with --live: forgetting factor, 0.95 ... 1")
     args = ap.parse_args(argv)
+    taps = WpeParams.taps if args.taps is None else args.taps
     if args.live:
         if args.chunk < 1 or args.block < 1:
             ap.error("--chunk and --block must be >= 1")
         if os.path.isdir(args.src):
             ap.error("--live takes one wav file")
 
+        if args.joint:
+            ap.error("--joint is the offline operator's: the streaming form is single-channel")
+
         def make(dev, n_streams, rate):
-            params = WpeStreamParams(taps=args.taps, delay=args.delay, forget=args.forget)
+            params = WpeStreamParams(taps=taps, delay=args.delay, forget=args.forget)
             return StreamDereverberator(dev, n_streams=n_streams, block_frames=args.block, params=params, gain=args.gain, input_rate=rate)
         try:
             return run_live(make, args.src, args.dst, args.chunk, args.reference)
         except ValueError as exc:
             ap.error(str(exc))
     try:
-        params = WpeParams(taps=args.taps, delay=args.delay, iterations=args.iterations)
+        params = WpeParams(taps=taps, delay=args.delay, iterations=args.iterations)
     except ValueError as exc:
         ap.error(str(exc))
-    return run_files(Dereverberator(params=params, gain=args.gain), args.src, args.dst, args.reference)
+    dn = Dereverberator(params=params, gain=args.gain, channels="joint" if args.joint else "separate")
+    dn._default_taps = args.taps is None                     # --joint without --taps: 32 // channels of each file
+    try:
+        return run_files(dn, args.src, args.dst, args.reference)
+    except ValueError as exc:
+        ap.error(str(exc))
 
 
 if __name__ == "__main__":

@@ -33,7 +33,7 @@
 
 #include <stddef.h>
 
-/* The 68 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 70 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -688,12 +688,69 @@ ADN_API int adn_spectral_gain_windows(const float *windows, float *y, int n_rows
  * Limits (ADN_ERR_INVALID before any launch): NULL or misaligned spec / spec_out / mag_out; n_clips, n_frames, n_bins >= 1;
  * width >= n_frames with a mag_out; overlapping spec and spec_out; launch grid < 2^31 workgroups; the parameters as above.
  * ADN_ERR_WORKSPACE: workspace_bytes below adn_wpe_workspace_bytes.  Element offsets are 64-bit.
- * For audio that is still arriving, online / recursive WPE: the next section, "dereverb stream".
- * Not here: more than one channel; any tuning by ear. */
+ * For audio that is still arriving, online / recursive WPE: the section after next, "dereverb stream".
+ * Not here: more than one channel treated jointly (the next section, "dereverb multichannel"); any tuning by ear. */
 typedef struct adn_wpe_params { int taps, delay, iterations; float loading, power_floor; } adn_wpe_params;
 ADN_API int adn_wpe_workspace_bytes(int n_clips, int n_frames, int n_bins, const adn_wpe_params *params, size_t *bytes);
 ADN_API int adn_wpe(const float *spec, int n_clips, int n_frames, int n_bins, const adn_wpe_params *params, void *workspace,
                     size_t workspace_bytes, float *spec_out, float *mag_out, int width, void *stream);
+
+/* ---- dereverb multichannel: joint WPE of the channels of a recording ---------------------------------------------------------------
+ * No reference counterpart and no checkpoint.  The library DEFINES the operator below (float64 restatement:
+ * tests/dereverb_mc_ref.py); it is UNPINNED against any package.  It is multichannel WPE (Nakatani et al. 2010; Yoshioka and
+ * Nakatani 2012): the late reverberation of every channel is predicted from the past frames of ALL channels of the recording, with
+ * one variance per frame shared by the channels.  A second microphone sees the same source through another filter, which is what
+ * makes the joint prediction remove more than C separate ones (host figures: profiles/bench_dereverb_mc.md).
+ * Not validated: the defaults are design values taken from those host figures; they were not tuned by ear.
+ *
+ * A group is the C channels of one recording, 1 <= C <= 8; every (group, bin) is independent.  X_{t,c} is channel c at frame t,
+ * zero for t < 0.  The stacked vector has N = C K entries, x~_t[r] = X_{t-D-j, c} at r = c K + j: channel-major, the lag ascending
+ * inside a channel.  In fp32, with the rounding rules of "dereverb" (the weight applied once as w_t x~_t[r], each component
+ * rounded; complex multiply-adds as two fmaf per component; max(x, c) as `x < c ? c : x`; correctly rounded division and square
+ * root):
+ *   p_{t,c} = fmaf(re, re, im * im)
+ *   phi     = max(rho (sum_c sum_t p_{t,c}) / (T C), 1e-30)                     (c ascending; a channel's sum as "dereverb" forms it)
+ *   d^(0)   = X
+ *   for i = 1 ... I:
+ *       lam_t = max((sum_c |d^(i-1)_{t,c}|^2) / C, phi),  w_t = 1 / lam_t       (c ascending)
+ *       R_rs  = sum_t (w_t x~_t[r]) conj(x~_t[s])                               N x N Hermitian
+ *       P_rc  = sum_t (w_t x~_t[r]) conj(X_{t,c})                               N x C
+ *       A     = R + ((delta tr(R)) / N + 1e-30) I                               (tr(R) = sum_r Re R_rr, r ascending; A_rr is real)
+ *       A = L L^H once; for every channel c: L y = P_c, L^H G_c = y             (inner sums in "dereverb"'s order)
+ *       d^(i)_{t,c} = X_{t,c} - sum_r conj(G_rc) x~_t[r]                        (r ascending over the entries whose frame exists)
+ *   output d^(I); optional magnitude M_{t,c} = sqrtf(fmaf(dre, dre, dim * dim))
+ * The sums over t run frame after frame from t = 0; phi's per-channel sums are the partial sums of the frames t = q mod LPB, added
+ * for q ascending, LPB = 16, 32 or 64 from (C, K) alone.  No order depends on the batch or on which bins share the call.
+ * Parameters: adn_wpe_params.  NULL = the defaults of "dereverb" with taps = 32 / C (integer division: 32, 16, 10, 8, 6, 5, 4, 4),
+ * the longest filter the stacked size 32 admits -- a design value from the host figures, not tuned by ear.
+ * Legal (ADN_ERR_INVALID otherwise, before any launch, the message starts "adn_wpe_mc" and names the field): the ranges of
+ * "dereverb", 1 <= channels <= 8 and channels * taps <= 32.
+ * Consequences: with C = 1 every statement reduces to "dereverb", and adn_wpe_mc(channels = 1) returns adn_wpe's bits (the call is
+ * forwarded to the same kernel); the first D frames of every channel come back bit for bit; a group with T <= D comes back bit
+ * for bit; an all-zero group gives zeros; a non-finite value is confined to its own (group, bin), whose content is then
+ * unspecified.
+ *
+ * What is pinned.  The result is bounded against the float64 restatement (tests/test_gpu_dereverb_mc.py: per group
+ * max |d - d64| <= 4 FLOOR max |d64|, FLOOR the error of the same statements run in fp32 on the host).  Pinned bit for bit: two
+ * calls give the same result; a group gives the same bits alone or in any batch; a bin gives the same bits whichever other bins
+ * are in the call.  NOT pinned: the bits against numpy; the bits under a permutation of the channels (the stacked order enters
+ * every sum).  Deterministic: no atomics.
+ *
+ * Layouts: spec and spec_out are (n_groups * channels, n_frames, n_bins, 2) fp32, the C channels of a group consecutive clips --
+ * what adn_stft_complex writes for an (n_groups * C, L) batch -- 8-byte aligned; they may not overlap.  mag_out may be NULL;
+ * otherwise it is (n_groups * channels, 1, n_bins, width) fp32 with width >= n_frames.  The call writes columns [0, n_frames) of
+ * mag_out, all of spec_out and not one byte else.  It may use the workspace and only the workspace; adn_wpe_mc_workspace_bytes
+ * reports 0 today, and workspace may then be NULL.
+ * Cost: one launch for all iterations, n_groups x ceil(n_bins / B) workgroups, B = 16, 8 or 4 bins from (C, K) (B C <= 32); the
+ * frames pass through LDS in chunks, so no limit on n_frames comes from LDS.  Per (group, bin) and iteration
+ * 4 T (N (N + 1) / 2 + 2 N C) FMAs.  No atomics, no constant table; nothing blocks or allocates.
+ * Limits (ADN_ERR_INVALID before any launch): as adn_wpe, with n_groups in n_clips' place, and n_groups * channels < 2^31.
+ * ADN_ERR_WORKSPACE: workspace_bytes below adn_wpe_mc_workspace_bytes.  Element offsets are 64-bit.
+ * Not here: streaming or online multichannel WPE ("dereverb stream" is single-channel); beamforming; N > 32; any tuning by ear. */
+ADN_API int adn_wpe_mc_workspace_bytes(int n_groups, int channels, int n_frames, int n_bins, const adn_wpe_params *params,
+                                       size_t *bytes);
+ADN_API int adn_wpe_mc(const float *spec, int n_groups, int channels, int n_frames, int n_bins, const adn_wpe_params *params,
+                       void *workspace, size_t workspace_bytes, float *spec_out, float *mag_out, int width, void *stream);
 
 /* ---- dereverb stream: recursive WPE, one update per frame, for audio that is still arriving -----------------------------------------
  * No reference counterpart and no checkpoint.  The library DEFINES the operator below (float64 restatement:
