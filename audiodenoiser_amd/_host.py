@@ -91,9 +91,10 @@ def unet_windows(who, model, x: torch.Tensor, batch_windows: int) -> torch.Tenso
 
 
 # ---------------------------------------------------------------------------------------------------------------- command lines
-def report(src, dst, ref_path) -> str:
+def report(src, dst, ref_path, per_channel: bool = False) -> str:
     """One JSON line: the four metrics of the noisy input and of the denoised output against the clean reference, at the
-    file's rate, each pair cut to the shorter of the two (mono mixes)."""
+    file's rate, each pair cut to the shorter of the two (mono mixes).  ``per_channel`` adds ``si_sdr_per_channel`` to both: the
+    SI-SDR of every channel of the file against the (mono) reference."""
     import json
     from .metrics import evaluate
     from .wav import read_wav
@@ -106,6 +107,10 @@ def report(src, dst, ref_path) -> str:
         n = min(len(audio), len(ref))
         m = evaluate(audio[:n], ref[:n], sr=int(rate))
         row[key] = {k: float(v[0]) for k, v in m.items()}
+        if per_channel:
+            chans = np.ascontiguousarray(read_wav(path, mono=False)[0].T[:, :n], dtype=np.float32)
+            each = evaluate(chans, np.broadcast_to(ref[:n], chans.shape).copy(), sr=int(rate))["si_sdr"]
+            row[key]["si_sdr_per_channel"] = [float(v) for v in each]
     return json.dumps(row)
 
 
@@ -128,7 +133,7 @@ def run_files(dn, src, dst, reference) -> int:
     return 0
 
 
-def run_live(make, src, dst, chunk, reference) -> int:
+def run_live(make, src, dst, chunk, reference, per_channel: bool = False) -> int:
     """The wav file ``src`` pushed ``chunk`` samples at a time, at its own rate, through the stream object that
     ``make(device, n_streams, rate)`` returns -- every channel a stream -- and written to ``dst``."""
     from .wav import read_wav, write_wav
@@ -143,5 +148,5 @@ def run_live(make, src, dst, chunk, reference) -> int:
     write_wav(dst, np.ascontiguousarray(out.cpu().numpy().T), rate)
     print(f"{src} -> {dst}: {x.shape[1]} samples at {rate} Hz in pushes of {chunk} at its own rate, latency {latency} samples")
     if reference is not None:
-        print(report(src, dst, reference))
+        print(report(src, dst, reference, per_channel))
     return 0

@@ -1068,7 +1068,120 @@ int adn_wpe_stream_pool(void *pstate, size_t pstate_bytes, int n_slots, int n_ff
     return ADN_OK;
 }
 
-static const char *resample_stream_text = ": rates must be >= 1 with max(up, down) <= 4096 after dividing by their gcd, and at most "
+/* ---- streaming multichannel dereverberation: recursive joint WPE (adn.h, "dereverb stream multichannel") --------------------- */
+// The parameters of a joint call on `channels` channels (NULL = the defaults of "dereverb stream" with taps = 32 / channels):
+// the parent's ranges, then the rules that need the channel count.  k->K is the taps PER CHANNEL.
+static int wpe_mc_stream_consts(const char *who, int channels, const adn_wpe_stream_params *params, adn::WpeStreamConsts *k)
+{
+    const std::string w(who);
+    if (channels < 1 || channels > 8) return fail(ADN_ERR_INVALID, w + ": need 1 <= channels <= 8");
+    const adn_wpe_stream_params defaults = {32 / channels, 3, 0.99f, 300.f, 0.01f, 0.9f};
+    const adn_wpe_stream_params *p = params ? params : &defaults;
+    const int rc = wpe_stream_consts(who, p, k);
+    if (rc != ADN_OK) return rc;
+    if (channels * p->taps > 32) return fail(ADN_ERR_INVALID, w + ": need channels * taps <= 32");
+    // the window 1 / (1 - forget) must hold twice the N unknowns (adn.h); in double, on the fp32 value the kernel uses
+    if (channels >= 2 && !(2.0 * (double)(channels * p->taps) * (1.0 - (double)p->forget) <= 1.0))
+        return fail(ADN_ERR_INVALID, w + ": need 2 channels taps (1 - forget) <= 1 with more than one channel (forget too low for the stacked size)");
+    return ADN_OK;
+}
+
+static size_t wpe_mc_stream_bytes(int n_slots, int n_bins, int channels, const adn::WpeStreamConsts &k)
+{
+    const long rec = channels == 1 ? adn::wpe_stream_record_floats(k.K, k.D) : adn::wpe_mc_stream_record_floats(channels, k.K, k.D);
+    return (size_t)n_slots * (size_t)n_bins * (size_t)rec * sizeof(float);
+}
+
+// The joint WPE state of a call: n_slots x n_bins records, 8-byte aligned, at least adn_wpe_mc_stream_state_bytes.
+static int wpe_mc_stream_state(const char *who, const void *wstate, size_t wstate_bytes, int n_slots, int n_bins, int channels,
+                               const adn::WpeStreamConsts &k)
+{
+    const std::string w(who);
+    if (!wstate) return fail(ADN_ERR_INVALID, w + ": null pointer (the WPE state)");
+    if (n_slots < 1 || n_slots > (1 << 20) || n_bins < 1 || n_bins > (1 << 20))
+        return fail(ADN_ERR_INVALID, w + ": need 1 <= n_slots <= 2^20 and 1 <= n_bins <= 2^20");
+    if (wstate_bytes < wpe_mc_stream_bytes(n_slots, n_bins, channels, k))
+        return fail(ADN_ERR_WORKSPACE, w + ": the WPE state is smaller than adn_wpe_mc_stream_state_bytes");
+    if (!aligned_to(wstate, 8)) return fail(ADN_ERR_INVALID, w + ": the WPE state must be 8-byte aligned");
+    return ADN_OK;
+}
+
+int adn_wpe_mc_stream_state_bytes(int n_slots, int channels, int n_bins, const adn_wpe_stream_params *params, size_t *bytes)
+{
+    adn::WpeStreamConsts k;
+    if (!bytes) return fail(ADN_ERR_INVALID, "adn_wpe_mc_stream_state_bytes: null pointer");
+    if (n_slots < 1 || n_slots > (1 << 20) || n_bins < 1 || n_bins > (1 << 20))
+        return fail(ADN_ERR_INVALID, "adn_wpe_mc_stream_state_bytes: need 1 <= n_slots <= 2^20 and 1 <= n_bins <= 2^20");
+    const int rc = wpe_mc_stream_consts("adn_wpe_mc_stream_state_bytes", channels, params, &k);
+    if (rc != ADN_OK) return rc;
+    *bytes = wpe_mc_stream_bytes(n_slots, n_bins, channels, k);
+    return ADN_OK;
+}
+
+int adn_wpe_mc_online(const float *spec, int n_groups, int channels, int n_frames, int n_bins, long first_frame,
+                      const adn_wpe_stream_params *params, void *state, size_t state_bytes, int n_slots, float *spec_out, float *mag_out,
+                      int width, int col0, void *stream)
+{
+    adn::WpeStreamConsts k;
+    if (!spec || !spec_out) return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: null pointer (spec, spec_out)");
+    if (n_groups < 1 || n_frames < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: n_groups, n_frames and n_bins must be >= 1");
+    if (first_frame < 0 || first_frame + n_frames >= (1L << 31))
+        return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: need first_frame >= 0 and first_frame + n_frames < 2^31");
+    int rc = wpe_mc_stream_consts("adn_wpe_mc_online", channels, params, &k);
+    if (rc != ADN_OK) return rc;
+    if ((long)n_groups * channels > 0x7fffffffL) return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: need n_groups * channels < 2^31");
+    rc = wpe_mc_stream_state("adn_wpe_mc_online", state, state_bytes, n_slots, n_bins, channels, k);
+    if (rc != ADN_OK) return rc;
+    if (n_groups > n_slots) return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: group i uses slot i: need n_groups <= n_slots");
+    if (mag_out && (col0 < 0 || width < 1 || (long)col0 + n_frames > width))
+        return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: need col0 >= 0 and col0 + n_frames <= width");
+    if (!aligned_to(spec, 8) || !aligned_to(spec_out, 8) || !aligned_to(mag_out, 4))
+        return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: spec and spec_out must be 8-byte aligned, mag_out 4-byte aligned");
+    const char *a = reinterpret_cast<const char *>(spec), *b = reinterpret_cast<const char *>(spec_out);
+    const size_t span = (size_t)n_groups * (size_t)channels * (size_t)n_frames * (size_t)n_bins * 2 * sizeof(float);
+    if (a < b + span && b < a + span) return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: spec and spec_out may not overlap");
+    if (adn::wpe_stream_grid(n_groups, n_bins) > 0x7fffffffL)
+        return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: grid too large (n_groups x ceil(n_bins / 8) >= 2^31)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (channels == 1)                                   // every statement is "dereverb stream": the same kernel, its bits
+        ADN_LAUNCH(adn::launch_wpe_online(spec, n_groups, n_frames, n_bins, (int)first_frame, k, static_cast<float *>(state), spec_out,
+                                          mag_out, width, col0, st), "adn_wpe_mc_online");
+    else
+        ADN_LAUNCH(adn::launch_wpe_mc_online(spec, n_groups, channels, n_frames, n_bins, (int)first_frame, k, static_cast<float *>(state),
+                                             spec_out, mag_out, width, col0, st), "adn_wpe_mc_online");
+    return ADN_OK;
+}
+
+int adn_wpe_mc_stream(void *sstate, size_t sstate_bytes, float *y, int n_streams, int channels, long first_step, int n_steps,
+                      long final_length, int n_fft, int hop, int window, int block, int lookahead, int max_steps,
+                      const adn_wpe_stream_params *params, void *wpe_state, size_t wpe_state_bytes, void *stream)
+{
+    adn::StreamGeom g;
+    adn::StreamCall c;
+    adn::WpeStreamConsts k;
+    int rc = stream_state("adn_wpe_mc_stream", sstate, sstate_bytes, n_streams, n_fft, hop, window, block, lookahead, max_steps, &g);
+    if (rc != ADN_OK) return rc;
+    if (lookahead != 0) return fail(ADN_ERR_INVALID, "adn_wpe_mc_stream: the operator is causal: lookahead must be 0");
+    if (!y) return fail(ADN_ERR_INVALID, "adn_wpe_mc_stream: null pointer");
+    if (!aligned_to(y, 4)) return fail(ADN_ERR_INVALID, "adn_wpe_mc_stream: y must be 4-byte aligned");
+    rc = stream_call("adn_wpe_mc_stream", g, first_step, n_steps, final_length, &c);
+    if (rc != ADN_OK) return rc;
+    rc = wpe_mc_stream_consts("adn_wpe_mc_stream", channels, params, &k);
+    if (rc != ADN_OK) return rc;
+    if (n_streams % channels) return fail(ADN_ERR_INVALID, "adn_wpe_mc_stream: n_streams must be a multiple of channels");
+    rc = wpe_mc_stream_state("adn_wpe_mc_stream", wpe_state, wpe_state_bytes, n_streams / channels, n_fft / 2 + 1, channels, k);
+    if (rc != ADN_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (channels == 1)
+        ADN_LAUNCH(adn::launch_wpe_stream(static_cast<float *>(sstate), y, n_streams, g, c, k, static_cast<float *>(wpe_state), st),
+                   "adn_wpe_mc_stream");
+    else
+        ADN_LAUNCH(adn::launch_wpe_mc_stream(static_cast<float *>(sstate), y, n_streams, channels, g, c, k,
+                                             static_cast<float *>(wpe_state), st), "adn_wpe_mc_stream");
+    return ADN_OK;
+}
+
+static const char *resample_stream_text =": rates must be >= 1 with max(up, down) <= 4096 after dividing by their gcd, and at most "
                                           "16384 carried samples (2 floor(half / up) + ceil(down / up) + 1)";
 
 static bool resample_stream_plan_ok(int src_rate, int dst_rate, adn::ResampleStreamGeom *g)

@@ -585,6 +585,16 @@ hipError_t launch_wpe_stream(float *state, float *y, int n_streams, const Stream
                              const WpeStreamConsts &c, float *wstate, hipStream_t st);
 hipError_t launch_wpe_stream_pool(float *state, float *y, const StreamGeom &g, const StreamPoolRows &rows, const WpeStreamConsts &c,
                                   float *wstate, hipStream_t st);
+// Streaming multichannel dereverberation (dereverb_mc_stream_kernels.hip; adn.h, "dereverb stream multichannel"): the same
+// recursion on the N = C K stacked past frames of the C consecutive rows of a group, 2 <= C <= 8 and C K <= 32 (C = 1 is the
+// launches above), c.K the taps per channel.  wstate: wpe_mc_stream_record_floats(C, K, D) floats per (slot, bin), group i = slot
+// i.  The layouts are those of launch_wpe_online / launch_wpe_stream with n_groups * C rows / streams; the grid is
+// wpe_stream_grid(n_groups, F).
+long wpe_mc_stream_record_floats(int C, int K, int D);
+hipError_t launch_wpe_mc_online(const void *spec, int n_groups, int C, int T, int F, int first_frame, const WpeStreamConsts &c,
+                                float *wstate, void *spec_out, float *mag_out, int width, int col0, hipStream_t st);
+hipError_t launch_wpe_mc_stream(float *state, float *y, int n_streams, int C, const StreamGeom &g, const StreamCall &call,
+                                const WpeStreamConsts &c, float *wstate, hipStream_t st);
 hipError_t launch_quantize_pad(const float *in, int n, int h, int w, float *out, int H, int W, hipStream_t st);
 hipError_t launch_per_clip_l1(const float *a, const float *b, int n_clips, long elems, float *out, hipStream_t st);
 // Polyphase resampler and SNR mixer (resample_kernels.hip).  resample_ratio: up / down of a rate pair, false outside the limits

@@ -37,29 +37,12 @@
 // What binds is the per-frame chain of one workgroup, 8 us: 2 K correctly rounded divisions by alpha per lane (the definition
 // divides), both sides of the divergent k <= j branch, three passes of K LDS broadcasts, four barriers.  No atomics, no
 // workspace, no constant table.
-#include "adn_internal.h"
+#include "wpe_stream_frames.h"                        // the rounding rules and the frame sources: shared with dereverb_mc_stream_kernels.hip
 
 #include <type_traits>
 
 namespace adn {
 namespace {
-
-constexpr int WS_G = 32;                             // lanes per group = the most taps
-constexpr int WS_GROUPS = 8;                         // groups (bins) per workgroup
-constexpr int WS_HMAX = 40;                          // D + K at most
-
-// max(x, c) of adn.h: a NaN x stays NaN
-__device__ __forceinline__ float max_keep_nan(float x, float c) { return x < c ? c : x; }
-
-// acc + a b and acc + a conj(b), two fmaf per component (adn.h, "dereverb stream", "Arithmetic")
-__device__ __forceinline__ float2 cfma(float2 a, float2 b, float2 acc)
-{
-    return make_float2(fmaf(-a.y, b.y, fmaf(a.x, b.x, acc.x)), fmaf(a.y, b.x, fmaf(a.x, b.y, acc.y)));
-}
-__device__ __forceinline__ float2 cfma_conj(float2 a, float2 b, float2 acc)
-{
-    return make_float2(fmaf(a.y, b.y, fmaf(a.x, b.x, acc.x)), fmaf(a.y, b.x, fmaf(-a.x, b.y, acc.y)));
-}
 
 // The LDS of one group
 struct GroupLds {
@@ -129,78 +112,6 @@ __device__ __forceinline__ float2 step(float2 x, bool first, float &s, float2 (&
     if (j == 0) l.ring[pos] = x;
     __syncthreads();
     return e;
-}
-
-// ---------------------------------------------------------------------------------------------- where the frames are
-struct FrameMajor {
-    const float2 *spec;
-    float2 *out;
-    float *mag;                          // may be null
-    int T, width, col0, first_frame;
-};
-
-template <class Rows>
-struct InRing {
-    float *state;                        // the adn_stream_* / pool state
-    float *y;                            // the windows buffer
-    StreamGeom g;
-    Rows rows;
-};
-
-__device__ __forceinline__ StreamCall call_of(const StreamCall &c, const StreamGeom &, long) { return c; }
-__device__ __forceinline__ StreamCall call_of(const StreamPoolRows &t, const StreamGeom &g, long row)
-{
-    return stream_call_of(g, t.row[row].step, 1, t.row[row].final_length);
-}
-__device__ __forceinline__ long slot_of(const StreamCall &, long row) { return row; }
-__device__ __forceinline__ long slot_of(const StreamPoolRows &t, long row) { return t.row[row].slot; }
-
-// What a group needs to know about its row: the state slot, the frames [t0, t1], and the addresses of frame t
-struct RowFrames {
-    long slot;
-    int t0, t1;
-};
-
-__device__ __forceinline__ RowFrames frames_of(const FrameMajor &s, long row, int, StreamCall &)
-{
-    return RowFrames{row, s.first_frame, s.first_frame + s.T - 1};
-}
-template <class Rows>
-__device__ __forceinline__ RowFrames frames_of(const InRing<Rows> &s, long row, int, StreamCall &c)
-{
-    c = call_of(s.rows, s.g, row);
-    return RowFrames{slot_of(s.rows, row), c.f_first, c.f_last};
-}
-
-__device__ __forceinline__ float2 load_frame(const FrameMajor &s, const RowFrames &, const StreamCall &, long row, int F, int bin, int t)
-{
-    return s.spec[(row * s.T + (t - s.first_frame)) * (long)F + bin];
-}
-__device__ __forceinline__ void store_frame(const FrameMajor &s, const RowFrames &, const StreamCall &, long row, int F, int bin, int t,
-                                            float2 d, float m)
-{
-    const long i = t - s.first_frame;
-    s.out[(row * s.T + i) * (long)F + bin] = d;
-    if (s.mag) s.mag[(row * F + bin) * (long)s.width + s.col0 + i] = m;
-}
-template <class Rows>
-__device__ __forceinline__ float2 *ring_cell(const InRing<Rows> &s, const RowFrames &r, int F, int bin, int t)
-{
-    return reinterpret_cast<float2 *>(s.state + s.g.x_off) + (r.slot * s.g.RX + t % s.g.RX) * (long)F + bin;
-}
-template <class Rows>
-__device__ __forceinline__ float2 load_frame(const InRing<Rows> &s, const RowFrames &r, const StreamCall &, long, int F, int bin, int t)
-{
-    return *ring_cell(s, r, F, bin, t);
-}
-template <class Rows>
-__device__ __forceinline__ void store_frame(const InRing<Rows> &s, const RowFrames &r, const StreamCall &c, long row, int F, int bin, int t,
-                                            float2 d, float m)
-{
-    *ring_cell(s, r, F, bin, t) = d;
-    // frame t is local frame W - B + t mod B of step t / B (look-ahead 0), window (row n_steps + step - first) of the buffer
-    const int st = t / s.g.B;
-    s.y[((row * c.n_steps + (st - c.first)) * (long)F + bin) * s.g.W + (s.g.W - s.g.B) + (t - st * s.g.B)] = m;
 }
 
 template <class Src>

@@ -1,0 +1,102 @@
+// What the two recursive WPE kernels share (dereverb_stream_kernels.hip, dereverb_mc_stream_kernels.hip): the rounding rules of
+// adn.h, "dereverb stream", "Arithmetic", and the places a row's frames come from.  One definition, so that a joint stream of one
+// recording and C single-channel streams read and write the same cells by the same arithmetic.  Everything is in an unnamed
+// namespace on purpose: each of the two translation units instantiates its own kernels on these types, and the single-channel
+// kernels keep the symbols and the code they had when this text stood in their file (tools/kernel_isa_digest.py).
+#pragma once
+#include "adn_internal.h"
+
+namespace adn {
+namespace {
+
+constexpr int WS_G = 32;                             // lanes per group = the most taps
+constexpr int WS_GROUPS = 8;                         // groups (bins) per workgroup
+constexpr int WS_HMAX = 40;                          // D + K at most
+
+// max(x, c) of adn.h: a NaN x stays NaN
+__device__ __forceinline__ float max_keep_nan(float x, float c) { return x < c ? c : x; }
+
+// acc + a b and acc + a conj(b), two fmaf per component (adn.h, "dereverb stream", "Arithmetic")
+__device__ __forceinline__ float2 cfma(float2 a, float2 b, float2 acc)
+{
+    return make_float2(fmaf(-a.y, b.y, fmaf(a.x, b.x, acc.x)), fmaf(a.y, b.x, fmaf(a.x, b.y, acc.y)));
+}
+__device__ __forceinline__ float2 cfma_conj(float2 a, float2 b, float2 acc)
+{
+    return make_float2(fmaf(a.y, b.y, fmaf(a.x, b.x, acc.x)), fmaf(a.y, b.x, fmaf(-a.x, b.y, acc.y)));
+}
+
+// ---------------------------------------------------------------------------------------------- where the frames are
+struct FrameMajor {
+    const float2 *spec;
+    float2 *out;
+    float *mag;                          // may be null
+    int T, width, col0, first_frame;
+};
+
+template <class Rows>
+struct InRing {
+    float *state;                        // the adn_stream_* / pool state
+    float *y;                            // the windows buffer
+    StreamGeom g;
+    Rows rows;
+};
+
+__device__ __forceinline__ StreamCall call_of(const StreamCall &c, const StreamGeom &, long) { return c; }
+__device__ __forceinline__ StreamCall call_of(const StreamPoolRows &t, const StreamGeom &g, long row)
+{
+    return stream_call_of(g, t.row[row].step, 1, t.row[row].final_length);
+}
+__device__ __forceinline__ long slot_of(const StreamCall &, long row) { return row; }
+__device__ __forceinline__ long slot_of(const StreamPoolRows &t, long row) { return t.row[row].slot; }
+
+// What a group needs to know about its row: the state slot, the frames [t0, t1], and the addresses of frame t
+struct RowFrames {
+    long slot;
+    int t0, t1;
+};
+
+__device__ __forceinline__ RowFrames frames_of(const FrameMajor &s, long row, int, StreamCall &)
+{
+    return RowFrames{row, s.first_frame, s.first_frame + s.T - 1};
+}
+template <class Rows>
+__device__ __forceinline__ RowFrames frames_of(const InRing<Rows> &s, long row, int, StreamCall &c)
+{
+    c = call_of(s.rows, s.g, row);
+    return RowFrames{slot_of(s.rows, row), c.f_first, c.f_last};
+}
+
+__device__ __forceinline__ float2 load_frame(const FrameMajor &s, const RowFrames &, const StreamCall &, long row, int F, int bin, int t)
+{
+    return s.spec[(row * s.T + (t - s.first_frame)) * (long)F + bin];
+}
+__device__ __forceinline__ void store_frame(const FrameMajor &s, const RowFrames &, const StreamCall &, long row, int F, int bin, int t,
+                                            float2 d, float m)
+{
+    const long i = t - s.first_frame;
+    s.out[(row * s.T + i) * (long)F + bin] = d;
+    if (s.mag) s.mag[(row * F + bin) * (long)s.width + s.col0 + i] = m;
+}
+template <class Rows>
+__device__ __forceinline__ float2 *ring_cell(const InRing<Rows> &s, const RowFrames &r, int F, int bin, int t)
+{
+    return reinterpret_cast<float2 *>(s.state + s.g.x_off) + (r.slot * s.g.RX + t % s.g.RX) * (long)F + bin;
+}
+template <class Rows>
+__device__ __forceinline__ float2 load_frame(const InRing<Rows> &s, const RowFrames &r, const StreamCall &, long, int F, int bin, int t)
+{
+    return *ring_cell(s, r, F, bin, t);
+}
+template <class Rows>
+__device__ __forceinline__ void store_frame(const InRing<Rows> &s, const RowFrames &r, const StreamCall &c, long row, int F, int bin, int t,
+                                            float2 d, float m)
+{
+    *ring_cell(s, r, F, bin, t) = d;
+    // frame t is local frame W - B + t mod B of step t / B (look-ahead 0), window (row n_steps + step - first) of the buffer
+    const int st = t / s.g.B;
+    s.y[((row * c.n_steps + (st - c.first)) * (long)F + bin) * s.g.W + (s.g.W - s.g.B) + (t - st * s.g.B)] = m;
+}
+
+}  // namespace
+}  // namespace adn

@@ -10,9 +10,11 @@
     live = StreamDereverberator(n_streams=2)           # audio that is still arriving: recursive WPE, one update per frame
     out = live.push(block); ...; out = live.flush()    # the surface of StreamDenoiser; DereverbStreamPool: that of StreamPool
     d, mag, state = wpe_online(spec)                   # the recursion on a spectrogram; pass state and first_frame to go on
+    live = StreamDereverberator(n_streams=2, channels=2)   # the two streams are ONE recording: the recursive joint form
+    d, mag, state = wpe_online_joint(spec, 2)          # the joint recursion, (n_groups * 2, T, F)
 
     python -m audiodenoiser_amd.dereverb IN OUT [--reference CLEAN] [--taps K] [--delay D] [--iterations I] [--gain] [--joint]
-    python -m audiodenoiser_amd.dereverb IN OUT --live [--chunk N] [--block B] [--forget A] [--gain] [--reference CLEAN]
+    python -m audiodenoiser_amd.dereverb IN OUT --live [--chunk N] [--block B] [--forget A] [--gain] [--joint] [--reference CLEAN]
 
 The operator is DEFINED in ``include/adn.h`` ("dereverb"; float64 restatement: ``tests/dereverb_ref.py``) and is unpinned against
 any package: single-channel WPE, delayed linear prediction per frequency bin with the variance re-estimated from the last result
@@ -43,7 +45,14 @@ place, exactly as ``StreamSpectralDenoiser`` / ``SpectralStreamPool`` carry the 
 same columns afterwards, the streaming form of the cascade.  A row that starts at frame 0 starts fresh whatever the WPE state
 holds, so there is nothing to reset.
 
-What is NOT here: more than one channel in the streaming classes (they stay single-channel), look-ahead or iterated online
+``StreamDereverberator(channels=C)`` is the joint form of that recursion, DEFINED in ``include/adn.h`` ("dereverb stream
+multichannel"; float64 restatement: ``tests/dereverb_mc_stream_ref.py``; ``csrc/dereverb_mc_stream_kernels.hip``): ``C``
+consecutive streams are one recording, an N x N matrix with ``N = C * taps <= 32`` and N x C taps per (recording, bin), one
+variance shared by the channels; ``adn_wpe_mc_stream`` stands in ``adn_wpe_stream``'s place and nothing else changes.
+``params=None`` takes ``taps = 32 // C``.  With more than one channel ``2 N (1 - forget) <= 1`` must hold (the header says why).
+``wpe_online_joint`` is the recursion on spectrograms.
+
+What is NOT here: multichannel streams in ``DereverbStreamPool`` (it stays single-channel), look-ahead or iterated online
 variants, beamforming, any tuning of the defaults by ear.  There is no CPU path.
 """
 from __future__ import annotations
@@ -62,8 +71,8 @@ from .denoise import Denoiser
 from .griffin_lim import stft_complex
 from .stream import POOL_MAX_ROWS, PoolBook, StreamDenoiser, StreamPool, _check_stream_args, causal_carrier
 
-__all__ = ["WpeParams", "wpe", "wpe_joint", "Dereverberator", "WpeStreamParams", "wpe_online", "wpe_stream_state_bytes", "StreamDereverberator",
-           "DereverbStreamPool"]
+__all__ = ["WpeParams", "wpe", "wpe_joint", "Dereverberator", "WpeStreamParams", "wpe_online", "wpe_stream_state_bytes",
+           "wpe_online_joint", "wpe_stream_state_bytes_joint", "StreamDereverberator", "DereverbStreamPool"]
 
 
 @dataclasses.dataclass(frozen=True)
@@ -243,6 +252,35 @@ def wpe_stream_state_bytes(n_slots: int, n_bins: int, params: WpeStreamParams = 
     return int(need.value)
 
 
+def _joint_stream_params(who, params, channels):
+    """The parameters of a joint streaming call on ``channels`` channels: ``params``, or the defaults with ``taps = 32 //
+    channels``.  ValueError for a channel count outside 1 ... 8, for ``channels * taps > 32`` and, with more than one channel, for
+    ``2 channels taps (1 - forget) > 1`` on the fp32 value of ``forget`` -- the rules of "dereverb stream multichannel", checked
+    here because here the channel count is known, before anything looks at a device."""
+    if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= 8:
+        raise ValueError(f"{who}: need an integer 1 <= channels <= 8")
+    if params is None:
+        return WpeStreamParams(taps=32 // channels)
+    if not isinstance(params, WpeStreamParams):
+        raise TypeError(f"{who}: params must be a WpeStreamParams")
+    n = channels * params.taps
+    if n > 32:
+        raise ValueError(f"{who}: need channels * taps <= 32 (channels {channels}, taps {params.taps})")
+    if channels > 1 and not 2.0 * n * (1.0 - ctypes.c_float(float(params.forget)).value) <= 1.0:
+        raise ValueError(f"{who}: need 2 channels taps (1 - forget) <= 1 with more than one channel: forget >= {1 - 1 / (2 * n):.6f} "
+                         f"at channels * taps = {n} (forget {params.forget})")
+    return params
+
+
+def wpe_stream_state_bytes_joint(n_slots: int, channels: int, n_bins: int, params: WpeStreamParams = None) -> int:
+    """``adn_wpe_mc_stream_state_bytes``: the bytes of the opaque joint WPE state of ``n_slots`` groups of ``channels`` channels
+    and ``n_bins`` bins (no device needed).  ``params=None``: the defaults with ``taps = 32 // channels``."""
+    need = ctypes.c_size_t(0)
+    _lib.check(_lib.load().adn_wpe_mc_stream_state_bytes(n_slots, channels, n_bins, _stream_params("wpe_stream_state_bytes_joint", params),
+                                                         ctypes.byref(need)), "adn_wpe_mc_stream_state_bytes")
+    return int(need.value)
+
+
 def wpe_online(spec: torch.Tensor, state: torch.Tensor = None, first_frame: int = 0, params: WpeStreamParams = None,
                mag_out: torch.Tensor = None, col0: int = 0):
     """``adn_wpe_online`` on the current stream.  ``spec``: complex64 ``(n_rows, T, F)`` on a ROCm device, the frames
@@ -250,50 +288,77 @@ def wpe_online(spec: torch.Tensor, state: torch.Tensor = None, first_frame: int 
     them (None allocates one; with ``first_frame = 0`` every row starts fresh whatever it holds); it is updated IN PLACE.
     ``mag_out``: float32 ``(n_rows, 1, F, width)`` whose columns ``[col0, col0 + T)`` are written and nothing else; None allocates
     ``(n_rows, 1, F, T)``.  Returns ``(d, mag_out, state)``, ``d`` a new complex64 tensor of ``spec``'s shape."""
+    return _wpe_online("wpe_online", spec, None, state, first_frame, params, mag_out, col0)
+
+
+def wpe_online_joint(spec: torch.Tensor, channels: int, state: torch.Tensor = None, first_frame: int = 0,
+                     params: WpeStreamParams = None, mag_out: torch.Tensor = None, col0: int = 0):
+    """``adn_wpe_mc_online`` on the current stream: ``wpe_online`` with the leading dimension ``n_groups * channels``, the
+    ``channels`` channels of a recording consecutive rows, dereverberated jointly; the state (``wpe_stream_state_bytes_joint``)
+    has a slot per GROUP.  ``params=None``: the defaults with ``taps = 32 // channels``.  ValueError if the leading dimension is
+    no multiple of ``channels``, ``channels * taps > 32`` or the forget rule is broken.  ``channels = 1`` returns ``wpe_online``'s
+    bits, state included."""
+    params = _joint_stream_params("wpe_online_joint", params, channels)
+    if isinstance(spec, torch.Tensor) and spec.dim() == 3 and spec.shape[0] % channels:
+        raise ValueError(f"wpe_online_joint: the leading dimension {spec.shape[0]} is not a multiple of channels = {channels}")
+    return _wpe_online("wpe_online_joint", spec, channels, state, first_frame, params, mag_out, col0)
+
+
+def _wpe_online(who, spec, channels, state, first_frame, params, mag_out, col0):
+    """``adn_wpe_online`` (``channels=None``) or ``adn_wpe_mc_online`` on the current stream."""
     if not isinstance(spec, torch.Tensor) or not spec.is_cuda or spec.dtype != torch.complex64 or spec.dim() != 3:
-        raise ValueError("wpe_online: expected a (n_rows, n_frames, n_bins) complex64 tensor on a ROCm device")
-    p = _stream_params("wpe_online", params)
+        raise ValueError(f"{who}: expected a (n_rows, n_frames, n_bins) complex64 tensor on a ROCm device")
+    p = _stream_params(who, params)
     n, t, f = spec.shape
     if n < 1 or t < 1 or f < 1:
-        raise ValueError("wpe_online: need at least one row, one frame and one bin")
+        raise ValueError(f"{who}: need at least one row, one frame and one bin")
     if not (isinstance(first_frame, int) and first_frame >= 0 and isinstance(col0, int) and col0 >= 0):
-        raise ValueError("wpe_online: need integers first_frame >= 0 and col0 >= 0")
+        raise ValueError(f"{who}: need integers first_frame >= 0 and col0 >= 0")
     dev = spec.device
-    need = wpe_stream_state_bytes(n, f, params)
+    slots = n if channels is None else n // channels
+    need = wpe_stream_state_bytes(n, f, params) if channels is None else wpe_stream_state_bytes_joint(slots, channels, f, params)
     if state is None:
         if first_frame != 0:
-            raise ValueError("wpe_online: first_frame > 0 continues a row: pass the state of the call before")
+            raise ValueError(f"{who}: first_frame > 0 continues a row: pass the state of the call before")
         state = torch.empty((need,), dtype=torch.uint8, device=dev)
     elif (not isinstance(state, torch.Tensor) or not state.is_cuda or state.device != dev or state.dtype != torch.uint8
           or state.dim() != 1 or state.numel() < need or not state.is_contiguous()):
-        raise ValueError("wpe_online: state must be a contiguous uint8 tensor of at least wpe_stream_state_bytes on spec's device")
+        raise ValueError(f"{who}: state must be a contiguous uint8 tensor of at least wpe_stream_state_bytes on spec's device")
     s = torch.view_as_real(spec.contiguous())
     if mag_out is None:
         if col0 != 0:
-            raise ValueError("wpe_online: col0 needs a mag_out buffer")
+            raise ValueError(f"{who}: col0 needs a mag_out buffer")
         mag_out = torch.empty((n, 1, f, t), dtype=torch.float32, device=dev)
     elif (not isinstance(mag_out, torch.Tensor) or not mag_out.is_cuda or mag_out.device != dev or mag_out.dtype != torch.float32
           or mag_out.dim() != 4 or tuple(mag_out.shape[:3]) != (n, 1, f) or not mag_out.is_contiguous()):
-        raise ValueError("wpe_online: mag_out must be a contiguous (n_rows, 1, n_bins, width) float32 tensor on spec's device")
+        raise ValueError(f"{who}: mag_out must be a contiguous (n_rows, 1, n_bins, width) float32 tensor on spec's device")
     out = torch.empty((n, t, f, 2), dtype=torch.float32, device=dev)
+    L = _lib.load()
+    run, shape = (L.adn_wpe_online, (n,)) if channels is None else (L.adn_wpe_mc_online, (slots, channels))
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().adn_wpe_online(s.data_ptr(), n, t, f, first_frame, p, state.data_ptr(), state.numel(), n,
-                                              out.data_ptr(), mag_out.data_ptr(), int(mag_out.shape[3]), col0, current_stream(dev)),
-                   "adn_wpe_online")
+        _lib.check(run(s.data_ptr(), *shape, t, f, first_frame, p, state.data_ptr(), state.numel(), slots, out.data_ptr(),
+                       mag_out.data_ptr(), int(mag_out.shape[3]), col0, current_stream(dev)), run.__name__)
     return torch.view_as_complex(out), mag_out, state
 
 
-def _wpe_setup(sd, who, device, n_slots, n_fft, params, gain, gain_params):
+def _wpe_setup(sd, who, device, n_slots, n_fft, params, gain, gain_params, channels=1):
     """What both stream classes carry for the operator, ``n_slots`` rows of it: the parameters, the WPE state and the gain's three
-    floats per bin, on the device this returns.  Refuses parameter types before it looks at the device."""
+    floats per bin, on the device this returns.  Refuses parameter types before it looks at the device.  ``channels > 1``:
+    ``channels`` consecutive rows are one recording, a WPE slot per recording; the gain stays per row."""
     _stream_params(who, params)
+    joint = _joint_stream_params(who, params, channels) if channels != 1 else None
+    if n_slots % channels:
+        raise ValueError(f"{who}: n_streams = {n_slots} is not a multiple of channels = {channels}")
     sd.gain_params = _spectral_params(who, gain_params, "gain_params")
     dev = rocm_device(who, device)
     sd.model = None
-    sd.params = WpeStreamParams() if params is None else params
+    sd.channels = channels
+    sd.params = joint if joint is not None else WpeStreamParams() if params is None else params
     sd.gain = bool(gain)
     f = n_fft // 2 + 1
-    sd._wpe_state = torch.empty((wpe_stream_state_bytes(n_slots, f, sd.params),), dtype=torch.uint8, device=dev)
+    need = (wpe_stream_state_bytes(n_slots, f, sd.params) if channels == 1 else
+            wpe_stream_state_bytes_joint(n_slots // channels, channels, f, sd.params))
+    sd._wpe_state = torch.empty((need,), dtype=torch.uint8, device=dev)
     sd._gain_state = torch.empty((n_slots, 3, f), dtype=torch.float32, device=dev)
     return dev
 
@@ -301,7 +366,7 @@ def _wpe_setup(sd, who, device, n_slots, n_fft, params, gain, gain_params):
 def _wpe_then_gain(sd, x: torch.Tensor, rows, n_steps: int, first_step: int = 0, final_length: int = -1) -> torch.Tensor:
     """The operator of both stream classes between ``analyze`` and ``emit``, in place on the analysed windows ``x``; every state
     is read from ``sd`` when it runs.  ``rows=None``: the lockstep object's steps ``first_step ..``, ``n_steps`` per stream
-    (``adn_wpe_stream``).  Otherwise a pool tick's rows ``(slot, step, final_length)``, one step each, ``POOL_MAX_ROWS`` a call
+    (``adn_wpe_stream``, or ``adn_wpe_mc_stream`` when ``sd.channels`` consecutive streams are one recording).  Otherwise a pool tick's rows ``(slot, step, final_length)``, one step each, ``POOL_MAX_ROWS`` a call
     (``adn_wpe_stream_pool``).  With ``sd.gain`` the spectral gain follows each call on the columns it wrote."""
     L = _lib.load()
     state = (sd._state.data_ptr(), sd._state.numel())
@@ -312,7 +377,10 @@ def _wpe_then_gain(sd, x: torch.Tensor, rows, n_steps: int, first_step: int = 0,
         plan, groups = sd.book.plan, [(x[i:i + POOL_MAX_ROWS], rows[i:i + POOL_MAX_ROWS]) for i in range(0, len(rows), POOL_MAX_ROWS)]
     for part, group in groups:
         with torch.cuda.device(sd.device):
-            if group is None:
+            if group is None and sd.channels != 1:
+                _lib.check(L.adn_wpe_mc_stream(*state, part.data_ptr(), sd.n_streams, sd.channels, first_step, n_steps, final_length,
+                                               *plan, sd.max_steps, *wpe_args), "adn_wpe_mc_stream")
+            elif group is None:
                 _lib.check(L.adn_wpe_stream(*state, part.data_ptr(), sd.n_streams, first_step, n_steps, final_length, *plan,
                                             sd.max_steps, *wpe_args), "adn_wpe_stream")
             else:
@@ -331,15 +399,22 @@ class StreamDereverberator(StreamDenoiser):
     stream geometry needs: each run of steps calls ``adn_wpe_stream`` in place on the analysed windows -- ``d`` into the frames the
     steps emit, ``|d|`` into the ``block_frames`` columns ``adn_stream_emit`` reads -- and with ``gain=True`` then
     ``adn_spectral_gain_windows`` on the same columns (``gain_params``), whose three floats per bin live beside the WPE state.  The
-    WPE state needs no reset: a stream's frame 0 starts it afresh.  ``block_frames = 4``: as ``StreamSpectralDenoiser``."""
+    WPE state needs no reset: a stream's frame 0 starts it afresh.  ``block_frames = 4``: as ``StreamSpectralDenoiser``.
+
+    ``channels = C > 1``: ``n_streams`` is a multiple of ``C`` and ``C`` consecutive streams are the microphones of ONE recording,
+    dereverberated jointly (``adn_wpe_mc_stream``, "dereverb stream multichannel").  ``params=None`` then takes ``taps = 32 // C``;
+    a ``params`` with ``C * taps > 32`` or ``2 C taps (1 - forget) > 1`` is a ValueError here.  The gain, the resamplers of
+    ``input_rate`` and everything else stay per stream.  ``channels = 1`` is the single-channel object, bit for bit."""
 
     def __init__(self, device=None, n_streams: int = 1, sample_rate: int = 8000, n_fft: int = 512, hop_length: int = 128,
                  block_frames: int = 4, params: WpeStreamParams = None, gain: bool = False, gain_params: SpectralParams = None,
-                 input_rate=None):
+                 input_rate=None, channels: int = 1):
         window, ahead, batch = causal_carrier(block_frames)
         _check_stream_args("StreamDereverberator", n_streams, sample_rate, n_fft, hop_length, window, block_frames, ahead, batch,
                            input_rate)
-        dev = _wpe_setup(self, "StreamDereverberator", device, n_streams, n_fft, params, gain, gain_params)
+        if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= 8:
+            raise ValueError("StreamDereverberator: need an integer 1 <= channels <= 8")
+        dev = _wpe_setup(self, "StreamDereverberator", device, n_streams, n_fft, params, gain, gain_params, channels)
         self._setup(dev, n_streams, sample_rate, n_fft, hop_length, window, block_frames, ahead, batch, input_rate)
 
     def reset(self):
@@ -366,7 +441,7 @@ class DereverbStreamPool(StreamPool):
                  gain_params: SpectralParams = None, input_rates=None):
         window, ahead, _ = causal_carrier(block_frames)
         self.book = PoolBook(max_streams, backlog_steps, n_fft, hop_length, window, block_frames, ahead, input_rates, sample_rate)
-        dev = _wpe_setup(self, "DereverbStreamPool", device, max_streams, n_fft, params, gain, gain_params)
+        dev = _wpe_setup(self, "DereverbStreamPool", device, max_streams, n_fft, params, gain, gain_params)   # channels = 1: see the module text
         self.batch_windows = POOL_MAX_ROWS
         self._setup(dev)
 
@@ -391,12 +466,13 @@ def main(argv=None) -> int:
     ap.add_argument("--reference", metavar="CLEAN", default=None,
                     help="the dry wav of IN (or a folder with IN's file names): print one JSON line of metrics per file")
     ap.add_argument("--taps", type=int, default=None,
-                    help=f"prediction taps K, 1 ... 32 (default {WpeParams.taps}; with --joint 32 // channels, per channel)")
+                    help=f"prediction taps K, 1 ... 32 (default {WpeParams.taps}; with --joint 32 // channels, per channel, --live too)")
     ap.add_argument("--delay", type=int, default=WpeParams.delay, help="prediction delay D in frames, 1 ... 8")
     ap.add_argument("--iterations", type=int, default=WpeParams.iterations, help="iterations I, 1 ... 8")
     ap.add_argument("--gain", action="store_true", help="run the spectral baseline's Wiener gain on the result of WPE")
     ap.add_argument("--joint", action="store_true",
-                    help="dereverberate the channels of a file together (multichannel WPE, channels * taps <= 32), not one by one")
+                    help="dereverberate the channels of a file together (multichannel WPE, channels * taps <= 32), not one by one; "
+                         "with --live the recursive joint form (forget >= 1 - 1 / (2 channels taps))")
     ap.add_argument("--live", action="store_true",
                     help="push the file (not a folder) through the streaming form (recursive WPE) at its own rate, as a live feed arrives")
     ap.add_argument("--chunk", type=int, default=1024, help="with --live: samples per push, at the file's rate")
@@ -410,14 +486,16 @@ def main(argv=None) -> int:
         if os.path.isdir(args.src):
             ap.error("--live takes one wav file")
 
-        if args.joint:
-            ap.error("--joint is the offline operator's: the streaming form is single-channel")
-
         def make(dev, n_streams, rate):
-            params = WpeStreamParams(taps=taps, delay=args.delay, forget=args.forget)
-            return StreamDereverberator(dev, n_streams=n_streams, block_frames=args.block, params=params, gain=args.gain, input_rate=rate)
+            channels = n_streams if args.joint else 1            # --joint: the wav's channels are one recording
+            if not 1 <= channels <= 8:
+                raise ValueError(f"--joint: {channels} channels; the joint form takes 1 ... 8")
+            k = 32 // channels if args.joint and args.taps is None else taps
+            params = WpeStreamParams(taps=k, delay=args.delay, forget=args.forget)
+            return StreamDereverberator(dev, n_streams=n_streams, block_frames=args.block, params=params, gain=args.gain, input_rate=rate,
+                                        channels=channels)
         try:
-            return run_live(make, args.src, args.dst, args.chunk, args.reference)
+            return run_live(make, args.src, args.dst, args.chunk, args.reference, per_channel=args.joint)
         except ValueError as exc:
             ap.error(str(exc))
     try:

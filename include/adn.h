@@ -33,7 +33,7 @@
 
 #include <stddef.h>
 
-/* The 70 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 73 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -746,7 +746,8 @@ ADN_API int adn_wpe(const float *spec, int n_clips, int n_frames, int n_bins, co
  * 4 T (N (N + 1) / 2 + 2 N C) FMAs.  No atomics, no constant table; nothing blocks or allocates.
  * Limits (ADN_ERR_INVALID before any launch): as adn_wpe, with n_groups in n_clips' place, and n_groups * channels < 2^31.
  * ADN_ERR_WORKSPACE: workspace_bytes below adn_wpe_mc_workspace_bytes.  Element offsets are 64-bit.
- * Not here: streaming or online multichannel WPE ("dereverb stream" is single-channel); beamforming; N > 32; any tuning by ear. */
+ * For audio that is still arriving, the recursive joint form: "dereverb stream multichannel", below.
+ * Not here: beamforming; N > 32; any tuning by ear. */
 ADN_API int adn_wpe_mc_workspace_bytes(int n_groups, int channels, int n_frames, int n_bins, const adn_wpe_params *params,
                                        size_t *bytes);
 ADN_API int adn_wpe_mc(const float *spec, int n_groups, int channels, int n_frames, int n_bins, const adn_wpe_params *params,
@@ -830,7 +831,8 @@ ADN_API int adn_wpe_mc(const float *spec, int n_groups, int channels, int n_fram
  * steps and the rows (more than ADN_STREAM_POOL_MAX_ROWS rows, a slot out of range or named twice); launch grid < 2^31 workgroups;
  * the parameters as above.  ADN_ERR_WORKSPACE: a state below its size function's bytes.  Element offsets are 64-bit.
  * adn_wpe_stream_state_bytes is host-only (no device needed).
- * Not here: more than one channel; look-ahead or iterated online variants; any tuning by ear. */
+ * More than one channel treated jointly: the next section, "dereverb stream multichannel".
+ * Not here: look-ahead or iterated online variants; any tuning by ear. */
 typedef struct adn_wpe_stream_params { int taps, delay; float forget, loading, power_floor, smooth; } adn_wpe_stream_params;
 ADN_API int adn_wpe_stream_state_bytes(int n_slots, int n_bins, const adn_wpe_stream_params *params, size_t *bytes);
 ADN_API int adn_wpe_online(const float *spec, int n_rows, int n_frames, int n_bins, long first_frame,
@@ -842,6 +844,84 @@ ADN_API int adn_wpe_stream(void *stream_state, size_t stream_state_bytes, float 
 ADN_API int adn_wpe_stream_pool(void *pool_state, size_t pool_state_bytes, int n_slots, int n_fft, int hop, int window, int block,
                                 int lookahead, long ring_samples, const adn_stream_pool_row *rows, int n_rows, float *y,
                                 const adn_wpe_stream_params *params, void *wpe_state, size_t wpe_state_bytes, void *stream);
+
+/* ---- dereverb stream multichannel: recursive joint WPE of the channels of a live recording -----------------------------------------
+ * No reference counterpart and no checkpoint.  The library DEFINES the operator below (float64 restatement:
+ * tests/dereverb_mc_stream_ref.py); it is UNPINNED against any package.  It is to "dereverb stream" what "dereverb multichannel" is
+ * to "dereverb": recursive least squares per (group, bin), every channel's late reverberation predicted from the past frames of
+ * ALL channels of the recording, one variance per frame shared by the channels.  It is causal.
+ * Not validated: the defaults are the parent's with the longest filter the stacked size admits; they were not tuned by ear.
+ *
+ * A group is the C channels of one recording, 1 <= C <= 8, and N = C K <= 32; every (group, bin) is independent.  X_{t,c} is
+ * channel c at frame t, zero for t < 0.  The stacked vector is "dereverb multichannel"'s: x~[r] = X_{t-D-j, c} at r = c K + j, from
+ * raw inputs, never outputs.  G is N x C (column c predicts channel c), P is N x N.  In fp32, with the rounding rules of "dereverb
+ * stream" (a complex multiply-add is two fmaf per component, the real-part product first; sums start at +0; divisions and the
+ * square root are correctly rounded, componentwise; max(x, c) is `x < c ? c : x`; 1 / delta and 1 - beta are formed once in fp32):
+ *   first frame (t = 0):  G = 0 (N x C),  P = (1 / delta) I (N x N),  s_0 = p_0
+ *   p_t    = (sum_c fmaf(re_c, re_c, im_c * im_c)) / C                 (c ascending, then one division by (float) C)
+ *   s_t    = beta s_{t-1} + (1 - beta) p_t                              (t > 0)
+ *   phi_t  = max(rho s_t, 1e-30)
+ *   e_c    = X_{t,c} - sum_r conj(G_rc) x~_r                            (r ascending; the OUTPUT d_{t,c})
+ *   lam_t  = max((sum_c |e_c|^2) / C, phi_t)                            (c ascending; |.|^2 as p)
+ *   u_r    = sum_s P_rs x~_s   (s ascending);   q = sum_r Re(conj(x~_r) u_r)   (r ascending)
+ *   den    = alpha lam_t + q;   k_r = u_r / den
+ *   P_rs  <- (P_rs - k_r conj(u_s)) / alpha for r >= s;  Im P_rr := 0;  P_sr := conj(P_rs)
+ *   G_rc  <- G_rc + k_r conj(e_c)
+ *   M_{t,c} = sqrtf(fmaf(e.re, e.re, e.im * e.im))                      (the optional magnitude)
+ * The Hermitian update is part of the DEFINITION, as in "dereverb stream".  The recursion is exact RLS with C right-hand sides:
+ * with the lam_t it produced, G after T frames solves the stacked normal equations
+ *   (alpha^T delta I + sum_t alpha^(T-1-t) x~_t x~_t^H / lam_t) G_c = sum_t alpha^(T-1-t) x~_t conj(X_{t,c}) / lam_t
+ * (tests/test_dereverb_mc_stream_host.py, alpha = 1, to 1e-9 in float64).
+ * Parameters: adn_wpe_stream_params, taps PER CHANNEL.  NULL = the defaults of "dereverb stream" with taps = 32 / C (integer
+ * division).
+ * Legal (ADN_ERR_INVALID otherwise, before any launch, the message starts with the function's name and names the field): the
+ * ranges of "dereverb stream"; 1 <= channels <= 8; channels * taps <= 32; and for C >= 2 additionally 2 N (1 - forget) <= 1,
+ * evaluated in double on the fp32 value of forget: N = 32 admits forget >= 0.984375, N = 16 0.96875, and N <= 10 every fp32 value
+ * above 0.95 (0.95f itself is 0.94999999 and misses the rule at N = 10 by 2.4e-7).  The reason: 1 / (1 - forget) is the length of
+ * the window in frames, and below the rule the window holds fewer frames than twice the N unknowns; the fp32 recursion then loses
+ * accuracy or goes non-finite at N = 32 -- on the host, 40 s at N = 32: forget 0.985 stays finite (error 5e-4 of the maximum);
+ * forget 0.97 reaches 2.4e-3 at (2, 16) and diverges at (8, 4); forget 0.95 goes non-finite at (8, 4) within 30 s, and stays
+ * finite at N = 20, 16 and 10 (profiles/bench_dereverb_mc_stream.md).  The rule does not apply to C = 1, whose definition and
+ * pins are "dereverb stream"'s.
+ * Consequences: with C = 1 every statement is "dereverb stream" ((+0 + p) / 1 = p), the call is forwarded to that kernel and
+ * returns its bits, state included; the first D frames of every channel come back bit for bit; an all-zero group gives zeros; a
+ * non-finite value is confined to its own (group, bin) -- ALL C channels of that bin stay poisoned from then on, no other bin or
+ * group is touched; a group whose first frame of the call is frame 0 starts fresh whatever the state holds: no reset, no
+ * sentinel.  Not claimed: the wind-up of an exactly-zero group, as in "dereverb stream".
+ *
+ * What is pinned.  The result is bounded against the float64 restatement (tests/test_gpu_dereverb_mc_stream.py: per group
+ * max |d - d64| <= 4 FLOOR max |d64|, FLOOR the error of the same statements run in fp32 on the host).  Pinned bit for bit: two
+ * calls give the same result; any cut of a group's frames into calls; a group alone or in any batch, in whatever slot; a bin
+ * whichever other bins share the call; a lockstep stream (adn_wpe_mc_stream) against adn_wpe_mc_online on the same spectrogram.
+ * NOT pinned: the bits against numpy; a permutation of the channels (the stacked order enters every sum).  Deterministic: no
+ * atomics, no reduction across lanes.
+ *
+ * State (adn_wpe_mc_stream_state_bytes(n_slots, channels, n_bins, params), caller-owned, opaque, 8-byte aligned; its size depends
+ * on channels, taps and delay; host-only, and it validates everything about the parameters): per (slot, bin) the full P, G, s and
+ * per channel a ring of the last D + K raw frames.  A slot is a GROUP.  With channels = 1 it is adn_wpe_stream_state_bytes'.
+ *
+ * Two entry points, one step function:
+ *   adn_wpe_mc_online: adn_wpe_online with the leading dimension n_groups * channels, a group's channels consecutive rows --
+ *     adn_wpe_mc's layout; mag_out (n_groups * channels, 1, n_bins, width), columns [col0, col0 + n_frames).  Group i uses slot i.
+ *     It writes those columns, all of spec_out, the state of its groups, and not one byte else.
+ *   adn_wpe_mc_stream: adn_wpe_stream for an adn_stream_* state whose streams g C ... g C + C - 1 are group g (n_streams a
+ *     multiple of channels): d in place into each channel's ring cells, M into columns [window - block, window) of each channel's
+ *     windows of y.  wpe_state has n_streams / channels slots.  adn_stream_analyze and adn_stream_emit are what they were.
+ * Cost: one launch, n_groups x ceil(n_bins / 8) workgroups of 8 bins, 32 lanes per (group, bin); no workspace, no atomics, no
+ * constant table; nothing blocks or allocates.  A call's time is the per-frame chain of a workgroup:
+ * profiles/bench_dereverb_mc_stream.md.
+ * Limits (ADN_ERR_INVALID before any launch; a refused call writes nothing): those of adn_wpe_online with n_groups in n_rows'
+ * place, and n_groups * channels < 2^31; everything adn_wpe_stream refuses, and n_streams % channels != 0.  ADN_ERR_WORKSPACE: a
+ * state below adn_wpe_mc_stream_state_bytes.  Element offsets are 64-bit.
+ * Not here: the stream pool with multichannel streams; look-ahead; beamforming; N > 32; any tuning by ear. */
+ADN_API int adn_wpe_mc_stream_state_bytes(int n_slots, int channels, int n_bins, const adn_wpe_stream_params *params, size_t *bytes);
+ADN_API int adn_wpe_mc_online(const float *spec, int n_groups, int channels, int n_frames, int n_bins, long first_frame,
+                              const adn_wpe_stream_params *params, void *state, size_t state_bytes, int n_slots, float *spec_out,
+                              float *mag_out, int width, int col0, void *stream);
+ADN_API int adn_wpe_mc_stream(void *stream_state, size_t stream_state_bytes, float *y, int n_streams, int channels, long first_step,
+                              int n_steps, long final_length, int n_fft, int hop, int window, int block, int lookahead,
+                              int max_steps, const adn_wpe_stream_params *params, void *wpe_state, size_t wpe_state_bytes,
+                              void *stream);
 
 /* ---- environment switches -------------------------------------------------------------------------------------------------
  * Read ONCE, when a U-Net handle is created (never per call).  None is needed in production: the defaults are the measured best
