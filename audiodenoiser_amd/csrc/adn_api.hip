@@ -561,12 +561,25 @@ int adn_spectral_gain_windows(const float *windows, float *y, int n_rows, int n_
     return ADN_OK;
 }
 
-/* ---- dereverberation baseline: per-bin WPE (adn.h, "dereverb") ---------------------------------------------------- */
+/* ---- dereverberation: WPE per bin, one channel or the channels of a recording jointly (adn.h, "dereverb", "dereverb multichannel") */
+// The two entry points of a pair share one body: the single-channel one is the joint one at channels = 1, where the rules that need
+// the channel count cannot fire.  What differs between them is passed in: the name in front of every message, what the messages
+// call the batch dimension and one member of it, the sizing function they name, and the taps that params = NULL stands for -- 0: the
+// operator's own (20), for the single-channel functions; 32 / channels for the joint ones, channels = 1 included.  Which kernel
+// runs is the launcher's choice.
+struct WpeCall {
+    const char *name, *n_rows, *row, *sizer;
+    int default_taps;
+};
+// (an illegal channel count is refused before the value is used)
+static int joint_default_taps(int channels) { return 32 / (channels < 1 ? 1 : channels); }
+
 // The parameters of a call (NULL = the defaults), refused outside their legal ranges; the message names the field.
-static int wpe_consts(const char *who, const adn_wpe_params *params, adn::WpeConsts *k)
+static int wpe_consts(const char *who, const adn_wpe_params *params, int default_taps, adn::WpeConsts *k)
 {
     const std::string w(who);
-    const adn_wpe_params defaults = {20, 3, 3, 1e-3f, 1e-3f};
+    adn_wpe_params defaults = {20, 3, 3, 1e-3f, 1e-3f};
+    if (default_taps) defaults.taps = default_taps;
     const adn_wpe_params p = params ? *params : defaults;
     if (p.taps < 1 || p.taps > 32) return fail(ADN_ERR_INVALID, w + ": need 1 <= taps <= 32");
     if (p.delay < 1 || p.delay > 8) return fail(ADN_ERR_INVALID, w + ": need 1 <= delay <= 8");
@@ -582,96 +595,73 @@ static int wpe_consts(const char *who, const adn_wpe_params *params, adn::WpeCon
     return ADN_OK;
 }
 
-static int wpe_shape(const char *who, int n_clips, int n_frames, int n_bins, const adn_wpe_params *params, adn::WpeConsts *k)
+static int wpe_shape(const WpeCall &c, int n_groups, int channels, int n_frames, int n_bins, const adn_wpe_params *params,
+                     adn::WpeConsts *k)
 {
-    const std::string w(who);
-    if (n_clips < 1 || n_frames < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, w + ": n_clips, n_frames and n_bins must be >= 1");
-    const int rc = wpe_consts(who, params, k);
-    if (rc != ADN_OK) return rc;
-    if (adn::wpe_grid(n_clips, n_bins, k->K) > 0x7fffffffL)
-        return fail(ADN_ERR_INVALID, w + ": grid too large (n_clips x ceil(n_bins / bins per workgroup) >= 2^31)");
+    const std::string w(c.name);
+    if (n_groups < 1 || n_frames < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, w + ": " + c.n_rows + ", n_frames and n_bins must be >= 1");
+    if (channels < 1 || channels > 8) return fail(ADN_ERR_INVALID, w + ": need 1 <= channels <= 8");
+    if ((long)n_groups * channels > 0x7fffffffL) return fail(ADN_ERR_INVALID, w + ": need n_groups * channels < 2^31");
+    ADN_TRY(wpe_consts(c.name, params, c.default_taps, k));
+    if (channels * k->K > 32) return fail(ADN_ERR_INVALID, w + ": need channels * taps <= 32");
+    if (adn::wpe_grid(n_groups, channels, n_bins, k->K) > 0x7fffffffL)
+        return fail(ADN_ERR_INVALID, w + ": grid too large (" + c.n_rows + " x ceil(n_bins / bins per workgroup) >= 2^31)");
+    return ADN_OK;
+}
+
+static int wpe_workspace_bytes(const WpeCall &c, int n_groups, int channels, int n_frames, int n_bins, const adn_wpe_params *params,
+                               size_t *bytes)
+{
+    adn::WpeConsts k;
+    if (!bytes) return fail(ADN_ERR_INVALID, std::string(c.name) + ": null pointer");
+    ADN_TRY(wpe_shape(c, n_groups, channels, n_frames, n_bins, params, &k));
+    *bytes = 0;                                          // R, P, the factor and the taps of a (group, bin) never leave the chip
+    return ADN_OK;
+}
+
+static int wpe(const WpeCall &c, const float *spec, int n_groups, int channels, int n_frames, int n_bins, const adn_wpe_params *params,
+               void *workspace, size_t workspace_bytes, float *spec_out, float *mag_out, int width, void *stream)
+{
+    const std::string w(c.name);
+    adn::WpeConsts k;
+    if (!spec || !spec_out) return fail(ADN_ERR_INVALID, w + ": null pointer (spec, spec_out)");
+    ADN_TRY(wpe_shape(c, n_groups, channels, n_frames, n_bins, params, &k));
+    if (mag_out && width < n_frames) return fail(ADN_ERR_INVALID, w + ": need width >= n_frames");
+    if (!aligned_to(spec, 8) || !aligned_to(spec_out, 8) || !aligned_to(mag_out, 4))
+        return fail(ADN_ERR_INVALID, w + ": spec and spec_out must be 8-byte aligned, mag_out 4-byte aligned");
+    const size_t need = 0;                               // what c.sizer reports
+    if (workspace_bytes < need || (need && !workspace)) return fail(ADN_ERR_WORKSPACE, w + ": workspace smaller than " + c.sizer);
+    const char *a = reinterpret_cast<const char *>(spec), *b = reinterpret_cast<const char *>(spec_out);
+    const size_t span = (size_t)n_groups * (size_t)channels * (size_t)n_frames * (size_t)n_bins * 2 * sizeof(float);
+    if (a < b + span && b < a + span) return fail(ADN_ERR_INVALID, w + ": spec and spec_out may not overlap");
+    ADN_LAUNCH(adn::launch_wpe(spec, n_groups, channels, n_frames, n_bins, k, spec_out, mag_out, width, static_cast<hipStream_t>(stream)),
+               c.name);
     return ADN_OK;
 }
 
 int adn_wpe_workspace_bytes(int n_clips, int n_frames, int n_bins, const adn_wpe_params *params, size_t *bytes)
 {
-    adn::WpeConsts k;
-    if (!bytes) return fail(ADN_ERR_INVALID, "adn_wpe_workspace_bytes: null pointer");
-    const int rc = wpe_shape("adn_wpe_workspace_bytes", n_clips, n_frames, n_bins, params, &k);
-    if (rc != ADN_OK) return rc;
-    *bytes = 0;                                          // R, P, the factor and the taps of a row never leave the chip
-    return ADN_OK;
+    return wpe_workspace_bytes({"adn_wpe_workspace_bytes", "n_clips", "clip", "", 0}, n_clips, 1, n_frames, n_bins, params, bytes);
 }
 
 int adn_wpe(const float *spec, int n_clips, int n_frames, int n_bins, const adn_wpe_params *params, void *workspace,
             size_t workspace_bytes, float *spec_out, float *mag_out, int width, void *stream)
 {
-    adn::WpeConsts k;
-    if (!spec || !spec_out) return fail(ADN_ERR_INVALID, "adn_wpe: null pointer (spec, spec_out)");
-    const int rc = wpe_shape("adn_wpe", n_clips, n_frames, n_bins, params, &k);
-    if (rc != ADN_OK) return rc;
-    if (mag_out && width < n_frames) return fail(ADN_ERR_INVALID, "adn_wpe: need width >= n_frames");
-    if (!aligned_to(spec, 8) || !aligned_to(spec_out, 8) || !aligned_to(mag_out, 4))
-        return fail(ADN_ERR_INVALID, "adn_wpe: spec and spec_out must be 8-byte aligned, mag_out 4-byte aligned");
-    const size_t need = 0;                               // adn_wpe_workspace_bytes
-    if (workspace_bytes < need || (need && !workspace)) return fail(ADN_ERR_WORKSPACE, "adn_wpe: workspace smaller than adn_wpe_workspace_bytes");
-    const char *a = reinterpret_cast<const char *>(spec), *b = reinterpret_cast<const char *>(spec_out);
-    const size_t span = (size_t)n_clips * (size_t)n_frames * (size_t)n_bins * 2 * sizeof(float);
-    if (a < b + span && b < a + span) return fail(ADN_ERR_INVALID, "adn_wpe: spec and spec_out may not overlap");
-    ADN_LAUNCH(adn::launch_wpe(spec, n_clips, n_frames, n_bins, k, spec_out, mag_out, width, static_cast<hipStream_t>(stream)), "adn_wpe");
-    return ADN_OK;
-}
-
-/* ---- multichannel dereverberation: joint WPE of a recording's channels (adn.h, "dereverb multichannel") ---------------- */
-// The shape and the parameters of a call: NULL = the defaults of "dereverb" with taps = 32 / channels.
-static int wpe_mc_shape(const char *who, int n_groups, int channels, int n_frames, int n_bins, const adn_wpe_params *params,
-                        adn::WpeConsts *k)
-{
-    const std::string w(who);
-    if (n_groups < 1 || n_frames < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, w + ": n_groups, n_frames and n_bins must be >= 1");
-    if (channels < 1 || channels > 8) return fail(ADN_ERR_INVALID, w + ": need 1 <= channels <= 8");
-    if ((long)n_groups * channels > 0x7fffffffL) return fail(ADN_ERR_INVALID, w + ": need n_groups * channels < 2^31");
-    const adn_wpe_params defaults = {32 / channels, 3, 3, 1e-3f, 1e-3f};
-    const int rc = wpe_consts(who, params ? params : &defaults, k);
-    if (rc != ADN_OK) return rc;
-    if (channels * k->K > 32) return fail(ADN_ERR_INVALID, w + ": need channels * taps <= 32");
-    const long grid = channels == 1 ? adn::wpe_grid(n_groups, n_bins, k->K) : adn::wpe_mc_grid(n_groups, channels, n_bins, k->K);
-    if (grid > 0x7fffffffL) return fail(ADN_ERR_INVALID, w + ": grid too large (n_groups x ceil(n_bins / bins per workgroup) >= 2^31)");
-    return ADN_OK;
+    return wpe({"adn_wpe", "n_clips", "clip", "adn_wpe_workspace_bytes", 0}, spec, n_clips, 1, n_frames, n_bins, params, workspace,
+               workspace_bytes, spec_out, mag_out, width, stream);
 }
 
 int adn_wpe_mc_workspace_bytes(int n_groups, int channels, int n_frames, int n_bins, const adn_wpe_params *params, size_t *bytes)
 {
-    adn::WpeConsts k;
-    if (!bytes) return fail(ADN_ERR_INVALID, "adn_wpe_mc_workspace_bytes: null pointer");
-    const int rc = wpe_mc_shape("adn_wpe_mc_workspace_bytes", n_groups, channels, n_frames, n_bins, params, &k);
-    if (rc != ADN_OK) return rc;
-    *bytes = 0;                                          // R, P, the factor and the taps of a (group, bin) never leave the chip
-    return ADN_OK;
+    return wpe_workspace_bytes({"adn_wpe_mc_workspace_bytes", "n_groups", "group", "", joint_default_taps(channels)}, n_groups, channels,
+                               n_frames, n_bins, params, bytes);
 }
 
 int adn_wpe_mc(const float *spec, int n_groups, int channels, int n_frames, int n_bins, const adn_wpe_params *params, void *workspace,
                size_t workspace_bytes, float *spec_out, float *mag_out, int width, void *stream)
 {
-    adn::WpeConsts k;
-    if (!spec || !spec_out) return fail(ADN_ERR_INVALID, "adn_wpe_mc: null pointer (spec, spec_out)");
-    const int rc = wpe_mc_shape("adn_wpe_mc", n_groups, channels, n_frames, n_bins, params, &k);
-    if (rc != ADN_OK) return rc;
-    if (mag_out && width < n_frames) return fail(ADN_ERR_INVALID, "adn_wpe_mc: need width >= n_frames");
-    if (!aligned_to(spec, 8) || !aligned_to(spec_out, 8) || !aligned_to(mag_out, 4))
-        return fail(ADN_ERR_INVALID, "adn_wpe_mc: spec and spec_out must be 8-byte aligned, mag_out 4-byte aligned");
-    const size_t need = 0;                               // adn_wpe_mc_workspace_bytes
-    if (workspace_bytes < need || (need && !workspace))
-        return fail(ADN_ERR_WORKSPACE, "adn_wpe_mc: workspace smaller than adn_wpe_mc_workspace_bytes");
-    const char *a = reinterpret_cast<const char *>(spec), *b = reinterpret_cast<const char *>(spec_out);
-    const size_t span = (size_t)n_groups * (size_t)channels * (size_t)n_frames * (size_t)n_bins * 2 * sizeof(float);
-    if (a < b + span && b < a + span) return fail(ADN_ERR_INVALID, "adn_wpe_mc: spec and spec_out may not overlap");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (channels == 1)                                   // every statement reduces to "dereverb": the same kernel, the same bits
-        ADN_LAUNCH(adn::launch_wpe(spec, n_groups, n_frames, n_bins, k, spec_out, mag_out, width, st), "adn_wpe_mc");
-    else
-        ADN_LAUNCH(adn::launch_wpe_mc(spec, n_groups, channels, n_frames, n_bins, k, spec_out, mag_out, width, st), "adn_wpe_mc");
-    return ADN_OK;
+    return wpe({"adn_wpe_mc", "n_groups", "group", "adn_wpe_mc_workspace_bytes", joint_default_taps(channels)}, spec, n_groups, channels,
+               n_frames, n_bins, params, workspace, workspace_bytes, spec_out, mag_out, width, stream);
 }
 
 /* ---- streaming denoiser: plan, state, analysis, emit (adn.h, "stream") ------------------------------------------- */
@@ -944,12 +934,16 @@ int adn_stream_pool_emit(void *state, size_t state_bytes, int n_slots, int n_fft
     return ADN_OK;
 }
 
-/* ---- streaming dereverberation: recursive WPE (adn.h, "dereverb stream") ------------------------------------------- */
-// The parameters of a call (NULL = the defaults), refused outside their legal ranges; the message names the field.
-static int wpe_stream_consts(const char *who, const adn_wpe_stream_params *params, adn::WpeStreamConsts *k)
+/* ---- streaming dereverberation: recursive WPE, one channel or jointly (adn.h, "dereverb stream", "dereverb stream multichannel") */
+// One body per pair, as for the offline operator above (WpeCall).  The parameters of a call on `channels` channels (NULL = the
+// defaults), refused outside their legal ranges, then the rules that need the channel count.  k->K is the taps PER CHANNEL.
+static int wpe_stream_consts(const char *who, int channels, const adn_wpe_stream_params *params, int default_taps,
+                             adn::WpeStreamConsts *k)
 {
     const std::string w(who);
-    const adn_wpe_stream_params defaults = {20, 3, 0.99f, 300.f, 0.01f, 0.9f};
+    if (channels < 1 || channels > 8) return fail(ADN_ERR_INVALID, w + ": need 1 <= channels <= 8");
+    adn_wpe_stream_params defaults = {20, 3, 0.99f, 300.f, 0.01f, 0.9f};
+    if (default_taps) defaults.taps = default_taps;
     const adn_wpe_stream_params p = params ? *params : defaults;
     if (p.taps < 1 || p.taps > 32) return fail(ADN_ERR_INVALID, w + ": need 1 <= taps <= 32");
     if (p.delay < 1 || p.delay > 8) return fail(ADN_ERR_INVALID, w + ": need 1 <= delay <= 8");
@@ -965,221 +959,162 @@ static int wpe_stream_consts(const char *who, const adn_wpe_stream_params *param
     k->rho = p.power_floor;
     k->beta = p.smooth;
     k->one_minus_beta = 1.f - p.smooth;
+    if (channels * p.taps > 32) return fail(ADN_ERR_INVALID, w + ": need channels * taps <= 32");
+    // the window 1 / (1 - forget) must hold twice the N unknowns (adn.h); in double, on the fp32 value the kernel uses
+    if (channels >= 2 && !(2.0 * (double)(channels * p.taps) * (1.0 - (double)p.forget) <= 1.0))
+        return fail(ADN_ERR_INVALID, w + ": need 2 channels taps (1 - forget) <= 1 with more than one channel (forget too low for the stacked size)");
     return ADN_OK;
 }
 
-// The WPE state of a call: n_slots x n_bins records, 8-byte aligned, at least adn_wpe_stream_state_bytes.
-static int wpe_stream_state(const char *who, const void *wstate, size_t wstate_bytes, int n_slots, int n_bins, const adn::WpeStreamConsts &k)
+static size_t wpe_stream_bytes(int n_slots, int n_bins, int channels, const adn::WpeStreamConsts &k)
 {
-    const std::string w(who);
+    return (size_t)n_slots * (size_t)n_bins * (size_t)adn::wpe_stream_record_floats(channels, k.K, k.D) * sizeof(float);
+}
+
+// The WPE state of a call: n_slots x n_bins records, 8-byte aligned, at least what c.sizer reports.
+static int wpe_stream_state(const WpeCall &c, const void *wstate, size_t wstate_bytes, int n_slots, int n_bins, int channels,
+                            const adn::WpeStreamConsts &k)
+{
+    const std::string w(c.name);
     if (!wstate) return fail(ADN_ERR_INVALID, w + ": null pointer (the WPE state)");
     if (n_slots < 1 || n_slots > (1 << 20) || n_bins < 1 || n_bins > (1 << 20))
         return fail(ADN_ERR_INVALID, w + ": need 1 <= n_slots <= 2^20 and 1 <= n_bins <= 2^20");
-    const size_t need = (size_t)n_slots * (size_t)n_bins * (size_t)adn::wpe_stream_record_floats(k.K, k.D) * sizeof(float);
-    if (wstate_bytes < need) return fail(ADN_ERR_WORKSPACE, w + ": the WPE state is smaller than adn_wpe_stream_state_bytes");
+    if (wstate_bytes < wpe_stream_bytes(n_slots, n_bins, channels, k))
+        return fail(ADN_ERR_WORKSPACE, w + ": the WPE state is smaller than " + c.sizer);
     if (!aligned_to(wstate, 8)) return fail(ADN_ERR_INVALID, w + ": the WPE state must be 8-byte aligned");
+    return ADN_OK;
+}
+
+static int wpe_stream_state_bytes(const WpeCall &c, int n_slots, int channels, int n_bins, const adn_wpe_stream_params *params,
+                                  size_t *bytes)
+{
+    const std::string w(c.name);
+    adn::WpeStreamConsts k;
+    if (!bytes) return fail(ADN_ERR_INVALID, w + ": null pointer");
+    if (n_slots < 1 || n_slots > (1 << 20) || n_bins < 1 || n_bins > (1 << 20))
+        return fail(ADN_ERR_INVALID, w + ": need 1 <= n_slots <= 2^20 and 1 <= n_bins <= 2^20");
+    ADN_TRY(wpe_stream_consts(c.name, channels, params, c.default_taps, &k));
+    *bytes = wpe_stream_bytes(n_slots, n_bins, channels, k);
+    return ADN_OK;
+}
+
+static int wpe_online(const WpeCall &c, const float *spec, int n_groups, int channels, int n_frames, int n_bins, long first_frame,
+                      const adn_wpe_stream_params *params, void *state, size_t state_bytes, int n_slots, float *spec_out,
+                      float *mag_out, int width, int col0, void *stream)
+{
+    const std::string w(c.name);
+    adn::WpeStreamConsts k;
+    if (!spec || !spec_out) return fail(ADN_ERR_INVALID, w + ": null pointer (spec, spec_out)");
+    if (n_groups < 1 || n_frames < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, w + ": " + c.n_rows + ", n_frames and n_bins must be >= 1");
+    if (first_frame < 0 || first_frame + n_frames >= (1L << 31))
+        return fail(ADN_ERR_INVALID, w + ": need first_frame >= 0 and first_frame + n_frames < 2^31");
+    ADN_TRY(wpe_stream_consts(c.name, channels, params, c.default_taps, &k));
+    if ((long)n_groups * channels > 0x7fffffffL) return fail(ADN_ERR_INVALID, w + ": need n_groups * channels < 2^31");
+    ADN_TRY(wpe_stream_state(c, state, state_bytes, n_slots, n_bins, channels, k));
+    if (n_groups > n_slots) return fail(ADN_ERR_INVALID, w + ": " + c.row + " i uses slot i: need " + c.n_rows + " <= n_slots");
+    if (mag_out && (col0 < 0 || width < 1 || (long)col0 + n_frames > width))
+        return fail(ADN_ERR_INVALID, w + ": need col0 >= 0 and col0 + n_frames <= width");
+    if (!aligned_to(spec, 8) || !aligned_to(spec_out, 8) || !aligned_to(mag_out, 4))
+        return fail(ADN_ERR_INVALID, w + ": spec and spec_out must be 8-byte aligned, mag_out 4-byte aligned");
+    const char *a = reinterpret_cast<const char *>(spec), *b = reinterpret_cast<const char *>(spec_out);
+    const size_t span = (size_t)n_groups * (size_t)channels * (size_t)n_frames * (size_t)n_bins * 2 * sizeof(float);
+    if (a < b + span && b < a + span) return fail(ADN_ERR_INVALID, w + ": spec and spec_out may not overlap");
+    if (adn::wpe_stream_grid(n_groups, n_bins) > 0x7fffffffL)
+        return fail(ADN_ERR_INVALID, w + ": grid too large (" + c.n_rows + " x ceil(n_bins / 8) >= 2^31)");
+    ADN_LAUNCH(adn::launch_wpe_online(spec, n_groups, channels, n_frames, n_bins, (int)first_frame, k, static_cast<float *>(state),
+                                      spec_out, mag_out, width, col0, static_cast<hipStream_t>(stream)), c.name);
+    return ADN_OK;
+}
+
+static int wpe_stream(const WpeCall &c, void *sstate, size_t sstate_bytes, float *y, int n_streams, int channels, long first_step,
+                      int n_steps, long final_length, int n_fft, int hop, int window, int block, int lookahead, int max_steps,
+                      const adn_wpe_stream_params *params, void *wpe_state, size_t wpe_state_bytes, void *stream)
+{
+    const std::string w(c.name);
+    adn::StreamGeom g;
+    adn::StreamCall call;
+    adn::WpeStreamConsts k;
+    ADN_TRY(stream_state(c.name, sstate, sstate_bytes, n_streams, n_fft, hop, window, block, lookahead, max_steps, &g));
+    if (lookahead != 0) return fail(ADN_ERR_INVALID, w + ": the operator is causal: lookahead must be 0");
+    if (!y) return fail(ADN_ERR_INVALID, w + ": null pointer");
+    if (!aligned_to(y, 4)) return fail(ADN_ERR_INVALID, w + ": y must be 4-byte aligned");
+    ADN_TRY(stream_call(c.name, g, first_step, n_steps, final_length, &call));
+    ADN_TRY(wpe_stream_consts(c.name, channels, params, c.default_taps, &k));
+    if (n_streams % channels) return fail(ADN_ERR_INVALID, w + ": n_streams must be a multiple of channels");
+    ADN_TRY(wpe_stream_state(c, wpe_state, wpe_state_bytes, n_streams / channels, n_fft / 2 + 1, channels, k));
+    ADN_LAUNCH(adn::launch_wpe_stream(static_cast<float *>(sstate), y, n_streams, channels, g, call, k, static_cast<float *>(wpe_state),
+                                      static_cast<hipStream_t>(stream)), c.name);
     return ADN_OK;
 }
 
 int adn_wpe_stream_state_bytes(int n_slots, int n_bins, const adn_wpe_stream_params *params, size_t *bytes)
 {
-    adn::WpeStreamConsts k;
-    if (!bytes) return fail(ADN_ERR_INVALID, "adn_wpe_stream_state_bytes: null pointer");
-    if (n_slots < 1 || n_slots > (1 << 20) || n_bins < 1 || n_bins > (1 << 20))
-        return fail(ADN_ERR_INVALID, "adn_wpe_stream_state_bytes: need 1 <= n_slots <= 2^20 and 1 <= n_bins <= 2^20");
-    const int rc = wpe_stream_consts("adn_wpe_stream_state_bytes", params, &k);
-    if (rc != ADN_OK) return rc;
-    *bytes = (size_t)n_slots * (size_t)n_bins * (size_t)adn::wpe_stream_record_floats(k.K, k.D) * sizeof(float);
-    return ADN_OK;
+    return wpe_stream_state_bytes({"adn_wpe_stream_state_bytes", "n_rows", "row", "", 0}, n_slots, 1, n_bins, params, bytes);
 }
 
 int adn_wpe_online(const float *spec, int n_rows, int n_frames, int n_bins, long first_frame, const adn_wpe_stream_params *params,
                    void *state, size_t state_bytes, int n_slots, float *spec_out, float *mag_out, int width, int col0, void *stream)
 {
-    adn::WpeStreamConsts k;
-    if (!spec || !spec_out) return fail(ADN_ERR_INVALID, "adn_wpe_online: null pointer (spec, spec_out)");
-    if (n_rows < 1 || n_frames < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, "adn_wpe_online: n_rows, n_frames and n_bins must be >= 1");
-    if (first_frame < 0 || first_frame + n_frames >= (1L << 31))
-        return fail(ADN_ERR_INVALID, "adn_wpe_online: need first_frame >= 0 and first_frame + n_frames < 2^31");
-    int rc = wpe_stream_consts("adn_wpe_online", params, &k);
-    if (rc != ADN_OK) return rc;
-    rc = wpe_stream_state("adn_wpe_online", state, state_bytes, n_slots, n_bins, k);
-    if (rc != ADN_OK) return rc;
-    if (n_rows > n_slots) return fail(ADN_ERR_INVALID, "adn_wpe_online: row i uses slot i: need n_rows <= n_slots");
-    if (mag_out && (col0 < 0 || width < 1 || (long)col0 + n_frames > width))
-        return fail(ADN_ERR_INVALID, "adn_wpe_online: need col0 >= 0 and col0 + n_frames <= width");
-    if (!aligned_to(spec, 8) || !aligned_to(spec_out, 8) || !aligned_to(mag_out, 4))
-        return fail(ADN_ERR_INVALID, "adn_wpe_online: spec and spec_out must be 8-byte aligned, mag_out 4-byte aligned");
-    const char *a = reinterpret_cast<const char *>(spec), *b = reinterpret_cast<const char *>(spec_out);
-    const size_t span = (size_t)n_rows * (size_t)n_frames * (size_t)n_bins * 2 * sizeof(float);
-    if (a < b + span && b < a + span) return fail(ADN_ERR_INVALID, "adn_wpe_online: spec and spec_out may not overlap");
-    if (adn::wpe_stream_grid(n_rows, n_bins) > 0x7fffffffL)
-        return fail(ADN_ERR_INVALID, "adn_wpe_online: grid too large (n_rows x ceil(n_bins / 8) >= 2^31)");
-    ADN_LAUNCH(adn::launch_wpe_online(spec, n_rows, n_frames, n_bins, (int)first_frame, k, static_cast<float *>(state), spec_out, mag_out,
-                                      width, col0, static_cast<hipStream_t>(stream)), "adn_wpe_online");
-    return ADN_OK;
+    return wpe_online({"adn_wpe_online", "n_rows", "row", "adn_wpe_stream_state_bytes", 0}, spec, n_rows, 1, n_frames, n_bins,
+                      first_frame, params, state, state_bytes, n_slots, spec_out, mag_out, width, col0, stream);
 }
 
 int adn_wpe_stream(void *sstate, size_t sstate_bytes, float *y, int n_streams, long first_step, int n_steps,
                    long final_length, int n_fft, int hop, int window, int block, int lookahead, int max_steps,
                    const adn_wpe_stream_params *params, void *wpe_state, size_t wpe_state_bytes, void *stream)
 {
-    adn::StreamGeom g;
-    adn::StreamCall c;
-    adn::WpeStreamConsts k;
-    int rc = stream_state("adn_wpe_stream", sstate, sstate_bytes, n_streams, n_fft, hop, window, block, lookahead, max_steps, &g);
-    if (rc != ADN_OK) return rc;
-    if (lookahead != 0) return fail(ADN_ERR_INVALID, "adn_wpe_stream: the operator is causal: lookahead must be 0");
-    if (!y) return fail(ADN_ERR_INVALID, "adn_wpe_stream: null pointer");
-    if (!aligned_to(y, 4)) return fail(ADN_ERR_INVALID, "adn_wpe_stream: y must be 4-byte aligned");
-    rc = stream_call("adn_wpe_stream", g, first_step, n_steps, final_length, &c);
-    if (rc != ADN_OK) return rc;
-    rc = wpe_stream_consts("adn_wpe_stream", params, &k);
-    if (rc != ADN_OK) return rc;
-    rc = wpe_stream_state("adn_wpe_stream", wpe_state, wpe_state_bytes, n_streams, n_fft / 2 + 1, k);
-    if (rc != ADN_OK) return rc;
-    ADN_LAUNCH(adn::launch_wpe_stream(static_cast<float *>(sstate), y, n_streams, g, c, k, static_cast<float *>(wpe_state),
-                                      static_cast<hipStream_t>(stream)), "adn_wpe_stream");
-    return ADN_OK;
-}
-
-int adn_wpe_stream_pool(void *pstate, size_t pstate_bytes, int n_slots, int n_fft, int hop, int window, int block,
-                        int lookahead, long ring_samples, const adn_stream_pool_row *rows, int n_rows, float *y,
-                        const adn_wpe_stream_params *params, void *wpe_state, size_t wpe_state_bytes, void *stream)
-{
-    PoolState p;
-    adn::StreamPoolRows t = {};
-    adn::WpeStreamConsts k;
-    int max_new, max_span;
-    long max_out;
-    int rc = pool_state("adn_wpe_stream_pool", pstate, pstate_bytes, n_slots, n_fft, hop, window, block, lookahead, ring_samples, &p);
-    if (rc != ADN_OK) return rc;
-    if (lookahead != 0) return fail(ADN_ERR_INVALID, "adn_wpe_stream_pool: the operator is causal: lookahead must be 0");
-    if (!y) return fail(ADN_ERR_INVALID, "adn_wpe_stream_pool: null pointer");
-    if (!aligned_to(y, 4)) return fail(ADN_ERR_INVALID, "adn_wpe_stream_pool: y must be 4-byte aligned");
-    rc = pool_rows("adn_wpe_stream_pool", p, n_slots, rows, n_rows, &t, &max_new, &max_span, &max_out);
-    if (rc != ADN_OK) return rc;
-    rc = wpe_stream_consts("adn_wpe_stream_pool", params, &k);
-    if (rc != ADN_OK) return rc;
-    rc = wpe_stream_state("adn_wpe_stream_pool", wpe_state, wpe_state_bytes, n_slots, n_fft / 2 + 1, k);
-    if (rc != ADN_OK) return rc;
-    ADN_LAUNCH(adn::launch_wpe_stream_pool(static_cast<float *>(pstate), y, p.g, t, k, static_cast<float *>(wpe_state),
-                                           static_cast<hipStream_t>(stream)), "adn_wpe_stream_pool");
-    return ADN_OK;
-}
-
-/* ---- streaming multichannel dereverberation: recursive joint WPE (adn.h, "dereverb stream multichannel") --------------------- */
-// The parameters of a joint call on `channels` channels (NULL = the defaults of "dereverb stream" with taps = 32 / channels):
-// the parent's ranges, then the rules that need the channel count.  k->K is the taps PER CHANNEL.
-static int wpe_mc_stream_consts(const char *who, int channels, const adn_wpe_stream_params *params, adn::WpeStreamConsts *k)
-{
-    const std::string w(who);
-    if (channels < 1 || channels > 8) return fail(ADN_ERR_INVALID, w + ": need 1 <= channels <= 8");
-    const adn_wpe_stream_params defaults = {32 / channels, 3, 0.99f, 300.f, 0.01f, 0.9f};
-    const adn_wpe_stream_params *p = params ? params : &defaults;
-    const int rc = wpe_stream_consts(who, p, k);
-    if (rc != ADN_OK) return rc;
-    if (channels * p->taps > 32) return fail(ADN_ERR_INVALID, w + ": need channels * taps <= 32");
-    // the window 1 / (1 - forget) must hold twice the N unknowns (adn.h); in double, on the fp32 value the kernel uses
-    if (channels >= 2 && !(2.0 * (double)(channels * p->taps) * (1.0 - (double)p->forget) <= 1.0))
-        return fail(ADN_ERR_INVALID, w + ": need 2 channels taps (1 - forget) <= 1 with more than one channel (forget too low for the stacked size)");
-    return ADN_OK;
-}
-
-static size_t wpe_mc_stream_bytes(int n_slots, int n_bins, int channels, const adn::WpeStreamConsts &k)
-{
-    const long rec = channels == 1 ? adn::wpe_stream_record_floats(k.K, k.D) : adn::wpe_mc_stream_record_floats(channels, k.K, k.D);
-    return (size_t)n_slots * (size_t)n_bins * (size_t)rec * sizeof(float);
-}
-
-// The joint WPE state of a call: n_slots x n_bins records, 8-byte aligned, at least adn_wpe_mc_stream_state_bytes.
-static int wpe_mc_stream_state(const char *who, const void *wstate, size_t wstate_bytes, int n_slots, int n_bins, int channels,
-                               const adn::WpeStreamConsts &k)
-{
-    const std::string w(who);
-    if (!wstate) return fail(ADN_ERR_INVALID, w + ": null pointer (the WPE state)");
-    if (n_slots < 1 || n_slots > (1 << 20) || n_bins < 1 || n_bins > (1 << 20))
-        return fail(ADN_ERR_INVALID, w + ": need 1 <= n_slots <= 2^20 and 1 <= n_bins <= 2^20");
-    if (wstate_bytes < wpe_mc_stream_bytes(n_slots, n_bins, channels, k))
-        return fail(ADN_ERR_WORKSPACE, w + ": the WPE state is smaller than adn_wpe_mc_stream_state_bytes");
-    if (!aligned_to(wstate, 8)) return fail(ADN_ERR_INVALID, w + ": the WPE state must be 8-byte aligned");
-    return ADN_OK;
+    return wpe_stream({"adn_wpe_stream", "n_rows", "row", "adn_wpe_stream_state_bytes", 0}, sstate, sstate_bytes, y, n_streams, 1,
+                      first_step, n_steps, final_length, n_fft, hop, window, block, lookahead, max_steps, params, wpe_state,
+                      wpe_state_bytes, stream);
 }
 
 int adn_wpe_mc_stream_state_bytes(int n_slots, int channels, int n_bins, const adn_wpe_stream_params *params, size_t *bytes)
 {
-    adn::WpeStreamConsts k;
-    if (!bytes) return fail(ADN_ERR_INVALID, "adn_wpe_mc_stream_state_bytes: null pointer");
-    if (n_slots < 1 || n_slots > (1 << 20) || n_bins < 1 || n_bins > (1 << 20))
-        return fail(ADN_ERR_INVALID, "adn_wpe_mc_stream_state_bytes: need 1 <= n_slots <= 2^20 and 1 <= n_bins <= 2^20");
-    const int rc = wpe_mc_stream_consts("adn_wpe_mc_stream_state_bytes", channels, params, &k);
-    if (rc != ADN_OK) return rc;
-    *bytes = wpe_mc_stream_bytes(n_slots, n_bins, channels, k);
-    return ADN_OK;
+    return wpe_stream_state_bytes({"adn_wpe_mc_stream_state_bytes", "n_groups", "group", "", joint_default_taps(channels)}, n_slots,
+                                  channels, n_bins, params, bytes);
 }
 
 int adn_wpe_mc_online(const float *spec, int n_groups, int channels, int n_frames, int n_bins, long first_frame,
                       const adn_wpe_stream_params *params, void *state, size_t state_bytes, int n_slots, float *spec_out, float *mag_out,
                       int width, int col0, void *stream)
 {
-    adn::WpeStreamConsts k;
-    if (!spec || !spec_out) return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: null pointer (spec, spec_out)");
-    if (n_groups < 1 || n_frames < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: n_groups, n_frames and n_bins must be >= 1");
-    if (first_frame < 0 || first_frame + n_frames >= (1L << 31))
-        return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: need first_frame >= 0 and first_frame + n_frames < 2^31");
-    int rc = wpe_mc_stream_consts("adn_wpe_mc_online", channels, params, &k);
-    if (rc != ADN_OK) return rc;
-    if ((long)n_groups * channels > 0x7fffffffL) return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: need n_groups * channels < 2^31");
-    rc = wpe_mc_stream_state("adn_wpe_mc_online", state, state_bytes, n_slots, n_bins, channels, k);
-    if (rc != ADN_OK) return rc;
-    if (n_groups > n_slots) return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: group i uses slot i: need n_groups <= n_slots");
-    if (mag_out && (col0 < 0 || width < 1 || (long)col0 + n_frames > width))
-        return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: need col0 >= 0 and col0 + n_frames <= width");
-    if (!aligned_to(spec, 8) || !aligned_to(spec_out, 8) || !aligned_to(mag_out, 4))
-        return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: spec and spec_out must be 8-byte aligned, mag_out 4-byte aligned");
-    const char *a = reinterpret_cast<const char *>(spec), *b = reinterpret_cast<const char *>(spec_out);
-    const size_t span = (size_t)n_groups * (size_t)channels * (size_t)n_frames * (size_t)n_bins * 2 * sizeof(float);
-    if (a < b + span && b < a + span) return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: spec and spec_out may not overlap");
-    if (adn::wpe_stream_grid(n_groups, n_bins) > 0x7fffffffL)
-        return fail(ADN_ERR_INVALID, "adn_wpe_mc_online: grid too large (n_groups x ceil(n_bins / 8) >= 2^31)");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (channels == 1)                                   // every statement is "dereverb stream": the same kernel, its bits
-        ADN_LAUNCH(adn::launch_wpe_online(spec, n_groups, n_frames, n_bins, (int)first_frame, k, static_cast<float *>(state), spec_out,
-                                          mag_out, width, col0, st), "adn_wpe_mc_online");
-    else
-        ADN_LAUNCH(adn::launch_wpe_mc_online(spec, n_groups, channels, n_frames, n_bins, (int)first_frame, k, static_cast<float *>(state),
-                                             spec_out, mag_out, width, col0, st), "adn_wpe_mc_online");
-    return ADN_OK;
+    return wpe_online({"adn_wpe_mc_online", "n_groups", "group", "adn_wpe_mc_stream_state_bytes", joint_default_taps(channels)}, spec,
+                      n_groups, channels, n_frames, n_bins, first_frame, params, state, state_bytes, n_slots, spec_out, mag_out, width,
+                      col0, stream);
 }
 
 int adn_wpe_mc_stream(void *sstate, size_t sstate_bytes, float *y, int n_streams, int channels, long first_step, int n_steps,
                       long final_length, int n_fft, int hop, int window, int block, int lookahead, int max_steps,
                       const adn_wpe_stream_params *params, void *wpe_state, size_t wpe_state_bytes, void *stream)
 {
-    adn::StreamGeom g;
-    adn::StreamCall c;
+    return wpe_stream({"adn_wpe_mc_stream", "n_groups", "group", "adn_wpe_mc_stream_state_bytes", joint_default_taps(channels)}, sstate,
+                      sstate_bytes, y, n_streams, channels, first_step, n_steps, final_length, n_fft, hop, window, block, lookahead,
+                      max_steps, params, wpe_state, wpe_state_bytes, stream);
+}
+
+// The pool's rows are single-channel streams: it shares the parameter and the state checks (channels = 1) and keeps its own rows.
+int adn_wpe_stream_pool(void *pstate, size_t pstate_bytes, int n_slots, int n_fft, int hop, int window, int block,
+                        int lookahead, long ring_samples, const adn_stream_pool_row *rows, int n_rows, float *y,
+                        const adn_wpe_stream_params *params, void *wpe_state, size_t wpe_state_bytes, void *stream)
+{
+    const WpeCall c = {"adn_wpe_stream_pool", "n_rows", "row", "adn_wpe_stream_state_bytes", 0};
+    PoolState p;
+    adn::StreamPoolRows t = {};
     adn::WpeStreamConsts k;
-    int rc = stream_state("adn_wpe_mc_stream", sstate, sstate_bytes, n_streams, n_fft, hop, window, block, lookahead, max_steps, &g);
-    if (rc != ADN_OK) return rc;
-    if (lookahead != 0) return fail(ADN_ERR_INVALID, "adn_wpe_mc_stream: the operator is causal: lookahead must be 0");
-    if (!y) return fail(ADN_ERR_INVALID, "adn_wpe_mc_stream: null pointer");
-    if (!aligned_to(y, 4)) return fail(ADN_ERR_INVALID, "adn_wpe_mc_stream: y must be 4-byte aligned");
-    rc = stream_call("adn_wpe_mc_stream", g, first_step, n_steps, final_length, &c);
-    if (rc != ADN_OK) return rc;
-    rc = wpe_mc_stream_consts("adn_wpe_mc_stream", channels, params, &k);
-    if (rc != ADN_OK) return rc;
-    if (n_streams % channels) return fail(ADN_ERR_INVALID, "adn_wpe_mc_stream: n_streams must be a multiple of channels");
-    rc = wpe_mc_stream_state("adn_wpe_mc_stream", wpe_state, wpe_state_bytes, n_streams / channels, n_fft / 2 + 1, channels, k);
-    if (rc != ADN_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (channels == 1)
-        ADN_LAUNCH(adn::launch_wpe_stream(static_cast<float *>(sstate), y, n_streams, g, c, k, static_cast<float *>(wpe_state), st),
-                   "adn_wpe_mc_stream");
-    else
-        ADN_LAUNCH(adn::launch_wpe_mc_stream(static_cast<float *>(sstate), y, n_streams, channels, g, c, k,
-                                             static_cast<float *>(wpe_state), st), "adn_wpe_mc_stream");
+    int max_new, max_span;
+    long max_out;
+    ADN_TRY(pool_state(c.name, pstate, pstate_bytes, n_slots, n_fft, hop, window, block, lookahead, ring_samples, &p));
+    if (lookahead != 0) return fail(ADN_ERR_INVALID, "adn_wpe_stream_pool: the operator is causal: lookahead must be 0");
+    if (!y) return fail(ADN_ERR_INVALID, "adn_wpe_stream_pool: null pointer");
+    if (!aligned_to(y, 4)) return fail(ADN_ERR_INVALID, "adn_wpe_stream_pool: y must be 4-byte aligned");
+    ADN_TRY(pool_rows(c.name, p, n_slots, rows, n_rows, &t, &max_new, &max_span, &max_out));
+    ADN_TRY(wpe_stream_consts(c.name, 1, params, c.default_taps, &k));
+    ADN_TRY(wpe_stream_state(c, wpe_state, wpe_state_bytes, n_slots, n_fft / 2 + 1, 1, k));
+    ADN_LAUNCH(adn::launch_wpe_stream_pool(static_cast<float *>(pstate), y, p.g, t, k, static_cast<float *>(wpe_state),
+                                           static_cast<hipStream_t>(stream)), c.name);
     return ADN_OK;
 }
+
 
 static const char *resample_stream_text =": rates must be >= 1 with max(up, down) <= 4096 after dividing by their gcd, and at most "
                                           "16384 carried samples (2 floor(half / up) + ceil(down / up) + 1)";

@@ -25,6 +25,12 @@ inline int fail_hip(hipError_t e, const char *what)
         hipError_t e_ = (call);                         \
         if (e_ != hipSuccess) return adn::fail_hip(e_, #call); \
     } while (0)
+// a check that has set the message itself: its code goes on to the caller
+#define ADN_TRY(call)                                   \
+    do {                                                \
+        const int rc_ = (call);                         \
+        if (rc_ != ADN_OK) return rc_;                  \
+    } while (0)
 // launches that may need a constant table: a cold lookup on a capturing stream is the CALLER's error (adn.h, Conventions)
 inline int fail_launch(hipError_t e, const char *what)
 {

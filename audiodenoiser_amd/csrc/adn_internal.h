@@ -468,22 +468,19 @@ struct SpectralRows {
 };
 hipError_t launch_spectral_gain_windows(const float *windows, float *y, int n_rows, int n_steps, int F, int W, int col0, int n_cols,
                                         const SpectralConsts &k, float *state, const SpectralRows &rows, hipStream_t st);
-// Dereverberation baseline (dereverb_kernels.hip; adn.h, "dereverb"): I iterations of K-tap WPE at delay D on every (clip, bin)
-// row of a frame-major float2 spectrogram, in one launch without a workspace.  mag_out (may be null) is bin-major
-// [clip][F][width], columns [0, T) written.  wpe_grid: the workgroups of the launch, n_clips x ceil(F / (256 / lanes per bin)).
+// Dereverberation (dereverb_mc_kernels.hip, dereverb_kernels.hip; adn.h, "dereverb" and "dereverb multichannel"): I iterations of
+// WPE at K taps per channel and delay D on the N = C K stacked past frames of the C consecutive clips of a group, 1 <= C <= 8 and
+// C K <= 32, for every (group, bin) of a frame-major float2 spectrogram [group * C + channel][frame][F], in one launch without a
+// workspace.  mag_out (may be null) is bin-major [group * C + channel][F][width], columns [0, T) written.  C = 1 is the
+// single-channel operator and runs its own kernel; the launcher chooses, callers pass C and never ask.  wpe_grid: the workgroups of
+// the launch, n_groups x ceil(F / (256 / lanes per bin)).
 struct WpeConsts {
     int K, D, I;
     float loading, rho;
 };
-long wpe_grid(int n_clips, int F, int K);
-hipError_t launch_wpe(const void *spec, int n_clips, int T, int F, const WpeConsts &k, void *spec_out, float *mag_out, int width,
-                      hipStream_t st);
-// Multichannel dereverberation (dereverb_mc_kernels.hip; adn.h, "dereverb multichannel"): the same iterations on the N = C K
-// stacked past frames of the C consecutive clips of a group, 2 <= C <= 8 and C K <= 32 (C = 1 is launch_wpe), one launch, no
-// workspace.  The layouts are launch_wpe's with n_groups * C clips.  wpe_mc_grid: n_groups x ceil(F / (256 / lanes per bin)).
-long wpe_mc_grid(int n_groups, int C, int F, int K);
-hipError_t launch_wpe_mc(const void *spec, int n_groups, int C, int T, int F, const WpeConsts &k, void *spec_out, float *mag_out,
-                         int width, hipStream_t st);
+long wpe_grid(int n_groups, int C, int F, int K);
+hipError_t launch_wpe(const void *spec, int n_groups, int C, int T, int F, const WpeConsts &k, void *spec_out, float *mag_out,
+                      int width, hipStream_t st);
 // Streaming denoiser (stream_kernels.hip; adn.h, "stream").  StreamGeom: the plan and the layout of the state buffer of one batch
 // of streams, in floats (sections X, mag, hist, tail; `total` floats in all); stream_geom is false outside the limits of adn.h.
 // StreamCall: what one call of n_steps steps from step `first` covers, derived from the step index alone (stream_call):
@@ -567,34 +564,28 @@ hipError_t launch_stream_windows(const float *state, int n_streams, const Stream
                                  hipStream_t st);
 hipError_t launch_stream_emit(const float *y, int n_streams, const StreamGeom &g, const StreamCall &c, float *state, float *audio,
                               long out_stride, hipStream_t st);
-// Streaming dereverberation (dereverb_stream_kernels.hip; adn.h, "dereverb stream"): one RLS update per frame on every row.
-// WpeStreamConsts: the parameters and the two constants derived from them once per call on the host, in fp32: p0 = 1 / loading,
-// 1 - smooth.  wstate: wpe_stream_record_floats(K, D) floats per (slot, bin), [slot][bin] consecutive; a row that starts at frame
-// 0 reads none of it.  The three launches differ in where a row's frames are: frame-major spectrograms (row i = slot i, frames
-// first_frame .. first_frame + T - 1); the X ring of a lockstep stream state (frames f_first .. f_last of `call`, in place, M_t
-// into columns [W - B, W) of y); the same for the rows of a pool.  wpe_stream_grid: the workgroups of a launch.
+// Streaming dereverberation (dereverb_mc_stream_kernels.hip, dereverb_stream_kernels.hip; adn.h, "dereverb stream" and "dereverb
+// stream multichannel"): one RLS update per frame on the N = C K stacked past frames of the C consecutive rows of a group,
+// 1 <= C <= 8 and C K <= 32, c.K the taps per channel.  C = 1 is the single-channel operator and runs its own kernel; the launcher
+// chooses.  WpeStreamConsts: the parameters and the two constants derived from them once per call on the host, in fp32:
+// p0 = 1 / loading, 1 - smooth.  wstate: wpe_stream_record_floats(C, K, D) = 2 N^2 + 2 N C + 2 C (D + K) + 2 floats per (slot,
+// bin), [slot][bin] consecutive, group i = slot i; a group that starts at frame 0 reads none of it.  The launches differ in where a
+// row's frames are: frame-major spectrograms (n_groups * C rows, frames first_frame .. first_frame + T - 1); the X rings of a
+// lockstep stream state whose streams g C .. g C + C - 1 are group g (frames f_first .. f_last of `call`, in place, M_t into
+// columns [W - B, W) of y); the same for the rows of a pool.  wpe_stream_grid: the workgroups of a launch over n_rows groups.
 struct WpeStreamConsts {
     int K, D;
     float alpha, p0, rho, beta, one_minus_beta;
 };
-long wpe_stream_record_floats(int K, int D);
+long wpe_stream_record_floats(int C, int K, int D);
 long wpe_stream_grid(long n_rows, int F);
-hipError_t launch_wpe_online(const void *spec, int n_rows, int T, int F, int first_frame, const WpeStreamConsts &c, float *wstate,
-                             void *spec_out, float *mag_out, int width, int col0, hipStream_t st);
-hipError_t launch_wpe_stream(float *state, float *y, int n_streams, const StreamGeom &g, const StreamCall &call,
+hipError_t launch_wpe_online(const void *spec, int n_groups, int C, int T, int F, int first_frame, const WpeStreamConsts &c,
+                             float *wstate, void *spec_out, float *mag_out, int width, int col0, hipStream_t st);
+hipError_t launch_wpe_stream(float *state, float *y, int n_streams, int C, const StreamGeom &g, const StreamCall &call,
                              const WpeStreamConsts &c, float *wstate, hipStream_t st);
+// a pool's rows are single-channel streams: C is fixed at 1
 hipError_t launch_wpe_stream_pool(float *state, float *y, const StreamGeom &g, const StreamPoolRows &rows, const WpeStreamConsts &c,
                                   float *wstate, hipStream_t st);
-// Streaming multichannel dereverberation (dereverb_mc_stream_kernels.hip; adn.h, "dereverb stream multichannel"): the same
-// recursion on the N = C K stacked past frames of the C consecutive rows of a group, 2 <= C <= 8 and C K <= 32 (C = 1 is the
-// launches above), c.K the taps per channel.  wstate: wpe_mc_stream_record_floats(C, K, D) floats per (slot, bin), group i = slot
-// i.  The layouts are those of launch_wpe_online / launch_wpe_stream with n_groups * C rows / streams; the grid is
-// wpe_stream_grid(n_groups, F).
-long wpe_mc_stream_record_floats(int C, int K, int D);
-hipError_t launch_wpe_mc_online(const void *spec, int n_groups, int C, int T, int F, int first_frame, const WpeStreamConsts &c,
-                                float *wstate, void *spec_out, float *mag_out, int width, int col0, hipStream_t st);
-hipError_t launch_wpe_mc_stream(float *state, float *y, int n_streams, int C, const StreamGeom &g, const StreamCall &call,
-                                const WpeStreamConsts &c, float *wstate, hipStream_t st);
 hipError_t launch_quantize_pad(const float *in, int n, int h, int w, float *out, int H, int W, hipStream_t st);
 hipError_t launch_per_clip_l1(const float *a, const float *b, int n_clips, long elems, float *out, hipStream_t st);
 // Polyphase resampler and SNR mixer (resample_kernels.hip).  resample_ratio: up / down of a rate pair, false outside the limits

@@ -31,7 +31,7 @@
 // correlation (the 4 x 4 blocks compute 4 T 16 nb (nb + 1) / 2, 1.04 x that at K = 20) and 4 T K for the filter, the solve K^3 / 6.
 // Measured times: profiles/bench_dereverb.md.
 #include "adn_internal.h"
-#include "wpe_solve.h"                               // max_keep_nan, wpe_solve: shared with dereverb_mc_kernels.hip
+#include "wpe_solve.h"                               // the grid, the block decode, wpe_solve: shared with dereverb_mc_kernels.hip
 
 namespace adn {
 namespace {
@@ -50,11 +50,7 @@ __device__ __forceinline__ float2 wpe_filter(const float2 *xs, int pitch, const 
 #pragma clang fp contract(off)
     float2 d = xs[0];
     const float2 *p = xs - (long)D * pitch;
-    for (int j = 0; j < n; ++j, p -= pitch) {
-        const float2 c = g[j], x = *p;
-        d.x = fmaf(-c.y, x.y, fmaf(-c.x, x.x, d.x));
-        d.y = fmaf(c.y, x.x, fmaf(-c.x, x.y, d.y));
-    }
+    for (int j = 0; j < n; ++j, p -= pitch) d = cfms_conj(g[j], *p, d);
     return d;
 }
 
@@ -84,9 +80,8 @@ __global__ __launch_bounds__(WPE_THREADS) void wpe_kernel(const float2 *__restri
     const bool live = b0 + ib < F;
     // one group of LPB lanes per bin: bin gb, block (rb, cb) of the lower triangle, rb >= cb
     const int gb = tid / LPB, gl = tid % LPB;
-    int rb = 0;
-    while ((rb + 1) * (rb + 2) / 2 <= gl) ++rb;
-    int cb = gl - rb * (rb + 1) / 2;
+    int rb, cb;
+    wpe_tri_block(gl, rb, cb);
     const bool owner = rb < nb;                          // lanes past the last block compute block (0, 0) again and keep nothing
     if (!owner) rb = cb = 0;
 
@@ -179,13 +174,8 @@ __global__ __launch_bounds__(WPE_THREADS) void wpe_kernel(const float2 *__restri
                         for (int a = 0; a < 4; ++a) {    // lag 4 rb + a of frame s sits at xr[s - a + 3]
                             const float2 u = make_float2(w[s] * xr[s - a + 3].x, w[s] * xr[s - a + 3].y);
 #pragma unroll
-                            for (int c = 0; c < 4; ++c) {    // += u conj(v)
-                                const float2 v = xc[s - c + 3];
-                                acc[a][c].x = fmaf(u.y, v.y, fmaf(u.x, v.x, acc[a][c].x));
-                                acc[a][c].y = fmaf(-u.x, v.y, fmaf(u.y, v.x, acc[a][c].y));
-                            }
-                            accP[a].x = fmaf(u.y, xt[s].y, fmaf(u.x, xt[s].x, accP[a].x));
-                            accP[a].y = fmaf(-u.x, xt[s].y, fmaf(u.y, xt[s].x, accP[a].y));
+                            for (int c = 0; c < 4; ++c) acc[a][c] = cfma_conj_yx(u, xc[s - c + 3], acc[a][c]);
+                            accP[a] = cfma_conj_yx(u, xt[s], accP[a]);
                         }
                     }
                 }
@@ -215,7 +205,7 @@ template <int LPB>
 hipError_t launch(const void *spec, int n_clips, int T, int F, const WpeConsts &k, void *spec_out, float *mag_out, int width,
                   hipStream_t st)
 {
-    const long grid = wpe_grid(n_clips, F, k.K);
+    const long grid = wpe_grid_1ch(n_clips, F, k.K);
     if (grid > 0x7fffffffL) return hipErrorInvalidValue;
     const int tiles = (int)(grid / n_clips);
     hipLaunchKernelGGL(wpe_kernel<LPB>, dim3((unsigned)grid), dim3(WPE_THREADS), 0, st, static_cast<const float2 *>(spec),
@@ -225,14 +215,10 @@ hipError_t launch(const void *spec, int n_clips, int T, int F, const WpeConsts &
 
 }  // namespace
 
-long wpe_grid(int n_clips, int F, int K)
-{
-    const long bins = WPE_THREADS / wpe_lanes_per_bin(K);
-    return (((long)F + bins - 1) / bins) * n_clips;
-}
+long wpe_grid_1ch(int n_clips, int F, int K) { return wpe_tile_grid(n_clips, F, wpe_lanes_per_bin(K)); }
 
-hipError_t launch_wpe(const void *spec, int n_clips, int T, int F, const WpeConsts &k, void *spec_out, float *mag_out, int width,
-                      hipStream_t st)
+hipError_t launch_wpe_1ch(const void *spec, int n_clips, int T, int F, const WpeConsts &k, void *spec_out, float *mag_out, int width,
+                          hipStream_t st)
 {
     switch (wpe_lanes_per_bin(k.K)) {
     case 16: return launch<16>(spec, n_clips, T, F, k, spec_out, mag_out, width, st);

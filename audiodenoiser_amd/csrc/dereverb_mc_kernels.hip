@@ -1,7 +1,7 @@
 // Multichannel dereverberation for gfx950: joint WPE of the C channels of a recording (2 <= C <= 8; C = 1 is adn_wpe itself and is
-// forwarded to it by the entry point), all iterations of a (group, bin) in one launch.  Definition: include/adn.h, "dereverb
-// multichannel"; float64 restatement: tests/dereverb_mc_ref.py.  The single-channel sibling is dereverb_kernels.hip, whose shape
-// this file keeps; the Cholesky solve is the same code (wpe_solve.h) with C right-hand sides.
+// forwarded to its kernel by launch_wpe below), all iterations of a (group, bin) in one launch.  Definition: include/adn.h,
+// "dereverb multichannel"; float64 restatement: tests/dereverb_mc_ref.py.  The single-channel sibling is dereverb_kernels.hip,
+// whose shape this file keeps; the Cholesky solve is the same code (wpe_solve.h) with C right-hand sides.
 //
 // Layouts: X and the result are FRAME-major [group * C + channel][frame][F] float2 (adn_stft_complex of an (n_groups C, L) batch);
 // the optional magnitudes are bin-major [group * C + channel][F][width] with the frame fastest.
@@ -103,8 +103,7 @@ __global__ __launch_bounds__(WPE_MC_THREADS) void wpe_mc_kernel(const float2 *__
     int rb = 0, cb = 0;
     bool pblock = false;
     if (gl < nR) {
-        while ((rb + 1) * (rb + 2) / 2 <= gl) ++rb;
-        cb = gl - rb * (rb + 1) / 2;
+        wpe_tri_block(gl, rb, cb);
     } else if (gl < nR + nb * cq) {
         pblock = true;
         rb = (gl - nR) / cq;
@@ -206,6 +205,7 @@ __global__ __launch_bounds__(WPE_MC_THREADS) void wpe_mc_kernel(const float2 *__
 #pragma unroll
                                 for (int c = 0; c < 8; ++c) {
                                     if (c < C) {
+                                        // cfms_conj(q, v, d[c]) written out: as a call it moves this kernel's instructions
                                         const float2 q = gr[c * WPE_MC_NMAX];
                                         d[c].x = fmaf(-q.y, v.y, fmaf(-q.x, v.x, d[c].x));
                                         d[c].y = fmaf(q.y, v.x, fmaf(-q.x, v.y, d[c].y));
@@ -285,7 +285,7 @@ __global__ __launch_bounds__(WPE_MC_THREADS) void wpe_mc_kernel(const float2 *__
                         for (int a = 0; a < 4; ++a) {
                             const float2 u = make_float2(w[s] * xr[s][a].x, w[s] * xr[s][a].y);
 #pragma unroll
-                            for (int c = 0; c < 4; ++c) {    // += u conj(v)
+                            for (int c = 0; c < 4; ++c) {    // += u conj(v): cfma_conj_yx, written out for the same reason
                                 const float2 v = xc[s][c];
                                 acc[a][c].x = fmaf(u.y, v.y, fmaf(u.x, v.x, acc[a][c].x));
                                 acc[a][c].y = fmaf(-u.x, v.y, fmaf(u.y, v.x, acc[a][c].y));
@@ -322,7 +322,7 @@ template <int LPB>
 hipError_t launch(const void *spec, int n_groups, int C, int T, int F, const WpeConsts &k, void *spec_out, float *mag_out, int width,
                   hipStream_t st)
 {
-    const long grid = wpe_mc_grid(n_groups, C, F, k.K);
+    const long grid = wpe_grid(n_groups, C, F, k.K);
     if (grid > 0x7fffffffL) return hipErrorInvalidValue;
     const int tiles = (int)(grid / n_groups);
     if (k.K % 4 == 0)
@@ -336,16 +336,17 @@ hipError_t launch(const void *spec, int n_groups, int C, int T, int F, const Wpe
 
 }  // namespace
 
-long wpe_mc_grid(int n_groups, int C, int F, int K)
+long wpe_grid(int n_groups, int C, int F, int K)
 {
-    const long bins = WPE_MC_THREADS / wpe_mc_lanes_per_bin(C, K);
-    return (((long)F + bins - 1) / bins) * n_groups;
+    return C == 1 ? wpe_grid_1ch(n_groups, F, K) : wpe_tile_grid(n_groups, F, wpe_mc_lanes_per_bin(C, K));
 }
 
-hipError_t launch_wpe_mc(const void *spec, int n_groups, int C, int T, int F, const WpeConsts &k, void *spec_out, float *mag_out,
-                         int width, hipStream_t st)
+hipError_t launch_wpe(const void *spec, int n_groups, int C, int T, int F, const WpeConsts &k, void *spec_out, float *mag_out,
+                      int width, hipStream_t st)
 {
-    if (C < 2 || C > 8 || C * k.K > WPE_MC_NMAX) return hipErrorInvalidValue;      // C = 1 is launch_wpe's
+    // every statement of one channel reduces to "dereverb": the single-channel kernel, its bits
+    if (C == 1) return launch_wpe_1ch(spec, n_groups, T, F, k, spec_out, mag_out, width, st);
+    if (C < 1 || C > 8 || C * k.K > WPE_MC_NMAX) return hipErrorInvalidValue;
     switch (wpe_mc_lanes_per_bin(C, k.K)) {
     case 16: return launch<16>(spec, n_groups, C, T, F, k, spec_out, mag_out, width, st);
     case 32: return launch<32>(spec, n_groups, C, T, F, k, spec_out, mag_out, width, st);

@@ -1,6 +1,6 @@
 // Streaming multichannel dereverberation for gfx950: recursive (RLS) joint WPE of the C channels of a recording, one update per
 // frame and (group, bin).  Definition: include/adn.h, "dereverb stream multichannel"; float64 restatement:
-// tests/dereverb_mc_stream_ref.py.  C = 1 never comes here: the ABI forwards it to dereverb_stream_kernels.hip.
+// tests/dereverb_mc_stream_ref.py.  C = 1 runs the kernel of dereverb_stream_kernels.hip: the launchers at the end choose.
 //
 // State of a (slot, bin) (adn_wpe_mc_stream_state_bytes; REC = 2 N^2 + 2 N C + 2 C (D + K) + 2 floats, N = C K, records [slot][bin]
 // consecutive; at C = 1 this is the single-channel record):
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(WS_G * WS_GROUPS) void wpe_mc_stream_kernel(Src src
     const RowFrames rc{chan, r0.t0, r0.t1};
     const bool mine = live && r < C;
     const bool fresh = r0.t0 == 0;
-    const long rec = 2L * N * N + 2L * N * C + 2L * C * H + 2;
+    const long rec = 2L * N * N + 2L * N * C + 2L * C * H + 2;   // wpe_stream_record_floats(C, K, D)
     float *st = wstate + (g * F + (live ? bin : 0)) * rec;
     float2 *stP = reinterpret_cast<float2 *>(st), *stG = stP + N * N, *stH = stG + N * C;
     float *stS = reinterpret_cast<float *>(stH + C * H);
@@ -190,9 +190,7 @@ __global__ __launch_bounds__(WS_G * WS_GROUPS) void wpe_mc_stream_kernel(Src src
     }
 
     if (live) {
-#pragma unroll
-        for (int k = 0; k < WS_G; ++k)
-            if (k < N && r < N) stP[k * N + r] = Pr[k];
+        store_P_row(Pr, stP, r, N);
         if (r < N)
             for (int ch = 0; ch < C; ++ch) stG[ch * N + r] = l.G[ch * MS_GP + r];
         for (int h = r; h < C * H; h += WS_G) stH[h] = l.ring[h];
@@ -206,7 +204,7 @@ __global__ __launch_bounds__(WS_G * WS_GROUPS) void wpe_mc_stream_kernel(Src src
 template <class Src>
 hipError_t launch(const Src &src, long n_groups, int C, int F, const WpeStreamConsts &c, float *wstate, hipStream_t st)
 {
-    const long groupsF = ((long)F + WS_GROUPS - 1) / WS_GROUPS, grid = groupsF * n_groups;
+    const long groupsF = ws_tiles(F), grid = wpe_stream_grid(n_groups, F);
     if (grid > 0x7fffffffL || C < 2 || C > MS_CMAX || C * c.K > WS_G || C * (c.D + c.K) > MS_RING) return hipErrorInvalidValue;
     hipLaunchKernelGGL(wpe_mc_stream_kernel<Src>, dim3((unsigned)grid), dim3(WS_G * WS_GROUPS), 0, st, src, c, C, wstate, F, (int)groupsF);
     return hipGetLastError();
@@ -214,18 +212,23 @@ hipError_t launch(const Src &src, long n_groups, int C, int F, const WpeStreamCo
 
 }  // namespace
 
-long wpe_mc_stream_record_floats(int C, int K, int D) { return 2L * C * K * C * K + 2L * C * K * C + 2L * C * (D + K) + 2; }
+// P (N x N), G (N x C), C rings of D + K frames, s and a pad, N = C K: what the kernels above and of dereverb_stream_kernels.hip lay out
+long wpe_stream_record_floats(int C, int K, int D) { return 2L * C * K * C * K + 2L * C * K * C + 2L * C * (D + K) + 2; }
 
-hipError_t launch_wpe_mc_online(const void *spec, int n_groups, int C, int T, int F, int first_frame, const WpeStreamConsts &c,
-                                float *wstate, void *spec_out, float *mag_out, int width, int col0, hipStream_t st)
+// every statement of one channel is "dereverb stream": C = 1 runs the single-channel kernel, its bits
+hipError_t launch_wpe_online(const void *spec, int n_groups, int C, int T, int F, int first_frame, const WpeStreamConsts &c,
+                             float *wstate, void *spec_out, float *mag_out, int width, int col0, hipStream_t st)
 {
+    if (C == 1) return launch_wpe_online_1ch(spec, n_groups, T, F, first_frame, c, wstate, spec_out, mag_out, width, col0, st);
     FrameMajor src{static_cast<const float2 *>(spec), static_cast<float2 *>(spec_out), mag_out, T, width, col0, first_frame};
     return launch(src, n_groups, C, F, c, wstate, st);
 }
 
-hipError_t launch_wpe_mc_stream(float *state, float *y, int n_streams, int C, const StreamGeom &g, const StreamCall &call,
-                                const WpeStreamConsts &c, float *wstate, hipStream_t st)
+hipError_t launch_wpe_stream(float *state, float *y, int n_streams, int C, const StreamGeom &g, const StreamCall &call,
+                             const WpeStreamConsts &c, float *wstate, hipStream_t st)
 {
+    if (C == 1) return launch_wpe_stream_1ch(state, y, n_streams, g, call, c, wstate, st);
+    if (C < 1) return hipErrorInvalidValue;
     if (call.f_last < call.f_first) return hipSuccess;
     InRing<StreamCall> src{state, y, g, call};
     return launch(src, n_streams / C, C, g.n_fft / 2 + 1, c, wstate, st);

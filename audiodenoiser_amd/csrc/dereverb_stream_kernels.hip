@@ -37,7 +37,7 @@
 // What binds is the per-frame chain of one workgroup, 8 us: 2 K correctly rounded divisions by alpha per lane (the definition
 // divides), both sides of the divergent k <= j branch, three passes of K LDS broadcasts, four barriers.  No atomics, no
 // workspace, no constant table.
-#include "wpe_stream_frames.h"                        // the rounding rules and the frame sources: shared with dereverb_mc_stream_kernels.hip
+#include "wpe_stream_frames.h"                        // the frame sources: shared with dereverb_mc_stream_kernels.hip
 
 #include <type_traits>
 
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(WS_G * WS_GROUPS) void wpe_stream_kernel(Src src, W
     StreamCall call;
     const RowFrames r = frames_of(src, row, F, call);
     const bool fresh = r.t0 == 0;
-    const long rec = 2L * K * K + 4L * K + 2L * c.D + 2;
+    const long rec = 2L * K * K + 4L * K + 2L * c.D + 2;         // wpe_stream_record_floats(1, K, D)
     float *st = wstate + (r.slot * F + (live ? bin : 0)) * rec;
     float2 *stP = reinterpret_cast<float2 *>(st), *stG = stP + K * K, *stH = stG + K;
     float *stS = reinterpret_cast<float *>(stH + H);
@@ -159,9 +159,7 @@ __global__ __launch_bounds__(WS_G * WS_GROUPS) void wpe_stream_kernel(Src src, W
     }
 
     if (live) {
-#pragma unroll
-        for (int k = 0; k < WS_G; ++k)
-            if (k < K && j < K) stP[k * K + j] = Pr[k];
+        store_P_row(Pr, stP, j, K);
         if (j < K) stG[j] = l.g[j];
         for (int h = j; h < H; h += WS_G) stH[h] = l.ring[h];
         if (j == 0) {
@@ -174,7 +172,7 @@ __global__ __launch_bounds__(WS_G * WS_GROUPS) void wpe_stream_kernel(Src src, W
 template <class Src>
 hipError_t launch(const Src &src, long n_rows, int F, const WpeStreamConsts &c, float *wstate, hipStream_t st)
 {
-    const long groupsF = ((long)F + WS_GROUPS - 1) / WS_GROUPS, grid = groupsF * n_rows;
+    const long groupsF = ws_tiles(F), grid = wpe_stream_grid(n_rows, F);
     if (grid > 0x7fffffffL) return hipErrorInvalidValue;
     hipLaunchKernelGGL(wpe_stream_kernel<Src>, dim3((unsigned)grid), dim3(WS_G * WS_GROUPS), 0, st, src, c, wstate, F, (int)groupsF);
     return hipGetLastError();
@@ -182,25 +180,25 @@ hipError_t launch(const Src &src, long n_rows, int F, const WpeStreamConsts &c, 
 
 }  // namespace
 
-long wpe_stream_record_floats(int K, int D) { return 2L * K * K + 4L * K + 2L * D + 2; }
+long wpe_stream_grid(long n_rows, int F) { return n_rows * ws_tiles(F); }
 
-long wpe_stream_grid(long n_rows, int F) { return n_rows * (((long)F + WS_GROUPS - 1) / WS_GROUPS); }
-
-hipError_t launch_wpe_online(const void *spec, int n_rows, int T, int F, int first_frame, const WpeStreamConsts &c, float *wstate,
-                             void *spec_out, float *mag_out, int width, int col0, hipStream_t st)
+hipError_t launch_wpe_online_1ch(const void *spec, int n_rows, int T, int F, int first_frame, const WpeStreamConsts &c, float *wstate,
+                                 void *spec_out, float *mag_out, int width, int col0, hipStream_t st)
 {
     FrameMajor src{static_cast<const float2 *>(spec), static_cast<float2 *>(spec_out), mag_out, T, width, col0, first_frame};
     return launch(src, n_rows, F, c, wstate, st);
 }
 
-hipError_t launch_wpe_stream(float *state, float *y, int n_streams, const StreamGeom &g, const StreamCall &call,
-                             const WpeStreamConsts &c, float *wstate, hipStream_t st)
+hipError_t launch_wpe_stream_1ch(float *state, float *y, int n_streams, const StreamGeom &g, const StreamCall &call,
+                                 const WpeStreamConsts &c, float *wstate, hipStream_t st)
 {
     if (call.f_last < call.f_first) return hipSuccess;
     InRing<StreamCall> src{state, y, g, call};
     return launch(src, n_streams, g.n_fft / 2 + 1, c, wstate, st);
 }
 
+// the pool's rows are single-channel streams: C is fixed at 1 here (a joint pool would be launch(src, rows.n / C, C, ...) of
+// dereverb_mc_stream_kernels.hip on the same source)
 hipError_t launch_wpe_stream_pool(float *state, float *y, const StreamGeom &g, const StreamPoolRows &rows, const WpeStreamConsts &c,
                                   float *wstate, hipStream_t st)
 {

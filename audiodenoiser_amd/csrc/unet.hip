@@ -760,10 +760,6 @@ int forward_impl(adn_unet *h, const float *x, float *y, int N, int F, int T, voi
     do {                                                    \
         if (timed) ADN_HIP(hipEventRecord(ev[evi++], st));  \
     } while (0)
-#define ADN_TRY(call)                                       \
-    do {                                                    \
-        if (int rc_ = (call)) return rc_;                   \
-    } while (0)
 
     // block output `idx` = what layer `layer` of NET wrote to `buf`
     auto export_tap = [&](int idx, const void *buf, int layer) -> hipError_t {
@@ -871,7 +867,6 @@ int forward_impl(adn_unet *h, const float *x, float *y, int N, int F, int T, voi
         ++h->timing_count;
     }
 #undef ADN_MARK
-#undef ADN_TRY
     if (taps && taps[9])
         ADN_HIP(hipMemcpyAsync(taps[9], y, (size_t)N * h->n_classes * F * T * sizeof(float), hipMemcpyDeviceToDevice, st));
     return ADN_OK;

@@ -1,13 +1,25 @@
-// The Cholesky solve of the offline WPE kernels (dereverb_kernels.hip, dereverb_mc_kernels.hip): one definition, so that the
-// multichannel operator at one channel and the single-channel one cannot drift apart.  include/adn.h, "dereverb": A = L L^H column
-// by column, L y = P, L^H g = y, inner sums sequential in k.
+// What the two offline WPE kernels share (dereverb_kernels.hip, dereverb_mc_kernels.hip): the grid of a launch, the block a lane
+// owns, and the Cholesky solve: one definition, so that the multichannel operator at one channel and the single-channel one
+// cannot drift apart.  include/adn.h, "dereverb": A = L L^H column by column, L y = P, L^H g = y, inner sums sequential in k.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "wpe_common.h"                              // max_keep_nan, the complex multiply-adds
 
 namespace adn {
 
-// max(x, c) of adn.h: a NaN x stays NaN
-__device__ __forceinline__ float max_keep_nan(float x, float c) { return x < c ? c : x; }
+// The workgroups of an offline launch: n rows (clips or groups) x ceil(F / bins of a 256-lane tile at `lanes` lanes per bin)
+inline long wpe_tile_grid(int n, int F, int lanes)
+{
+    const long bins = 256 / lanes;
+    return (((long)F + bins - 1) / bins) * n;
+}
+
+// Lane gl's block (rb, cb) of a lower triangle cut into blocks, row after row: block rb (rb + 1) / 2 + cb, cb <= rb
+__device__ __forceinline__ void wpe_tri_block(int gl, int &rb, int &cb)
+{
+    rb = 0;
+    while ((rb + 1) * (rb + 2) / 2 <= gl) ++rb;
+    cb = gl - rb * (rb + 1) / 2;
+}
 
 // The solve of one row by its group of LPB lanes (lane gl): A (packed lower triangle, row r at r (r + 1) / 2) holds R; g holds
 // n_rhs right-hand sides P, column c at g + c * pitch, n_rhs <= LPB.  On return the columns hold the taps.  One factorisation; lane
@@ -44,9 +56,8 @@ __device__ __forceinline__ void wpe_solve(float2 *A, float2 *g, int K, float loa
             float2 *rr = A + r * (r + 1) / 2;
             float2 v = rr[c];
             for (int k = 0; k < c; ++k) {            // v -= L_rk conj(L_ck)
-                const float2 a = rr[k], b = rc[k];
-                v.x = fmaf(-a.y, b.y, fmaf(-a.x, b.x, v.x));
-                v.y = fmaf(a.x, b.y, fmaf(-a.y, b.x, v.y));
+                const float2 a = rr[k];
+                v = cfma_conj_yx(make_float2(-a.x, -a.y), rc[k], v);
             }
             rr[c] = make_float2(v.x / lcc, v.y / lcc);
         }
@@ -58,18 +69,15 @@ __device__ __forceinline__ void wpe_solve(float2 *A, float2 *g, int K, float loa
             const float2 *rr = A + r * (r + 1) / 2;
             float2 v = g[r];
             for (int k = 0; k < r; ++k) {            // v -= L_rk y_k
-                const float2 a = rr[k], y = g[k];
-                v.x = fmaf(a.y, y.y, fmaf(-a.x, y.x, v.x));
-                v.y = fmaf(-a.y, y.x, fmaf(-a.x, y.y, v.y));
+                const float2 a = rr[k];
+                v = cfma(make_float2(-a.x, -a.y), g[k], v);
             }
             g[r] = make_float2(v.x / rr[r].x, v.y / rr[r].x);
         }
         for (int r = K - 1; r >= 0; --r) {           // L^H g = y
             float2 v = g[r];
             for (int k = K - 1; k > r; --k) {        // v -= conj(L_kr) g_k
-                const float2 a = A[k * (k + 1) / 2 + r], y = g[k];
-                v.x = fmaf(-a.y, y.y, fmaf(-a.x, y.x, v.x));
-                v.y = fmaf(a.y, y.x, fmaf(-a.x, y.y, v.y));
+                v = cfms_conj(A[k * (k + 1) / 2 + r], g[k], v);
             }
             const float lrr = A[r * (r + 1) / 2 + r].x;
             g[r] = make_float2(v.x / lrr, v.y / lrr);

@@ -1,10 +1,10 @@
-// What the two recursive WPE kernels share (dereverb_stream_kernels.hip, dereverb_mc_stream_kernels.hip): the rounding rules of
-// adn.h, "dereverb stream", "Arithmetic", and the places a row's frames come from.  One definition, so that a joint stream of one
-// recording and C single-channel streams read and write the same cells by the same arithmetic.  Everything is in an unnamed
+// What the two recursive WPE kernels share (dereverb_stream_kernels.hip, dereverb_mc_stream_kernels.hip): the grid, the store of a
+// record's P rows and the places a row's frames come from (the rounding rules are wpe_common.h's).  One definition, so that a joint
+// stream of one recording and C single-channel streams read and write the same cells by the same arithmetic.  Everything is in an unnamed
 // namespace on purpose: each of the two translation units instantiates its own kernels on these types, and the single-channel
 // kernels keep the symbols and the code they had when this text stood in their file (tools/kernel_isa_digest.py).
 #pragma once
-#include "adn_internal.h"
+#include "wpe_common.h"
 
 namespace adn {
 namespace {
@@ -13,17 +13,17 @@ constexpr int WS_G = 32;                             // lanes per group = the mo
 constexpr int WS_GROUPS = 8;                         // groups (bins) per workgroup
 constexpr int WS_HMAX = 40;                          // D + K at most
 
-// max(x, c) of adn.h: a NaN x stays NaN
-__device__ __forceinline__ float max_keep_nan(float x, float c) { return x < c ? c : x; }
+// workgroups per row (or group of rows) of a launch: WS_GROUPS bins each
+inline long ws_tiles(int F) { return ((long)F + WS_GROUPS - 1) / WS_GROUPS; }
 
-// acc + a b and acc + a conj(b), two fmaf per component (adn.h, "dereverb stream", "Arithmetic")
-__device__ __forceinline__ float2 cfma(float2 a, float2 b, float2 acc)
+// Lane r holds row r of P in Pr; a record keeps element (r, s) at s N + r.  (The load of that row, u = P x~, q and the Hermitian
+// update are the same statements in both kernels too, but stay written out in each: as shared functions they moved the kernels'
+// instructions and five of fifteen rows of the timing tables past the parent's spread -- profiles/wpe_family.md.)
+__device__ __forceinline__ void store_P_row(const float2 (&Pr)[WS_G], float2 *stP, int r, int N)
 {
-    return make_float2(fmaf(-a.y, b.y, fmaf(a.x, b.x, acc.x)), fmaf(a.y, b.x, fmaf(a.x, b.y, acc.y)));
-}
-__device__ __forceinline__ float2 cfma_conj(float2 a, float2 b, float2 acc)
-{
-    return make_float2(fmaf(a.y, b.y, fmaf(a.x, b.x, acc.x)), fmaf(a.y, b.x, fmaf(-a.x, b.y, acc.y)));
+#pragma unroll
+    for (int k = 0; k < WS_G; ++k)
+        if (k < N && r < N) stP[k * N + r] = Pr[k];
 }
 
 // ---------------------------------------------------------------------------------------------- where the frames are

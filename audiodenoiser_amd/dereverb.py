@@ -101,30 +101,53 @@ class WpeParams:
         return _lib.WpeParamsStruct(int(self.taps), int(self.delay), int(self.iterations), float(self.loading), float(self.power_floor))
 
 
+def _spec_dims(who, row, spec):
+    """``spec`` is a complex64 ``(rows, frames, bins)`` tensor on a ROCm device: its shape.  ``row``: what ``who`` calls a row."""
+    if not isinstance(spec, torch.Tensor) or not spec.is_cuda or spec.dtype != torch.complex64 or spec.dim() != 3:
+        raise ValueError(f"{who}: expected a (n_{row}s, n_frames, n_bins) complex64 tensor on a ROCm device")
+    return spec.shape
+
+
+def _need_cells(who, row, n, t, f):
+    if n < 1 or t < 1 or f < 1:
+        raise ValueError(f"{who}: need at least one {row}, one frame and one bin")
+
+
+def _mag_buffer(who, row, mag_out, n, t, f, dev):
+    """``mag_out`` checked against ``spec``'s ``(n, t, f)`` and device; None allocates ``(n, 1, f, t)``."""
+    if mag_out is None:
+        return torch.empty((n, 1, f, t), dtype=torch.float32, device=dev)
+    if (not isinstance(mag_out, torch.Tensor) or not mag_out.is_cuda or mag_out.device != dev or mag_out.dtype != torch.float32
+            or mag_out.dim() != 4 or tuple(mag_out.shape[:3]) != (n, 1, f) or not mag_out.is_contiguous()):
+        raise ValueError(f"{who}: mag_out must be a contiguous (n_{row}s, 1, n_bins, width) float32 tensor on spec's device")
+    return mag_out
+
+
+def _entry(name, count, channels):
+    """The C function of an operator and the arguments that size its batch: ``adn_wpe<name>`` and ``(count,)`` for the
+    single-channel form (``channels=None``), ``adn_wpe_mc<name>`` and ``(count, channels)`` for the joint one.  The library treats
+    the joint function at one channel like its sibling; the names in its messages and the taps of ``params=NULL`` differ, so each
+    Python function keeps calling its own."""
+    L = _lib.load()
+    return (getattr(L, "adn_wpe" + name), (count,)) if channels is None else (getattr(L, "adn_wpe_mc" + name), (count, channels))
+
+
 def _wpe(who, spec, channels, params, mag_out):
     """``adn_wpe`` (``channels=None``) or ``adn_wpe_mc`` on the current stream, the workspace allocated here."""
-    if not isinstance(spec, torch.Tensor) or not spec.is_cuda or spec.dtype != torch.complex64 or spec.dim() != 3:
-        raise ValueError(f"{who}: expected a (n_clips, n_frames, n_bins) complex64 tensor on a ROCm device")
-    n, t, f = spec.shape
-    if n < 1 or t < 1 or f < 1:
-        raise ValueError(f"{who}: need at least one clip, one frame and one bin")
+    n, t, f = _spec_dims(who, "clip", spec)
+    _need_cells(who, "clip", n, t, f)
     dev = spec.device
     s = torch.view_as_real(spec.contiguous())
-    if mag_out is None:
-        mag_out = torch.empty((n, 1, f, t), dtype=torch.float32, device=dev)
-    elif (not isinstance(mag_out, torch.Tensor) or not mag_out.is_cuda or mag_out.device != dev or mag_out.dtype != torch.float32
-          or mag_out.dim() != 4 or tuple(mag_out.shape[:3]) != (n, 1, f) or not mag_out.is_contiguous()):
-        raise ValueError(f"{who}: mag_out must be a contiguous (n_clips, 1, n_bins, width) float32 tensor on spec's device")
+    mag_out = _mag_buffer(who, "clip", mag_out, n, t, f, dev)
     out = torch.empty((n, t, f, 2), dtype=torch.float32, device=dev)
     p = ctypes.byref(params.to_struct()) if params is not None else None
-    L = _lib.load()
-    size, run, shape = ((L.adn_wpe_workspace_bytes, L.adn_wpe, (n, t, f)) if channels is None else
-                        (L.adn_wpe_mc_workspace_bytes, L.adn_wpe_mc, (n // channels, channels, t, f)))
+    groups = n if channels is None else n // channels
+    (size, shape), (run, _) = _entry("_workspace_bytes", groups, channels), _entry("", groups, channels)
     need = ctypes.c_size_t(0)
-    _lib.check(size(*shape, p, ctypes.byref(need)), size.__name__)
+    _lib.check(size(*shape, t, f, p, ctypes.byref(need)), size.__name__)
     ws = torch.empty((need.value,), dtype=torch.uint8, device=dev) if need.value else None
     with torch.cuda.device(dev):
-        _lib.check(run(s.data_ptr(), *shape, p, ws.data_ptr() if ws is not None else None, need.value, out.data_ptr(),
+        _lib.check(run(s.data_ptr(), *shape, t, f, p, ws.data_ptr() if ws is not None else None, need.value, out.data_ptr(),
                        mag_out.data_ptr(), int(mag_out.shape[3]), current_stream(dev)), run.__name__)
     return torch.view_as_complex(out), mag_out
 
@@ -139,18 +162,33 @@ def wpe(spec: torch.Tensor, params: WpeParams = None, mag_out: torch.Tensor = No
     return _wpe("wpe", spec, None, params, mag_out)
 
 
-def _joint_params(who, params, channels):
-    """The parameters of a joint call on ``channels`` channels: ``params``, or the defaults with ``taps = 32 // channels``.
-    ValueError for a channel count outside 1 ... 8 and for ``channels * taps > 32``, before anything looks at a device."""
+def _check_channels(who, channels):
     if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= 8:
         raise ValueError(f"{who}: need an integer 1 <= channels <= 8")
+
+
+def _joint_rules(cls, who, params, channels):
+    """The parameters (a ``cls``: ``WpeParams`` or ``WpeStreamParams``) of a joint call on ``channels`` channels: ``params``, or
+    the defaults with ``taps = 32 // channels``.  ValueError for a channel count outside 1 ... 8, for ``channels * taps > 32`` and
+    -- the streaming form only, with more than one channel -- for ``2 channels taps (1 - forget) > 1`` on the fp32 value of
+    ``forget``: the rules of "dereverb multichannel" and "dereverb stream multichannel", checked here because here the channel
+    count is known, before anything looks at a device."""
+    _check_channels(who, channels)
     if params is None:
-        return WpeParams(taps=32 // channels)
-    if not isinstance(params, WpeParams):
-        raise TypeError(f"{who}: params must be a WpeParams")
-    if channels * params.taps > 32:
+        return cls(taps=32 // channels)
+    if not isinstance(params, cls):
+        raise TypeError(f"{who}: params must be a {cls.__name__}")
+    n = channels * params.taps
+    if n > 32:
         raise ValueError(f"{who}: need channels * taps <= 32 (channels {channels}, taps {params.taps})")
+    if cls is WpeStreamParams and channels > 1 and not 2.0 * n * (1.0 - ctypes.c_float(float(params.forget)).value) <= 1.0:
+        raise ValueError(f"{who}: need 2 channels taps (1 - forget) <= 1 with more than one channel: forget >= {1 - 1 / (2 * n):.6f} "
+                         f"at channels * taps = {n} (forget {params.forget})")
     return params
+
+
+def _joint_params(who, params, channels):
+    return _joint_rules(WpeParams, who, params, channels)
 
 
 def wpe_joint(spec: torch.Tensor, channels: int, params: WpeParams = None, mag_out: torch.Tensor = None):
@@ -172,10 +210,12 @@ class Dereverberator(Denoiser):
     of a recording are dereverberated together (``wpe_joint``): ``(C, L)`` is one recording of ``C <= 8`` channels, ``(N, C, L)``
     a batch, ``denoise_file`` takes the wav's channels as one recording; ``params=None`` then takes ``taps = 32 // C``, and a
     ``params`` with ``C * taps > 32`` is a ValueError of the call.  A mono input is the single-channel path; the gain runs per
-    channel on the joint result."""
+    channel on the joint result.  ``joint_default_taps=True`` (keyword only; the command line's "no ``--taps``") keeps that
+    ``32 // C`` rule with a ``params`` that sets the other fields; None: exactly when ``params`` is None."""
 
     def __init__(self, device=None, sample_rate: int = 8000, n_fft: int = 512, hop_length: int = 128, params: WpeParams = None,
-                 gain: bool = False, gain_params: SpectralParams = None, channels: str = "separate"):
+                 gain: bool = False, gain_params: SpectralParams = None, channels: str = "separate", *,
+                 joint_default_taps: bool = None):
         check_stft_plan("Dereverberator", n_fft, hop_length, sample_rate)
         if params is not None and not isinstance(params, WpeParams):
             raise TypeError("Dereverberator: params must be a WpeParams")
@@ -184,7 +224,7 @@ class Dereverberator(Denoiser):
         self.params = WpeParams() if params is None else params
         self.channels = channels
         self.joint_channels = channels == "joint"            # Denoiser.denoise: (C, L) is one recording, _core is told C
-        self._default_taps = params is None                  # joint: taps = 32 // C
+        self._default_taps = params is None if joint_default_taps is None else bool(joint_default_taps)   # joint: taps = 32 // C
         self.gain = bool(gain)
         self.gain_params = _spectral_params("Dereverberator", gain_params, "gain_params")
         self.model = None
@@ -244,41 +284,27 @@ def _stream_params(who, params):
     return ctypes.byref(params.to_struct()) if params is not None else None
 
 
-def wpe_stream_state_bytes(n_slots: int, n_bins: int, params: WpeStreamParams = None) -> int:
-    """``adn_wpe_stream_state_bytes``: the bytes of the opaque WPE state of ``n_slots`` rows of ``n_bins`` bins (no device needed)."""
+def _state_bytes(who, n_slots, channels, n_bins, params):
+    """``adn_wpe_stream_state_bytes`` (``channels=None``) or ``adn_wpe_mc_stream_state_bytes``."""
+    size, lead = _entry("_stream_state_bytes", n_slots, channels)
     need = ctypes.c_size_t(0)
-    _lib.check(_lib.load().adn_wpe_stream_state_bytes(n_slots, n_bins, _stream_params("wpe_stream_state_bytes", params),
-                                                      ctypes.byref(need)), "adn_wpe_stream_state_bytes")
+    _lib.check(size(*lead, n_bins, _stream_params(who, params), ctypes.byref(need)), size.__name__)
     return int(need.value)
 
 
+def wpe_stream_state_bytes(n_slots: int, n_bins: int, params: WpeStreamParams = None) -> int:
+    """``adn_wpe_stream_state_bytes``: the bytes of the opaque WPE state of ``n_slots`` rows of ``n_bins`` bins (no device needed)."""
+    return _state_bytes("wpe_stream_state_bytes", n_slots, None, n_bins, params)
+
+
 def _joint_stream_params(who, params, channels):
-    """The parameters of a joint streaming call on ``channels`` channels: ``params``, or the defaults with ``taps = 32 //
-    channels``.  ValueError for a channel count outside 1 ... 8, for ``channels * taps > 32`` and, with more than one channel, for
-    ``2 channels taps (1 - forget) > 1`` on the fp32 value of ``forget`` -- the rules of "dereverb stream multichannel", checked
-    here because here the channel count is known, before anything looks at a device."""
-    if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= 8:
-        raise ValueError(f"{who}: need an integer 1 <= channels <= 8")
-    if params is None:
-        return WpeStreamParams(taps=32 // channels)
-    if not isinstance(params, WpeStreamParams):
-        raise TypeError(f"{who}: params must be a WpeStreamParams")
-    n = channels * params.taps
-    if n > 32:
-        raise ValueError(f"{who}: need channels * taps <= 32 (channels {channels}, taps {params.taps})")
-    if channels > 1 and not 2.0 * n * (1.0 - ctypes.c_float(float(params.forget)).value) <= 1.0:
-        raise ValueError(f"{who}: need 2 channels taps (1 - forget) <= 1 with more than one channel: forget >= {1 - 1 / (2 * n):.6f} "
-                         f"at channels * taps = {n} (forget {params.forget})")
-    return params
+    return _joint_rules(WpeStreamParams, who, params, channels)
 
 
 def wpe_stream_state_bytes_joint(n_slots: int, channels: int, n_bins: int, params: WpeStreamParams = None) -> int:
     """``adn_wpe_mc_stream_state_bytes``: the bytes of the opaque joint WPE state of ``n_slots`` groups of ``channels`` channels
     and ``n_bins`` bins (no device needed).  ``params=None``: the defaults with ``taps = 32 // channels``."""
-    need = ctypes.c_size_t(0)
-    _lib.check(_lib.load().adn_wpe_mc_stream_state_bytes(n_slots, channels, n_bins, _stream_params("wpe_stream_state_bytes_joint", params),
-                                                         ctypes.byref(need)), "adn_wpe_mc_stream_state_bytes")
-    return int(need.value)
+    return _state_bytes("wpe_stream_state_bytes_joint", n_slots, channels, n_bins, params)
 
 
 def wpe_online(spec: torch.Tensor, state: torch.Tensor = None, first_frame: int = 0, params: WpeStreamParams = None,
@@ -306,17 +332,14 @@ def wpe_online_joint(spec: torch.Tensor, channels: int, state: torch.Tensor = No
 
 def _wpe_online(who, spec, channels, state, first_frame, params, mag_out, col0):
     """``adn_wpe_online`` (``channels=None``) or ``adn_wpe_mc_online`` on the current stream."""
-    if not isinstance(spec, torch.Tensor) or not spec.is_cuda or spec.dtype != torch.complex64 or spec.dim() != 3:
-        raise ValueError(f"{who}: expected a (n_rows, n_frames, n_bins) complex64 tensor on a ROCm device")
+    n, t, f = _spec_dims(who, "row", spec)
     p = _stream_params(who, params)
-    n, t, f = spec.shape
-    if n < 1 or t < 1 or f < 1:
-        raise ValueError(f"{who}: need at least one row, one frame and one bin")
+    _need_cells(who, "row", n, t, f)
     if not (isinstance(first_frame, int) and first_frame >= 0 and isinstance(col0, int) and col0 >= 0):
         raise ValueError(f"{who}: need integers first_frame >= 0 and col0 >= 0")
     dev = spec.device
     slots = n if channels is None else n // channels
-    need = wpe_stream_state_bytes(n, f, params) if channels is None else wpe_stream_state_bytes_joint(slots, channels, f, params)
+    need = _state_bytes(who, slots, channels, f, params)
     if state is None:
         if first_frame != 0:
             raise ValueError(f"{who}: first_frame > 0 continues a row: pass the state of the call before")
@@ -325,16 +348,11 @@ def _wpe_online(who, spec, channels, state, first_frame, params, mag_out, col0):
           or state.dim() != 1 or state.numel() < need or not state.is_contiguous()):
         raise ValueError(f"{who}: state must be a contiguous uint8 tensor of at least wpe_stream_state_bytes on spec's device")
     s = torch.view_as_real(spec.contiguous())
-    if mag_out is None:
-        if col0 != 0:
-            raise ValueError(f"{who}: col0 needs a mag_out buffer")
-        mag_out = torch.empty((n, 1, f, t), dtype=torch.float32, device=dev)
-    elif (not isinstance(mag_out, torch.Tensor) or not mag_out.is_cuda or mag_out.device != dev or mag_out.dtype != torch.float32
-          or mag_out.dim() != 4 or tuple(mag_out.shape[:3]) != (n, 1, f) or not mag_out.is_contiguous()):
-        raise ValueError(f"{who}: mag_out must be a contiguous (n_rows, 1, n_bins, width) float32 tensor on spec's device")
+    if mag_out is None and col0 != 0:
+        raise ValueError(f"{who}: col0 needs a mag_out buffer")
+    mag_out = _mag_buffer(who, "row", mag_out, n, t, f, dev)
     out = torch.empty((n, t, f, 2), dtype=torch.float32, device=dev)
-    L = _lib.load()
-    run, shape = (L.adn_wpe_online, (n,)) if channels is None else (L.adn_wpe_mc_online, (slots, channels))
+    run, shape = _entry("_online", slots, channels)
     with torch.cuda.device(dev):
         _lib.check(run(s.data_ptr(), *shape, t, f, first_frame, p, state.data_ptr(), state.numel(), slots, out.data_ptr(),
                        mag_out.data_ptr(), int(mag_out.shape[3]), col0, current_stream(dev)), run.__name__)
@@ -356,8 +374,7 @@ def _wpe_setup(sd, who, device, n_slots, n_fft, params, gain, gain_params, chann
     sd.params = joint if joint is not None else WpeStreamParams() if params is None else params
     sd.gain = bool(gain)
     f = n_fft // 2 + 1
-    need = (wpe_stream_state_bytes(n_slots, f, sd.params) if channels == 1 else
-            wpe_stream_state_bytes_joint(n_slots // channels, channels, f, sd.params))
+    need = _state_bytes(who, n_slots // channels, None if channels == 1 else channels, f, sd.params)
     sd._wpe_state = torch.empty((need,), dtype=torch.uint8, device=dev)
     sd._gain_state = torch.empty((n_slots, 3, f), dtype=torch.float32, device=dev)
     return dev
@@ -377,12 +394,10 @@ def _wpe_then_gain(sd, x: torch.Tensor, rows, n_steps: int, first_step: int = 0,
         plan, groups = sd.book.plan, [(x[i:i + POOL_MAX_ROWS], rows[i:i + POOL_MAX_ROWS]) for i in range(0, len(rows), POOL_MAX_ROWS)]
     for part, group in groups:
         with torch.cuda.device(sd.device):
-            if group is None and sd.channels != 1:
-                _lib.check(L.adn_wpe_mc_stream(*state, part.data_ptr(), sd.n_streams, sd.channels, first_step, n_steps, final_length,
-                                               *plan, sd.max_steps, *wpe_args), "adn_wpe_mc_stream")
-            elif group is None:
-                _lib.check(L.adn_wpe_stream(*state, part.data_ptr(), sd.n_streams, first_step, n_steps, final_length, *plan,
-                                            sd.max_steps, *wpe_args), "adn_wpe_stream")
+            if group is None:
+                run, lead = _entry("_stream", sd.n_streams, None if sd.channels == 1 else sd.channels)
+                _lib.check(run(*state, part.data_ptr(), *lead, first_step, n_steps, final_length, *plan, sd.max_steps, *wpe_args),
+                           run.__name__)
             else:
                 _lib.check(L.adn_wpe_stream_pool(*state, *sd._args, sd._rows(group), len(group), part.data_ptr(), *wpe_args),
                            "adn_wpe_stream_pool")
@@ -412,8 +427,7 @@ class StreamDereverberator(StreamDenoiser):
         window, ahead, batch = causal_carrier(block_frames)
         _check_stream_args("StreamDereverberator", n_streams, sample_rate, n_fft, hop_length, window, block_frames, ahead, batch,
                            input_rate)
-        if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= 8:
-            raise ValueError("StreamDereverberator: need an integer 1 <= channels <= 8")
+        _check_channels("StreamDereverberator", channels)
         dev = _wpe_setup(self, "StreamDereverberator", device, n_streams, n_fft, params, gain, gain_params, channels)
         self._setup(dev, n_streams, sample_rate, n_fft, hop_length, window, block_frames, ahead, batch, input_rate)
 
@@ -502,8 +516,9 @@ def main(argv=None) -> int:
         params = WpeParams(taps=taps, delay=args.delay, iterations=args.iterations)
     except ValueError as exc:
         ap.error(str(exc))
-    dn = Dereverberator(params=params, gain=args.gain, channels="joint" if args.joint else "separate")
-    dn._default_taps = args.taps is None                     # --joint without --taps: 32 // channels of each file
+    # --joint without --taps: 32 // channels of each file
+    dn = Dereverberator(params=params, gain=args.gain, channels="joint" if args.joint else "separate",
+                        joint_default_taps=args.taps is None)
     try:
         return run_files(dn, args.src, args.dst, args.reference)
     except ValueError as exc:

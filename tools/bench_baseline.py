@@ -19,43 +19,20 @@ Kernel-level numbers: rocprofv3 --kernel-trace --stats -- python tools/bench_bas
 """
 import argparse
 import json
-import math
 import os
-import statistics
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bench_common import time_ms  # noqa: E402
 
 HBM_BPS = 8.0e12
 RATE = 8000
 N_FFT, HOP = 512, 128
 CASES = (("one_hour", 60, 60 * RATE), ("one_clip_3s", 1, 3 * RATE))
-
-
-def time_ms(fn, warmup, groups, window_ms):
-    import torch
-    for _ in range(warmup):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    steps = max(3, int(math.ceil(window_ms / max(e0.elapsed_time(e1), 1e-3))))
-    out = []
-    for _ in range(groups):
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(steps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / steps)
-    return {"ms": round(statistics.median(out), 4), "ms_min": round(min(out), 4), "ms_max": round(max(out), 4), "steps_per_window": steps}
 
 
 def main():

@@ -23,44 +23,20 @@ Kernel-level numbers: rocprofv3 --kernel-trace --stats -- python tools/bench_der
 """
 import argparse
 import json
-import math
 import os
-import re
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bench_common import time_ms, write_marked_block  # noqa: E402
 
 HBM_BPS = 8.0e12
 FMA_PER_S = 157.3e12 / 2           # peak fp32 vector rate of the MI355X, two flops per FMA
 RATE = 8000
 N_FFT, HOP = 512, 128
 CASES = (("one_hour", 60, 60 * RATE), ("one_clip_3s", 1, 3 * RATE))
-
-
-def time_ms(fn, warmup, groups, window_ms):
-    import torch
-    for _ in range(warmup):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    steps = max(3, int(math.ceil(window_ms / max(e0.elapsed_time(e1), 1e-3))))
-    out = []
-    for _ in range(groups):
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(steps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / steps)
-    return {"ms": round(statistics.median(out), 4), "ms_min": round(min(out), 4), "ms_max": round(max(out), 4), "steps_per_window": steps}
 
 
 def torch_wpe(spec, taps=20, delay=3, iterations=3, loading=1e-3, power_floor=1e-3):
@@ -187,10 +163,7 @@ def main():
              + "".join(f"| {label} | {sdr[key]} dB | {sdr['restatement_float64'][i]} dB |\n" for i, (label, key) in enumerate(
                  (("reverberant input", "input"), ("WPE", "wpe"), ("spectral baseline alone", "spectral_baseline"),
                   ("WPE, then spectral baseline", "wpe_then_spectral_baseline")))))
-    doc = open(args.out).read()
-    doc, cnt = re.subn(r"(<!-- device:begin -->\n).*?(<!-- device:end -->)", lambda m: m.group(1) + block + m.group(2), doc, flags=re.S)
-    assert cnt == 1, "the marked device block of the profile note"
-    open(args.out, "w").write(doc)
+    write_marked_block(args.out, block)
 
 
 if __name__ == "__main__":

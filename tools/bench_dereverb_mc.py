@@ -22,16 +22,15 @@ tests/baseline_cases.py through the device's Freeverb (audiodenoiser_amd.reverb)
 """
 import argparse
 import json
-import math
 import os
-import re
-import statistics
 import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bench_common import time_ms, write_marked_block  # noqa: E402
 
 FMA_PER_S = 157.3e12 / 2           # peak fp32 vector rate of the MI355X, two flops per FMA
 RATE = 8000
@@ -43,29 +42,6 @@ ALONE_TAPS = 20
 CASES = (("one_hour", 30, 60 * RATE), ("one_recording_3s", 1, 3 * RATE))
 STEPS = ("kernel", "denoise", "torch")
 STEP_LIMIT_S = 300
-
-
-def time_ms(fn, warmup, groups, window_ms):
-    import torch
-    for _ in range(warmup):
-        fn()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    fn()
-    e1.record()
-    torch.cuda.synchronize()
-    steps = max(3, int(math.ceil(window_ms / max(e0.elapsed_time(e1), 1e-3))))
-    out = []
-    for _ in range(groups):
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(steps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / steps)
-    return {"ms": round(statistics.median(out), 4), "ms_min": round(min(out), 4), "ms_max": round(max(out), 4), "steps_per_window": steps}
 
 
 def torch_wpe_mc(spec, channels, taps, delay=3, iterations=3, loading=1e-3, power_floor=1e-3):
@@ -225,10 +201,7 @@ def main():
              f"{cell(clip, 'torch_wpe_mc_k16', 'ms')} ms ({ratio(clip, 'torch_wpe_mc_k16', 'adn_wpe_mc_k16')} x) |\n"
              f"| torch composition against `adn_wpe_mc`, max relative difference | {cell(hour, 'torch_wpe_mc_k16', 'max_rel_diff_from_adn_wpe_mc', '{:.3g}')} | "
              f"{cell(clip, 'torch_wpe_mc_k16', 'max_rel_diff_from_adn_wpe_mc', '{:.3g}')} |\n")
-    doc = open(args.out).read()
-    doc, cnt = re.subn(r"(<!-- device:begin -->\n).*?(<!-- device:end -->)", lambda m: m.group(1) + block + m.group(2), doc, flags=re.S)
-    assert cnt == 1, "the marked device block of the profile note"
-    open(args.out, "w").write(doc)
+    write_marked_block(args.out, block)
     return 0
 
 

@@ -25,13 +25,13 @@ import argparse
 import ctypes
 import json
 import os
-import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from bench_common import write_marked_block  # noqa: E402
 
 STEP = 32
 HBM_BPS = 8.0e12
@@ -243,11 +243,7 @@ def main():
         fmt = lambda v: " / ".join(f"{s:.2f}" for s in v)  # noqa: E731
         for r in (r for r in records if r["record"] == "si_sdr"):
             text += f"| {r['form']} | {fmt(r['device'])} | {fmt(r['restatement'])} |\n"
-        md = os.path.join(args.write, "bench_dereverb_mc_stream.md")
-        doc = open(md).read()
-        doc, cnt = re.subn(r"(<!-- device:begin -->\n).*?(<!-- device:end -->)", lambda m: m.group(1) + text + m.group(2), doc, flags=re.S)
-        assert cnt == 1
-        open(md, "w").write(doc)
+        write_marked_block(os.path.join(args.write, "bench_dereverb_mc_stream.md"), text)
 
 
 if __name__ == "__main__":

@@ -22,13 +22,13 @@ import argparse
 import ctypes
 import json
 import os
-import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+from bench_common import write_marked_block  # noqa: E402
 
 STEP = 32
 HBM_BPS = 8.0e12
@@ -207,11 +207,7 @@ def main():
                   "the clip of the host block:\n\n| path | device | float64 restatement |\n|---|---|---|\n"
                   f"| reverberant input | {rec['input']:.3f} dB | {r_in:.3f} dB |\n| stream | {rec['stream']:.3f} dB | {r_stream:.3f} dB |\n"
                   f"| stream, then the spectral gain | {rec['stream_gain']:.3f} dB | {r_gain:.3f} dB |\n")
-        md = os.path.join(args.write, "bench_dereverb_stream.md")
-        doc = open(md).read()
-        doc, cnt = re.subn(r"(<!-- device:begin -->\n).*?(<!-- device:end -->)", lambda m: m.group(1) + text + m.group(2), doc, flags=re.S)
-        assert cnt == 1
-        open(md, "w").write(doc)
+        write_marked_block(os.path.join(args.write, "bench_dereverb_stream.md"), text)
 
 
 if __name__ == "__main__":

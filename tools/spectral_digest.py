@@ -26,7 +26,15 @@ their lockstep stream forms at the working rate and at 48 kHz, and their pools w
 push_many / step / close -- block_frames 8, pushes of 1, 3, 8, 2 hops in turn.  Those lines use public names only, so the script
 also compares two versions of the PYTHON layer over one library: import the other commit's package first and run this file in
 that process (`runpy.run_path`; a package already imported wins over the path added below), ADN_LIBADN_PATH naming the one
-built library."""
+built library.
+
+Last comes the WPE family on random complex spectrograms (`wpe_family`; no STFT in front): 33 bins -- no multiple of the 4, 8 or 16
+bins of a workgroup -- and 3 clips or groups.  Offline: taps 4, 20, 24, 32 (the 16-, 16-, 32- and 64-lane kernels) and the joint
+form at (channels, taps) = (2, 8), (2, 5), (3, 7), (4, 8), (8, 4), (8, 1), (1, 5) (both block layouts, every lane count, the lane
+doubling at 8 channels, the forward to the single-channel kernel), each at 70 frames (two staged chunks, 70 % 4 != 0) and at 3
+(fewer than delay + taps).  Online: taps 1, 20, 32 and the joint form at (2, 16), (3, 7), (8, 4), (8, 1), (1, 20), two calls of 5
+then 9 frames with the state carried; d, the magnitudes and the state bytes are hashed.  `python tools/spectral_digest.py --wpe`
+prints the `operators` lines and that section alone."""
 import hashlib
 import os
 import sys
@@ -231,9 +239,48 @@ def operators(n_fft):
             lockstep(StreamDereverberator, f"StreamDereverberator {tag} gain={int(gain)}", a[:, :length * (rate or 8000) // 8000], hop,
                      rate, gain=gain)
         pooled(DereverbStreamPool, f"DereverbStreamPool {tag} gain={int(gain)}", feeds, hop, gain=gain)
+    # the three channels as ONE recording: the joint forms
+    say(f"Dereverberator joint {tag} L={length}",
+        Dereverberator(DEV, n_fft=n_fft, hop_length=hop, channels="joint").denoise(a[:, :length]))
+    for gain in (False, True):
+        for rate in (None, 48000):
+            lockstep(StreamDereverberator, f"StreamDereverberator channels=3 {tag} gain={int(gain)}",
+                     a[:, :length * (rate or 8000) // 8000], hop, rate, gain=gain, channels=3)
+
+
+def wpe_family():
+    """The four WPE operators on random complex spectrograms: see the module text."""
+    from audiodenoiser_amd.dereverb import WpeParams, WpeStreamParams, wpe, wpe_joint, wpe_online, wpe_online_joint
+    f, n = 33, 3
+
+    def spec(seed, rows, t):
+        return torch.view_as_complex((rand(seed, rows, t, f, 2) * 2 - 1).to(DEV))
+
+    for t in (70, 3):
+        for taps in (4, 20, 24, 32):
+            say(f"wpe F={f} clips={n} T={t} taps={taps}", *wpe(spec(4000 + t, n, t), WpeParams(taps=taps)))
+        for c, k in ((2, 8), (2, 5), (3, 7), (4, 8), (8, 4), (8, 1), (1, 5)):
+            say(f"wpe_joint F={f} groups={n} T={t} channels={c} taps={k}", *wpe_joint(spec(4100 + 10 * c + t, n * c, t), c, WpeParams(taps=k)))
+
+    def two_calls(what, run, x, p):                 # frames 0 .. 4, then 5 .. 13 on the state the first call left
+        d1, m1, state = run(x[:, :5].contiguous(), None, 0, p)
+        d2, m2, state = run(x[:, 5:].contiguous(), state, 5, p)
+        say(what, d1, m1, d2, m2, state)
+
+    for taps in (1, 20, 32):
+        two_calls(f"wpe_online F={f} rows={n} T=5+9 taps={taps}", wpe_online, spec(4200 + taps, n, 14), WpeStreamParams(taps=taps))
+    for c, k in ((2, 16), (3, 7), (8, 4), (8, 1), (1, 20)):
+        two_calls(f"wpe_online_joint F={f} groups={n} T=5+9 channels={c} taps={k}",
+                  lambda x, state, first, p, c=c: wpe_online_joint(x, c, state, first, p), spec(4300 + 10 * c + k, n * c, 14),
+                  WpeStreamParams(taps=k))
 
 
 def main():
+    if "--wpe" in sys.argv[1:]:
+        with torch.no_grad():
+            for n_fft in (64, 512):
+                operators(n_fft)
+            return wpe_family()
     model = UNet(1, 1).eval().to(DEV)              # the classes ask for one; fake_network runs in its place
     with torch.no_grad():
         for n_fft in N_FFTS:
@@ -242,6 +289,7 @@ def main():
             stream(model, n_fft)
             if n_fft in (64, 512):
                 operators(n_fft)
+        wpe_family()
 
 
 if __name__ == "__main__":
