@@ -1,0 +1,246 @@
+"""Mask-driven MVDR beamformer: the C microphones of a recording to ONE enhanced channel, no checkpoint needed.
+
+    from audiodenoiser_amd.beamform import Beamformer, MvdrParams, mvdr
+    bf = Beamformer()                                  # no model: the current ROCm device, 8 kHz, n_fft 512, hop 128
+    mono = bf.denoise(recording, sr=44100)             # (C, L) -> (L,); (N, C, L) -> (N, L); numpy -> numpy, tensor -> tensor
+    bf.denoise_file("room4ch.wav", "out.wav")          # the wav's channels are one recording; a mono wav is written
+    Beamformer(gain=True)                              # MVDR, then the Wiener gain of the spectral baseline on its result
+    Beamformer(wpe=True, gain=True)                    # joint WPE, then MVDR, then the gain
+    Beamformer(mask="model", model=unet)               # the mask from a trained U-Net: a neural beamformer
+    y, mag = mvdr(spec, mag_estimate, channels)        # the operator on spectrograms
+
+    python -m audiodenoiser_amd.beamform IN OUT [--reference CLEAN] [--ref-channel R] [--wpe] [--gain] [--model CKPT]
+
+The operator is DEFINED in ``include/adn.h`` ("beamform"; float64 restatement: ``tests/beamform_ref.py``;
+``csrc/beamform_kernels.hip``) and is unpinned against any package: the MVDR beamformer in Souden's form,
+``w = Phi_n^-1 Phi_s u / tr(Phi_n^-1 Phi_s)``, per (recording, bin), with the two spatial covariance matrices weighted by a
+time-frequency mask.  The mask comes from any per-channel magnitude estimate ``M`` of the wanted signal,
+``m_t = clip(sum_c M^2 / sum_c |X|^2, rho, 1 - rho)``.  ``Beamformer`` is ``Denoiser`` with this in the network's place:
+
+1. ``adn_stft_complex`` of every channel, ``T = 1 + L // hop`` frames;
+2. with ``wpe=True`` ``adn_wpe_mc`` on the channels jointly (``wpe_params=None``: ``taps = 32 // C``);
+3. the mask magnitudes: ``mask="spectral"`` runs ``adn_spectral_gain`` on every channel (``mask_params``); ``mask="model"`` runs the
+   given U-Net on every channel through the window plan of ``Denoiser`` (windows, network, stitch, clamped at zero);
+4. ``adn_mvdr``: one spectrogram per recording, and its magnitudes into a zeroed ``(n, 1, F, max(T, 16))`` buffer;
+5. with ``gain=True`` ``adn_spectral_gain`` on that spectrogram writes the magnitudes instead (``gain_params``);
+6. ``adn_denoise_resynth`` with one window per recording and the phase of the beamformer's output.
+
+The rate handling is ``Denoiser``'s: resample in, resample out, the input's sample count.  The defaults (reference channel 0,
+loading 1e-3, mask floor 1e-3) are the values of the host prototype (``profiles/bench_beamform.md``); they were not tuned by ear.
+
+What is NOT here: streaming or recursive beamforming, GEV or rank-one variants, WPD, more than 8 channels.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes
+import dataclasses
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._host import check_stft_plan, current_stream, model_device, rocm_device, run_files, stage
+from .baseline import SpectralParams, _spectral_params, spectral_gain
+from .denoise import Denoiser
+from .dereverb import WpeParams, _check_channels, _joint_params, _mag_buffer, _need_cells, _spec_dims, wpe_joint
+from .griffin_lim import stft_complex
+from .resample import _resample_device
+from .wav import read_wav, write_wav
+
+__all__ = ["MvdrParams", "mvdr", "Beamformer"]
+
+
+@dataclasses.dataclass(frozen=True)
+class MvdrParams:
+    """``adn_mvdr_params`` of ``include/adn.h`` with its defaults and its legal ranges (``ref_channel < channels`` is the call's)."""
+    ref_channel: int = 0
+    loading: float = 1e-3
+    mask_floor: float = 1e-3
+
+    def __post_init__(self):
+        v = self.ref_channel
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 7:
+            raise ValueError("MvdrParams: need an integer 0 <= ref_channel <= 7")
+        for name in ("loading", "mask_floor"):
+            if math.isnan(float(getattr(self, name))):
+                raise ValueError(f"MvdrParams: {name} is NaN")
+        if not 1e-6 <= float(self.loading) <= 1.0:
+            raise ValueError("MvdrParams: need 1e-6 <= loading <= 1")
+        if not 1e-6 <= float(self.mask_floor) <= 0.25:
+            raise ValueError("MvdrParams: need 1e-6 <= mask_floor <= 0.25")
+
+    def to_struct(self) -> "_lib.MvdrParamsStruct":
+        return _lib.MvdrParamsStruct(int(self.ref_channel), float(self.loading), float(self.mask_floor))
+
+
+def _mvdr_params(who, params, channels):
+    """The parameters of a call on ``channels`` channels: a ``MvdrParams`` whose reference channel exists, None for the defaults."""
+    _check_channels(who, channels)
+    if params is None:
+        return None
+    if not isinstance(params, MvdrParams):
+        raise TypeError(f"{who}: params must be a MvdrParams")
+    if params.ref_channel >= channels:
+        raise ValueError(f"{who}: need ref_channel < channels (ref_channel {params.ref_channel}, channels {channels})")
+    return params
+
+
+def mvdr(spec: torch.Tensor, mag: torch.Tensor, channels: int, params: MvdrParams = None, mag_out: torch.Tensor = None):
+    """``adn_mvdr`` on the current stream.  ``spec``: complex64 ``(n_groups * channels, T, F)`` on a ROCm device, the ``channels``
+    channels of a recording consecutive clips (``stft_complex`` of an ``(n_groups * channels, L)`` batch).  ``mag``: float32
+    ``(n_groups * channels, 1, F, mag_width)``, ``mag_width >= T``, a magnitude estimate of the wanted signal per channel whose
+    columns ``[0, T)`` are read -- what ``spectral_gain``, ``wpe_joint`` and the U-Net return.  ``mag_out``: float32
+    ``(n_groups, 1, F, width)``, ``width >= T``, whose columns ``[0, T)`` are written and nothing else; None allocates
+    ``(n_groups, 1, F, T)``.  The workspace is allocated here.  Returns ``(spec_out, mag_out)``, ``spec_out`` a new complex64
+    ``(n_groups, T, F)``.  ValueError, before any device call, if the leading dimension is no multiple of ``channels``, the
+    reference channel does not exist, or a shape, dtype or device does not fit."""
+    who = "mvdr"
+    params = _mvdr_params(who, params, channels)
+    if isinstance(spec, torch.Tensor) and spec.dim() == 3 and spec.shape[0] % channels:
+        raise ValueError(f"{who}: the leading dimension {spec.shape[0]} is not a multiple of channels = {channels}")
+    n, t, f = _spec_dims(who, "clip", spec)
+    _need_cells(who, "clip", n, t, f)
+    dev = spec.device
+    if (not isinstance(mag, torch.Tensor) or not mag.is_cuda or mag.device != dev or mag.dtype != torch.float32 or mag.dim() != 4
+            or tuple(mag.shape[:3]) != (n, 1, f) or mag.shape[3] < t):
+        raise ValueError(f"{who}: mag must be a (n_clips, 1, n_bins, mag_width >= n_frames) float32 tensor on spec's device")
+    groups = n // channels
+    mag_out = _mag_buffer(who, "group", mag_out, groups, t, f, dev)
+    if mag_out.shape[3] < t:
+        raise ValueError(f"{who}: mag_out must be at least n_frames wide")
+    s, m = torch.view_as_real(spec.contiguous()), mag.contiguous()
+    out = torch.empty((groups, t, f, 2), dtype=torch.float32, device=dev)
+    p = ctypes.byref(params.to_struct()) if params is not None else None
+    L = _lib.load()
+    need = ctypes.c_size_t(0)
+    _lib.check(L.adn_mvdr_workspace_bytes(groups, channels, t, f, p, ctypes.byref(need)), "adn_mvdr_workspace_bytes")
+    ws = torch.empty((need.value,), dtype=torch.uint8, device=dev) if need.value else None
+    with torch.cuda.device(dev):
+        _lib.check(L.adn_mvdr(s.data_ptr(), m.data_ptr(), int(m.shape[3]), groups, channels, t, f, p,
+                              ws.data_ptr() if ws is not None else None, need.value, out.data_ptr(), mag_out.data_ptr(),
+                              int(mag_out.shape[3]), current_stream(dev)), "adn_mvdr")
+    return torch.view_as_complex(out), mag_out
+
+
+class Beamformer(Denoiser):
+    """``Denoiser`` with the beamformer in the network's place: ``(C, L)`` is ONE recording of ``C <= 8`` microphones and comes
+    back as ``(L,)``, ``(N, C, L)`` a batch of recordings that comes back as ``(N, L)``; ``(L,)`` is one channel and goes
+    through the same pipeline.  ``mask="spectral"``: the spectral baseline's gain of every channel drives the mask
+    (``mask_params``); ``mask="model"``: ``model``, a ``UNet(1, 1)`` in eval mode on a ROCm device, does.  ``wpe=True`` runs joint
+    WPE first (``wpe_params=None``: ``taps = 32 // C``), ``gain=True`` the spectral gain on the result (``gain_params``).  A
+    ``params`` whose reference channel the input does not have is a ValueError of the call."""
+
+    def __init__(self, device=None, sample_rate: int = 8000, n_fft: int = 512, hop_length: int = 128, params: MvdrParams = None,
+                 mask: str = "spectral", mask_params: SpectralParams = None, wpe: bool = False, wpe_params: WpeParams = None,
+                 gain: bool = False, gain_params: SpectralParams = None, model=None):
+        check_stft_plan("Beamformer", n_fft, hop_length, sample_rate)
+        if params is not None and not isinstance(params, MvdrParams):
+            raise TypeError("Beamformer: params must be a MvdrParams")
+        if wpe_params is not None and not isinstance(wpe_params, WpeParams):
+            raise TypeError("Beamformer: wpe_params must be a WpeParams")
+        if mask not in ("spectral", "model"):
+            raise ValueError("Beamformer: mask must be 'spectral' or 'model'")
+        if (mask == "model") != (model is not None):
+            raise ValueError("Beamformer: mask='model' needs a model, and a model needs mask='model'")
+        self.params, self.mask = params, mask
+        self.mask_params = _spectral_params("Beamformer", mask_params, "mask_params")
+        self.gain_params = _spectral_params("Beamformer", gain_params, "gain_params")
+        self.wpe, self.wpe_params, self.gain = bool(wpe), wpe_params, bool(gain)
+        self.model = None                                    # the beamformer itself has no window plan; the mask network has its own
+        self._net = None
+        if model is not None:
+            dev = model_device("Beamformer", model)
+            if device is not None and torch.device(device).type != "cuda":
+                raise RuntimeError("Beamformer: the device must be a ROCm device; there is no CPU path")
+            self._net = Denoiser(model, sample_rate, n_fft, hop_length)
+        else:
+            dev = rocm_device("Beamformer", device)
+        self._setup(dev, sample_rate, n_fft, hop_length, "beamformed")
+
+    def mask_magnitudes(self, spec: torch.Tensor) -> torch.Tensor:
+        """complex64 ``(n_clips, T, F)`` -> the magnitude estimate ``(n_clips, 1, F, T)`` that drives the mask, per channel."""
+        if self._net is None:
+            return spectral_gain(spec, self.mask_params)[0]
+        n, t, _ = spec.shape
+        return self._net.stitch(self._net.network(self._net.windows(spec)), n, t, clamp=True)[:, None]
+
+    def _core(self, x: torch.Tensor, rand, channels: int = 1) -> torch.Tensor:
+        """``x`` (n_groups * channels, L) at the working rate, ``channels`` consecutive clips one recording -> (n_groups, L)."""
+        length = x.shape[1]
+        params = _mvdr_params("Beamformer", self.params, channels)
+        spec = stft_complex(x, self.n_fft, self.hop_length)
+        n, t, f = spec.shape
+        if self.wpe:
+            spec, _ = wpe_joint(spec, channels, _joint_params("Beamformer", self.wpe_params, channels))
+        y = torch.zeros((n // channels, 1, f, max(t, 16)), dtype=torch.float32, device=x.device)
+        out, _ = mvdr(spec, self.mask_magnitudes(spec), channels, params, y)
+        if self.gain:
+            spectral_gain(out, self.gain_params, None, y, 0)
+        return self._resynth(y, out, length, int(y.shape[3]), 0)
+
+    def denoise(self, audio, sr=None, rand=None):
+        """``audio`` float32 at rate ``sr`` (default: the working rate): ``(C, L)`` -> ``(L,)``, ``(N, C, L)`` -> ``(N, L)``,
+        ``(L,)`` -> ``(L,)``, at the same rate and sample count.  numpy in -> numpy out, tensor on a ROCm device in -> tensor
+        there out; everything between the input copy and the output copy runs on the device on the current stream."""
+        a, is_np = stage("Beamformer.denoise", audio, self.device)
+        if a.dim() not in (1, 2, 3) or min(a.shape) < 1:
+            raise ValueError("Beamformer.denoise: audio must be (L,), (C, L) or (N, C, L) with at least one sample")
+        channels = 1 if a.dim() == 1 else int(a.shape[-2])
+        _mvdr_params("Beamformer.denoise", self.params, channels)
+        length = int(a.shape[-1])
+        x = a.reshape(-1, length).contiguous()
+        rate = self.sample_rate if sr is None else int(sr)
+        if rate != self.sample_rate:
+            low = self._core(_resample_device(x, rate, self.sample_rate), rand, channels)
+            up = _resample_device(low, self.sample_rate, rate)
+            if up.shape[1] >= length:
+                out = up[:, :length].contiguous()
+            else:
+                out = torch.zeros((up.shape[0], length), dtype=torch.float32, device=x.device)
+                out[:, :up.shape[1]] = up
+        else:
+            out = self._core(x, rand, channels)
+        out = out if a.dim() == 3 else out[0]
+        return out.cpu().numpy() if is_np else out
+
+    def denoise_file(self, src, dst, subtype: str = "PCM_16"):
+        """``read_wav(src)``, its channels one recording -> ``denoise`` at the file's rate -> a mono ``write_wav(dst)``.  Returns
+        ``(n_samples, sample_rate)``."""
+        audio, rate = read_wav(src, mono=False)              # (L, channels)
+        out = self.denoise(np.ascontiguousarray(audio.T), sr=rate)
+        write_wav(dst, out, rate, subtype)
+        return int(audio.shape[0]), int(rate)
+
+
+def main(argv=None) -> int:
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m audiodenoiser_amd.beamform",
+                                 description="Beamform a multichannel wav file, or a folder of them, to mono (mask-driven MVDR).")
+    ap.add_argument("src", metavar="IN", help="a wav file whose channels are the microphones, or a folder of such files")
+    ap.add_argument("dst", metavar="OUT", help="the mono wav file to write, or the folder to write into")
+    ap.add_argument("--reference", metavar="CLEAN", default=None,
+                    help="the clean wav of IN (or a folder with IN's file names): print one JSON line of metrics per file")
+    ap.add_argument("--ref-channel", type=int, default=MvdrParams.ref_channel, help="the microphone the output is aligned to, 0 ... 7")
+    ap.add_argument("--wpe", action="store_true", help="run joint WPE (taps = 32 // channels) before the beamformer")
+    ap.add_argument("--gain", action="store_true", help="run the spectral baseline's Wiener gain on the beamformer's result")
+    ap.add_argument("--model", metavar="CKPT", default=None,
+                    help="take the mask from this U-Net checkpoint instead of the spectral gain (the state_dict of UNet(1, 1))")
+    args = ap.parse_args(argv)
+    try:
+        params = MvdrParams(ref_channel=args.ref_channel)
+    except ValueError as exc:
+        ap.error(str(exc))
+    model = None
+    if args.model is not None:
+        from .denoise import _load_model
+        model = _load_model(args.model, "f32", _lib.staging_device())
+    bf = Beamformer(params=params, mask="model" if model is not None else "spectral", wpe=args.wpe, gain=args.gain, model=model)
+    try:
+        return run_files(bf, args.src, args.dst, args.reference)
+    except ValueError as exc:
+        ap.error(str(exc))
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -664,6 +664,72 @@ int adn_wpe_mc(const float *spec, int n_groups, int channels, int n_frames, int 
                n_frames, n_bins, params, workspace, workspace_bytes, spec_out, mag_out, width, stream);
 }
 
+/* ---- beamformer: mask-driven MVDR of the channels of a recording (adn.h, "beamform") ----------------------------- */
+// The sizing function and the operator share one validation: `who` is the name in front of every message.
+static int mvdr_shape(const char *who, int n_groups, int channels, int n_frames, int n_bins, const adn_mvdr_params *params,
+                      adn::MvdrConsts *k)
+{
+    const std::string w(who);
+    if (n_groups < 1 || n_frames < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, w + ": n_groups, n_frames and n_bins must be >= 1");
+    if (channels < 1 || channels > 8) return fail(ADN_ERR_INVALID, w + ": need 1 <= channels <= 8");
+    if ((long)n_groups * channels > 0x7fffffffL) return fail(ADN_ERR_INVALID, w + ": need n_groups * channels < 2^31");
+    const adn_mvdr_params defaults = {0, 1e-3f, 1e-3f};
+    const adn_mvdr_params p = params ? *params : defaults;
+    if (p.ref_channel < 0 || p.ref_channel >= channels) return fail(ADN_ERR_INVALID, w + ": need 0 <= ref_channel < channels");
+    // written so that a NaN fails every test
+    if (!(p.loading >= 1e-6f && p.loading <= 1.f)) return fail(ADN_ERR_INVALID, w + ": need 1e-6 <= loading <= 1");
+    if (!(p.mask_floor >= 1e-6f && p.mask_floor <= 0.25f)) return fail(ADN_ERR_INVALID, w + ": need 1e-6 <= mask_floor <= 0.25");
+    k->ref = p.ref_channel;
+    k->loading = p.loading;
+    k->rho = p.mask_floor;
+    k->one_minus_rho = 1.f - p.mask_floor;
+    if (adn::mvdr_grid(n_groups, channels, n_bins) > 0x7fffffffL)
+        return fail(ADN_ERR_INVALID, w + ": grid too large (n_groups x ceil(n_bins / bins per workgroup) >= 2^31)");
+    return ADN_OK;
+}
+
+int adn_mvdr_workspace_bytes(int n_groups, int channels, int n_frames, int n_bins, const adn_mvdr_params *params, size_t *bytes)
+{
+    adn::MvdrConsts k;
+    if (!bytes) return fail(ADN_ERR_INVALID, "adn_mvdr_workspace_bytes: null pointer");
+    ADN_TRY(mvdr_shape("adn_mvdr_workspace_bytes", n_groups, channels, n_frames, n_bins, params, &k));
+    *bytes = 0;                                          // the covariances, the factor and the filter of a (group, bin) never leave the chip
+    return ADN_OK;
+}
+
+int adn_mvdr(const float *spec, const float *mag, int mag_width, int n_groups, int channels, int n_frames, int n_bins,
+             const adn_mvdr_params *params, void *workspace, size_t workspace_bytes, float *spec_out, float *mag_out, int width,
+             void *stream)
+{
+    const std::string w("adn_mvdr");
+    adn::MvdrConsts k;
+    if (!spec || !mag || !spec_out) return fail(ADN_ERR_INVALID, w + ": null pointer (spec, mag, spec_out)");
+    ADN_TRY(mvdr_shape("adn_mvdr", n_groups, channels, n_frames, n_bins, params, &k));
+    if (mag_width < n_frames) return fail(ADN_ERR_INVALID, w + ": need mag_width >= n_frames");
+    if (mag_out && width < n_frames) return fail(ADN_ERR_INVALID, w + ": need width >= n_frames");
+    if (!aligned_to(spec, 8) || !aligned_to(spec_out, 8) || !aligned_to(mag, 4) || !aligned_to(mag_out, 4))
+        return fail(ADN_ERR_INVALID, w + ": spec and spec_out must be 8-byte aligned, mag and mag_out 4-byte aligned");
+    const size_t need = 0;                               // what adn_mvdr_workspace_bytes reports
+    if (workspace_bytes < need || (need && !workspace))
+        return fail(ADN_ERR_WORKSPACE, w + ": workspace smaller than adn_mvdr_workspace_bytes");
+    const size_t cells = (size_t)n_groups * (size_t)n_bins;
+    const auto overlap = [](const void *p, size_t np, const void *q, size_t nq) {
+        const char *a = reinterpret_cast<const char *>(p), *b = reinterpret_cast<const char *>(q);
+        return a < b + nq && b < a + np;
+    };
+    const size_t in_spec = cells * channels * n_frames * 2 * sizeof(float), out_spec = cells * n_frames * 2 * sizeof(float);
+    const size_t in_mag = cells * channels * mag_width * sizeof(float), out_mag = mag_out ? cells * width * sizeof(float) : 0;
+    if (overlap(spec, in_spec, spec_out, out_spec) || overlap(mag, in_mag, spec_out, out_spec))
+        return fail(ADN_ERR_INVALID, w + ": spec_out may not overlap spec or mag");
+    if (mag_out && (overlap(spec, in_spec, mag_out, out_mag) || overlap(mag, in_mag, mag_out, out_mag) ||
+                    overlap(spec_out, out_spec, mag_out, out_mag)))
+        return fail(ADN_ERR_INVALID, w + ": mag_out may not overlap spec, mag or spec_out");
+    ADN_LAUNCH(adn::launch_mvdr(spec, mag, mag_width, n_groups, channels, n_frames, n_bins, k, spec_out, mag_out, width,
+                                static_cast<hipStream_t>(stream)),
+               "adn_mvdr");
+    return ADN_OK;
+}
+
 /* ---- streaming denoiser: plan, state, analysis, emit (adn.h, "stream") ------------------------------------------- */
 static const char *stream_plan_text = ": need a power-of-two n_fft in [64, 4096], 1 <= hop <= n_fft / 4, window >= 16, block >= 1, "
                                       "lookahead >= 0, block + lookahead <= window, n_streams >= 1 and 1 <= max_steps <= 65536";

@@ -481,6 +481,18 @@ struct WpeConsts {
 long wpe_grid(int n_groups, int C, int F, int K);
 hipError_t launch_wpe(const void *spec, int n_groups, int C, int T, int F, const WpeConsts &k, void *spec_out, float *mag_out,
                       int width, hipStream_t st);
+// Beamformer (beamform_kernels.hip; adn.h, "beamform"): mask-driven MVDR of the C consecutive clips of a group, 1 <= C <= 8, for every
+// (group, bin) of a frame-major float2 spectrogram [group * C + channel][frame][F] and bin-major mask magnitudes
+// [group * C + channel][F][mag_width], in one launch without a workspace.  spec_out is [group][frame][F] float2; mag_out (may be
+// null) is [group][F][width], columns [0, T) written.  MvdrConsts: the parameters and 1 - mask_floor, derived once per call on the
+// host in fp32.  mvdr_grid: the workgroups of the launch, n_groups x ceil(F / (64 / lanes per bin)), 4 lanes up to C = 4, 8 beyond.
+struct MvdrConsts {
+    int ref;
+    float loading, rho, one_minus_rho;
+};
+long mvdr_grid(int n_groups, int C, int F);
+hipError_t launch_mvdr(const void *spec, const float *mag, int mag_width, int n_groups, int C, int T, int F, const MvdrConsts &k,
+                       void *spec_out, float *mag_out, int width, hipStream_t st);
 // Streaming denoiser (stream_kernels.hip; adn.h, "stream").  StreamGeom: the plan and the layout of the state buffer of one batch
 // of streams, in floats (sections X, mag, hist, tail; `total` floats in all); stream_geom is false outside the limits of adn.h.
 // StreamCall: what one call of n_steps steps from step `first` covers, derived from the step index alone (stream_call):

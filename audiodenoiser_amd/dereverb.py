@@ -53,7 +53,8 @@ variance shared by the channels; ``adn_wpe_mc_stream`` stands in ``adn_wpe_strea
 ``wpe_online_joint`` is the recursion on spectrograms.
 
 What is NOT here: multichannel streams in ``DereverbStreamPool`` (it stays single-channel), look-ahead or iterated online
-variants, beamforming, any tuning of the defaults by ear.  There is no CPU path.
+variants, any tuning of the defaults by ear.  Combining the channels into one is ``audiodenoiser_amd.beamform`` (``Beamformer``,
+``wpe=True`` puts ``wpe_joint`` in front of it).  There is no CPU path.
 """
 from __future__ import annotations
 

@@ -33,7 +33,7 @@
 
 #include <stddef.h>
 
-/* The 73 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 75 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -747,7 +747,8 @@ ADN_API int adn_wpe(const float *spec, int n_clips, int n_frames, int n_bins, co
  * Limits (ADN_ERR_INVALID before any launch): as adn_wpe, with n_groups in n_clips' place, and n_groups * channels < 2^31.
  * ADN_ERR_WORKSPACE: workspace_bytes below adn_wpe_mc_workspace_bytes.  Element offsets are 64-bit.
  * For audio that is still arriving, the recursive joint form: "dereverb stream multichannel", below.
- * Not here: beamforming; N > 32; any tuning by ear. */
+ * Combining the channels into one: "beamform", below.
+ * Not here: N > 32; any tuning by ear. */
 ADN_API int adn_wpe_mc_workspace_bytes(int n_groups, int channels, int n_frames, int n_bins, const adn_wpe_params *params,
                                        size_t *bytes);
 ADN_API int adn_wpe_mc(const float *spec, int n_groups, int channels, int n_frames, int n_bins, const adn_wpe_params *params,
@@ -913,7 +914,8 @@ ADN_API int adn_wpe_stream_pool(void *pool_state, size_t pool_state_bytes, int n
  * Limits (ADN_ERR_INVALID before any launch; a refused call writes nothing): those of adn_wpe_online with n_groups in n_rows'
  * place, and n_groups * channels < 2^31; everything adn_wpe_stream refuses, and n_streams % channels != 0.  ADN_ERR_WORKSPACE: a
  * state below adn_wpe_mc_stream_state_bytes.  Element offsets are 64-bit.
- * Not here: the stream pool with multichannel streams; look-ahead; beamforming; N > 32; any tuning by ear. */
+ * Combining the channels into one (offline only): the next section, "beamform".
+ * Not here: the stream pool with multichannel streams; look-ahead; N > 32; any tuning by ear. */
 ADN_API int adn_wpe_mc_stream_state_bytes(int n_slots, int channels, int n_bins, const adn_wpe_stream_params *params, size_t *bytes);
 ADN_API int adn_wpe_mc_online(const float *spec, int n_groups, int channels, int n_frames, int n_bins, long first_frame,
                               const adn_wpe_stream_params *params, void *state, size_t state_bytes, int n_slots, float *spec_out,
@@ -922,6 +924,72 @@ ADN_API int adn_wpe_mc_stream(void *stream_state, size_t stream_state_bytes, flo
                               int n_steps, long final_length, int n_fft, int hop, int window, int block, int lookahead,
                               int max_steps, const adn_wpe_stream_params *params, void *wpe_state, size_t wpe_state_bytes,
                               void *stream);
+
+/* ---- beamform: mask-driven MVDR, the channels of a recording to one enhanced channel ---------------------------------------------------
+ * No reference counterpart and no checkpoint.  The library DEFINES the operator below (float64 restatement:
+ * tests/beamform_ref.py); it is UNPINNED against any package.  It is the MVDR beamformer in Souden's form (Souden, Benesty and
+ * Affes 2010), w = Phi_n^-1 Phi_s u / tr(Phi_n^-1 Phi_s), with the two spatial covariance matrices weighted by a time-frequency
+ * mask, and the mask taken from ANY per-channel magnitude estimate of the wanted signal: the Wiener gain of "baseline"
+ * (adn_spectral_gain), the magnitudes adn_wpe_mc returns, or the U-Net's output -- all three write the layout read here.
+ * Not validated: the defaults are the values of the host prototype (profiles/bench_beamform.md); they were not tuned by ear.
+ *
+ * A group is the C channels of one recording, 1 <= C <= 8; every (group, bin) is independent.  X_{t,c} is the complex STFT of
+ * channel c at frame t, M_{t,c} >= 0 the magnitude estimate.  In fp32, with the rounding rules of "dereverb" (the weight applied
+ * once as m_t X_{t,r}, each component rounded; complex multiply-adds as two fmaf per component; max(x, c) as `x < c ? c : x` and
+ * min(x, c) as `x > c ? c : x`, so a NaN x stays NaN; correctly rounded division and square root; no fp contraction):
+ *   p_{t,c} = fmaf(re, re, im * im)
+ *   s_t = sum_c M_{t,c}^2,   q_t = sum_c p_{t,c}                               (c ascending from 0; each square rounded, then added)
+ *   m_t = q_t > 0 ? min(max(s_t / q_t, rho), 1 - rho) : rho,   n_t = 1 - m_t   (1 - rho rounded once)
+ *   Phi_s[r][k] = sum_t (m_t X_{t,r}) conj(X_{t,k}),   Phi_n likewise with n_t (r >= k; the upper triangle is the conjugate and
+ *                                                                              the imaginary part of the diagonal is dropped)
+ *   A = Phi_n + ((delta tr(Phi_n)) / C + 1e-30) I                              (tr over r ascending; the diagonal is real)
+ *   A = L L^H once; for every column c: L y = Phi_s[:, c], L^H G_c = y         (inner sums in "dereverb"'s order)
+ *   tau = max(sum_c Re G_cc, 1e-30)                                            (c ascending)
+ *   w_c = G[c][ref] / tau                                                      (row c of column ref, each component divided)
+ *   Y_t = sum_c conj(w_c) X_{t,c}                                              (c ascending from 0; re: X.x w.x, then X.y w.y;
+ *                                                                               im: -X.x w.y, then X.y w.x)
+ *   optional M^out_t = sqrtf(fmaf(Yre, Yre, Yim * Yim))
+ * The sums over t run frame after frame from t = 0, (m_t X_{t,r}) conj(X_{t,k}) accumulated as re: u.x v.x, then u.y v.y; im:
+ * u.y v.x, then -u.x v.y ("dereverb"'s order).  No order depends on the batch or on which bins share the call.  The clip of the
+ * mask to [rho, 1 - rho] is part of the definition: it keeps Phi_n from vanishing on a clean recording and Phi_s from vanishing
+ * on a noise-only bin, so no input with energy gives a degenerate solve.
+ * Parameters (adn_mvdr_params; NULL = the defaults): ref_channel 0, loading delta 1e-3, mask_floor rho 1e-3 -- the values of the
+ * host prototype, not tuned by ear.  Legal (ADN_ERR_INVALID otherwise, before any launch, the message starts "adn_mvdr" and names
+ * the field; a NaN is illegal): 0 <= ref_channel < channels; 1e-6 <= loading <= 1; 1e-6 <= mask_floor <= 0.25.
+ * Consequences: with C = 1, G is real, w = G / G = 1 and the output equals X as values (a signed zero may differ) in every bin whose
+ * G is at least 1e-30; an all-zero group gives zeros (A = 1e-30 I, Phi_s = 0, w = 0); a non-finite value is confined to its own
+ * (group, bin), whose content is then unspecified.  NOT a consequence: invariance under a common scale of M -- n_t = 1 - m_t does
+ * not scale with m_t, so even a power of two changes the result (the restatement confirms that it does).
+ *
+ * What is pinned.  The result is bounded against the float64 restatement (tests/test_gpu_beamform.py: per group
+ * max |Y - Y64| <= 4 FLOOR max |Y64|, FLOOR the error of the same statements run in fp32 on the host).  mag_out is bit for bit
+ * sqrtf(fmaf(re, re, im * im)) of spec_out.  Pinned bit for bit: two calls give the same result; a group gives the same bits alone
+ * or in any batch; a bin gives the same bits whichever other bins are in the call; mag_width and width do not enter.  NOT pinned: the
+ * bits against numpy; the bits under a permutation of the channels.  Deterministic: no atomics.
+ *
+ * Layouts: spec is (n_groups * channels, n_frames, n_bins, 2) fp32, the C channels of a group consecutive clips -- adn_wpe_mc's
+ * layout, what adn_stft_complex writes for an (n_groups * C, L) batch -- 8-byte aligned.  mag is (n_groups * channels, 1, n_bins,
+ * mag_width) fp32 with mag_width >= n_frames, columns [0, n_frames) read: what adn_spectral_gain, adn_wpe_mc and the U-Net write.
+ * spec_out is (n_groups, n_frames, n_bins, 2), 8-byte aligned.  mag_out may be NULL; otherwise it is (n_groups, 1, n_bins, width)
+ * with width >= n_frames, the layout adn_denoise_resynth reads.  No output may overlap an input or the other output.  The call
+ * writes columns [0, n_frames) of mag_out, all of spec_out and not one byte else.  It may use the workspace and only the
+ * workspace; adn_mvdr_workspace_bytes reports 0 today (the covariances, the factor and the filter stay on chip), and workspace may
+ * then be NULL.
+ * Cost: one launch, n_groups x ceil(n_bins / B) workgroups of one wave, B = 16 bins up to C = 4 and 8 beyond; the frames pass through LDS in
+ * chunks, twice (the sums, then the filter), so no limit on n_frames comes from LDS.  Per (group, bin) 4 T (C (C + 1) + C) FMAs.
+ * No atomics, no constant table (a capture may hold a first call); nothing blocks or allocates.
+ * Limits (ADN_ERR_INVALID before any launch; a refused call writes nothing): NULL or misaligned spec / mag / spec_out / mag_out;
+ * n_groups, n_frames, n_bins >= 1; n_groups * channels < 2^31; mag_width >= n_frames; width >= n_frames with a mag_out; overlap;
+ * launch grid < 2^31 workgroups; the parameters as above.  ADN_ERR_WORKSPACE: workspace_bytes below adn_mvdr_workspace_bytes.
+ * Element offsets are 64-bit.
+ * Not here: streaming or recursive beamforming; GEV or rank-one variants; WPD (the joint convolutional beamformer); more than 8
+ * channels; any tuning by ear. */
+typedef struct adn_mvdr_params { int ref_channel; float loading, mask_floor; } adn_mvdr_params;
+ADN_API int adn_mvdr_workspace_bytes(int n_groups, int channels, int n_frames, int n_bins, const adn_mvdr_params *params,
+                                     size_t *bytes);
+ADN_API int adn_mvdr(const float *spec, const float *mag, int mag_width, int n_groups, int channels, int n_frames, int n_bins,
+                     const adn_mvdr_params *params, void *workspace, size_t workspace_bytes, float *spec_out, float *mag_out,
+                     int width, void *stream);
 
 /* ---- environment switches -------------------------------------------------------------------------------------------------
  * Read ONCE, when a U-Net handle is created (never per call).  None is needed in production: the defaults are the measured best
