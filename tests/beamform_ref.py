@@ -67,8 +67,9 @@ def mask(specs, mags, rho, dtype=np.float64):
     return m
 
 
-def mvdr(specs, mags, params=None, dtype=np.float64, with_filter=False):
-    """specs (C, T, F) complex, mags (C, F, width >= T) real -> Y (T, F) complex in `dtype`'s precision; with_filter: also w (F, C)."""
+def mvdr(specs, mags, params=None, dtype=np.float64, with_filter=False, order="pairwise"):
+    """specs (C, T, F) complex, mags (C, F, width >= T) real -> Y (T, F) complex in `dtype`'s precision; with_filter: also w (F, C).
+    order: how the sums over t of both covariances are formed, as in dereverb_ref.wpe."""
     specs = np.asarray(specs)
     C = specs.shape[0]
     p = dict(DEFAULTS)
@@ -90,7 +91,7 @@ def mvdr(specs, mags, params=None, dtype=np.float64, with_filter=False):
             for r in range(C):
                 u = _weighted(X[r], wgt, ct)                                      # m_t X_{t,r}: each component rounded
                 for k in range(r + 1):
-                    P[:, r, k] = (u * np.conj(X[k])).sum(axis=-1, dtype=ct)
+                    P[:, r, k] = dr._sum_t(u * np.conj(X[k]), ct, order)
                     P[:, k, r] = np.conj(P[:, r, k])
                 P[:, r, r] = P[:, r, r].real                                      # the diagonal's imaginary part is dropped
             phi.append(P)

@@ -34,8 +34,9 @@ def check_params(p, channels):
         raise ValueError("channels * taps")
 
 
-def wpe_mc(specs, params=None, dtype=np.float64, with_taps=False):
-    """specs (C, T, F) complex -> d (C, T, F) complex in `dtype`'s precision; with_taps: also G (F, N, C)."""
+def wpe_mc(specs, params=None, dtype=np.float64, with_taps=False, order="pairwise"):
+    """specs (C, T, F) complex -> d (C, T, F) complex in `dtype`'s precision; with_taps: also G (F, N, C).  order: how every sum
+    over t is formed, as in dereverb_ref.wpe."""
     specs = np.asarray(specs)
     C = specs.shape[0]
     p = defaults(C) if 1 <= C <= MAX_CHANNELS else dict(dr.DEFAULTS)
@@ -52,7 +53,7 @@ def wpe_mc(specs, params=None, dtype=np.float64, with_taps=False):
     with np.errstate(all="ignore"):
         total = np.zeros(F, dt)
         for c in range(C):                                                        # channels ascending
-            total = total + dr._power(X[c], dt).sum(axis=-1, dtype=dt)
+            total = total + dr._sum_t(dr._power(X[c], dt), dt, order)
         phi = dr._max(rho * total / dt(T * C), tiny)
         # past[c K + j][:, t] = X_{t-D-j, c}, zero before frame 0: the stacked vector, channel-major, the lag ascending
         past = np.zeros((N, F, T), ct)
@@ -73,10 +74,10 @@ def wpe_mc(specs, params=None, dtype=np.float64, with_taps=False):
             P = np.zeros((F, N, C), ct)
             for r in range(N):
                 for q in range(r + 1):
-                    R[:, r, q] = (u[r] * np.conj(past[q])).sum(axis=-1, dtype=ct)
+                    R[:, r, q] = dr._sum_t(u[r] * np.conj(past[q]), ct, order)
                     R[:, q, r] = np.conj(R[:, r, q])
                 for c in range(C):
-                    P[:, r, c] = (u[r] * np.conj(X[c])).sum(axis=-1, dtype=ct)
+                    P[:, r, c] = dr._sum_t(u[r] * np.conj(X[c]), ct, order)
             tr = np.zeros(F, dt)
             for r in range(N):
                 tr = tr + R[:, r, r].real

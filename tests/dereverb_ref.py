@@ -74,8 +74,19 @@ def _cholesky_solve(A, P):
     return g
 
 
-def wpe(spec, params=None, dtype=np.float64, with_taps=False):
-    """spec (T, F) complex -> d (T, F) complex in `dtype`'s precision (complex128 / complex64); with_taps: also g (F, K)."""
+def _sum_t(x, dtype, order):
+    """The sum over t (the last axis) in `dtype`: "pairwise" is numpy's sum of a contiguous row; "sequential" adds frame after frame
+    from t = 0, the order include/adn.h states for the device (a cumulative sum is sequential in numpy)."""
+    if order == "pairwise":
+        return x.sum(axis=-1, dtype=dtype)
+    if order == "sequential":
+        return x.cumsum(axis=-1, dtype=dtype)[..., -1]
+    raise ValueError("order")
+
+
+def wpe(spec, params=None, dtype=np.float64, with_taps=False, order="pairwise"):
+    """spec (T, F) complex -> d (T, F) complex in `dtype`'s precision (complex128 / complex64); with_taps: also g (F, K).
+    order: how every sum over t is formed, "pairwise" (the reference, and what FLOOR was measured with) or "sequential"."""
     p = dict(DEFAULTS)
     p.update(params or {})
     check_params(p)
@@ -87,7 +98,7 @@ def wpe(spec, params=None, dtype=np.float64, with_taps=False):
     F, T = X.shape                                                                # every sum over t is numpy's pairwise sum of
     tiny = dt(1e-30)                                                              # one row, whatever the other rows are
     with np.errstate(all="ignore"):
-        phi = _max(rho * _power(X, dt).sum(axis=-1, dtype=dt) / dt(T), tiny)
+        phi = _max(rho * _sum_t(_power(X, dt), dt, order) / dt(T), tiny)
         # past[j][:, t] = X_{t-D-j}, zero before frame 0
         past = np.zeros((K, F, T), ct)
         for j in range(K):
@@ -102,9 +113,9 @@ def wpe(spec, params=None, dtype=np.float64, with_taps=False):
             P = np.zeros((F, K), ct)
             for j in range(K):
                 for k in range(j + 1):
-                    R[:, j, k] = (u[j] * np.conj(past[k])).sum(axis=-1, dtype=ct)
+                    R[:, j, k] = _sum_t(u[j] * np.conj(past[k]), ct, order)
                     R[:, k, j] = np.conj(R[:, j, k])
-                P[:, j] = (u[j] * np.conj(X)).sum(axis=-1, dtype=ct)
+                P[:, j] = _sum_t(u[j] * np.conj(X), ct, order)
             idx = np.arange(K)
             tr = np.zeros(F, dt)
             for j in range(K):

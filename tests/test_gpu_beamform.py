@@ -7,6 +7,12 @@ Bounds (derived, not tuned):
   The cases with fewer frames than channels (rank-deficient covariances) and the one at loading 1e-6 are held to beamform_ref.FLOOR,
   which they set; every other case to the six times smaller FLOOR_FULL_RANK.  The restatement is applied to the DOWNLOADED device
   spectrogram and the DOWNLOADED device mask magnitudes, so neither the STFT's nor the gain's own error enters.
+* adn_mvdr, per (group, bin): E = max_t |Y_dev - Y_64| / max_t |Y_64| <= 4 floor for every bin of every group, beside the bound
+  above (tests/solver_bounds.py).  The floor is the case's own: the largest E of the float32 restatement on the same inputs over
+  every bin, the three groups, both reference channels and both orders of the sums over t (pairwise and sequential), measured
+  when the test runs, never below 2^-23 and never from the device.  The same bound holds the tilted cases (an 80 dB slope over
+  the bins of the spectrograms and of the mask magnitudes, built on the host and uploaded), and a power of two per bin,
+  2^-((5 b) mod 13), has to come back bit for bit as the equally scaled unscaled result.
 * mag_out against sqrtf(fmaf(re, re, im * im)) of the device's own spec_out, evaluated in float32 on the host: equal bit for bit.
 * Repeat, batch, bin-subset, pitch, one-channel, zero-group and isolation tests: exact equality, as include/adn.h pins them.
 * End to end: bit-identical to the public pieces composed by hand; SI-SDR within the quality cap of tests/test_gpu_dereverb.py (at
@@ -15,6 +21,8 @@ Measured on the MI355X: parity uses at most 0.69 of a floor among the full-rank 
 3.4e-5 of max |Y|; 0.66 of FLOOR among the rank-deficient ones (T = 1, C = 8, ref 7, 2.1e-4 of max |Y|); 0.01 of FLOOR at loading
 1e-6; the median over all 212 comparisons 0.05.  SI-SDR of the class 1.62 -> 4.74 dB at C = 2 and 1.62 -> 7.77 dB at C = 4: the
 restatement's, to the printed digits.
+Per bin (profiles/solver_bins.md): at most 2.34 of the case's floor (bound 4): n_fft 64, T = 23, C = 2, ref 0, group 1, bin 15,
+E 4.4e-6; the tilted cases at most 2.04, the power-of-two cases 1.75 and bit for bit; the median over the 118 runs 0.90.
 """
 import ctypes
 import os
@@ -26,9 +34,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import beamform_cases as bc  # noqa: E402
-import beamform_ref as bf  # noqa: E402
 import dereverb_ref as dr  # noqa: E402
 import footprint as fp  # noqa: E402
+import solver_bounds as sb  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -99,11 +107,11 @@ def _parity(dev, n_fft, n_frames, channels, extra):
     from audiodenoiser_amd.beamform import mvdr
     floor, f = bc.floor_for(n_frames, channels, extra), n_fft // 2 + 1
     spec, mag = _inputs(dev, n_fft, n_frames, channels, extra)
-    spec_h = spec.cpu().numpy().astype(np.complex128).reshape(3, channels, n_frames, f)
-    mag_h = mag.cpu().numpy()[:, 0].reshape(3, channels, f, -1)
+    # the float64 restatement at both reference channels and the case's own float32 floor
+    bounds = sb.mvdr_bounds(spec.cpu().numpy(), mag.cpu().numpy()[:, 0], channels, bc.params_of(extra, 0))
     for ref in bc.refs_of(channels):
         kw = bc.params_of(extra, ref)
-        want = [bf.mvdr(spec_h[g], mag_h[g], kw) for g in range(3)]
+        want = list(bounds.ref[ref])
         for n_groups in bc.PARITY_GROUPS:
             got, out_mag = mvdr(spec[:n_groups * channels].contiguous(), mag[:n_groups * channels].contiguous(), channels, _params(kw))
             assert got.shape == (n_groups, n_frames, f) and got.dtype == torch.complex64
@@ -115,6 +123,8 @@ def _parity(dev, n_fft, n_frames, channels, extra):
                       f"{err / scale:.3g} of max |Y| ({err / scale / floor:.2f} floors of {floor:.2g}; bound 4)")
                 assert err <= 4.0 * floor * scale, (n_groups, g, err / scale)
             assert np.array_equal(out_mag.cpu().numpy()[:, 0].view(np.int32), _mag_of(got_h).transpose(0, 2, 1).view(np.int32))
+            sb.check(f"{sb.mvdr_label(n_fft, n_frames, channels, extra)} [ref {ref} groups {n_groups}]", got_h,
+                     bounds.ref[ref][:n_groups], bounds)
 
 
 @pytest.mark.parametrize("channels", bc.PARITY_CHANNELS, ids=lambda c: f"C{c}")
@@ -127,6 +137,52 @@ def test_parity_with_the_float64_restatement(dev, n_frames, channels):
                          ids=("n_fft512", "loading1e-6", "wide_mag", "uniform_mask"))
 def test_parity_at_the_wide_transform_the_weakest_loading_a_wide_pitch_and_another_mask(dev, case):
     _parity(dev, *case)
+
+
+def _upload(dev, a):
+    return torch.from_numpy(np.array(a, order="C")).to(dev)                # a writable copy: the cases are read-only
+
+
+@pytest.mark.parametrize("channels", sb.TILTED_MVDR, ids=lambda c: f"C{c}")
+def test_a_tilted_spectrum_is_held_bin_by_bin(dev, channels):
+    """80 dB from the first bin to the last, the mask magnitudes scaled alike: the group-wide bound allows the quiet bins an error
+    of their own size."""
+    from audiodenoiser_amd.beamform import mvdr
+    c = channels
+    spec, mags = sb.mvdr_inputs(64, sb.TILTED_FRAMES, c)
+    spec_h, mags_h = sb.scale_spec(spec, sb.tilt(33)), sb.scale_mags(mags, sb.tilt(33))
+    bounds = sb.mvdr_bounds(spec_h, mags_h, c)
+    for ref in bc.refs_of(c):
+        for n_groups in bc.PARITY_GROUPS:
+            got, out_mag = mvdr(_upload(dev, spec_h[:n_groups * c]), _upload(dev, mags_h[:n_groups * c, None]), c,
+                                _params(dict(ref_channel=ref)))
+            got_h = got.cpu().numpy()
+            sb.check(f"{sb.mvdr_label(64, sb.TILTED_FRAMES, c, None, 'tilted')} [ref {ref} groups {n_groups}]", got_h,
+                     bounds.ref[ref][:n_groups], bounds)
+            assert np.array_equal(out_mag.cpu().numpy()[:, 0].view(np.int32), _mag_of(got_h).transpose(0, 2, 1).view(np.int32))
+
+
+@pytest.mark.parametrize("channels", sb.TILTED_MVDR, ids=lambda c: f"C{c}")
+def test_a_power_of_two_per_bin_comes_back_bit_for_bit(dev, channels):
+    """The mask, both normalised covariances' solve and the filter are scale-free and the 1e-30 constants far below an ulp of what
+    they are added to, so 2^-k times a bin's spectrogram and magnitudes is 2^-k times its output, exactly
+    (tests/test_solver_bounds_host.py checks that the float32 restatement has the property, and here that no square leaves the
+    normal range)."""
+    from audiodenoiser_amd.beamform import mvdr
+    c, f = channels, sb.pow2(33)
+    spec, mags = sb.mvdr_inputs(64, sb.TILTED_FRAMES, c)
+    s_spec, s_mags = sb.scale_spec(spec, f), sb.scale_mags(mags, f)
+    sb.assert_squares_stay_normal(s_spec, s_mags)
+    ft = _upload(dev, f.astype(np.float32))
+    bounds = sb.mvdr_bounds(s_spec, s_mags, c)
+    for ref in bc.refs_of(c):
+        p = _params(dict(ref_channel=ref))
+        plain, plain_mag = mvdr(_upload(dev, spec), _upload(dev, mags[:, None]), c, p)
+        got, out_mag = mvdr(_upload(dev, s_spec), _upload(dev, s_mags[:, None]), c, p)
+        sb.assert_squares_stay_normal(got.cpu().numpy())
+        assert _same(got, torch.view_as_complex(torch.view_as_real(plain) * ft[None, None, :, None])), ref
+        assert _same(out_mag, plain_mag * ft[None, None, :, None]), ref
+        sb.check(f"{sb.mvdr_label(64, sb.TILTED_FRAMES, c, None, 'pow2')} [ref {ref}]", got.cpu().numpy(), bounds.ref[ref], bounds)
 
 
 # ---- 3. exact pins ---------------------------------------------------------------------------------------------------------------

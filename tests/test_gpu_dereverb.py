@@ -5,6 +5,11 @@ Bounds (derived, not tuned):
 * adn_wpe, per clip: max |d_dev - d_64| <= 4 FLOOR max |d_64|.  FLOOR (dereverb_ref.FLOOR) is the error of the same statements run
   in float32 on the host over these very cases (python tests/dereverb_cases.py), never a device figure; the factor 4 is the
   project's convention.  The restatement is applied to the DOWNLOADED device spectrogram, so the STFT's own error does not enter.
+* adn_wpe, per (clip, bin): E = max_t |d_dev - d_64| / max_t |d_64| <= 4 floor for every bin of every clip, beside the bound above
+  (tests/solver_bounds.py).  The floor is the case's own: the largest E of the float32 restatement on the same input over every
+  bin, the three clips and both orders of the sums over t (pairwise and sequential), measured when the test runs, never below
+  2^-23 and never from the device.  The same bound holds the tilted cases (an 80 dB slope over the bins, built on the host and
+  uploaded), and a power of two per bin, 2^-((5 b) mod 13), has to come back bit for bit as the equally scaled unscaled result.
 * mag_out against |spec_out| computed in float64 from the device's own spec_out: 2 ulp (one rounding of im * im, one of the fmaf,
   one of the square root, which halves the relative error of its argument: under 1.5 ulp).
 * Repeat, batch, bin-subset, pass-through and isolation tests: exact equality, as include/adn.h pins them.
@@ -14,6 +19,8 @@ Bounds (derived, not tuned):
 Measured on the MI355X: parity uses at most 1.42 of a floor (bound 4): n_fft 512, T = 97, loading 1e-6, clip 0, 4.1e-4 of max |d|;
 at the defaults at most 0.34 (n_fft 64, T = 22, clip 1), the median over all cases 0.05; the inverse-STFT link 1.7e-7 - 2.1e-7 of
 the maximum; SI-SDR 3.33 -> 6.54 dB, the cascade 8.79 dB against 6.49 dB for the gain alone: the restatement's, to the printed digits.
+Per bin (profiles/solver_bins.md): at most 2.85 of the case's floor (bound 4): n_fft 64, T = 5, clip 0, bin 14, E 6.3e-5; the tilted
+cases at most 1.35, the power-of-two case 0.83 and bit for bit; the median over the 57 runs 1.05.
 """
 import ctypes
 import os
@@ -28,6 +35,7 @@ import denoise_ref  # noqa: E402
 import dereverb_cases as dc  # noqa: E402
 import dereverb_ref as dr  # noqa: E402
 import footprint as fp  # noqa: E402
+import solver_bounds as sb  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -81,8 +89,8 @@ def _raw(spec, spec_out, mag_out, params=None, ws=None, ws_bytes=0, width=None, 
 def _parity(dev, n_fft, n_frames, kw):
     from audiodenoiser_amd.dereverb import wpe
     spec = _spec(dev, n_fft, n_frames, 3)
-    spec_h = spec.cpu().numpy().astype(np.complex128)
-    want = [dr.wpe(spec_h[c], kw) for c in range(3)]
+    bounds = sb.wpe_bounds(spec.cpu().numpy(), kw)             # the float64 restatement and the case's own float32 floor
+    want = list(bounds.ref)
     worst = 0.0
     for n_clips in dc.PARITY_CLIPS:
         got, mag = wpe(spec[:n_clips].contiguous(), _params(kw))
@@ -99,6 +107,7 @@ def _parity(dev, n_fft, n_frames, kw):
             ref = np.sqrt(got_h[c].real.astype(np.float64) ** 2 + got_h[c].imag.astype(np.float64) ** 2).T      # (F, T)
             ulps = np.abs(mag_h[c].astype(np.float64) - ref) / np.spacing(np.maximum(ref, np.finfo(np.float32).tiny).astype(np.float32))
             assert ulps.max() <= 2.0, (n_clips, c, float(ulps.max()))
+        sb.check(f"{sb.wpe_label(n_fft, n_frames, kw)} [clips {n_clips}]", got_h, bounds.ref[:n_clips], bounds)
     return worst
 
 
@@ -112,6 +121,46 @@ def test_parity_with_the_float64_restatement(dev, n_fft, n_frames):
 @pytest.mark.parametrize("n_fft", dc.PARITY_N_FFT)
 def test_parity_at_other_parameters(dev, n_fft, kw):
     _parity(dev, n_fft, dc.EXTRA_FRAMES, kw)
+
+
+def _upload(dev, a):
+    return torch.from_numpy(np.array(a, order="C")).to(dev)                # a writable copy: the cases are read-only
+
+
+def _mag_within_2_ulp(got_h, mag_h):
+    ref = np.sqrt(got_h.real.astype(np.float64) ** 2 + got_h.imag.astype(np.float64) ** 2).transpose(0, 2, 1)   # (n, F, T)
+    ulps = np.abs(mag_h.astype(np.float64) - ref) / np.spacing(np.maximum(ref, np.finfo(np.float32).tiny).astype(np.float32))
+    assert ulps.max() <= 2.0, float(ulps.max())
+
+
+@pytest.mark.parametrize("n_fft", sb.TILTED_WPE)
+def test_a_tilted_spectrum_is_held_bin_by_bin(dev, n_fft):
+    """80 dB from the first bin to the last: the clip-wide bound allows the quiet bins an error of their own size."""
+    from audiodenoiser_amd.dereverb import wpe
+    spec_h = sb.scale_spec(sb.wpe_spec(n_fft, sb.TILTED_FRAMES), sb.tilt(n_fft // 2 + 1))
+    bounds = sb.wpe_bounds(spec_h)
+    for n_clips in dc.PARITY_CLIPS:
+        got, mag = wpe(_upload(dev, spec_h[:n_clips]))
+        got_h = got.cpu().numpy()
+        sb.check(f"{sb.wpe_label(n_fft, sb.TILTED_FRAMES, None, 'tilted')} [clips {n_clips}]", got_h, bounds.ref[:n_clips], bounds)
+        _mag_within_2_ulp(got_h, mag.cpu().numpy()[:, 0])
+
+
+def test_a_power_of_two_per_bin_comes_back_bit_for_bit(dev):
+    """R, the taps and the weights' product with the signal are scale-free and the 1e-30 constants far below an ulp of what they
+    are added to, so 2^-k times a bin's input is 2^-k times its output, exactly (tests/test_solver_bounds_host.py checks that the
+    float32 restatement has the property, and here that no square leaves the normal range)."""
+    from audiodenoiser_amd.dereverb import wpe
+    base, f = sb.wpe_spec(64, sb.TILTED_FRAMES), sb.pow2(33)
+    scaled = sb.scale_spec(base, f)
+    sb.assert_squares_stay_normal(scaled)
+    ft = _upload(dev, f.astype(np.float32))
+    plain, plain_mag = wpe(_upload(dev, base))
+    got, mag = wpe(_upload(dev, scaled))
+    sb.assert_squares_stay_normal(got.cpu().numpy())
+    assert _same(got, torch.view_as_complex(torch.view_as_real(plain) * ft[None, None, :, None]))
+    assert _same(mag, plain_mag * ft[None, None, :, None])
+    sb.check(sb.wpe_label(64, sb.TILTED_FRAMES, None, "pow2"), got.cpu().numpy(), sb.wpe_bounds(scaled).ref, sb.wpe_bounds(scaled))
 
 
 # ---- 2. exact pins ---------------------------------------------------------------------------------------------------------------

@@ -7,6 +7,12 @@ Bounds (derived, not tuned):
   convention.  The one case at loading 1e-6 is held to dereverb_mc_ref.FLOOR, which it sets; every case at the default loading to
   the 140 times smaller FLOOR_DEFAULT_LOADING.  The restatement is applied to the DOWNLOADED device spectrogram, so the STFT's
   own error does not enter.
+* adn_wpe_mc, per (row, bin): E = max_t |d_dev - d_64| / max_t |d_64| <= 4 floor for every bin of every channel of every group,
+  beside the bound above (tests/solver_bounds.py).  The floor is the case's own: the largest E of the float32 restatement on the
+  same input over every bin, the three groups and both orders of the sums over t (pairwise and sequential), measured when the
+  test runs, never below 2^-23 and never from the device.  The same bound holds the tilted cases (an 80 dB slope over the bins,
+  built on the host and uploaded), and a power of two per bin, 2^-((5 b) mod 13), has to come back bit for bit as the equally
+  scaled unscaled result.
 * mag_out against sqrtf(fmaf(re, re, im * im)) of the device's own spec_out, evaluated in float32 on the host: equal bit for bit.
 * Repeat, batch, bin-subset, one-channel, pass-through, zero-group and isolation tests: exact equality, as include/adn.h pins them.
 * End to end: bit-identical to the public pieces composed by hand; SI-SDR within the quality cap of tests/test_gpu_dereverb.py
@@ -14,6 +20,9 @@ Bounds (derived, not tuned):
 Measured on the MI355X: parity uses at most 3.94 of a floor at the default loading (bound 4): n_fft 64, T = 97, (8, 4), group 1,
 2.7e-4 of max |d|; next 3.61 at (2, 10), T = 97; 3.24 of its own floor at loading 1e-6; the median over all 176 comparisons 0.04.
 SI-SDR of the joint class 3.33 -> 9.95 and 3.36 -> 10.52 dB: the restatement's, to the printed digits.
+Per bin (profiles/solver_bins.md): at most 3.62 of the case's floor (bound 4): the power-of-two case at (2, 10), T = 97, group 0,
+channel 0, bin 1, E 3.2e-4 -- the bin of the group-wide figure above; 3.18 there unscaled, 2.59 tilted; both power-of-two cases bit
+for bit; the median over the 94 runs 0.85.
 """
 import ctypes
 import os
@@ -25,9 +34,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dereverb_mc_cases as mc  # noqa: E402
-import dereverb_mc_ref as mr  # noqa: E402
 import dereverb_ref as dr  # noqa: E402
 import footprint as fp  # noqa: E402
+import solver_bounds as sb  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -84,8 +93,8 @@ def _parity(dev, n_fft, n_frames, ck, extra):
     from audiodenoiser_amd.dereverb import wpe_joint
     channels, kw, floor = ck[0], mc.params_of(ck, extra), mc.floor_for(extra)
     spec = _spec(dev, n_fft, n_frames, channels)
-    spec_h = spec.cpu().numpy().astype(np.complex128).reshape(3, channels, n_frames, -1)
-    want = [mr.wpe_mc(spec_h[g], kw) for g in range(3)]
+    bounds = sb.wpe_mc_bounds(spec.cpu().numpy(), channels, kw)     # the float64 restatement and the case's own float32 floor
+    want = list(bounds.ref.reshape(3, channels, n_frames, -1))
     for n_groups in mc.PARITY_GROUPS:
         got, mag = wpe_joint(spec[:n_groups * channels].contiguous(), channels, _params(kw))
         assert got.shape == (n_groups * channels, n_frames, n_fft // 2 + 1) and got.dtype == torch.complex64
@@ -97,6 +106,8 @@ def _parity(dev, n_fft, n_frames, ck, extra):
                   f"{err / scale:.3g} of max |d| ({err / scale / floor:.2f} floors of {floor:.2g}; bound 4)")
             assert err <= 4.0 * floor * scale, (n_groups, g, err / scale)
         assert np.array_equal(mag_h.view(np.int32), _mag_of(got.cpu().numpy()).transpose(0, 2, 1).view(np.int32))
+        sb.check(f"{sb.mc_label(n_fft, n_frames, ck, extra)} [groups {n_groups}]", got.cpu().numpy(),
+                 bounds.ref[:n_groups * channels], bounds)
 
 
 @pytest.mark.parametrize("ck", mc.PARITY_CK, ids=lambda ck: f"C{ck[0]}K{ck[1]}")
@@ -108,6 +119,44 @@ def test_parity_with_the_float64_restatement(dev, n_frames, ck):
 @pytest.mark.parametrize("case", (mc.WIDE_CASE, mc.LOADING_CASE), ids=("n_fft512", "loading1e-6"))
 def test_parity_at_the_wide_transform_and_the_weakest_loading(dev, case):
     _parity(dev, *case)
+
+
+def _upload(dev, a):
+    return torch.from_numpy(np.array(a, order="C")).to(dev)                # a writable copy: the cases are read-only
+
+
+@pytest.mark.parametrize("ck", sb.TILTED_MC, ids=lambda ck: f"C{ck[0]}K{ck[1]}")
+def test_a_tilted_spectrum_is_held_bin_by_bin(dev, ck):
+    """80 dB from the first bin to the last: the group-wide bound allows the quiet bins an error of their own size."""
+    from audiodenoiser_amd.dereverb import wpe_joint
+    c, kw = ck[0], mc.params_of(ck)
+    spec_h = sb.scale_spec(sb.mc_spec(64, sb.TILTED_FRAMES, c), sb.tilt(33))
+    bounds = sb.wpe_mc_bounds(spec_h, c, kw)
+    for n_groups in mc.PARITY_GROUPS:
+        got, mag = wpe_joint(_upload(dev, spec_h[:n_groups * c]), c, _params(kw))
+        got_h = got.cpu().numpy()
+        sb.check(f"{sb.mc_label(64, sb.TILTED_FRAMES, ck, None, 'tilted')} [groups {n_groups}]", got_h, bounds.ref[:n_groups * c], bounds)
+        assert np.array_equal(mag.cpu().numpy()[:, 0].view(np.int32), _mag_of(got_h).transpose(0, 2, 1).view(np.int32))
+
+
+@pytest.mark.parametrize("ck", sb.TILTED_MC, ids=lambda ck: f"C{ck[0]}K{ck[1]}")
+def test_a_power_of_two_per_bin_comes_back_bit_for_bit(dev, ck):
+    """R, the taps and the weights' product with the signal are scale-free and the 1e-30 constants far below an ulp of what they
+    are added to, so 2^-k times a bin's input is 2^-k times its output, exactly (tests/test_solver_bounds_host.py checks that the
+    float32 restatement has the property, and here that no square leaves the normal range)."""
+    from audiodenoiser_amd.dereverb import wpe_joint
+    c, kw = ck[0], mc.params_of(ck)
+    base, f = sb.mc_spec(64, sb.TILTED_FRAMES, c), sb.pow2(33)
+    scaled = sb.scale_spec(base, f)
+    sb.assert_squares_stay_normal(scaled)
+    ft = _upload(dev, f.astype(np.float32))
+    plain, plain_mag = wpe_joint(_upload(dev, base), c, _params(kw))
+    got, mag = wpe_joint(_upload(dev, scaled), c, _params(kw))
+    sb.assert_squares_stay_normal(got.cpu().numpy())
+    assert _same(got, torch.view_as_complex(torch.view_as_real(plain) * ft[None, None, :, None]))
+    assert _same(mag, plain_mag * ft[None, None, :, None])
+    bounds = sb.wpe_mc_bounds(scaled, c, kw)
+    sb.check(sb.mc_label(64, sb.TILTED_FRAMES, ck, None, "pow2"), got.cpu().numpy(), bounds.ref, bounds)
 
 
 # ---- 2. exact pins ---------------------------------------------------------------------------------------------------------------
