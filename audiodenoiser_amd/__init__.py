@@ -10,7 +10,8 @@ __all__ = ["UNet", "SpectrogramDataset", "WavToSpecDataset", "audio_to_magnitude
            "resample_length", "mix_snr", "load_audio", "StreamResampler", "Denoiser", "StreamDenoiser", "StreamPool", "ReverbSettings",
            "snr", "si_sdr", "seg_snr", "stoi", "evaluate", "SpectralDenoiser", "SpectralParams",
            "StreamSpectralDenoiser", "SpectralStreamPool", "spectral_gain_windows", "Dereverberator", "WpeParams",
-           "WpeStreamParams", "wpe_online", "StreamDereverberator", "DereverbStreamPool", "Beamformer", "MvdrParams", "mvdr"]
+           "WpeStreamParams", "wpe_online", "StreamDereverberator", "DereverbStreamPool", "Beamformer", "MvdrParams", "mvdr",
+           "MvdrStreamParams", "mvdr_online", "mvdr_stream_state_bytes", "StreamBeamformer"]
 # (resample / reverb themselves: audiodenoiser_amd.resample.resample, audiodenoiser_amd.reverb.reverb -- the modules own the names)
 
 
@@ -39,7 +40,7 @@ def __getattr__(name):
     if name in ("Dereverberator", "WpeParams", "WpeStreamParams", "wpe_online", "StreamDereverberator", "DereverbStreamPool"):
         import importlib
         return getattr(importlib.import_module(".dereverb", __name__), name)
-    if name in ("Beamformer", "MvdrParams", "mvdr"):
+    if name in ("Beamformer", "MvdrParams", "mvdr", "MvdrStreamParams", "mvdr_online", "mvdr_stream_state_bytes", "StreamBeamformer"):
         import importlib
         return getattr(importlib.import_module(".beamform", __name__), name)
     if name in ("StreamDenoiser", "StreamPool"):

@@ -135,7 +135,8 @@ def run_files(dn, src, dst, reference) -> int:
 
 def run_live(make, src, dst, chunk, reference, per_channel: bool = False) -> int:
     """The wav file ``src`` pushed ``chunk`` samples at a time, at its own rate, through the stream object that
-    ``make(device, n_streams, rate)`` returns -- every channel a stream -- and written to ``dst``."""
+    ``make(device, n_streams, rate)`` returns -- every channel a stream -- and written to ``dst``.  An object that returns one
+    row of samples per push (``StreamBeamformer`` on one recording) gives a mono file."""
     from .wav import read_wav, write_wav
     audio, rate = read_wav(src, mono=False)                  # (L, channels)
     dev = _lib.staging_device()
@@ -144,7 +145,7 @@ def run_live(make, src, dst, chunk, reference, per_channel: bool = False) -> int
     outs = [sd.push(x[:, i:i + chunk]) for i in range(0, x.shape[1], chunk)]
     latency = sd.latency_input_samples
     outs.append(sd.flush())
-    out = torch.cat(outs, dim=1)
+    out = torch.cat(outs, dim=-1)
     write_wav(dst, np.ascontiguousarray(out.cpu().numpy().T), rate)
     print(f"{src} -> {dst}: {x.shape[1]} samples at {rate} Hz in pushes of {chunk} at its own rate, latency {latency} samples")
     if reference is not None:

@@ -116,6 +116,10 @@ def load() -> ctypes.CDLL:
         L.adn_wpe_mc_stream.argtypes = [vp, sz, vp, ci, ci, cl, ci, cl, ci, ci, ci, ci, ci, ci, wsp, vp, sz, vp]
         L.adn_mvdr_workspace_bytes.argtypes = [ci, ci, ci, ci, ctypes.POINTER(MvdrParamsStruct), ctypes.POINTER(sz)]
         L.adn_mvdr.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(MvdrParamsStruct), vp, sz, vp, vp, ci, vp]
+        msp = ctypes.POINTER(MvdrStreamParamsStruct)
+        L.adn_mvdr_stream_state_bytes.argtypes = [ci, ci, ci, msp, ctypes.POINTER(sz)]
+        L.adn_mvdr_online.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cl, msp, vp, sz, ci, vp, vp, ci, ci, vp]
+        L.adn_mvdr_stream.argtypes = [vp, sz, vp, ci, ci, cl, ci, cl, ci, ci, ci, ci, ci, ci, msp, vp, sz, vp]
         for name in ("adn_device_count", "adn_prepare", "adn_unet_create", "adn_unet_create_ex", "adn_unet_create_general", "adn_unet_channels",
                      "adn_unet_set_batch_invariant", "adn_unet_destroy", "adn_unet_workspace_bytes", "adn_unet_forward", "adn_unet_forward_taps", "adn_unet_set_timing", "adn_unet_get_timing",
                      "adn_stft_n_frames", "adn_stft_mag", "adn_stft_mag_fit", "adn_quantize_pad", "adn_per_clip_l1",
@@ -135,7 +139,8 @@ def load() -> ctypes.CDLL:
                      "adn_wpe_mc_workspace_bytes", "adn_wpe_mc",
                      "adn_wpe_stream_state_bytes", "adn_wpe_online", "adn_wpe_stream", "adn_wpe_stream_pool",
                      "adn_wpe_mc_stream_state_bytes", "adn_wpe_mc_online", "adn_wpe_mc_stream",
-                     "adn_mvdr_workspace_bytes", "adn_mvdr"):
+                     "adn_mvdr_workspace_bytes", "adn_mvdr",
+                     "adn_mvdr_stream_state_bytes", "adn_mvdr_online", "adn_mvdr_stream"):
             getattr(L, name).restype = ci
         _lib = L
         return L
@@ -161,6 +166,12 @@ class WpeStreamParamsStruct(ctypes.Structure):
 class MvdrParamsStruct(ctypes.Structure):
     """``adn_mvdr_params`` of include/adn.h (the Python face is ``audiodenoiser_amd.beamform.MvdrParams``)."""
     _fields_ = [("ref_channel", ctypes.c_int), ("loading", ctypes.c_float), ("mask_floor", ctypes.c_float)]
+
+
+class MvdrStreamParamsStruct(ctypes.Structure):
+    """``adn_mvdr_stream_params`` of include/adn.h (the Python face is ``audiodenoiser_amd.beamform.MvdrStreamParams``)."""
+    _fields_ = [("ref_channel", ctypes.c_int), ("refresh", ctypes.c_int), ("forget", ctypes.c_float), ("loading", ctypes.c_float),
+                ("mask_floor", ctypes.c_float)]
 
 
 class SpectralRow(ctypes.Structure):
@@ -215,4 +226,5 @@ EXPORTED_SYMBOLS = (
     "adn_wpe_stream_state_bytes", "adn_wpe_online", "adn_wpe_stream", "adn_wpe_stream_pool",
     "adn_wpe_mc_stream_state_bytes", "adn_wpe_mc_online", "adn_wpe_mc_stream",
     "adn_mvdr_workspace_bytes", "adn_mvdr",
+    "adn_mvdr_stream_state_bytes", "adn_mvdr_online", "adn_mvdr_stream",
 )

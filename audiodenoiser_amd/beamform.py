@@ -10,6 +10,7 @@
     y, mag = mvdr(spec, mag_estimate, channels)        # the operator on spectrograms
 
     python -m audiodenoiser_amd.beamform IN OUT [--reference CLEAN] [--ref-channel R] [--wpe] [--gain] [--model CKPT]
+    python -m audiodenoiser_amd.beamform IN OUT --live [--chunk N] [--block B] [--forget A] [--refresh R] [--wpe] [--gain]
 
 The operator is DEFINED in ``include/adn.h`` ("beamform"; float64 restatement: ``tests/beamform_ref.py``;
 ``csrc/beamform_kernels.hip``) and is unpinned against any package: the MVDR beamformer in Souden's form,
@@ -25,10 +26,28 @@ time-frequency mask.  The mask comes from any per-channel magnitude estimate ``M
 5. with ``gain=True`` ``adn_spectral_gain`` on that spectrogram writes the magnitudes instead (``gain_params``);
 6. ``adn_denoise_resynth`` with one window per recording and the phase of the beamformer's output.
 
+The live form is ``StreamBeamformer`` ("beamform stream" in ``include/adn.h``; float64 restatement:
+``tests/beamform_stream_ref.py``; ``csrc/beamform_stream_kernels.hip``): the two covariances carried on the device with a forgetting
+factor, updated once per frame, the same filter solved from them every ``refresh`` frames.  It is ``StreamDenoiser`` over
+``n_streams = groups * C`` microphone feeds with, between ``analyze`` and ``emit`` and in place on the analysed windows,
+
+1. with ``wpe=True`` ``adn_wpe_mc_stream`` (``wpe_params=None``: ``taps = 32 // C``);
+2. ``adn_spectral_gain_windows`` on the kept columns of every channel: the mask's magnitudes (``mask_params``);
+3. ``adn_mvdr_stream``: ``Y_t`` and ``|Y_t|`` over the group's first stream;
+4. with ``gain=True`` the spectral gain again, with a state of its own (``gain_params``);
+
+``adn_stream_emit`` then resynthesises every stream and the object keeps row ``g C`` of each group.  ``mvdr_online`` is the
+recursion on spectrograms.
+
+    sb = StreamBeamformer(n_streams=4, channels=4)     # one recording of four microphones, 8 kHz, block of 4 frames
+    mono = sb.push(block)                              # (4, m) -> (k,): what has become final
+    tail = sb.flush()
+    python -m audiodenoiser_amd.beamform IN OUT --live [--chunk N] [--block B] [--forget A] [--refresh R] [--wpe] [--gain]
+
 The rate handling is ``Denoiser``'s: resample in, resample out, the input's sample count.  The defaults (reference channel 0,
 loading 1e-3, mask floor 1e-3) are the values of the host prototype (``profiles/bench_beamform.md``); they were not tuned by ear.
 
-What is NOT here: streaming or recursive beamforming, GEV or rank-one variants, WPD, more than 8 channels.  There is no CPU path.
+What is NOT here: multichannel streams in a pool, look-ahead, GEV or rank-one variants, WPD, more than 8 channels.  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -40,15 +59,17 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._host import check_stft_plan, current_stream, model_device, rocm_device, run_files, stage
-from .baseline import SpectralParams, _spectral_params, spectral_gain
+from ._host import check_stft_plan, current_stream, model_device, rocm_device, run_files, run_live, stage
+from .baseline import SpectralParams, _gain_kept_columns, _spectral_params, spectral_gain
 from .denoise import Denoiser
-from .dereverb import WpeParams, _check_channels, _joint_params, _mag_buffer, _need_cells, _spec_dims, wpe_joint
+from .dereverb import (WpeParams, WpeStreamParams, _check_channels, _joint_params, _joint_stream_params, _mag_buffer, _need_cells,
+                       _spec_dims, _state_bytes, wpe_joint)
+from .stream import StreamDenoiser, _check_stream_args, causal_carrier
 from .griffin_lim import stft_complex
 from .resample import _resample_device
 from .wav import read_wav, write_wav
 
-__all__ = ["MvdrParams", "mvdr", "Beamformer"]
+__all__ = ["MvdrParams", "mvdr", "Beamformer", "MvdrStreamParams", "mvdr_stream_state_bytes", "mvdr_online", "StreamBeamformer"]
 
 
 @dataclasses.dataclass(frozen=True)
@@ -121,6 +142,191 @@ def mvdr(spec: torch.Tensor, mag: torch.Tensor, channels: int, params: MvdrParam
                               ws.data_ptr() if ws is not None else None, need.value, out.data_ptr(), mag_out.data_ptr(),
                               int(mag_out.shape[3]), current_stream(dev)), "adn_mvdr")
     return torch.view_as_complex(out), mag_out
+
+
+@dataclasses.dataclass(frozen=True)
+class MvdrStreamParams:
+    """``adn_mvdr_stream_params`` of ``include/adn.h`` ("beamform stream") with its defaults and its legal ranges
+    (``ref_channel < channels`` is the call's).  ``forget = 0.99`` is a window of 100 frames, 1.6 s at hop 128 and 8 kHz: a design
+    value, not tuned by ear."""
+    ref_channel: int = 0
+    refresh: int = 1
+    forget: float = 0.99
+    loading: float = 1e-3
+    mask_floor: float = 1e-3
+
+    def __post_init__(self):
+        for name, lo, hi in (("ref_channel", 0, 7), ("refresh", 1, 64)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError(f"MvdrStreamParams: need an integer {lo} <= {name} <= {hi}")
+        # the ranges hold for the fp32 values the library sees; a NaN fails every comparison
+        for name, lo, hi in (("forget", 0.9, 1.0), ("loading", 1e-6, 1.0), ("mask_floor", 1e-6, 0.25)):
+            v = float(getattr(self, name))
+            f32 = ctypes.c_float(v).value
+            if not lo <= v <= hi or not ctypes.c_float(lo).value <= f32 <= ctypes.c_float(hi).value:
+                raise ValueError(f"MvdrStreamParams: need {lo:g} <= {name} <= {hi:g}")
+
+    def to_struct(self) -> "_lib.MvdrStreamParamsStruct":
+        return _lib.MvdrStreamParamsStruct(int(self.ref_channel), int(self.refresh), float(self.forget), float(self.loading),
+                                           float(self.mask_floor))
+
+
+def _mvdr_stream_params(who, params, channels):
+    """The parameters of a live call on ``channels`` channels: a ``MvdrStreamParams`` whose reference channel exists, None for the
+    defaults."""
+    _check_channels(who, channels)
+    if params is None:
+        return None
+    if not isinstance(params, MvdrStreamParams):
+        raise TypeError(f"{who}: params must be a MvdrStreamParams")
+    if params.ref_channel >= channels:
+        raise ValueError(f"{who}: need ref_channel < channels (ref_channel {params.ref_channel}, channels {channels})")
+    return params
+
+
+def mvdr_stream_state_bytes(n_slots: int, channels: int, n_bins: int, params: MvdrStreamParams = None) -> int:
+    """``adn_mvdr_stream_state_bytes``: the bytes of the opaque state of ``n_slots`` groups of ``channels`` channels and ``n_bins``
+    bins (no device needed)."""
+    if params is not None and not isinstance(params, MvdrStreamParams):
+        raise TypeError("mvdr_stream_state_bytes: params must be a MvdrStreamParams")
+    need = ctypes.c_size_t(0)
+    p = ctypes.byref(params.to_struct()) if params is not None else None
+    _lib.check(_lib.load().adn_mvdr_stream_state_bytes(n_slots, channels, n_bins, p, ctypes.byref(need)), "adn_mvdr_stream_state_bytes")
+    return int(need.value)
+
+
+def mvdr_online(spec: torch.Tensor, mag: torch.Tensor, channels: int, state: torch.Tensor = None, first_frame: int = 0,
+                params: MvdrStreamParams = None, mag_out: torch.Tensor = None, col0: int = 0, mag_col0: int = 0):
+    """``adn_mvdr_online`` on the current stream.  ``spec``: complex64 ``(n_groups * channels, T, F)`` on a ROCm device, the frames
+    ``first_frame ... first_frame + T - 1`` of every row, the ``channels`` channels of a recording consecutive rows.  ``mag``:
+    float32 ``(n_groups * channels, 1, F, mag_width)`` whose columns ``[mag_col0, mag_col0 + T)`` are read.  ``state``: the uint8
+    tensor an earlier call returned for the frames before them (None allocates one; with ``first_frame = 0`` every group starts
+    fresh whatever it holds); it is updated IN PLACE, a slot per GROUP.  ``mag_out``: float32 ``(n_groups, 1, F, width)`` whose
+    columns ``[col0, col0 + T)`` are written and nothing else; None allocates ``(n_groups, 1, F, T)``.  Returns ``(y, mag_out,
+    state)``, ``y`` a new complex64 ``(n_groups, T, F)``.  ValueError, before any device call, if the leading dimension is no
+    multiple of ``channels``, the reference channel does not exist, or a shape, dtype or device does not fit."""
+    who = "mvdr_online"
+    params = _mvdr_stream_params(who, params, channels)
+    if isinstance(spec, torch.Tensor) and spec.dim() == 3 and spec.shape[0] % channels:
+        raise ValueError(f"{who}: the leading dimension {spec.shape[0]} is not a multiple of channels = {channels}")
+    n, t, f = _spec_dims(who, "row", spec)
+    _need_cells(who, "row", n, t, f)
+    if not (isinstance(first_frame, int) and first_frame >= 0 and isinstance(col0, int) and col0 >= 0 and isinstance(mag_col0, int)
+            and mag_col0 >= 0):
+        raise ValueError(f"{who}: need integers first_frame >= 0, col0 >= 0 and mag_col0 >= 0")
+    dev = spec.device
+    if (not isinstance(mag, torch.Tensor) or not mag.is_cuda or mag.device != dev or mag.dtype != torch.float32 or mag.dim() != 4
+            or tuple(mag.shape[:3]) != (n, 1, f) or mag.shape[3] < mag_col0 + t):
+        raise ValueError(f"{who}: mag must be a (n_rows, 1, n_bins, mag_width >= mag_col0 + n_frames) float32 tensor on spec's device")
+    groups = n // channels
+    need = mvdr_stream_state_bytes(groups, channels, f, params)
+    if state is None:
+        if first_frame != 0:
+            raise ValueError(f"{who}: first_frame > 0 continues a group: pass the state of the call before")
+        state = torch.empty((need,), dtype=torch.uint8, device=dev)
+    elif (not isinstance(state, torch.Tensor) or not state.is_cuda or state.device != dev or state.dtype != torch.uint8
+          or state.dim() != 1 or state.numel() < need or not state.is_contiguous()):
+        raise ValueError(f"{who}: state must be a contiguous uint8 tensor of at least mvdr_stream_state_bytes on spec's device")
+    if mag_out is None and col0 != 0:
+        raise ValueError(f"{who}: col0 needs a mag_out buffer")
+    mag_out = _mag_buffer(who, "group", mag_out, groups, t, f, dev)
+    if mag_out.shape[3] < col0 + t:
+        raise ValueError(f"{who}: mag_out must hold columns [col0, col0 + n_frames)")
+    s, m = torch.view_as_real(spec.contiguous()), mag.contiguous()
+    out = torch.empty((groups, t, f, 2), dtype=torch.float32, device=dev)
+    p = ctypes.byref(params.to_struct()) if params is not None else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().adn_mvdr_online(s.data_ptr(), m.data_ptr(), int(m.shape[3]), mag_col0, groups, channels, t, f,
+                                               first_frame, p, state.data_ptr(), state.numel(), groups, out.data_ptr(),
+                                               mag_out.data_ptr(), int(mag_out.shape[3]), col0, current_stream(dev)), "adn_mvdr_online")
+    return torch.view_as_complex(out), mag_out, state
+
+
+class StreamBeamformer(StreamDenoiser):
+    """``StreamDenoiser`` with the streaming beamformer in the network's place: ``n_streams`` is a multiple of ``channels`` and
+    ``channels`` consecutive streams are the microphones of ONE recording.  ``push`` and ``flush`` take ``(n_streams, m)`` and return
+    ``(n_streams // channels, k)``, or ``(k,)`` for one group; ``reset``, ``received``, ``emitted``, ``latency_samples`` and
+    ``input_rate`` are the parent's.
+
+    The operator is causal, so ``lookahead_frames`` is 0 and ``window_frames = max(16, block_frames)`` is only the carrier the
+    stream geometry needs.  Each run of steps works in place on the analysed windows: with ``wpe=True`` ``adn_wpe_mc_stream``
+    (``wpe_params=None``: ``taps = 32 // channels``); ``adn_spectral_gain_windows`` on the kept columns of every channel, the mask's
+    magnitudes (``mask_params``, its own ``(n_streams, 3, F)`` state); ``adn_mvdr_stream`` (``params``); with ``gain=True`` the
+    spectral gain again with a second state (``gain_params``).  ``adn_stream_emit`` resynthesises every stream and row ``g C`` of each
+    group is kept.  The MVDR and the WPE states need no reset: a stream's frame 0 starts them afresh; ``reset`` forgets both gain
+    states.  A ``params`` whose reference channel ``channels`` does not have is a ValueError here."""
+
+    def __init__(self, device=None, n_streams: int = 1, channels: int = 1, sample_rate: int = 8000, n_fft: int = 512,
+                 hop_length: int = 128, block_frames: int = 4, params: MvdrStreamParams = None, mask_params: SpectralParams = None,
+                 wpe: bool = False, wpe_params: WpeStreamParams = None, gain: bool = False, gain_params: SpectralParams = None,
+                 input_rate=None):
+        who = "StreamBeamformer"
+        window, ahead, batch = causal_carrier(block_frames)
+        _check_stream_args(who, n_streams, sample_rate, n_fft, hop_length, window, block_frames, ahead, batch, input_rate)
+        self.params = _mvdr_stream_params(who, params, channels)
+        if n_streams % channels:
+            raise ValueError(f"{who}: n_streams = {n_streams} is not a multiple of channels = {channels}")
+        self.mask_params = _spectral_params(who, mask_params, "mask_params")
+        self.gain_params = _spectral_params(who, gain_params, "gain_params")
+        self.wpe, self.gain, self.channels = bool(wpe), bool(gain), channels
+        if wpe_params is not None and not isinstance(wpe_params, WpeStreamParams):
+            raise TypeError(f"{who}: wpe_params must be a WpeStreamParams")
+        self.wpe_params = _joint_stream_params(who, wpe_params, channels) if self.wpe else None
+        dev = rocm_device(who, device)
+        self.model = None
+        f, groups = n_fft // 2 + 1, n_streams // channels
+        self._mvdr_state = torch.empty((mvdr_stream_state_bytes(groups, channels, f, self.params),), dtype=torch.uint8, device=dev)
+        self._mask_state = torch.empty((n_streams, 3, f), dtype=torch.float32, device=dev)
+        self._gain_state = torch.empty((n_streams, 3, f), dtype=torch.float32, device=dev)
+        self._wpe_state = None
+        if self.wpe:
+            need = _state_bytes(who, groups, None if channels == 1 else channels, f, self.wpe_params)
+            self._wpe_state = torch.empty((need,), dtype=torch.uint8, device=dev)
+        self._setup(dev, n_streams, sample_rate, n_fft, hop_length, window, block_frames, ahead, batch, input_rate)
+
+    def reset(self):
+        """Forget the running recording, both gains' noise estimates included: the object is ready for a new one."""
+        super().reset()
+        self._mask_state.fill_(-1.0)
+        self._gain_state.fill_(-1.0)
+
+    def network(self, x):
+        raise RuntimeError("StreamBeamformer: there is no network; the beamformer runs between analyze and emit (adn_mvdr_stream)")
+
+    def _steps(self, first_step, n_steps, final_length):
+        return (first_step, n_steps, final_length, *self._plan, self.max_steps)
+
+    def _beamform(self, x: torch.Tensor, first_step: int, n_steps: int, final_length: int = -1) -> torch.Tensor:
+        """``adn_mvdr_stream`` in place on the windows ``x`` whose kept columns hold the mask's magnitudes."""
+        p = ctypes.byref(self.params.to_struct()) if self.params is not None else None
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().adn_mvdr_stream(self._state.data_ptr(), self._state.numel(), x.data_ptr(), self.n_streams,
+                                                   self.channels, *self._steps(first_step, n_steps, final_length), p,
+                                                   self._mvdr_state.data_ptr(), self._mvdr_state.numel(), current_stream(self.device)),
+                       "adn_mvdr_stream")
+        return x
+
+    def _net(self, x: torch.Tensor, first_step: int, n_steps: int, final_length: int = -1) -> torch.Tensor:
+        if self.wpe:
+            joint = self.channels != 1
+            run = _lib.load().adn_wpe_mc_stream if joint else _lib.load().adn_wpe_stream
+            lead = (self.n_streams, self.channels) if joint else (self.n_streams,)
+            with torch.cuda.device(self.device):
+                _lib.check(run(self._state.data_ptr(), self._state.numel(), x.data_ptr(), *lead,
+                               *self._steps(first_step, n_steps, final_length), ctypes.byref(self.wpe_params.to_struct()),
+                               self._wpe_state.data_ptr(), self._wpe_state.numel(), current_stream(self.device)), run.__name__)
+        _gain_kept_columns(x, None, n_steps, self._mask_state, self._plan, self.mask_params)
+        self._beamform(x, first_step, n_steps, final_length)
+        if self.gain:
+            _gain_kept_columns(x, None, n_steps, self._gain_state, self._plan, self.gain_params)
+        return x
+
+    def _result(self, outs):
+        """Row ``g C`` of every group of what the streams returned: ``(n_groups, k)``, or ``(k,)`` for one group."""
+        out = self._cat(outs)[::self.channels]
+        out = out[0] if out.shape[0] == 1 else out.contiguous()
+        return out.cpu().numpy() if self._numpy else out
 
 
 class Beamformer(Denoiser):
@@ -226,7 +432,32 @@ def main(argv=None) -> int:
     ap.add_argument("--gain", action="store_true", help="run the spectral baseline's Wiener gain on the beamformer's result")
     ap.add_argument("--model", metavar="CKPT", default=None,
                     help="take the mask from this U-Net checkpoint instead of the spectral gain (the state_dict of UNet(1, 1))")
+    ap.add_argument("--live", action="store_true",
+                    help="push the file (not a folder) through the streaming beamformer at its own rate, as a live feed arrives")
+    ap.add_argument("--chunk", type=int, default=1024, help="with --live: samples per push, at the file's rate")
+    ap.add_argument("--block", type=int, default=4, help="with --live: frames per step (latency (block - 1) hop + n_fft samples)")
+    ap.add_argument("--forget", type=float, default=MvdrStreamParams.forget, help="with --live: forgetting factor, 0.9 ... 1")
+    ap.add_argument("--refresh", type=int, default=MvdrStreamParams.refresh, help="with --live: frames between two solves, 1 ... 64")
     args = ap.parse_args(argv)
+    if args.live:
+        import os
+        if args.chunk < 1 or args.block < 1:
+            ap.error("--chunk and --block must be >= 1")
+        if os.path.isdir(args.src):
+            ap.error("--live takes one wav file")
+        if args.model is not None:
+            ap.error("--live takes its mask from the spectral gain: no --model")
+
+        def make(dev, n_streams, rate):
+            if not 1 <= n_streams <= 8:
+                raise ValueError(f"--live: {n_streams} channels; the beamformer takes 1 ... 8")
+            live = MvdrStreamParams(ref_channel=args.ref_channel, refresh=args.refresh, forget=args.forget)
+            return StreamBeamformer(dev, n_streams=n_streams, channels=n_streams, block_frames=args.block, params=live, wpe=args.wpe,
+                                    gain=args.gain, input_rate=rate)
+        try:
+            return run_live(make, args.src, args.dst, args.chunk, args.reference)
+        except ValueError as exc:
+            ap.error(str(exc))
     try:
         params = MvdrParams(ref_channel=args.ref_channel)
     except ValueError as exc:

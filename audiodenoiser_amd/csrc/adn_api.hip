@@ -666,6 +666,20 @@ int adn_wpe_mc(const float *spec, int n_groups, int channels, int n_frames, int 
 
 /* ---- beamformer: mask-driven MVDR of the channels of a recording (adn.h, "beamform") ----------------------------- */
 // The sizing function and the operator share one validation: `who` is the name in front of every message.
+// The rules adn_mvdr and the streaming form share: the channel count and the three fields both parameter structs have.
+static int mvdr_fields(const std::string &w, int channels, int ref_channel, float loading, float mask_floor, adn::MvdrConsts *k)
+{
+    if (ref_channel < 0 || ref_channel >= channels) return fail(ADN_ERR_INVALID, w + ": need 0 <= ref_channel < channels");
+    // written so that a NaN fails every test
+    if (!(loading >= 1e-6f && loading <= 1.f)) return fail(ADN_ERR_INVALID, w + ": need 1e-6 <= loading <= 1");
+    if (!(mask_floor >= 1e-6f && mask_floor <= 0.25f)) return fail(ADN_ERR_INVALID, w + ": need 1e-6 <= mask_floor <= 0.25");
+    k->ref = ref_channel;
+    k->loading = loading;
+    k->rho = mask_floor;
+    k->one_minus_rho = 1.f - mask_floor;
+    return ADN_OK;
+}
+
 static int mvdr_shape(const char *who, int n_groups, int channels, int n_frames, int n_bins, const adn_mvdr_params *params,
                       adn::MvdrConsts *k)
 {
@@ -675,14 +689,7 @@ static int mvdr_shape(const char *who, int n_groups, int channels, int n_frames,
     if ((long)n_groups * channels > 0x7fffffffL) return fail(ADN_ERR_INVALID, w + ": need n_groups * channels < 2^31");
     const adn_mvdr_params defaults = {0, 1e-3f, 1e-3f};
     const adn_mvdr_params p = params ? *params : defaults;
-    if (p.ref_channel < 0 || p.ref_channel >= channels) return fail(ADN_ERR_INVALID, w + ": need 0 <= ref_channel < channels");
-    // written so that a NaN fails every test
-    if (!(p.loading >= 1e-6f && p.loading <= 1.f)) return fail(ADN_ERR_INVALID, w + ": need 1e-6 <= loading <= 1");
-    if (!(p.mask_floor >= 1e-6f && p.mask_floor <= 0.25f)) return fail(ADN_ERR_INVALID, w + ": need 1e-6 <= mask_floor <= 0.25");
-    k->ref = p.ref_channel;
-    k->loading = p.loading;
-    k->rho = p.mask_floor;
-    k->one_minus_rho = 1.f - p.mask_floor;
+    ADN_TRY(mvdr_fields(w, channels, p.ref_channel, p.loading, p.mask_floor, k));
     if (adn::mvdr_grid(n_groups, channels, n_bins) > 0x7fffffffL)
         return fail(ADN_ERR_INVALID, w + ": grid too large (n_groups x ceil(n_bins / bins per workgroup) >= 2^31)");
     return ADN_OK;
@@ -1255,6 +1262,117 @@ int adn_resample_stream(void *state, size_t state_bytes, const float *audio, lon
                     "the capture");
     if (e == hipErrorInvalidValue) return fail(ADN_ERR_INVALID, "adn_resample_stream: grid too large (n_streams x output blocks >= 2^31)");
     if (e != hipSuccess) return fail_hip(e, "adn_resample_stream");
+    return ADN_OK;
+}
+
+/* ---- streaming beamformer: recursive covariances, one filter per refresh (adn.h, "beamform stream") ------------------------------ */
+// The parameters of a call on `channels` channels (NULL = the defaults), refused outside their legal ranges.
+static int mvdr_stream_consts(const char *who, int channels, const adn_mvdr_stream_params *params, adn::MvdrStreamConsts *k)
+{
+    const std::string w(who);
+    if (channels < 1 || channels > 8) return fail(ADN_ERR_INVALID, w + ": need 1 <= channels <= 8");
+    const adn_mvdr_stream_params defaults = {0, 1, 0.99f, 1e-3f, 1e-3f};
+    const adn_mvdr_stream_params p = params ? *params : defaults;
+    if (p.refresh < 1 || p.refresh > 64) return fail(ADN_ERR_INVALID, w + ": need 1 <= refresh <= 64");
+    // written so that a NaN fails the test
+    if (!(p.forget >= 0.9f && p.forget <= 1.f)) return fail(ADN_ERR_INVALID, w + ": need 0.9 <= forget <= 1");
+    ADN_TRY(mvdr_fields(w, channels, p.ref_channel, p.loading, p.mask_floor, &k->m));
+    k->R = p.refresh;
+    k->alpha = p.forget;
+    return ADN_OK;
+}
+
+static size_t mvdr_stream_bytes(int n_slots, int n_bins, int channels)
+{
+    return (size_t)n_slots * (size_t)n_bins * (size_t)adn::mvdr_stream_record_floats(channels) * sizeof(float);
+}
+
+static int mvdr_stream_state(const std::string &w, const void *state, size_t state_bytes, int n_slots, int n_bins, int channels)
+{
+    if (!state) return fail(ADN_ERR_INVALID, w + ": null pointer (the MVDR state)");
+    if (n_slots < 1 || n_slots > (1 << 20) || n_bins < 1 || n_bins > (1 << 20))
+        return fail(ADN_ERR_INVALID, w + ": need 1 <= n_slots <= 2^20 and 1 <= n_bins <= 2^20");
+    if (state_bytes < mvdr_stream_bytes(n_slots, n_bins, channels))
+        return fail(ADN_ERR_WORKSPACE, w + ": the MVDR state is smaller than adn_mvdr_stream_state_bytes");
+    if (!aligned_to(state, 8)) return fail(ADN_ERR_INVALID, w + ": the MVDR state must be 8-byte aligned");
+    return ADN_OK;
+}
+
+int adn_mvdr_stream_state_bytes(int n_slots, int channels, int n_bins, const adn_mvdr_stream_params *params, size_t *bytes)
+{
+    const std::string w("adn_mvdr_stream_state_bytes");
+    adn::MvdrStreamConsts k;
+    if (!bytes) return fail(ADN_ERR_INVALID, w + ": null pointer");
+    if (n_slots < 1 || n_slots > (1 << 20) || n_bins < 1 || n_bins > (1 << 20))
+        return fail(ADN_ERR_INVALID, w + ": need 1 <= n_slots <= 2^20 and 1 <= n_bins <= 2^20");
+    ADN_TRY(mvdr_stream_consts("adn_mvdr_stream_state_bytes", channels, params, &k));
+    *bytes = mvdr_stream_bytes(n_slots, n_bins, channels);
+    return ADN_OK;
+}
+
+int adn_mvdr_online(const float *spec, const float *mag, int mag_width, int mag_col0, int n_groups, int channels, int n_frames,
+                    int n_bins, long first_frame, const adn_mvdr_stream_params *params, void *state, size_t state_bytes, int n_slots,
+                    float *spec_out, float *mag_out, int width, int col0, void *stream)
+{
+    const std::string w("adn_mvdr_online");
+    adn::MvdrStreamConsts k;
+    if (!spec || !mag || !spec_out) return fail(ADN_ERR_INVALID, w + ": null pointer (spec, mag, spec_out)");
+    if (n_groups < 1 || n_frames < 1 || n_bins < 1) return fail(ADN_ERR_INVALID, w + ": n_groups, n_frames and n_bins must be >= 1");
+    if (first_frame < 0 || first_frame + n_frames >= (1L << 31))
+        return fail(ADN_ERR_INVALID, w + ": need first_frame >= 0 and first_frame + n_frames < 2^31");
+    ADN_TRY(mvdr_stream_consts("adn_mvdr_online", channels, params, &k));
+    if ((long)n_groups * channels > 0x7fffffffL) return fail(ADN_ERR_INVALID, w + ": need n_groups * channels < 2^31");
+    ADN_TRY(mvdr_stream_state(w, state, state_bytes, n_slots, n_bins, channels));
+    if (n_groups > n_slots) return fail(ADN_ERR_INVALID, w + ": group i uses slot i: need n_groups <= n_slots");
+    if (mag_col0 < 0 || mag_width < 1 || (long)mag_col0 + n_frames > mag_width)
+        return fail(ADN_ERR_INVALID, w + ": need mag_col0 >= 0 and mag_col0 + n_frames <= mag_width");
+    if (mag_out && (col0 < 0 || width < 1 || (long)col0 + n_frames > width))
+        return fail(ADN_ERR_INVALID, w + ": need col0 >= 0 and col0 + n_frames <= width");
+    if (!aligned_to(spec, 8) || !aligned_to(spec_out, 8) || !aligned_to(mag, 4) || !aligned_to(mag_out, 4))
+        return fail(ADN_ERR_INVALID, w + ": spec and spec_out must be 8-byte aligned, mag and mag_out 4-byte aligned");
+    const size_t cells = (size_t)n_groups * (size_t)n_bins;
+    const auto overlap = [](const void *p, size_t np, const void *q, size_t nq) {
+        const char *a = reinterpret_cast<const char *>(p), *b = reinterpret_cast<const char *>(q);
+        return a < b + nq && b < a + np;
+    };
+    const size_t in_spec = cells * channels * n_frames * 2 * sizeof(float), out_spec = cells * n_frames * 2 * sizeof(float);
+    const size_t in_mag = cells * channels * mag_width * sizeof(float), out_mag = mag_out ? cells * width * sizeof(float) : 0;
+    const size_t st_bytes = mvdr_stream_bytes(n_slots, n_bins, channels);
+    if (overlap(spec, in_spec, spec_out, out_spec) || overlap(mag, in_mag, spec_out, out_spec) || overlap(state, st_bytes, spec_out, out_spec))
+        return fail(ADN_ERR_INVALID, w + ": spec_out may not overlap spec, mag or the state");
+    if (overlap(spec, in_spec, state, st_bytes) || overlap(mag, in_mag, state, st_bytes))
+        return fail(ADN_ERR_INVALID, w + ": the state may not overlap spec or mag");
+    if (mag_out && (overlap(spec, in_spec, mag_out, out_mag) || overlap(mag, in_mag, mag_out, out_mag) ||
+                    overlap(spec_out, out_spec, mag_out, out_mag) || overlap(state, st_bytes, mag_out, out_mag)))
+        return fail(ADN_ERR_INVALID, w + ": mag_out may not overlap spec, mag, spec_out or the state");
+    if (adn::mvdr_stream_grid(n_groups, channels, n_bins) > 0x7fffffffL)
+        return fail(ADN_ERR_INVALID, w + ": grid too large (n_groups x ceil(n_bins / bins per workgroup) >= 2^31)");
+    ADN_LAUNCH(adn::launch_mvdr_online(spec, mag, mag_width, mag_col0, n_groups, channels, n_frames, n_bins, (int)first_frame, k,
+                                       static_cast<float *>(state), spec_out, mag_out, width, col0, static_cast<hipStream_t>(stream)),
+               "adn_mvdr_online");
+    return ADN_OK;
+}
+
+int adn_mvdr_stream(void *sstate, size_t sstate_bytes, float *y, int n_streams, int channels, long first_step, int n_steps,
+                    long final_length, int n_fft, int hop, int window, int block, int lookahead, int max_steps,
+                    const adn_mvdr_stream_params *params, void *mvdr_state, size_t mvdr_state_bytes, void *stream)
+{
+    const std::string w("adn_mvdr_stream");
+    adn::StreamGeom g;
+    adn::StreamCall call;
+    adn::MvdrStreamConsts k;
+    ADN_TRY(stream_state("adn_mvdr_stream", sstate, sstate_bytes, n_streams, n_fft, hop, window, block, lookahead, max_steps, &g));
+    if (lookahead != 0) return fail(ADN_ERR_INVALID, w + ": the operator is causal: lookahead must be 0");
+    if (!y) return fail(ADN_ERR_INVALID, w + ": null pointer");
+    if (!aligned_to(y, 4)) return fail(ADN_ERR_INVALID, w + ": y must be 4-byte aligned");
+    ADN_TRY(stream_call("adn_mvdr_stream", g, first_step, n_steps, final_length, &call));
+    ADN_TRY(mvdr_stream_consts("adn_mvdr_stream", channels, params, &k));
+    if (n_streams % channels) return fail(ADN_ERR_INVALID, w + ": n_streams must be a multiple of channels");
+    ADN_TRY(mvdr_stream_state(w, mvdr_state, mvdr_state_bytes, n_streams / channels, n_fft / 2 + 1, channels));
+    if (adn::mvdr_stream_grid(n_streams / channels, channels, n_fft / 2 + 1) > 0x7fffffffL)
+        return fail(ADN_ERR_INVALID, w + ": grid too large (n_groups x ceil(n_bins / bins per workgroup) >= 2^31)");
+    ADN_LAUNCH(adn::launch_mvdr_stream(static_cast<float *>(sstate), y, n_streams, channels, g, call, k,
+                                       static_cast<float *>(mvdr_state), static_cast<hipStream_t>(stream)), "adn_mvdr_stream");
     return ADN_OK;
 }
 

@@ -598,6 +598,26 @@ hipError_t launch_wpe_stream(float *state, float *y, int n_streams, int C, const
 // a pool's rows are single-channel streams: C is fixed at 1
 hipError_t launch_wpe_stream_pool(float *state, float *y, const StreamGeom &g, const StreamPoolRows &rows, const WpeStreamConsts &c,
                                   float *wstate, hipStream_t st);
+// Streaming beamformer (beamform_stream_kernels.hip; adn.h, "beamform stream"): the recursion of the two covariances of "beamform",
+// one update per frame, a filter every R frames, for the C consecutive rows of a group, 1 <= C <= 8.  MvdrStreamConsts: MvdrConsts,
+// the refresh period R and the forgetting factor.  state: mvdr_stream_record_floats(C) = 2 (C (C + 1) + C) floats per (slot, bin) --
+// both packed triangles and the filter -- entry-major over the bins of a slot, group i = slot i; a group that starts at frame 0
+// reads none of it.  The launches differ in where the frames are, as launch_wpe_online / launch_wpe_stream: frame-major spectrograms
+// with bin-major mask magnitudes [group * C + channel][F][mag_width] from column mag_col0, the result [group][frame][F] and
+// [group][F][width] from col0; or the X rings of a lockstep stream state whose streams g C .. g C + C - 1 are group g, M_t read from
+// columns [W - B, W) of every channel's windows of y, Y_t and |Y_t| written in place over stream g C's.
+struct MvdrStreamConsts {
+    MvdrConsts m;
+    int R;
+    float alpha;
+};
+long mvdr_stream_record_floats(int C);
+long mvdr_stream_grid(long n_groups, int C, int F);
+hipError_t launch_mvdr_online(const void *spec, const float *mag, int mag_width, int mag_col0, int n_groups, int C, int T, int F,
+                              int first_frame, const MvdrStreamConsts &k, float *state, void *spec_out, float *mag_out, int width,
+                              int col0, hipStream_t st);
+hipError_t launch_mvdr_stream(float *sstate, float *y, int n_streams, int C, const StreamGeom &g, const StreamCall &call,
+                              const MvdrStreamConsts &k, float *state, hipStream_t st);
 hipError_t launch_quantize_pad(const float *in, int n, int h, int w, float *out, int H, int W, hipStream_t st);
 hipError_t launch_per_clip_l1(const float *a, const float *b, int n_clips, long elems, float *out, hipStream_t st);
 // Polyphase resampler and SNR mixer (resample_kernels.hip).  resample_ratio: up / down of a rate pair, false outside the limits

@@ -98,5 +98,42 @@ __device__ __forceinline__ void store_frame(const InRing<Rows> &s, const RowFram
     s.y[((row * c.n_steps + (st - c.first)) * (long)F + bin) * s.g.W + (s.g.W - s.g.B) + (t - st * s.g.B)] = m;
 }
 
+// ---------------------------------------------------------------------------------------------- frames that come with a magnitude
+// The streaming beamformer (beamform_stream_kernels.hip) reads C rows per group, each frame with a magnitude estimate M_t, and
+// writes ONE row per group.  Added beside the sources above, which keep their layout and their code:
+//   FrameMajorMasked      FrameMajor whose `out` / `mag` rows are GROUPS, plus mag_in [group C + c][F][mag_width] at mag_col0
+//   InRing<StreamCall>    M_t is read where store_frame above writes it (columns [W - B, W) of the row's windows); the output row of
+//                         group g is its first stream, g C
+struct FrameMajorMasked {
+    FrameMajor f;
+    const float *mag_in;
+    int mag_width, mag_col0;
+};
+
+__device__ __forceinline__ RowFrames frames_of(const FrameMajorMasked &s, long row, int F, StreamCall &c) { return frames_of(s.f, row, F, c); }
+__device__ __forceinline__ float2 load_frame(const FrameMajorMasked &s, const RowFrames &r, const StreamCall &c, long row, int F, int bin, int t)
+{
+    return load_frame(s.f, r, c, row, F, bin, t);
+}
+__device__ __forceinline__ void store_frame(const FrameMajorMasked &s, const RowFrames &r, const StreamCall &c, long row, int F, int bin, int t,
+                                            float2 d, float m)
+{
+    store_frame(s.f, r, c, row, F, bin, t, d, m);
+}
+__device__ __forceinline__ float load_mag(const FrameMajorMasked &s, const RowFrames &, const StreamCall &, long row, int F, int bin, int t)
+{
+    return s.mag_in[(row * F + bin) * (long)s.mag_width + s.mag_col0 + (t - s.f.first_frame)];
+}
+template <class Rows>
+__device__ __forceinline__ float load_mag(const InRing<Rows> &s, const RowFrames &, const StreamCall &c, long row, int F, int bin, int t)
+{
+    const int st = t / s.g.B;
+    return s.y[((row * c.n_steps + (st - c.first)) * (long)F + bin) * s.g.W + (s.g.W - s.g.B) + (t - st * s.g.B)];
+}
+// the row group g's result goes to, of C rows per group
+__device__ __forceinline__ long out_row_of(const FrameMajorMasked &, long g, int) { return g; }
+template <class Rows>
+__device__ __forceinline__ long out_row_of(const InRing<Rows> &, long g, int C) { return g * C; }
+
 }  // namespace
 }  // namespace adn

@@ -33,7 +33,7 @@
 
 #include <stddef.h>
 
-/* The 75 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 78 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -914,7 +914,7 @@ ADN_API int adn_wpe_stream_pool(void *pool_state, size_t pool_state_bytes, int n
  * Limits (ADN_ERR_INVALID before any launch; a refused call writes nothing): those of adn_wpe_online with n_groups in n_rows'
  * place, and n_groups * channels < 2^31; everything adn_wpe_stream refuses, and n_streams % channels != 0.  ADN_ERR_WORKSPACE: a
  * state below adn_wpe_mc_stream_state_bytes.  Element offsets are 64-bit.
- * Combining the channels into one (offline only): the next section, "beamform".
+ * Combining the channels into one: "beamform" (offline) and "beamform stream" (live, on the same stream state) below.
  * Not here: the stream pool with multichannel streams; look-ahead; N > 32; any tuning by ear. */
 ADN_API int adn_wpe_mc_stream_state_bytes(int n_slots, int channels, int n_bins, const adn_wpe_stream_params *params, size_t *bytes);
 ADN_API int adn_wpe_mc_online(const float *spec, int n_groups, int channels, int n_frames, int n_bins, long first_frame,
@@ -982,14 +982,95 @@ ADN_API int adn_wpe_mc_stream(void *stream_state, size_t stream_state_bytes, flo
  * n_groups, n_frames, n_bins >= 1; n_groups * channels < 2^31; mag_width >= n_frames; width >= n_frames with a mag_out; overlap;
  * launch grid < 2^31 workgroups; the parameters as above.  ADN_ERR_WORKSPACE: workspace_bytes below adn_mvdr_workspace_bytes.
  * Element offsets are 64-bit.
- * Not here: streaming or recursive beamforming; GEV or rank-one variants; WPD (the joint convolutional beamformer); more than 8
- * channels; any tuning by ear. */
+ * Not here: streaming or recursive beamforming (that is the next section, "beamform stream"); GEV or rank-one variants; WPD (the
+ * joint convolutional beamformer); more than 8 channels; any tuning by ear. */
 typedef struct adn_mvdr_params { int ref_channel; float loading, mask_floor; } adn_mvdr_params;
 ADN_API int adn_mvdr_workspace_bytes(int n_groups, int channels, int n_frames, int n_bins, const adn_mvdr_params *params,
                                      size_t *bytes);
 ADN_API int adn_mvdr(const float *spec, const float *mag, int mag_width, int n_groups, int channels, int n_frames, int n_bins,
                      const adn_mvdr_params *params, void *workspace, size_t workspace_bytes, float *spec_out, float *mag_out,
                      int width, void *stream);
+
+/* ---- beamform stream: recursive covariances, one filter per refresh, for a recording that is still arriving ------------------------
+ * No reference counterpart and no checkpoint.  The library DEFINES the operator below (float64 restatement:
+ * tests/beamform_stream_ref.py); it is UNPINNED against any package.  It is to "beamform" what "dereverb stream multichannel" is
+ * to "dereverb multichannel": the two mask-weighted spatial covariances are carried on the device with a forgetting factor, updated
+ * once per frame, and the filter of "beamform" is solved from them every R frames.  It is causal.
+ * Not validated: forget 0.99 is a window of 100 frames, 1.6 s at hop 128 and 8 kHz -- a design value, not tuned by ear; the other
+ * defaults are "beamform"'s.
+ *
+ * A group is the C channels of one recording, 1 <= C <= 8; every (group, bin) is independent.  In fp32, with the rounding rules of
+ * "beamform" (no fp contraction; complex multiply-adds as two fmaf per component in that section's order; max / min that keep a
+ * NaN; correctly rounded division and square root):
+ *   frame 0 of a group:  Phi_s = Phi_n = +0
+ *   m_t, n_t             exactly "beamform"'s, from M_{t,c} and X_{t,c}, rho = mask_floor
+ *   for r >= k:          Phi_s[r][k] <- (m_t X_{t,r}) conj(X_{t,k}) + alpha (.) Phi_s[r][k];   Phi_n likewise with n_t
+ *   if t % R == 0:       w <- "beamform"'s filter from the current Phi_s, Phi_n: A = Phi_n + ((delta tr Phi_n) / C + 1e-30) I, one
+ *                        Cholesky, C columns, tau, w_c = G[c][ref] / tau.  The diagonal's imaginary part is dropped where
+ *                        "beamform" drops it -- at use, not in the carried sum
+ *   else:                w is the carried one
+ *   Y_t = sum_c conj(w_c) X_{t,c}                                              ("beamform"'s order)
+ *   optional M^out_t = sqrtf(fmaf(Yre, Yre, Yim * Yim))
+ * alpha (.) Phi: each component is multiplied by alpha and rounded once; that product is the addend of the complex multiply-add
+ * (re: u.x v.x, then u.y v.y; im: u.y v.x, then -u.x v.y).  With alpha = 1 the sums are therefore "beamform"'s own, bit for bit.
+ * Frame 0 always solves, so w is always defined.
+ * Parameters (adn_mvdr_stream_params; NULL = the defaults): ref_channel 0, refresh R 1, forget alpha 0.99, loading delta 1e-3,
+ * mask_floor rho 1e-3.  Legal (ADN_ERR_INVALID otherwise, before any launch, the message starts with the function's name and
+ * names the field; a NaN is illegal): 0 <= ref_channel < channels; 1 <= refresh <= 64; 0.9 <= forget <= 1; 1e-6 <= loading <= 1;
+ * 1e-6 <= mask_floor <= 0.25.
+ * Consequences: with forget = 1 and refresh = 1, Y_{T-1} equals adn_mvdr's Y_{T-1} on frames 0 ... T-1, bit for bit; with
+ * refresh = R the frames t % R == 0 equal the refresh = 1 run; with C = 1 the output equals X as values wherever "beamform" says so
+ * (every bin whose G is at least 1e-30); an all-zero group gives zeros; a non-finite value is confined to its own (group, bin),
+ * which stays poisoned from then on; a group whose first frame of the call is frame 0 starts fresh whatever the state holds: no
+ * reset, no sentinel.  There is no wind-up: the covariances decay, and no inverse is carried that could grow -- an exactly-zero
+ * stretch leaves Phi <- alpha Phi and a solve of whatever is left.
+ * Quality on the host (tests/test_beamform_stream_host.py, profiles/bench_beamform_stream.md): SI-SDR after the first second, float64
+ * restatement, defaults: microphone 0 as recorded 1.50 dB; streaming MVDR 5.08 / 7.59 / 7.22 dB at C = 2 / 4 / 8 (offline MVDR with
+ * the same mask 4.61 / 7.72 / 9.09).  Every row beats microphone 0 by more than 1 dB, and every row is asserted.
+ *
+ * What is pinned.  The result is bounded per (group, bin) against the float64 restatement (tests/test_gpu_beamform_stream.py:
+ * E <= 4 floor, the floor the largest E of the fp32 restatement of the same case, never below 2^-23).  Pinned bit for bit: two
+ * calls give the same result; any cut of a group's frames into calls; a group alone or in any batch, in whatever slot; a bin
+ * whichever other bins share the call; mag_out against sqrtf(fmaf(re, re, im * im)) of spec_out; the last frame against adn_mvdr at
+ * forget 1, refresh 1; the frames t % R == 0 against refresh 1; a lockstep stream (adn_mvdr_stream) against adn_mvdr_online on the
+ * same ring spectrogram and magnitudes.  NOT pinned: the bits against numpy; a permutation of the channels.  Deterministic: no
+ * atomics, no reduction across lanes.
+ *
+ * State (adn_mvdr_stream_state_bytes(n_slots, channels, n_bins, params), caller-owned, opaque, 8-byte aligned; host-only, and it
+ * validates everything about the parameters): per (slot, bin) the two packed lower triangles and w, 2 (C (C + 1) + C) floats,
+ * entry-major over the bins of a slot.  A slot is a GROUP.
+ *
+ * Two entry points, one step function:
+ *   adn_mvdr_online: spec (n_groups * channels, n_frames, n_bins, 2), the frames first_frame ... first_frame + n_frames - 1 of
+ *     every row, a group's channels consecutive rows; mag (n_groups * channels, 1, n_bins, mag_width), columns [mag_col0, mag_col0 +
+ *     n_frames) read; spec_out (n_groups, n_frames, n_bins, 2); mag_out (n_groups, 1, n_bins, width), may be NULL, columns [col0,
+ *     col0 + n_frames) written.  Group i uses slot i.  It writes those columns, all of spec_out, the state of its groups, and not
+ *     one byte else.  No output may overlap an input, the state or the other output.
+ *   adn_mvdr_stream: between adn_stream_analyze and adn_stream_emit, for an adn_stream_* state whose streams g C ... g C + C - 1
+ *     are group g (n_streams a multiple of channels; lookahead must be 0).  It reads X_{t,c} from every channel's ring cells and
+ *     M_{t,c} from columns [window - block, window) of every channel's windows in y -- where adn_spectral_gain_windows or
+ *     adn_wpe_mc_stream left it -- and writes Y_t into the ring cells and |Y_t| into the same columns of the windows of the
+ *     group's FIRST stream only (g C, whatever ref_channel is), and no other byte; nothing for frames at and past the end of a
+ *     finished stream.  The lanes that read a (group, bin, frame) are the ones that write it, so doing this in place is safe.
+ *     mvdr_state has n_streams / channels slots.  adn_stream_emit is unchanged: it then emits all streams, and the host keeps row
+ *     g C of each group; what the C - 1 unused rows cost is measured in profiles/bench_beamform_stream.md.
+ * Cost: one launch, n_groups x ceil(n_bins / B) workgroups of one wave, B = 16 bins up to C = 4 and 8 beyond; the covariances stay in
+ * registers for the whole call; no workspace, no atomics, no constant table (a capture may hold a first call); nothing blocks or
+ * allocates.  A call's time is the per-frame chain of a workgroup: profiles/bench_beamform_stream.md.
+ * Limits (ADN_ERR_INVALID before any launch; a refused call writes nothing): those of adn_wpe_mc_online and adn_wpe_mc_stream with
+ * the new arguments: NULL or misaligned mag; mag_col0 >= 0 and mag_col0 + n_frames <= mag_width; overlap.  ADN_ERR_WORKSPACE: a state
+ * below adn_mvdr_stream_state_bytes.  Element offsets are 64-bit.
+ * Not here: the stream pool with multichannel streams; GEV, rank-one or WPD variants; look-ahead; an emit that skips the unused
+ * channels; any tuning by ear. */
+typedef struct adn_mvdr_stream_params { int ref_channel, refresh; float forget, loading, mask_floor; } adn_mvdr_stream_params;
+ADN_API int adn_mvdr_stream_state_bytes(int n_slots, int channels, int n_bins, const adn_mvdr_stream_params *params, size_t *bytes);
+ADN_API int adn_mvdr_online(const float *spec, const float *mag, int mag_width, int mag_col0, int n_groups, int channels,
+                            int n_frames, int n_bins, long first_frame, const adn_mvdr_stream_params *params, void *state,
+                            size_t state_bytes, int n_slots, float *spec_out, float *mag_out, int width, int col0, void *stream);
+ADN_API int adn_mvdr_stream(void *stream_state, size_t stream_state_bytes, float *y, int n_streams, int channels, long first_step,
+                            int n_steps, long final_length, int n_fft, int hop, int window, int block, int lookahead,
+                            int max_steps, const adn_mvdr_stream_params *params, void *mvdr_state, size_t mvdr_state_bytes,
+                            void *stream);
 
 /* ---- environment switches -------------------------------------------------------------------------------------------------
  * Read ONCE, when a U-Net handle is created (never per call).  None is needed in production: the defaults are the measured best
