@@ -11,7 +11,8 @@ __all__ = ["UNet", "SpectrogramDataset", "WavToSpecDataset", "audio_to_magnitude
            "snr", "si_sdr", "seg_snr", "stoi", "evaluate", "SpectralDenoiser", "SpectralParams",
            "StreamSpectralDenoiser", "SpectralStreamPool", "spectral_gain_windows", "Dereverberator", "WpeParams",
            "WpeStreamParams", "wpe_online", "StreamDereverberator", "DereverbStreamPool", "Beamformer", "MvdrParams", "mvdr",
-           "MvdrStreamParams", "mvdr_online", "mvdr_stream_state_bytes", "StreamBeamformer"]
+           "MvdrStreamParams", "mvdr_online", "mvdr_stream_state_bytes", "StreamBeamformer",
+           "BeamformStreamPool"]
 # (resample / reverb themselves: audiodenoiser_amd.resample.resample, audiodenoiser_amd.reverb.reverb -- the modules own the names)
 
 
@@ -40,7 +41,8 @@ def __getattr__(name):
     if name in ("Dereverberator", "WpeParams", "WpeStreamParams", "wpe_online", "StreamDereverberator", "DereverbStreamPool"):
         import importlib
         return getattr(importlib.import_module(".dereverb", __name__), name)
-    if name in ("Beamformer", "MvdrParams", "mvdr", "MvdrStreamParams", "mvdr_online", "mvdr_stream_state_bytes", "StreamBeamformer"):
+    if name in ("Beamformer", "MvdrParams", "mvdr", "MvdrStreamParams", "mvdr_online", "mvdr_stream_state_bytes", "StreamBeamformer",
+                "BeamformStreamPool"):
         import importlib
         return getattr(importlib.import_module(".beamform", __name__), name)
     if name in ("StreamDenoiser", "StreamPool"):

@@ -114,12 +114,14 @@ def load() -> ctypes.CDLL:
         L.adn_wpe_mc_stream_state_bytes.argtypes = [ci, ci, ci, wsp, ctypes.POINTER(sz)]
         L.adn_wpe_mc_online.argtypes = [vp, ci, ci, ci, ci, cl, wsp, vp, sz, ci, vp, vp, ci, ci, vp]
         L.adn_wpe_mc_stream.argtypes = [vp, sz, vp, ci, ci, cl, ci, cl, ci, ci, ci, ci, ci, ci, wsp, vp, sz, vp]
+        L.adn_wpe_mc_stream_pool.argtypes = [vp, sz, ci, ci, ci, ci, ci, ci, ci, cl, vp, ci, vp, wsp, vp, sz, vp]
         L.adn_mvdr_workspace_bytes.argtypes = [ci, ci, ci, ci, ctypes.POINTER(MvdrParamsStruct), ctypes.POINTER(sz)]
         L.adn_mvdr.argtypes = [vp, vp, ci, ci, ci, ci, ci, ctypes.POINTER(MvdrParamsStruct), vp, sz, vp, vp, ci, vp]
         msp = ctypes.POINTER(MvdrStreamParamsStruct)
         L.adn_mvdr_stream_state_bytes.argtypes = [ci, ci, ci, msp, ctypes.POINTER(sz)]
         L.adn_mvdr_online.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, cl, msp, vp, sz, ci, vp, vp, ci, ci, vp]
         L.adn_mvdr_stream.argtypes = [vp, sz, vp, ci, ci, cl, ci, cl, ci, ci, ci, ci, ci, ci, msp, vp, sz, vp]
+        L.adn_mvdr_stream_pool.argtypes = [vp, sz, ci, ci, ci, ci, ci, ci, ci, cl, vp, ci, vp, msp, vp, sz, vp]
         for name in ("adn_device_count", "adn_prepare", "adn_unet_create", "adn_unet_create_ex", "adn_unet_create_general", "adn_unet_channels",
                      "adn_unet_set_batch_invariant", "adn_unet_destroy", "adn_unet_workspace_bytes", "adn_unet_forward", "adn_unet_forward_taps", "adn_unet_set_timing", "adn_unet_get_timing",
                      "adn_stft_n_frames", "adn_stft_mag", "adn_stft_mag_fit", "adn_quantize_pad", "adn_per_clip_l1",
@@ -138,9 +140,9 @@ def load() -> ctypes.CDLL:
                      "adn_spectral_gain", "adn_spectral_gain_windows", "adn_wpe_workspace_bytes", "adn_wpe",
                      "adn_wpe_mc_workspace_bytes", "adn_wpe_mc",
                      "adn_wpe_stream_state_bytes", "adn_wpe_online", "adn_wpe_stream", "adn_wpe_stream_pool",
-                     "adn_wpe_mc_stream_state_bytes", "adn_wpe_mc_online", "adn_wpe_mc_stream",
+                     "adn_wpe_mc_stream_state_bytes", "adn_wpe_mc_online", "adn_wpe_mc_stream", "adn_wpe_mc_stream_pool",
                      "adn_mvdr_workspace_bytes", "adn_mvdr",
-                     "adn_mvdr_stream_state_bytes", "adn_mvdr_online", "adn_mvdr_stream"):
+                     "adn_mvdr_stream_state_bytes", "adn_mvdr_online", "adn_mvdr_stream", "adn_mvdr_stream_pool"):
             getattr(L, name).restype = ci
         _lib = L
         return L
@@ -224,7 +226,7 @@ EXPORTED_SYMBOLS = (
     "adn_spectral_gain", "adn_spectral_gain_windows", "adn_wpe_workspace_bytes", "adn_wpe",
     "adn_wpe_mc_workspace_bytes", "adn_wpe_mc",
     "adn_wpe_stream_state_bytes", "adn_wpe_online", "adn_wpe_stream", "adn_wpe_stream_pool",
-    "adn_wpe_mc_stream_state_bytes", "adn_wpe_mc_online", "adn_wpe_mc_stream",
+    "adn_wpe_mc_stream_state_bytes", "adn_wpe_mc_online", "adn_wpe_mc_stream", "adn_wpe_mc_stream_pool",
     "adn_mvdr_workspace_bytes", "adn_mvdr",
-    "adn_mvdr_stream_state_bytes", "adn_mvdr_online", "adn_mvdr_stream",
+    "adn_mvdr_stream_state_bytes", "adn_mvdr_online", "adn_mvdr_stream", "adn_mvdr_stream_pool",
 )

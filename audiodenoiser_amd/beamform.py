@@ -39,6 +39,15 @@ factor, updated once per frame, the same filter solved from them every ``refresh
 ``adn_stream_emit`` then resynthesises every stream and the object keeps row ``g C`` of each group.  ``mvdr_online`` is the
 recursion on spectrograms.
 
+``BeamformStreamPool`` is the same chain for many recordings with independent timing (``adn_wpe_mc_stream_pool``,
+``adn_mvdr_stream_pool``): a recording is ``C`` consecutive streams of a ``StreamPool``, the ready recordings of a tick go through
+one launch per kernel, and only the first row of each is resynthesised -- the pool's emit takes a row table, so the ``C - 1``
+unused channels are never emitted.
+
+    pool = BeamformStreamPool(max_recordings=16, channels=4)
+    rid = pool.open(); pool.push(rid, block); pool.close(rid)        # block (4, m)
+    for rid, mono, finished in pool.step(): ...                      # mono (k,)
+
     sb = StreamBeamformer(n_streams=4, channels=4)     # one recording of four microphones, 8 kHz, block of 4 frames
     mono = sb.push(block)                              # (4, m) -> (k,): what has become final
     tail = sb.flush()
@@ -47,7 +56,7 @@ recursion on spectrograms.
 The rate handling is ``Denoiser``'s: resample in, resample out, the input's sample count.  The defaults (reference channel 0,
 loading 1e-3, mask floor 1e-3) are the values of the host prototype (``profiles/bench_beamform.md``); they were not tuned by ear.
 
-What is NOT here: multichannel streams in a pool, look-ahead, GEV or rank-one variants, WPD, more than 8 channels.  There is no CPU path.
+What is NOT here: pools that mix channel counts, look-ahead, GEV or rank-one variants, WPD, more than 8 channels.  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -64,12 +73,13 @@ from .baseline import SpectralParams, _gain_kept_columns, _spectral_params, spec
 from .denoise import Denoiser
 from .dereverb import (WpeParams, WpeStreamParams, _check_channels, _joint_params, _joint_stream_params, _mag_buffer, _need_cells,
                        _spec_dims, _state_bytes, wpe_joint)
-from .stream import StreamDenoiser, _check_stream_args, causal_carrier
+from .stream import POOL_MAX_ROWS, RecordingBook, StreamDenoiser, StreamPool, _check_stream_args, causal_carrier
 from .griffin_lim import stft_complex
 from .resample import _resample_device
 from .wav import read_wav, write_wav
 
-__all__ = ["MvdrParams", "mvdr", "Beamformer", "MvdrStreamParams", "mvdr_stream_state_bytes", "mvdr_online", "StreamBeamformer"]
+__all__ = ["MvdrParams", "mvdr", "Beamformer", "MvdrStreamParams", "mvdr_stream_state_bytes", "mvdr_online", "StreamBeamformer",
+           "BeamformStreamPool"]
 
 
 @dataclasses.dataclass(frozen=True)
@@ -327,6 +337,92 @@ class StreamBeamformer(StreamDenoiser):
         out = self._cat(outs)[::self.channels]
         out = out[0] if out.shape[0] == 1 else out.contiguous()
         return out.cpu().numpy() if self._numpy else out
+
+
+class BeamformStreamPool(StreamPool):
+    """``StreamPool`` over RECORDINGS of ``channels`` microphones with the streaming beamformer in the network's place: recordings
+    that open, stall, close and run at their own rates, the ready ones batched into one launch per kernel.
+
+        pool = BeamformStreamPool(max_recordings=16, channels=4)
+        rid = pool.open()                                  # or open(input_rate=48000) with input_rates=(48000,)
+        pool.push(rid, block)                              # (4, m): the next samples of every microphone
+        for rid, mono, finished in pool.step(): ...        # (k,): what has become final of the ONE enhanced channel
+
+    Recording ``r`` owns the stream slots ``r C ... r C + C - 1`` of the pool state and slot ``r`` of the MVDR (and WPE) state
+    (``stream.RecordingBook``; ``include/adn.h``, ``adn_mvdr_stream_pool``).  A tick analyses the ``C`` rows of every ready
+    recording and then, in place on the windows and ``256 // C`` recordings a call: with ``wpe=True``
+    ``adn_wpe_mc_stream_pool`` (``wpe_params=None``: ``taps = 32 // C``); ``adn_spectral_gain_windows`` on every row, the mask's
+    magnitudes (``mask_params``); ``adn_mvdr_stream_pool`` (``params``).  It keeps the first window of each recording, runs the
+    optional output gain (``gain_params``, a state per recording) and ``adn_stream_pool_emit`` on those rows alone: the other
+    ``C - 1`` channels are never resynthesised, which is safe because an emit writes nothing but its own slot's overlap-add tail and
+    only that slot's later emits read it.  A recording at an ``input_rate`` comes in through ``C`` rows of
+    ``adn_stream_pool_push_rate`` and goes out through one of ``adn_stream_pool_emit_rate``.
+
+    Claimed: every recording is, bit for bit, what a solo ``StreamBeamformer(n_streams=C, channels=C, input_rate=...)`` returns for
+    the same samples, whatever its neighbours do; it returns as many samples as came in; a recording's slots are reusable without a
+    reset.  Not claimed: pools that mix channel counts; more than one step per recording and tick; graph capture of a tick."""
+
+    def __init__(self, device=None, max_recordings: int = 16, channels: int = 2, backlog_steps: int = 4, sample_rate: int = 8000,
+                 n_fft: int = 512, hop_length: int = 128, block_frames: int = 4, params: MvdrStreamParams = None,
+                 mask_params: SpectralParams = None, wpe: bool = False, wpe_params: WpeStreamParams = None, gain: bool = False,
+                 gain_params: SpectralParams = None, input_rates=None):
+        who = "BeamformStreamPool"
+        window, ahead, _ = causal_carrier(block_frames)
+        self.params = _mvdr_stream_params(who, params, channels)
+        self.book = RecordingBook(max_recordings, channels, backlog_steps, n_fft, hop_length, window, block_frames, ahead, input_rates,
+                                  sample_rate)
+        self.mask_params = _spectral_params(who, mask_params, "mask_params")
+        self.gain_params = _spectral_params(who, gain_params, "gain_params")
+        self.wpe, self.gain = bool(wpe), bool(gain)
+        if wpe_params is not None and not isinstance(wpe_params, WpeStreamParams):
+            raise TypeError(f"{who}: wpe_params must be a WpeStreamParams")
+        self.wpe_params = _joint_stream_params(who, wpe_params, channels) if self.wpe else None
+        dev = rocm_device(who, device)
+        self.model = None
+        self.batch_windows = POOL_MAX_ROWS
+        f = n_fft // 2 + 1
+        self._mvdr_state = torch.empty((mvdr_stream_state_bytes(max_recordings, channels, f, self.params),), dtype=torch.uint8, device=dev)
+        self._mask_state = torch.empty((max_recordings * channels, 3, f), dtype=torch.float32, device=dev)
+        self._gain_state = torch.empty((max_recordings, 3, f), dtype=torch.float32, device=dev)
+        self._wpe_state = None
+        if self.wpe:
+            need = _state_bytes(who, max_recordings, None if channels == 1 else channels, f, self.wpe_params)
+            self._wpe_state = torch.empty((need,), dtype=torch.uint8, device=dev)
+        self._setup(dev)
+
+    def reset(self):
+        """Forget every recording, both gains' noise estimates included: all slots are free."""
+        super().reset()
+        self._mask_state.fill_(-1.0)
+        self._gain_state.fill_(-1.0)
+
+    def network(self, x):
+        raise RuntimeError("BeamformStreamPool: there is no network; the beamformer runs between analyze and emit (adn_mvdr_stream_pool)")
+
+    def _emit_rows(self, rows):
+        return rows[::self.channels]
+
+    def _net(self, x: torch.Tensor, rows) -> torch.Tensor:
+        """The tick's stream rows ``rows`` (``C`` per recording) and their windows ``x`` -> the first window of each recording,
+        compacted, holding ``|Y|`` (or the output gain's result) in the kept columns."""
+        L, C, plan = _lib.load(), self.channels, self.book.plan
+        lead = (self._state.data_ptr(), self._state.numel(), self._args[0], C) + self._args[1:]
+        p = ctypes.byref(self.params.to_struct()) if self.params is not None else None
+        per = POOL_MAX_ROWS // C * C                         # whole recordings
+        for i in range(0, len(rows), per):
+            part, group = x[i:i + per], rows[i:i + per]
+            with torch.cuda.device(self.device):
+                if self.wpe:
+                    _lib.check(L.adn_wpe_mc_stream_pool(*lead, self._rows(group), len(group), part.data_ptr(),
+                                                        ctypes.byref(self.wpe_params.to_struct()), self._wpe_state.data_ptr(),
+                                                        self._wpe_state.numel(), current_stream(self.device)), "adn_wpe_mc_stream_pool")
+                _gain_kept_columns(part, group, 1, self._mask_state, plan, self.mask_params)
+                _lib.check(L.adn_mvdr_stream_pool(*lead, self._rows(group), len(group), part.data_ptr(), p, self._mvdr_state.data_ptr(),
+                                                  self._mvdr_state.numel(), current_stream(self.device)), "adn_mvdr_stream_pool")
+        y = x[::C].contiguous()
+        if self.gain:                                        # a state per recording: slot // C
+            _gain_kept_columns(y, [(slot // C, k, final) for slot, k, final in rows[::C]], 1, self._gain_state, plan, self.gain_params)
+        return y
 
 
 class Beamformer(Denoiser):

@@ -914,6 +914,26 @@ static int pool_rows(const char *who, const PoolState &p, int n_slots, const adn
     return ADN_OK;
 }
 
+// The rows of a call on RECORDINGS of `channels` streams (adn.h, adn_wpe_mc_stream_pool), pool_rows passed: recording r owns
+// the slots r C ... r C + C - 1, a group is C consecutive rows that name them in channel order and agree in step and final_length.
+static int pool_recordings(const char *who, int n_slots, int channels, const adn_stream_pool_row *rows, int n_rows)
+{
+    const std::string w(who);
+    if (n_slots % channels) return fail(ADN_ERR_INVALID, w + ": n_slots must be a multiple of channels");
+    if (n_rows % channels) return fail(ADN_ERR_INVALID, w + ": n_rows must be a multiple of channels (a recording is channels consecutive rows)");
+    for (int i = 0; i < n_rows; i += channels) {
+        if (rows[i].slot % channels)
+            return fail(ADN_ERR_INVALID, w + ": a group's first slot must be a multiple of channels (recording r owns slots r channels ...)");
+        for (int c = 1; c < channels; ++c) {
+            if (rows[i + c].slot != rows[i].slot + c)
+                return fail(ADN_ERR_INVALID, w + ": a group's slots must be consecutive, in channel order");
+            if (rows[i + c].step != rows[i].step || rows[i + c].final_length != rows[i].final_length)
+                return fail(ADN_ERR_INVALID, w + ": the rows of a group must agree in step and final_length");
+        }
+    }
+    return ADN_OK;
+}
+
 int adn_stream_pool_state_bytes(int n_slots, int n_fft, int hop, int window, int block, int lookahead, long ring_samples, size_t *bytes)
 {
     PoolState p;
@@ -1188,6 +1208,30 @@ int adn_wpe_stream_pool(void *pstate, size_t pstate_bytes, int n_slots, int n_ff
     return ADN_OK;
 }
 
+// The pool's rows are the channels of recordings: the checks of the pool call, of the joint parameters and of the groups.
+int adn_wpe_mc_stream_pool(void *pstate, size_t pstate_bytes, int n_slots, int channels, int n_fft, int hop, int window, int block,
+                           int lookahead, long ring_samples, const adn_stream_pool_row *rows, int n_rows, float *y,
+                           const adn_wpe_stream_params *params, void *wpe_state, size_t wpe_state_bytes, void *stream)
+{
+    const WpeCall c = {"adn_wpe_mc_stream_pool", "n_groups", "group", "adn_wpe_mc_stream_state_bytes", joint_default_taps(channels)};
+    const std::string w(c.name);
+    PoolState p;
+    adn::StreamPoolRows t = {};
+    adn::WpeStreamConsts k;
+    int max_new, max_span;
+    long max_out;
+    ADN_TRY(pool_state(c.name, pstate, pstate_bytes, n_slots, n_fft, hop, window, block, lookahead, ring_samples, &p));
+    if (lookahead != 0) return fail(ADN_ERR_INVALID, w + ": the operator is causal: lookahead must be 0");
+    if (!y) return fail(ADN_ERR_INVALID, w + ": null pointer");
+    if (!aligned_to(y, 4)) return fail(ADN_ERR_INVALID, w + ": y must be 4-byte aligned");
+    ADN_TRY(pool_rows(c.name, p, n_slots, rows, n_rows, &t, &max_new, &max_span, &max_out));
+    ADN_TRY(wpe_stream_consts(c.name, channels, params, c.default_taps, &k));
+    ADN_TRY(pool_recordings(c.name, n_slots, channels, rows, n_rows));
+    ADN_TRY(wpe_stream_state(c, wpe_state, wpe_state_bytes, n_slots / channels, n_fft / 2 + 1, channels, k));
+    ADN_LAUNCH(adn::launch_wpe_mc_stream_pool(static_cast<float *>(pstate), y, channels, p.g, t, k, static_cast<float *>(wpe_state),
+                                              static_cast<hipStream_t>(stream)), c.name);
+    return ADN_OK;
+}
 
 static const char *resample_stream_text =": rates must be >= 1 with max(up, down) <= 4096 after dividing by their gcd, and at most "
                                           "16384 carried samples (2 floor(half / up) + ceil(down / up) + 1)";
@@ -1373,6 +1417,30 @@ int adn_mvdr_stream(void *sstate, size_t sstate_bytes, float *y, int n_streams, 
         return fail(ADN_ERR_INVALID, w + ": grid too large (n_groups x ceil(n_bins / bins per workgroup) >= 2^31)");
     ADN_LAUNCH(adn::launch_mvdr_stream(static_cast<float *>(sstate), y, n_streams, channels, g, call, k,
                                        static_cast<float *>(mvdr_state), static_cast<hipStream_t>(stream)), "adn_mvdr_stream");
+    return ADN_OK;
+}
+
+int adn_mvdr_stream_pool(void *pstate, size_t pstate_bytes, int n_slots, int channels, int n_fft, int hop, int window, int block,
+                         int lookahead, long ring_samples, const adn_stream_pool_row *rows, int n_rows, float *y,
+                         const adn_mvdr_stream_params *params, void *mvdr_state, size_t mvdr_state_bytes, void *stream)
+{
+    const char *who = "adn_mvdr_stream_pool";
+    const std::string w(who);
+    PoolState p;
+    adn::StreamPoolRows t = {};
+    adn::MvdrStreamConsts k;
+    int max_new, max_span;
+    long max_out;
+    ADN_TRY(pool_state(who, pstate, pstate_bytes, n_slots, n_fft, hop, window, block, lookahead, ring_samples, &p));
+    if (lookahead != 0) return fail(ADN_ERR_INVALID, w + ": the operator is causal: lookahead must be 0");
+    if (!y) return fail(ADN_ERR_INVALID, w + ": null pointer");
+    if (!aligned_to(y, 4)) return fail(ADN_ERR_INVALID, w + ": y must be 4-byte aligned");
+    ADN_TRY(pool_rows(who, p, n_slots, rows, n_rows, &t, &max_new, &max_span, &max_out));
+    ADN_TRY(mvdr_stream_consts(who, channels, params, &k));
+    ADN_TRY(pool_recordings(who, n_slots, channels, rows, n_rows));
+    ADN_TRY(mvdr_stream_state(w, mvdr_state, mvdr_state_bytes, n_slots / channels, n_fft / 2 + 1, channels));
+    ADN_LAUNCH(adn::launch_mvdr_stream_pool(static_cast<float *>(pstate), y, channels, p.g, t, k, static_cast<float *>(mvdr_state),
+                                            static_cast<hipStream_t>(stream)), who);
     return ADN_OK;
 }
 

@@ -598,6 +598,10 @@ hipError_t launch_wpe_stream(float *state, float *y, int n_streams, int C, const
 // a pool's rows are single-channel streams: C is fixed at 1
 hipError_t launch_wpe_stream_pool(float *state, float *y, const StreamGeom &g, const StreamPoolRows &rows, const WpeStreamConsts &c,
                                   float *wstate, hipStream_t st);
+// a pool's RECORDINGS: C consecutive rows are the channels of one, their slots r C ... r C + C - 1 in channel order and their steps
+// equal (the caller has checked it); wstate slot r.  C = 1 is launch_wpe_stream_pool.
+hipError_t launch_wpe_mc_stream_pool(float *state, float *y, int C, const StreamGeom &g, const StreamPoolRows &rows,
+                                     const WpeStreamConsts &c, float *wstate, hipStream_t st);
 // Streaming beamformer (beamform_stream_kernels.hip; adn.h, "beamform stream"): the recursion of the two covariances of "beamform",
 // one update per frame, a filter every R frames, for the C consecutive rows of a group, 1 <= C <= 8.  MvdrStreamConsts: MvdrConsts,
 // the refresh period R and the forgetting factor.  state: mvdr_stream_record_floats(C) = 2 (C (C + 1) + C) floats per (slot, bin) --
@@ -618,6 +622,9 @@ hipError_t launch_mvdr_online(const void *spec, const float *mag, int mag_width,
                               int col0, hipStream_t st);
 hipError_t launch_mvdr_stream(float *sstate, float *y, int n_streams, int C, const StreamGeom &g, const StreamCall &call,
                               const MvdrStreamConsts &k, float *state, hipStream_t st);
+// the same for a pool's recordings, as launch_wpe_mc_stream_pool: Y_t and |Y_t| over the first row of each group
+hipError_t launch_mvdr_stream_pool(float *sstate, float *y, int C, const StreamGeom &g, const StreamPoolRows &rows,
+                                   const MvdrStreamConsts &k, float *state, hipStream_t st);
 hipError_t launch_quantize_pad(const float *in, int n, int h, int w, float *out, int H, int W, hipStream_t st);
 hipError_t launch_per_clip_l1(const float *a, const float *b, int n_clips, long elems, float *out, hipStream_t st);
 // Polyphase resampler and SNR mixer (resample_kernels.hip).  resample_ratio: up / down of a rate pair, false outside the limits

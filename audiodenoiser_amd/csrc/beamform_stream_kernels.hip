@@ -25,6 +25,9 @@
 // (the head of beamform_kernels.hip).  Every barrier is the wave's own.
 // In place (the ring source): the lanes that read the cells and the magnitudes of a (group, bin, frame) belong to the workgroup
 // that writes Y_t and |Y_t| over channel 0's, behind the barrier of stage 1; frame t + 1, fetched early, lives in other cells.
+// A pool's recordings (InRing<StreamPoolRows>): the C rows of group g name the stream slots r C ... r C + C - 1, which the entry
+// point has checked; the ring cells are those slots', the state slot is r, the windows of y are the rows' (wpe_stream_frames.h,
+// "groups of C rows").  Y_t and |Y_t| go over the group's first row only, as in lockstep.
 // Bit guarantees (adn.h).  Everything of a (group, bin) is computed by its own lanes from LDS cells addressed by the bin's slot in
 // the tile only as an offset: no value depends on the slot, on the tile's other bins or on the group's place in the batch.  Lanes
 // past the last bin walk the last bin again and store nothing.  No atomics, no workspace, no constant table.
@@ -70,12 +73,12 @@ __global__ __launch_bounds__(MS_THREADS) void mvdr_stream_kernel(Src src, MvdrSt
     const int sc = stager ? tid / BINS : 0, sb = tid % BINS;
     const int sbin = b0 + sb < F ? b0 + sb : F - 1;
     const long srow = grp * C + sc;
-    const RowFrames rs{srow, t0, t1};
+    const RowFrames rs{chan_slot_of(src, srow), t0, t1};
     // the lane that forms Y_t of bin ib
     const int ib = tid % BINS;
     const bool writer = tid < BINS && b0 + ib < F;
     const long orow = out_row_of(src, grp, C);
-    const RowFrames ro{orow, t0, t1};
+    const RowFrames ro{chan_slot_of(src, orow), t0, t1};
     // one group of LPB lanes per bin: bin gb; lane gl has entries gl, gl + LPB, ... of the packed triangle, (row r, column k <= r)
     const int gb = tid / LPB, gl = tid % LPB;
     const bool live = b0 + gb < F;
@@ -88,7 +91,7 @@ __global__ __launch_bounds__(MS_THREADS) void mvdr_stream_kernel(Src src, MvdrSt
         if (e < E) wpe_tri_block(e, er[j], ek[j]);
     }
 
-    float2 *st = state + grp * (long)(2 * E + C) * F;
+    float2 *st = state + group_slot_of(src, grp, C) * (long)(2 * E + C) * F;
     float2 as[EPL], an[EPL];
 #pragma unroll
     for (int j = 0; j < EPL; ++j) {
@@ -253,6 +256,15 @@ hipError_t launch_mvdr_stream(float *sstate, float *y, int n_streams, int C, con
     if (call.f_last < call.f_first) return hipSuccess;
     InRing<StreamCall> src{sstate, y, g, call};
     return launch(src, n_streams / C, C, g.n_fft / 2 + 1, k, state, st);
+}
+
+// rows.n / C recordings of C consecutive rows each (wpe_stream_frames.h, "groups of C rows")
+hipError_t launch_mvdr_stream_pool(float *sstate, float *y, int C, const StreamGeom &g, const StreamPoolRows &rows,
+                                   const MvdrStreamConsts &k, float *state, hipStream_t st)
+{
+    if (C < 1 || rows.n < C || rows.n % C) return hipErrorInvalidValue;
+    InRing<StreamPoolRows> src{sstate, y, g, rows};
+    return launch(src, rows.n / C, C, g.n_fft / 2 + 1, k, state, st);
 }
 
 }  // namespace adn

@@ -35,6 +35,10 @@
 //   FrameMajor            spec / spec_out [group C + c][frame][F] float2, mag_out [group C + c][F][width] at col0
 //   InRing<StreamCall>    the X rings of an adn_stream_* state whose streams g C ... g C + C - 1 are group g, in place; M_t into
 //                         columns [W - B, W) of each channel's windows.  Slot = group.
+//   InRing<StreamPoolRows> the same for a table of (slot, step, final_length) rows, C consecutive rows a recording: channel c of
+//                         group g is ring slot rows[g C + c].slot, the state slot is rows[g C].slot / C, the windows of y are row
+//                         g C + c.  The entry point has checked that a group's slots are r C ... r C + C - 1 in this order and
+//                         that its rows agree in step and final_length, so the frames of the first row are every channel's.
 // A channel of a group is a row of those structs, so a joint stream and C single-channel ones address the same cells.  The step
 // is one function, compiled with fp contraction off, every multiply-add an explicit fmaf: a lockstep stream equals
 // adn_wpe_mc_online on the same spectrogram bit for bit.
@@ -152,15 +156,15 @@ __global__ __launch_bounds__(WS_G * WS_GROUPS) void wpe_mc_stream_kernel(Src src
     const int K = c.K, N = C * K, H = c.D + K;
 
     // every channel of a group covers the same frames: those of its first one.  Lane r < C speaks for channel r, row g C + r of
-    // the frame source; the state slot is the group.
+    // the frame source; where its ring slot and the group's state slot are is the source's to say (wpe_stream_frames.h).
     StreamCall call;
     const RowFrames r0 = frames_of(src, g * C, F, call);
     const long chan = g * C + (r < C ? r : 0);
-    const RowFrames rc{chan, r0.t0, r0.t1};
+    const RowFrames rc{chan_slot_of(src, chan), r0.t0, r0.t1};
     const bool mine = live && r < C;
     const bool fresh = r0.t0 == 0;
     const long rec = 2L * N * N + 2L * N * C + 2L * C * H + 2;   // wpe_stream_record_floats(C, K, D)
-    float *st = wstate + (g * F + (live ? bin : 0)) * rec;
+    float *st = wstate + (group_slot_of(src, g, C) * F + (live ? bin : 0)) * rec;
     float2 *stP = reinterpret_cast<float2 *>(st), *stG = stP + N * N, *stH = stG + N * C;
     float *stS = reinterpret_cast<float *>(stH + C * H);
 
@@ -232,6 +236,16 @@ hipError_t launch_wpe_stream(float *state, float *y, int n_streams, int C, const
     if (call.f_last < call.f_first) return hipSuccess;
     InRing<StreamCall> src{state, y, g, call};
     return launch(src, n_streams / C, C, g.n_fft / 2 + 1, c, wstate, st);
+}
+
+// rows.n / C recordings of C consecutive rows each; C = 1 is the single-channel pool's kernel, its bits
+hipError_t launch_wpe_mc_stream_pool(float *state, float *y, int C, const StreamGeom &g, const StreamPoolRows &rows,
+                                     const WpeStreamConsts &c, float *wstate, hipStream_t st)
+{
+    if (C == 1) return launch_wpe_stream_pool(state, y, g, rows, c, wstate, st);
+    if (C < 1 || rows.n < C || rows.n % C) return hipErrorInvalidValue;
+    InRing<StreamPoolRows> src{state, y, g, rows};
+    return launch(src, rows.n / C, C, g.n_fft / 2 + 1, c, wstate, st);
 }
 
 }  // namespace adn

@@ -197,7 +197,7 @@ hipError_t launch_wpe_stream_1ch(float *state, float *y, int n_streams, const St
     return launch(src, n_streams, g.n_fft / 2 + 1, c, wstate, st);
 }
 
-// the pool's rows are single-channel streams: C is fixed at 1 here (a joint pool would be launch(src, rows.n / C, C, ...) of
+// the pool's rows are single-channel streams: C is fixed at 1 here (a pool of recordings is launch_wpe_mc_stream_pool of
 // dereverb_mc_stream_kernels.hip on the same source)
 hipError_t launch_wpe_stream_pool(float *state, float *y, const StreamGeom &g, const StreamPoolRows &rows, const WpeStreamConsts &c,
                                   float *wstate, hipStream_t st)

@@ -135,5 +135,23 @@ __device__ __forceinline__ long out_row_of(const FrameMajorMasked &, long g, int
 template <class Rows>
 __device__ __forceinline__ long out_row_of(const InRing<Rows> &, long g, int C) { return g * C; }
 
+// ---------------------------------------------------------------------------------------------- groups of C rows
+// The joint kernels (dereverb_mc_stream_kernels.hip, beamform_stream_kernels.hip) work on GROUPS of C consecutive rows and keep
+// one operator-state slot per group.  Two lookups say where a group's things are; overloads on the source, so that the frame-major
+// and the lockstep instantiations stay the code they were (row = ring slot, group = state slot):
+//   chan_slot_of    the ring slot of row `row` (= g C + c)
+//   group_slot_of   the operator-state slot of group g
+// A pool's rows name their slots: a recording r owns the stream slots r C ... r C + C - 1 in channel order (the entry points refuse
+// every other table), so its channel c is slot_of(rows, g C + c) and its operator-state slot is slot_of(rows, g C) / C.  The
+// window row in y stays the row index in every source.
+__device__ __forceinline__ long chan_slot_of(const FrameMajor &, long row) { return row; }
+__device__ __forceinline__ long chan_slot_of(const FrameMajorMasked &, long row) { return row; }
+template <class Rows>
+__device__ __forceinline__ long chan_slot_of(const InRing<Rows> &s, long row) { return slot_of(s.rows, row); }
+__device__ __forceinline__ long group_slot_of(const FrameMajor &, long g, int) { return g; }
+__device__ __forceinline__ long group_slot_of(const FrameMajorMasked &, long g, int) { return g; }
+__device__ __forceinline__ long group_slot_of(const InRing<StreamCall> &, long g, int) { return g; }
+__device__ __forceinline__ long group_slot_of(const InRing<StreamPoolRows> &s, long g, int C) { return slot_of(s.rows, g * C) / C; }
+
 }  // namespace
 }  // namespace adn

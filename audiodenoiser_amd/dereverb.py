@@ -50,9 +50,11 @@ multichannel"; float64 restatement: ``tests/dereverb_mc_stream_ref.py``; ``csrc/
 consecutive streams are one recording, an N x N matrix with ``N = C * taps <= 32`` and N x C taps per (recording, bin), one
 variance shared by the channels; ``adn_wpe_mc_stream`` stands in ``adn_wpe_stream``'s place and nothing else changes.
 ``params=None`` takes ``taps = 32 // C``.  With more than one channel ``2 N (1 - forget) <= 1`` must hold (the header says why).
-``wpe_online_joint`` is the recursion on spectrograms.
+``wpe_online_joint`` is the recursion on spectrograms.  ``DereverbStreamPool(channels=C)`` serves many such recordings with
+independent timing: recording ``r`` owns ``C`` consecutive stream slots of the pool and one slot of the joint state, and
+``adn_wpe_mc_stream_pool`` runs the ready ones in one launch (``stream.RecordingBook``).
 
-What is NOT here: multichannel streams in ``DereverbStreamPool`` (it stays single-channel), look-ahead or iterated online
+What is NOT here: pools that mix channel counts, look-ahead or iterated online
 variants, any tuning of the defaults by ear.  Combining the channels into one is ``audiodenoiser_amd.beamform`` (``Beamformer``,
 ``wpe=True`` puts ``wpe_joint`` in front of it).  There is no CPU path.
 """
@@ -70,7 +72,7 @@ from ._host import check_stft_plan, current_stream, rocm_device, run_files, run_
 from .baseline import SpectralParams, _gain_kept_columns, _spectral_params, spectral_gain
 from .denoise import Denoiser
 from .griffin_lim import stft_complex
-from .stream import POOL_MAX_ROWS, PoolBook, StreamDenoiser, StreamPool, _check_stream_args, causal_carrier
+from .stream import POOL_MAX_ROWS, PoolBook, RecordingBook, StreamDenoiser, StreamPool, _check_stream_args, causal_carrier
 
 __all__ = ["WpeParams", "wpe", "wpe_joint", "Dereverberator", "WpeStreamParams", "wpe_online", "wpe_stream_state_bytes",
            "wpe_online_joint", "wpe_stream_state_bytes_joint", "StreamDereverberator", "DereverbStreamPool"]
@@ -385,23 +387,28 @@ def _wpe_then_gain(sd, x: torch.Tensor, rows, n_steps: int, first_step: int = 0,
     """The operator of both stream classes between ``analyze`` and ``emit``, in place on the analysed windows ``x``; every state
     is read from ``sd`` when it runs.  ``rows=None``: the lockstep object's steps ``first_step ..``, ``n_steps`` per stream
     (``adn_wpe_stream``, or ``adn_wpe_mc_stream`` when ``sd.channels`` consecutive streams are one recording).  Otherwise a pool tick's rows ``(slot, step, final_length)``, one step each, ``POOL_MAX_ROWS`` a call
-    (``adn_wpe_stream_pool``).  With ``sd.gain`` the spectral gain follows each call on the columns it wrote."""
+    (``adn_wpe_stream_pool``); in a pool of recordings ``sd.channels`` consecutive rows are one, ``256 // channels`` recordings a
+    call (``adn_wpe_mc_stream_pool``).  With ``sd.gain`` the spectral gain follows each call on the columns it wrote."""
     L = _lib.load()
     state = (sd._state.data_ptr(), sd._state.numel())
     wpe_args = (ctypes.byref(sd.params.to_struct()), sd._wpe_state.data_ptr(), sd._wpe_state.numel(), current_stream(sd.device))
     if rows is None:
         plan, groups = sd._plan, [(x, None)]
     else:
-        plan, groups = sd.book.plan, [(x[i:i + POOL_MAX_ROWS], rows[i:i + POOL_MAX_ROWS]) for i in range(0, len(rows), POOL_MAX_ROWS)]
+        per = POOL_MAX_ROWS // sd.channels * sd.channels          # whole recordings
+        plan, groups = sd.book.plan, [(x[i:i + per], rows[i:i + per]) for i in range(0, len(rows), per)]
     for part, group in groups:
         with torch.cuda.device(sd.device):
             if group is None:
                 run, lead = _entry("_stream", sd.n_streams, None if sd.channels == 1 else sd.channels)
                 _lib.check(run(*state, part.data_ptr(), *lead, first_step, n_steps, final_length, *plan, sd.max_steps, *wpe_args),
                            run.__name__)
-            else:
+            elif sd.channels == 1:
                 _lib.check(L.adn_wpe_stream_pool(*state, *sd._args, sd._rows(group), len(group), part.data_ptr(), *wpe_args),
                            "adn_wpe_stream_pool")
+            else:
+                _lib.check(L.adn_wpe_mc_stream_pool(*state, sd._args[0], sd.channels, *sd._args[1:], sd._rows(group), len(group),
+                                                    part.data_ptr(), *wpe_args), "adn_wpe_mc_stream_pool")
         if sd.gain:
             _gain_kept_columns(part, group, n_steps, sd._gain_state, plan, sd.gain_params)
     return x
@@ -449,14 +456,25 @@ class DereverbStreamPool(StreamPool):
     ``room``, ``received`` and the rates are the parent's.  A tick calls ``adn_wpe_stream_pool`` once per group of up to 256 rows,
     in place on the analysed windows (and with ``gain=True`` ``adn_spectral_gain_windows`` with ``rows = (slot, step == 0)``).  A
     stream's frame 0 starts its slot afresh, so a slot is reusable without a reset.  Each stream is, bit for bit, what a solo
-    ``StreamDereverberator`` (at its ``input_rate``) returns for the same samples."""
+    ``StreamDereverberator`` (at its ``input_rate``) returns for the same samples.
+
+    ``channels = C > 1``: a pool of RECORDINGS of ``C`` microphones, dereverberated jointly (``adn_wpe_mc_stream_pool``;
+    ``RecordingBook``).  ``max_streams`` counts recordings, ``open`` returns a recording id, ``push(rid, block)`` takes ``(C, m)``,
+    ``step`` returns ``(rid, samples (C, k), finished)``; ``params=None`` takes ``taps = 32 // C``, with the rules of
+    ``StreamDereverberator(channels=C)``; the gain stays per channel.  Each recording is, bit for bit, what a solo
+    ``StreamDereverberator(n_streams=C, channels=C)`` returns.  ``channels = 1`` is the pool of single streams."""
 
     def __init__(self, device=None, max_streams: int = 64, backlog_steps: int = 4, sample_rate: int = 8000, n_fft: int = 512,
                  hop_length: int = 128, block_frames: int = 4, params: WpeStreamParams = None, gain: bool = False,
-                 gain_params: SpectralParams = None, input_rates=None):
+                 gain_params: SpectralParams = None, input_rates=None, channels: int = 1):
         window, ahead, _ = causal_carrier(block_frames)
-        self.book = PoolBook(max_streams, backlog_steps, n_fft, hop_length, window, block_frames, ahead, input_rates, sample_rate)
-        dev = _wpe_setup(self, "DereverbStreamPool", device, max_streams, n_fft, params, gain, gain_params)   # channels = 1: see the module text
+        _check_channels("DereverbStreamPool", channels)
+        if channels == 1:
+            self.book = PoolBook(max_streams, backlog_steps, n_fft, hop_length, window, block_frames, ahead, input_rates, sample_rate)
+        else:
+            self.book = RecordingBook(max_streams, channels, backlog_steps, n_fft, hop_length, window, block_frames, ahead, input_rates,
+                                      sample_rate)
+        dev = _wpe_setup(self, "DereverbStreamPool", device, max_streams * channels, n_fft, params, gain, gain_params, channels)
         self.batch_windows = POOL_MAX_ROWS
         self._setup(dev)
 
@@ -466,7 +484,8 @@ class DereverbStreamPool(StreamPool):
         self._gain_state.fill_(-1.0)
 
     def network(self, x):
-        raise RuntimeError("DereverbStreamPool: there is no network; WPE runs between analyze and emit (adn_wpe_stream_pool)")
+        raise RuntimeError("DereverbStreamPool: there is no network; WPE runs between analyze and emit (adn_wpe_stream_pool, "
+                           "adn_wpe_mc_stream_pool)")
 
     def _net(self, x: torch.Tensor, rows) -> torch.Tensor:
         return _wpe_then_gain(self, x, rows, 1)

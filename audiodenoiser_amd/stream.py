@@ -50,7 +50,7 @@ from ._host import check_stft_plan, model_device, run_live, stage, unet_windows
 from ._host import current_stream as _stream          # the name this module's methods have always called it by
 from .resample import prepare_resample, resample_stream_plan
 
-__all__ = ["StreamDenoiser", "StreamPool", "PoolBook", "stream_plan", "stream_rate_plan"]
+__all__ = ["StreamDenoiser", "StreamPool", "PoolBook", "RecordingBook", "stream_plan", "stream_rate_plan"]
 
 
 def stream_plan(received: int, n_fft: int = 512, hop_length: int = 128, window_frames: int = 192, block_frames: int = 16,
@@ -557,6 +557,40 @@ class PoolBook:
         return False
 
 
+class RecordingBook(PoolBook):
+    """A ``PoolBook`` over RECORDINGS of ``channels`` microphones (``include/adn.h``, ``adn_wpe_mc_stream_pool``): everything the
+    parent keeps -- ``received``, ``done``, ``room``, the rates -- exists once per recording, because the channels of a recording
+    start, advance and end together.  Recording ``r`` owns the stream slots ``r C ... r C + C - 1`` of the device state, so a row
+    ``(rid, step, final_length)`` of a tick expands to ``C`` stream rows in channel order (``stream_rows``), and a tick is cut into
+    calls of ``256 // C`` recordings (``calls``): a recording never straddles two calls.  One channel count per pool."""
+
+    def __init__(self, max_recordings: int = 16, channels: int = 2, backlog_steps: int = 4, n_fft: int = 512, hop_length: int = 128,
+                 window_frames: int = 192, block_frames: int = 16, lookahead_frames: int = 0, input_rates=None,
+                 sample_rate: int = 8000):
+        if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= 8:
+            raise ValueError("StreamPool: channels must be an integer in [1, 8]")
+        if not (isinstance(max_recordings, int) and 1 <= max_recordings and max_recordings * channels <= 1 << 20):
+            raise ValueError("StreamPool: max_recordings * channels must be in [1, 2^20]")
+        super().__init__(max_recordings, backlog_steps, n_fft, hop_length, window_frames, block_frames, lookahead_frames, input_rates,
+                         sample_rate)
+        self.channels, self.max_recordings = channels, max_recordings
+        self.n_slots = max_recordings * channels                          # stream slots of the device state
+        self.recordings_per_call = POOL_MAX_ROWS // channels
+
+    def slots(self, rid: int):
+        """The stream slots of recording ``rid``, in channel order."""
+        return range(rid * self.channels, (rid + 1) * self.channels)
+
+    def stream_rows(self, rows):
+        """``rows`` ``(rid, step, final_length)`` -> the stream rows ``(slot, step, final_length)``, ``C`` per recording."""
+        return [(slot, k, final) for rid, k, final in rows for slot in self.slots(rid)]
+
+    def calls(self, rows):
+        """``rows`` of recordings cut into the lists one library call takes: ``256 // C`` recordings each."""
+        n = self.recordings_per_call
+        return [rows[i:i + n] for i in range(0, len(rows), n)]
+
+
 class StreamPool:
     """Live streams that start, stop and arrive independently, served from one card: every ``step()`` runs ONE step of every
     stream that has one ready, all of them through the network as one batch.
@@ -599,7 +633,13 @@ class StreamPool:
     for whose samples ``room`` has kept the ring free, and the stream's last step is cut so that it has returned exactly as many
     samples as it received.  Claimed: a stream's output is, bit for bit with ``set_batch_invariant(True)``, that of
     ``StreamDenoiser(n_streams=1, input_rate=rate)`` for the same samples, whatever rates and timing its neighbours have.  Not
-    claimed: rates outside ``adn_resample``'s limits; anything ``StreamDenoiser(input_rate=...)`` does not claim."""
+    claimed: rates outside ``adn_resample``'s limits; anything ``StreamDenoiser(input_rate=...)`` does not claim.
+
+    Recordings.  A subclass whose ``book`` is a ``RecordingBook`` (``DereverbStreamPool(channels=C)``, ``BeamformStreamPool``) serves
+    RECORDINGS of ``C`` microphones: ``open`` returns a recording id, ``push`` takes ``(C, m)``, recording ``r`` lives in the device
+    slots ``r C ... r C + C - 1``, a tick's rows are its recordings' ``C`` stream rows in channel order, ``256 // C`` recordings a
+    call, and ``step`` returns ``(C, k)`` per recording -- or ``(k,)`` where ``_emit_rows`` keeps the first row of each.  This class
+    itself, and every pool with ``channels = 1``, is the pool of single streams above."""
 
     def __init__(self, model, max_streams: int = 64, backlog_steps: int = 4, n_fft: int = 512, hop_length: int = 128,
                  window_frames: int = 192, block_frames: int = 16, lookahead_frames: int = 0, batch_windows: int = 64,
@@ -613,11 +653,14 @@ class StreamPool:
         self._setup(dev)
 
     def _setup(self, dev):
-        """Everything of the constructor that needs no model, ``self.book`` given: the device state and the rates' histories."""
+        """Everything of the constructor that needs no model, ``self.book`` given: the device state and the rates' histories.
+        With a ``RecordingBook`` a stream of the pool is a recording of ``channels`` device slots; ``max_streams`` counts recordings."""
         max_streams = self.book.max_streams
         self.device = dev
         self.max_streams, self.n_bins = max_streams, self.book.n_fft // 2 + 1
-        self._args = (max_streams,) + self.book.plan + (self.book.ring_samples,)
+        self.channels = getattr(self.book, "channels", 1)
+        n_slots = max_streams * self.channels
+        self._args = (n_slots,) + self.book.plan + (self.book.ring_samples,)
         need = ctypes.c_size_t()
         _lib.check(_lib.load().adn_stream_pool_state_bytes(*self._args, ctypes.byref(need)), "adn_stream_pool_state_bytes")
         self._state = torch.empty(need.value, dtype=torch.uint8, device=dev)
@@ -625,10 +668,10 @@ class StreamPool:
         # streams at a rate of their own: the histories of their resamplers, two directions per slot (none without input_rates)
         self._rate_state = None
         if self.book.input_rates:
-            _lib.check(_lib.load().adn_stream_pool_rate_state_bytes(max_streams, self.book.max_history, ctypes.byref(need)),
+            _lib.check(_lib.load().adn_stream_pool_rate_state_bytes(n_slots, self.book.max_history, ctypes.byref(need)),
                        "adn_stream_pool_rate_state_bytes")
             self._rate_state = torch.empty(max(need.value, 8), dtype=torch.uint8, device=dev)
-            self._rate_args = (self._rate_state.data_ptr(), need.value, max_streams, self.book.max_history, self.book.sample_rate)
+            self._rate_args = (self._rate_state.data_ptr(), need.value, n_slots, self.book.max_history, self.book.sample_rate)
             for r in self.book.input_rates:                  # the coefficient tables, so that no push builds one
                 prepare_resample(r, self.book.sample_rate, dev)
                 prepare_resample(self.book.sample_rate, r, dev)
@@ -668,22 +711,27 @@ class StreamPool:
         if self.book.rate[sid] is not None:
             return self.push_many({sid: block})
         x, as_numpy = self._block(block)
-        m = x.shape[0]
+        m = x.shape[-1]
         at = self.book.take(sid, m)
         self._numpy[sid] = as_numpy
         if m == 0:
             return
         x = x.to(self.device).contiguous()
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().adn_stream_pool_write(self._state.data_ptr(), self._state.numel(), *self._args, sid, x.data_ptr(),
-                                                         m, at, _stream(self.device)), "adn_stream_pool_write")
+            for c in range(self.channels):                   # a recording: channel c into slot sid C + c, one write each
+                _lib.check(_lib.load().adn_stream_pool_write(self._state.data_ptr(), self._state.numel(), *self._args,
+                                                             sid * self.channels + c, x.data_ptr() + 4 * c * m, m, at,
+                                                             _stream(self.device)), "adn_stream_pool_write")
 
-    @staticmethod
-    def _block(block):
-        """``block`` as a float32 tensor of one dimension (on the host for numpy) and whether it was numpy."""
+    def _block(self, block):
+        """``block`` as a float32 tensor of one dimension (on the host for numpy) and whether it was numpy; ``(channels, m)`` in a
+        pool of recordings."""
         x, as_numpy = stage("StreamPool.push", block, None)
-        if x.dim() != 1:
-            raise ValueError("StreamPool.push: audio must be (m,), the samples of one stream")
+        if self.channels == 1:
+            if x.dim() != 1:
+                raise ValueError("StreamPool.push: audio must be (m,), the samples of one stream")
+        elif x.dim() != 2 or x.shape[0] != self.channels:
+            raise ValueError(f"StreamPool.push: audio must be (channels, m) = ({self.channels}, m), the samples of one recording")
         return x, as_numpy
 
     def _rate_rows(self, rows):
@@ -712,11 +760,11 @@ class StreamPool:
         for sid, block in blocks.items():
             book._live(sid, "push")
             x, as_numpy = self._block(block)
-            (book.check if book.rate[sid] is None else book.check_rate)(sid, x.shape[0])
+            (book.check if book.rate[sid] is None else book.check_rate)(sid, x.shape[-1])
             items.append((sid, x, as_numpy))
-        rows, parts, offset, undo = [], [], 0, []
+        rows, parts, offset, undo, C = [], [], 0, [], self.channels
         for sid, x, as_numpy in items:
-            m = x.shape[0]
+            m = x.shape[-1]
             if book.rate[sid] is None and self._rate_state is None:
                 self.push(sid, x if not as_numpy else x.numpy())
                 continue
@@ -727,12 +775,14 @@ class StreamPool:
             self._numpy[sid] = as_numpy
             if book.rate[sid] is None:                       # at the working rate among others: a copy row of the same call
                 before = book.take(sid, m)
-                rows.append((sid, book.sample_rate, min(before, 1), before, m, 0, offset))
+                rate, call = book.sample_rate, min(before, 1)
             else:
                 call, before = book.take_rate(sid, m)
-                rows.append((sid, book.rate[sid], call, before, m, 0, offset))
-            parts.append((x, as_numpy))
-            offset += m
+                rate = book.rate[sid]
+            for c in range(C):                               # a row per channel: slot sid C + c, its samples c m further on
+                rows.append((sid * C + c, rate, call, before, m, 0, offset + c * m))
+            parts.append((x.reshape(-1), as_numpy))
+            offset += C * m
         if not rows:
             return
         host = [x for x, as_numpy in parts if as_numpy]
@@ -755,12 +805,21 @@ class StreamPool:
         book._live(sid, "close")
         if book.rate[sid] is not None and book.status[sid] == book.RUNNING and book.received_in[sid] > 0:
             call, before = book.close_rate(sid)
-            self._push_rate([(sid, book.rate[sid], call, before, 0, 1, 0)], None)
+            self._push_rate([(slot, book.rate[sid], call, before, 0, 1, 0) for slot in self._slots(sid)], None)
         return book.close(sid)
 
     # ------------------------------------------------------------------ building blocks (device tensors)
+    def _slots(self, sid: int):
+        """The device slots of stream ``sid``: itself, or the ``channels`` slots of a recording in channel order."""
+        return range(sid * self.channels, (sid + 1) * self.channels)
+
     def _rows(self, rows):
         return (_lib.StreamPoolRow * len(rows))(*[_lib.StreamPoolRow(*r) for r in rows])
+
+    def _emit_rows(self, rows):
+        """The stream rows of a tick that ``emit`` takes back to audio, ``_net``'s result holding one window for each: all of them
+        here; a class whose operator leaves a recording's result in its first row keeps that one (``BeamformStreamPool``)."""
+        return rows
 
     def analyze(self, rows) -> torch.Tensor:
         """``adn_stream_pool_analyze``: rows ``(slot, step, final_length)``, at most 256 -> network input ``(n_rows, 1, F, W)``."""
@@ -796,29 +855,45 @@ class StreamPool:
         rows = self.book.rows()
         if not rows:
             return []
-        group = POOL_MAX_ROWS
-        groups = [rows[i:i + group] for i in range(0, len(rows), group)]
-        x = torch.cat([self.analyze(g) for g in groups]) if len(groups) > 1 else self.analyze(rows)
-        y = self._net(x, rows)
-        outs = [self.emit(y[i * group:i * group + len(g)], g) for i, g in enumerate(groups)]
+        book, C = self.book, self.channels
+        # the device's rows: a stream's own, or the C of a recording in channel order, 256 // C recordings a call
+        srows = rows if C == 1 else book.stream_rows(rows)
+        group = POOL_MAX_ROWS // C * C
+        groups = [srows[i:i + group] for i in range(0, len(srows), group)]
+        x = torch.cat([self.analyze(g) for g in groups]) if len(groups) > 1 else self.analyze(srows)
+        y = self._net(x, srows)
+        erows = self._emit_rows(srows)
+        E = len(erows) // len(rows)                      # rows of `out` per row of the tick: 1, or a recording's channels
+        groups = [erows[i:i + POOL_MAX_ROWS] for i in range(0, len(erows), POOL_MAX_ROWS)]
+        outs = [self.emit(y[i * POOL_MAX_ROWS:i * POOL_MAX_ROWS + len(g)], g) for i, g in enumerate(groups)]
         out = torch.cat(outs) if len(outs) > 1 else outs[0]
-        book = self.book
         calls, rated = book.rate_calls(rows)             # the rows of streams at a rate of their own go back to it
+        if C > 1:                                        # a call per emitted channel: slot sid C + e, row i E + e of `out`
+            calls = [(i * E + e, (c[0] * C + e,) + c[1:]) for i, c in calls for e in range(E)]
+            rated = {i: (None if j is None else j * E, n) for i, (j, n) in rated.items()}
         rout = self.emit_rate(out, calls) if calls else None
         plain = any(self._numpy[r[0]] and i not in rated for i, r in enumerate(rows))
         host = out.cpu().numpy() if plain else None
-        rhost = rout.cpu().numpy() if rout is not None and any(self._numpy[rows[i][0]] for i, _ in calls) else None
+        rhost = rout.cpu().numpy() if rout is not None and any(self._numpy[rows[i // E][0]] for i, _ in calls) else None
+        if C == 1 or E == 1:
+            def pick(a, i, n):
+                return a[i, :n]
+        else:                                            # a recording that keeps its channels: (C, n)
+            def pick(a, i, n):
+                return a[i:i + E, :n]
         result = []
         for i, (slot, k, final) in enumerate(rows):
             if i in rated:
                 j, n = rated[i]
                 if j is None:
                     samples = np.empty(0, dtype=np.float32) if self._numpy[slot] else out.new_empty(0)
+                    if C > 1 and E > 1:
+                        samples = samples.reshape(E, 0)
                 else:
-                    samples = rhost[j, :n].copy() if self._numpy[slot] else rout[j, :n].clone()
+                    samples = pick(rhost, j, n).copy() if self._numpy[slot] else pick(rout, j, n).clone()
             else:
                 n = book.count(k, final)
-                samples = host[i, :n].copy() if self._numpy[slot] else out[i, :n].clone()
+                samples = pick(host, i * E, n).copy() if self._numpy[slot] else pick(out, i * E, n).clone()
             result.append((slot, samples, book.ran(slot)))
         return result
 
@@ -849,7 +924,7 @@ class StreamPool:
                     parts[sid] = []
                 parts[sid].append(samples)
                 fin[sid] = finished
-        return [(sid, np.concatenate(parts[sid]) if isinstance(parts[sid][0], np.ndarray) else torch.cat(parts[sid]), fin[sid])
+        return [(sid, np.concatenate(parts[sid], axis=-1) if isinstance(parts[sid][0], np.ndarray) else torch.cat(parts[sid], dim=-1), fin[sid])
                 for sid in sorted(order)]
 
 

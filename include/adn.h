@@ -33,7 +33,7 @@
 
 #include <stddef.h>
 
-/* The 78 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
+/* The 80 functions below are the ONLY symbols libadn.so exports: the library is built with -fvisibility=hidden and linked with
  * a version script (audiodenoiser_amd/csrc/libadn.map: `adn_*` global, everything else local). */
 #if defined(__GNUC__)
 #define ADN_API __attribute__((visibility("default")))
@@ -901,21 +901,35 @@ ADN_API int adn_wpe_stream_pool(void *pool_state, size_t pool_state_bytes, int n
  * on channels, taps and delay; host-only, and it validates everything about the parameters): per (slot, bin) the full P, G, s and
  * per channel a ring of the last D + K raw frames.  A slot is a GROUP.  With channels = 1 it is adn_wpe_stream_state_bytes'.
  *
- * Two entry points, one step function:
+ * Three entry points, one step function:
  *   adn_wpe_mc_online: adn_wpe_online with the leading dimension n_groups * channels, a group's channels consecutive rows --
  *     adn_wpe_mc's layout; mag_out (n_groups * channels, 1, n_bins, width), columns [col0, col0 + n_frames).  Group i uses slot i.
  *     It writes those columns, all of spec_out, the state of its groups, and not one byte else.
  *   adn_wpe_mc_stream: adn_wpe_stream for an adn_stream_* state whose streams g C ... g C + C - 1 are group g (n_streams a
  *     multiple of channels): d in place into each channel's ring cells, M into columns [window - block, window) of each channel's
  *     windows of y.  wpe_state has n_streams / channels slots.  adn_stream_analyze and adn_stream_emit are what they were.
+ *   adn_wpe_mc_stream_pool: adn_wpe_stream_pool for a pool of RECORDINGS, between adn_stream_pool_analyze and
+ *     adn_stream_pool_emit on the same rows.  A recording is `channels` consecutive streams of the pool, the same count for the
+ *     whole pool (n_slots a multiple of it): recording r owns the stream slots r C ... r C + C - 1 and slot r of wpe_state, which has
+ *     n_slots / channels slots.  In the row table a recording is C consecutive rows that name its slots in channel order and carry
+ *     the same step and final_length; the recordings of a call come in any order, and n_rows / channels of them fit one call.  It
+ *     reads the frames the step emits from the ring cells of the recording's C slots, writes d back into the same cells and M into
+ *     columns [window - block, window) of the C rows' windows of y, the (n_rows, 1, F, window) buffer, reads and writes slot r of
+ *     wpe_state, and not one byte else: the slots of wpe_state the call does not name keep their bytes.  The table travels by
+ *     value; one launch.  Pinned bit for bit: the ring cells, the window columns and the state bytes against adn_wpe_mc_stream on a
+ *     lockstep state holding the same rings (tests/test_gpu_stream_pool_mc.py).  With channels = 1 the call is
+ *     adn_wpe_stream_pool's kernel and returns its bits, state included.
  * Cost: one launch, n_groups x ceil(n_bins / 8) workgroups of 8 bins, 32 lanes per (group, bin); no workspace, no atomics, no
  * constant table; nothing blocks or allocates.  A call's time is the per-frame chain of a workgroup:
  * profiles/bench_dereverb_mc_stream.md.
  * Limits (ADN_ERR_INVALID before any launch; a refused call writes nothing): those of adn_wpe_online with n_groups in n_rows'
- * place, and n_groups * channels < 2^31; everything adn_wpe_stream refuses, and n_streams % channels != 0.  ADN_ERR_WORKSPACE: a
- * state below adn_wpe_mc_stream_state_bytes.  Element offsets are 64-bit.
+ * place, and n_groups * channels < 2^31; everything adn_wpe_stream refuses, and n_streams % channels != 0; for the pool
+ * everything adn_wpe_stream_pool refuses, the parameter rules above, and n_slots % channels != 0, n_rows % channels != 0, a group
+ * whose first slot is no multiple of channels, whose slots are not consecutive in channel order, or whose rows differ in step or
+ * final_length.  ADN_ERR_WORKSPACE: a state below adn_wpe_mc_stream_state_bytes.  Element offsets are 64-bit.
  * Combining the channels into one: "beamform" (offline) and "beamform stream" (live, on the same stream state) below.
- * Not here: the stream pool with multichannel streams; look-ahead; N > 32; any tuning by ear. */
+ * Not here: the stream pool with mixed channel counts (one count per pool); more than one step per recording and call; look-ahead;
+ * N > 32; any tuning by ear. */
 ADN_API int adn_wpe_mc_stream_state_bytes(int n_slots, int channels, int n_bins, const adn_wpe_stream_params *params, size_t *bytes);
 ADN_API int adn_wpe_mc_online(const float *spec, int n_groups, int channels, int n_frames, int n_bins, long first_frame,
                               const adn_wpe_stream_params *params, void *state, size_t state_bytes, int n_slots, float *spec_out,
@@ -924,6 +938,10 @@ ADN_API int adn_wpe_mc_stream(void *stream_state, size_t stream_state_bytes, flo
                               int n_steps, long final_length, int n_fft, int hop, int window, int block, int lookahead,
                               int max_steps, const adn_wpe_stream_params *params, void *wpe_state, size_t wpe_state_bytes,
                               void *stream);
+ADN_API int adn_wpe_mc_stream_pool(void *pool_state, size_t pool_state_bytes, int n_slots, int channels, int n_fft, int hop,
+                                   int window, int block, int lookahead, long ring_samples, const adn_stream_pool_row *rows,
+                                   int n_rows, float *y, const adn_wpe_stream_params *params, void *wpe_state,
+                                   size_t wpe_state_bytes, void *stream);
 
 /* ---- beamform: mask-driven MVDR, the channels of a recording to one enhanced channel ---------------------------------------------------
  * No reference counterpart and no checkpoint.  The library DEFINES the operator below (float64 restatement:
@@ -1040,7 +1058,7 @@ ADN_API int adn_mvdr(const float *spec, const float *mag, int mag_width, int n_g
  * validates everything about the parameters): per (slot, bin) the two packed lower triangles and w, 2 (C (C + 1) + C) floats,
  * entry-major over the bins of a slot.  A slot is a GROUP.
  *
- * Two entry points, one step function:
+ * Three entry points, one step function:
  *   adn_mvdr_online: spec (n_groups * channels, n_frames, n_bins, 2), the frames first_frame ... first_frame + n_frames - 1 of
  *     every row, a group's channels consecutive rows; mag (n_groups * channels, 1, n_bins, mag_width), columns [mag_col0, mag_col0 +
  *     n_frames) read; spec_out (n_groups, n_frames, n_bins, 2); mag_out (n_groups, 1, n_bins, width), may be NULL, columns [col0,
@@ -1054,14 +1072,27 @@ ADN_API int adn_mvdr(const float *spec, const float *mag, int mag_width, int n_g
  *     finished stream.  The lanes that read a (group, bin, frame) are the ones that write it, so doing this in place is safe.
  *     mvdr_state has n_streams / channels slots.  adn_stream_emit is unchanged: it then emits all streams, and the host keeps row
  *     g C of each group; what the C - 1 unused rows cost is measured in profiles/bench_beamform_stream.md.
+ *   adn_mvdr_stream_pool: the same for a pool of RECORDINGS, between adn_stream_pool_analyze and adn_stream_pool_emit; the
+ *     recordings, their slots and their rows are adn_wpe_mc_stream_pool's ("dereverb stream multichannel"): recording r owns the
+ *     stream slots r C ... r C + C - 1 and slot r of mvdr_state (n_slots / channels slots), and is C consecutive rows in channel
+ *     order with one step and final_length.  It reads X_{t,c} from the ring cells of the C slots and M_{t,c} from columns
+ *     [window - block, window) of the C rows' windows of y, the (n_rows, 1, F, window) buffer, and writes Y_t into the ring cells of
+ *     the recording's FIRST slot and |Y_t| into the same columns of the group's FIRST row, slot r of mvdr_state, and not one byte
+ *     else.  The table travels by value; one launch.  Pinned bit for bit against adn_mvdr_stream on a lockstep state holding the
+ *     same rings: ring cells, window columns, state bytes (tests/test_gpu_stream_pool_mc.py).
+ *     The emit may then skip the unused channels: adn_stream_pool_emit takes a row table, so the caller hands it the first row of
+ *     each group and the first window of each group (y[::C], compacted) and nothing else.  That is safe because the emit kernel
+ *     writes no state but a slot's own overlap-add tail, and nothing reads that tail but that slot's own later emits: the slots
+ *     r C + 1 ... r C + C - 1 are never emitted, so their tails are never read.
  * Cost: one launch, n_groups x ceil(n_bins / B) workgroups of one wave, B = 16 bins up to C = 4 and 8 beyond; the covariances stay in
  * registers for the whole call; no workspace, no atomics, no constant table (a capture may hold a first call); nothing blocks or
  * allocates.  A call's time is the per-frame chain of a workgroup: profiles/bench_beamform_stream.md.
  * Limits (ADN_ERR_INVALID before any launch; a refused call writes nothing): those of adn_wpe_mc_online and adn_wpe_mc_stream with
- * the new arguments: NULL or misaligned mag; mag_col0 >= 0 and mag_col0 + n_frames <= mag_width; overlap.  ADN_ERR_WORKSPACE: a state
- * below adn_mvdr_stream_state_bytes.  Element offsets are 64-bit.
- * Not here: the stream pool with multichannel streams; GEV, rank-one or WPD variants; look-ahead; an emit that skips the unused
- * channels; any tuning by ear. */
+ * the new arguments: NULL or misaligned mag; mag_col0 >= 0 and mag_col0 + n_frames <= mag_width; overlap; for the pool what
+ * adn_wpe_mc_stream_pool refuses about the pool, the rows and the groups.  ADN_ERR_WORKSPACE: a state below
+ * adn_mvdr_stream_state_bytes.  Element offsets are 64-bit.
+ * Not here: the stream pool with mixed channel counts; more than one step per recording and call; GEV, rank-one or WPD variants; look-ahead;
+ * a lockstep emit that skips the unused channels (adn_stream_emit emits every stream); any tuning by ear. */
 typedef struct adn_mvdr_stream_params { int ref_channel, refresh; float forget, loading, mask_floor; } adn_mvdr_stream_params;
 ADN_API int adn_mvdr_stream_state_bytes(int n_slots, int channels, int n_bins, const adn_mvdr_stream_params *params, size_t *bytes);
 ADN_API int adn_mvdr_online(const float *spec, const float *mag, int mag_width, int mag_col0, int n_groups, int channels,
@@ -1071,6 +1102,9 @@ ADN_API int adn_mvdr_stream(void *stream_state, size_t stream_state_bytes, float
                             int n_steps, long final_length, int n_fft, int hop, int window, int block, int lookahead,
                             int max_steps, const adn_mvdr_stream_params *params, void *mvdr_state, size_t mvdr_state_bytes,
                             void *stream);
+ADN_API int adn_mvdr_stream_pool(void *pool_state, size_t pool_state_bytes, int n_slots, int channels, int n_fft, int hop, int window,
+                                 int block, int lookahead, long ring_samples, const adn_stream_pool_row *rows, int n_rows, float *y,
+                                 const adn_mvdr_stream_params *params, void *mvdr_state, size_t mvdr_state_bytes, void *stream);
 
 /* ---- environment switches -------------------------------------------------------------------------------------------------
  * Read ONCE, when a U-Net handle is created (never per call).  None is needed in production: the defaults are the measured best

@@ -11,7 +11,8 @@ Every case is one change to a legal call: each null pointer, each size at 0, eac
 NaN, params = NULL with a state one byte too small (which pins the default taps: 20 for the single-channel functions,
 32 / channels for the joint ones, channels = 1 included; the offline functions need no workspace, so there the default shows as
 "channels * taps <= 32" at 32 / channels + 1 taps only through explicit params), misalignment, overlap, col0 + n_frames > width,
-more rows than slots, lookahead != 0, n_streams % channels and the forget rule at (2, 16).  A call that is NOT refused would reach
+more rows than slots, lookahead != 0, n_streams % channels, the forget rule at (2, 16), and for the pool of recordings
+(adn_wpe_mc_stream_pool) n_slots % channels, n_rows % channels and the three rules of a group's rows.  A call that is NOT refused would reach
 the device: the script stops there with an error instead of printing a line."""
 import ctypes
 import math
@@ -184,12 +185,64 @@ def pool():
            ("WPE state misaligned", dict(state=STATE + 4))])
 
 
+def pool_mc():
+    """adn_wpe_mc_stream_pool: what the pool call refuses, what the joint parameters refuse, and the rules of a recording's rows."""
+    cls = _lib.WpeStreamParamsStruct
+    ring, fb = 4096, PLAN["n_fft"] // 2 + 1
+
+    def rows(*r):
+        return (_lib.StreamPoolRow * len(r))(*[_lib.StreamPoolRow(*x) for x in r])
+    for channels in (1, 2, 3, 8):
+        slots = 3 * channels                                             # three recordings
+        p = params(cls, STREAM, taps=2 if channels == 8 else 4)
+        tag = f"C={channels} "
+        pbytes = size_of(L.adn_stream_pool_state_bytes, slots, *PLAN.values(), ring)
+        assert pbytes <= 1 << 19
+
+        def need(pp, n=3):
+            return size_of(L.adn_wpe_mc_stream_state_bytes, n, channels, fb, ctypes.byref(pp) if pp is not None else None)
+
+        def table_of(*recordings):                                       # (recording, step, final_length) -> its C rows
+            return rows(*[(r * channels + c, k, final) for r, k, final in recordings for c in range(channels)])
+        good = dict(pstate=SSTATE, pbytes=pbytes, slots=slots, channels=channels, **PLAN, ring=ring, rows=table_of((2, 1, -1), (0, 0, -1)),
+                    n_rows=2 * channels, y=Y, params=p, state=STATE, state_bytes=need(p), stream=None)
+        cases = ([(tag + "state=NULL", dict(pstate=None)), (tag + "n_slots=0", dict(slots=0)), (tag + "n_fft=48", dict(n_fft=48)),
+                  (tag + "ring_samples=1", dict(ring=1)), (tag + "pool state one byte short", dict(pbytes=pbytes - 1)),
+                  (tag + "pool state misaligned", dict(pstate=SSTATE + 4)), (tag + "lookahead=1", dict(lookahead=1)),
+                  (tag + "y=NULL", dict(y=None)), (tag + "y misaligned", dict(y=Y + 2)), (tag + "rows=NULL", dict(rows=None)),
+                  (tag + "n_rows=0", dict(n_rows=0)), (tag + "n_rows=257", dict(n_rows=257)),
+                  (tag + "slot outside", dict(rows=table_of((3, 1, -1), (0, 0, -1)))),
+                  (tag + "slot twice", dict(rows=table_of((1, 0, -1), (1, 0, -1)))),
+                  (tag + "step=-1", dict(rows=table_of((2, -1, -1), (0, 0, -1)))),
+                  (tag + "final_length=0", dict(rows=table_of((2, 1, 0), (0, 0, -1))))] +
+                 [(tag + k, ch) for k, ch in param_cases(cls, STREAM, STREAM_BAD, channels)] +
+                 [(tag + "WPE state=NULL", dict(state=None)), (tag + "WPE state one byte short", dict(state_bytes=need(p) - 1)),
+                  (tag + "params=NULL, WPE state one byte short of the default taps", dict(params=None, state_bytes=need(None) - 1)),
+                  (tag + "WPE state misaligned", dict(state=STATE + 4))])
+        if channels >= 2:
+            swapped = [(2 * channels + c, 1, -1) for c in range(channels)]
+            swapped[0], swapped[1] = swapped[1], swapped[0]
+            shifted = [(1 + c, 0, -1) for c in range(channels)]
+            other_step = [(c, 0 if c else 1, -1) for c in range(channels)]
+            other_final = [(c, 0, -1 if c else 40) for c in range(channels)]
+            cases += [(tag + "forget rule", dict(params=params(cls, STREAM, taps=32 // channels, forget=0.98))),
+                      (tag + "n_slots % channels", dict(slots=slots + 1, pbytes=size_of(L.adn_stream_pool_state_bytes, slots + 1, *PLAN.values(), ring))),
+                      (tag + "n_rows % channels", dict(n_rows=2 * channels - 1)),
+                      (tag + "first slot no multiple of channels", dict(rows=rows(*shifted), n_rows=channels)),
+                      (tag + "slots not in channel order", dict(rows=rows(*swapped), n_rows=channels)),
+                      (tag + "rows differ in step", dict(rows=rows(*other_step), n_rows=channels)),
+                      (tag + "rows differ in final_length", dict(rows=rows(*other_final), n_rows=channels))]
+        table("adn_wpe_mc_stream_pool", ["pstate", "pbytes", "slots", "channels", *PLAN, "ring", "rows", "n_rows", "y", "params", "state",
+                                         "state_bytes", "stream"], good, cases)
+
+
 def main():
     for mc in (False, True):
         offline(mc)
     for mc in (False, True):
         online(mc)
     pool()
+    pool_mc()
 
 
 if __name__ == "__main__":
