@@ -591,9 +591,16 @@ ADN_API int adn_stoi(const float *est, const float *ref, const long *lengths, in
  *
  * What is pinned.  The result is bounded against the float64 restatement (tests/test_gpu_baseline.py: per clip
  * max |M - M64| <= 4 FLOOR max M64, FLOOR the error of the same statements run in fp32 on the host); it is NOT pinned bit for bit to
- * numpy.  Two things are pinned bit for bit: the result does not depend on how a row's frames were cut into calls (the state
- * carried from call to call), and it does not depend on which batch the clip is in.  Every frame goes through one step, compiled
- * with fp contraction off.  Deterministic: no atomics, two calls are bit-identical.
+ * numpy.  Beside that, every (clip, bin) is bounded against its own level (tests/recursive_bounds.py):
+ * E = max_t |M - M64| / max_t M64 <= 4 floor, and every entry of the state likewise against its own float64 value (a reference
+ * entry of 0 has to be exactly 0).  The floor is the case's own: the largest E of the fp32 restatement on the very spectrogram the
+ * device ran on, over every bin of the case's three clips, measured when the test runs, never below 2^-23, never a device figure
+ * and never above 1e-4 (a case whose floor is, bounds nothing and is not in the grid).  The same bound holds a spectrogram tilted
+ * by 80 dB over the bins.  Pinned bit for bit: the result does not depend on how a row's frames were cut into calls (the state
+ * carried from call to call), and it does not depend on which batch the clip is in; and, every rule being a ratio or homogeneous
+ * in p_t, a power of two per bin on the input comes back as that factor on M and its square on the state, while no square leaves
+ * fp32's normal range and N_t stays above its 1e-30.  Every frame goes through one step, compiled with fp contraction off.
+ * Deterministic: no atomics, two calls are bit-identical.
  *
  * Layouts: spec is frame-major (n_clips, n_frames, n_bins, 2) fp32 as adn_stft_complex writes it (8-byte aligned).  out is
  * (n_clips, 1, n_bins, width) fp32, the network-output layout adn_denoise_resynth reads: the call writes columns
@@ -799,9 +806,16 @@ ADN_API int adn_wpe_mc(const float *spec, int n_groups, int channels, int n_fram
  *
  * What is pinned.  The result is bounded against the float64 restatement (tests/test_gpu_dereverb_stream.py: per row
  * max |d - d64| <= 4 FLOOR max |d64|, FLOOR the error of the same statements run in fp32 on the host); it is NOT pinned bit for bit
- * to numpy.  Pinned bit for bit: two calls give the same result; cutting a row's frames into calls (the carried state) changes
- * nothing; a row gives the same bits alone or in any batch, in whatever slot; a bin gives the same bits whichever other bins share
- * the call; a stream of the pool equals the same stream in lockstep.  Deterministic: no atomics, no reduction across lanes.
+ * to numpy.  Beside that, every (row, bin) is bounded against its own level (tests/recursive_bounds.py):
+ * E = max_t |d - d64| / max_t |d64| <= 4 floor.  The floor is the case's own: the largest E of the fp32 restatement on the very
+ * spectrogram the device ran on, over every bin of the case's three rows and over two fp32 arithmetics -- every product rounded,
+ * and the "Arithmetic" paragraph above followed statement for statement -- measured when the test runs, never below 2^-23, never
+ * a device figure and never above 1e-4.  The same bound holds a spectrogram tilted by 80 dB over the bins.  The operator is NOT
+ * scale invariant (1 / delta and the 1e-30 under phi_t are absolute), so no power of two is pinned.  Pinned bit for bit: mag_out
+ * is sqrtf(fmaf(re, re, im * im)) of the spec_out of the same call; two calls give the same result; cutting a row's frames into
+ * calls (the carried state) changes nothing; a row gives the same bits alone or in any batch, in whatever slot; a bin gives the
+ * same bits whichever other bins share the call; a stream of the pool equals the same stream in lockstep.  Deterministic: no
+ * atomics, no reduction across lanes.
  *
  * State (adn_wpe_stream_state_bytes(n_slots, n_bins, params), caller-owned, opaque, 8-byte aligned, its size depends on taps and
  * delay): per (slot, bin) the taps g, the full P, s, and a ring of the last D + K raw frames indexed by the frame number -- the
@@ -891,7 +905,12 @@ ADN_API int adn_wpe_stream_pool(void *pool_state, size_t pool_state_bytes, int n
  * sentinel.  Not claimed: the wind-up of an exactly-zero group, as in "dereverb stream".
  *
  * What is pinned.  The result is bounded against the float64 restatement (tests/test_gpu_dereverb_mc_stream.py: per group
- * max |d - d64| <= 4 FLOOR max |d64|, FLOOR the error of the same statements run in fp32 on the host).  Pinned bit for bit: two
+ * max |d - d64| <= 4 FLOOR max |d64|, FLOOR the error of the same statements run in fp32 on the host).  Beside that, every
+ * (channel row, bin) is bounded against its own level, E = max_t |d - d64| / max_t |d64| <= 4 floor, the floor the case's own as in
+ * "dereverb stream": over every bin of the case's three groups and both fp32 arithmetics, measured when the test runs on the
+ * spectrogram the device ran on, never below 2^-23, never a device figure, never above 1e-4 (tests/recursive_bounds.py); a
+ * spectrogram tilted by 80 dB over the bins is held to the same bound, and no power of two is pinned, for the parent's reason.
+ * Pinned bit for bit: mag_out is sqrtf(fmaf(re, re, im * im)) of the spec_out of the same call; two
  * calls give the same result; any cut of a group's frames into calls; a group alone or in any batch, in whatever slot; a bin
  * whichever other bins share the call; a lockstep stream (adn_wpe_mc_stream) against adn_wpe_mc_online on the same spectrogram.
  * NOT pinned: the bits against numpy; a permutation of the channels (the stacked order enters every sum).  Deterministic: no

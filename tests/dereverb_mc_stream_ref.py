@@ -1,7 +1,8 @@
 """numpy restatement of the streaming multichannel dereverberator of include/adn.h ("dereverb stream multichannel") -- TEST
 INFRASTRUCTURE, written from the header text.  float64 is the reference; dtype=np.float32 carries every statement out in float32
 (every sum term by term in the header's order), which is how the float32 host floors FLOOR and FLOOR_AUDIO below were measured
-(python tests/dereverb_mc_stream_cases.py).  Vectorised over bins; a group's spectrograms are (C, T, F), frame-major like the
+(python tests/dereverb_mc_stream_cases.py); arithmetic="fma" is the other float32 form, the header's fmaf pairing and order, as in
+tests/dereverb_stream_ref.py.  Vectorised over bins; a group's spectrograms are (C, T, F), frame-major like the
 device's; the end-to-end form is built on tests/dereverb_stream_ref.py's transforms and on tests/baseline_ref.py's gain.  With
 C = 1 every float64 statement is evaluated by the very expression tests/dereverb_stream_ref.py uses, so the two agree exactly."""
 import numpy as np
@@ -44,17 +45,22 @@ def check_params(p, channels):
         raise ValueError("forget")
 
 
-def wpe_mc_online(specs, params=None, dtype=np.float64, state=None, first_frame=0, with_state=False, with_lam=False):
+def wpe_mc_online(specs, params=None, dtype=np.float64, state=None, first_frame=0, with_state=False, with_lam=False,
+                  arithmetic="plain"):
     """specs (C, T, F) complex, the frames first_frame ... first_frame + T - 1 of the C channels of ONE group -> d (C, T, F) complex
     in `dtype`'s precision.  `state` is what an earlier call returned (with_state=True); first_frame = 0 starts fresh whatever it
     holds.  with_state: also the state after the last frame, a dict G (F, C, N) (G[:, c, r] = G_rc), P (F, N, N), s (F,), past
-    (F, C, D + K - 1) = the last raw frames of every channel, oldest first.  with_lam: also lam (T, F)."""
+    (F, C, D + K - 1) = the last raw frames of every channel, oldest first.  with_lam: also lam (T, F).
+    arithmetic (float32 only): "plain" or "fma", as in dereverb_stream_ref.wpe_online: "fma" is the header's pairing and order of
+    every complex multiply-add and its componentwise divisions; "plain" is what FLOOR was measured with."""
     X = np.asarray(specs)
     C, T, F = X.shape
     p = defaults(C)
     p.update(params or {})
     check_params(p, C)
     dt = np.dtype(dtype).type
+    assert arithmetic in ds.ARITHMETICS and (arithmetic == "plain" or dt is np.float32)
+    fused = arithmetic == "fma"
     ct = np.complex64 if dt is np.float32 else np.complex128
     K, D = int(p["taps"]), int(p["delay"])
     N = C * K
@@ -91,7 +97,18 @@ def wpe_mc_online(specs, params=None, dtype=np.float64, state=None, first_frame=
             s = pw if first_frame + t == 0 else (beta * s + one_minus_beta * pw).astype(dt)
             phi = ds._max(rho * s, tiny)
             e = np.empty((F, C), ct)
-            if dt is np.float32:                                           # term by term, in the header's order
+            if fused:                                                      # term by term, in the header's order and pairing
+                pred = np.zeros((F, C), ct)
+                for r in range(N):
+                    pred = ds.cfma_conj(xt[:, r, None], G[:, :, r], pred)
+                e[:] = ds.cx(x.real - pred.real, x.imag - pred.imag)
+                u = np.zeros((F, N), ct)
+                for k in range(N):
+                    u = ds.cfma(P[:, :, k], xt[:, k, None], u)
+                q = np.zeros(F, dt)
+                for r in range(N):
+                    q = ds.fma(xt[:, r].imag, u[:, r].imag, ds.fma(xt[:, r].real, u[:, r].real, q))
+            elif dt is np.float32:                                         # term by term, in the header's order
                 pred = np.zeros((F, C), ct)                                # every channel's sum in r order, the channels side by side
                 for r in range(N):
                     pred = pred + np.conj(G[:, :, r]) * xt[:, r, None]
@@ -112,14 +129,19 @@ def wpe_mc_online(specs, params=None, dtype=np.float64, state=None, first_frame=
                 ee = (ee + ds._power(e[:, c], dt)).astype(dt)
             lam = ds._max((ee / fC).astype(dt), phi)
             den = (alpha * lam + q).astype(dt)
-            kk = (u / den[:, None]).astype(ct)
-            Pn = ((P - kk[:, :, None] * np.conj(u)[:, None, :]) / alpha).astype(ct)
+            if fused:
+                kk = ds.cx(u.real / den[:, None], u.imag / den[:, None])
+                Pn = ds.cfma_conj(-kk[:, :, None], u[:, None, :], P)
+                Pn = ds.cx(Pn.real / alpha, Pn.imag / alpha)
+            else:
+                kk = (u / den[:, None]).astype(ct)
+                Pn = ((P - kk[:, :, None] * np.conj(u)[:, None, :]) / alpha).astype(ct)
             Pn = np.where(low, Pn, np.conj(np.swapaxes(Pn, 1, 2)))          # the upper triangle is the lower one's conjugate
             Pn[:, idx, idx] = Pn[:, idx, idx].real
             P = Pn
             Gn = np.empty_like(G)
             for c in range(C):
-                Gn[:, c] = (G[:, c] + kk * np.conj(e[:, c])[:, None]).astype(ct)
+                Gn[:, c] = ds.cfma_conj(kk, e[:, c, None], G[:, c]) if fused else (G[:, c] + kk * np.conj(e[:, c])[:, None]).astype(ct)
             G = Gn
             d[:, t] = e.T
             lams[t] = lam

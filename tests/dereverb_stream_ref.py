@@ -1,7 +1,9 @@
 """numpy restatement of the streaming dereverberator of include/adn.h ("dereverb stream") -- TEST INFRASTRUCTURE, written from the
 header text.  float64 is the reference; dtype=np.float32 carries every statement out in float32 (every sum term by term in the
 header's order), which is how the float32 host floors FLOOR and FLOOR_AUDIO below were measured (python
-tests/dereverb_stream_cases.py).  Vectorised over bins; spectrograms are frame-major (T, F) like the device's; the end-to-end form
+tests/dereverb_stream_cases.py).  That float32 form rounds every product (numpy's complex64 arithmetic: arithmetic="plain"); with
+arithmetic="fma" the multiply-adds are the header's, two fmaf per component in its pairing and order (`fma`, `cfma`, `cfma_conj`
+below), and tests/recursive_bounds.py takes a case's floor over both.  Vectorised over bins; spectrograms are frame-major (T, F) like the device's; the end-to-end form
 is built on tests/denoise_ref.py's stft / istft / rephase and on tests/baseline_ref.py's gain."""
 import numpy as np
 
@@ -47,15 +49,46 @@ def _power(z, dt):
     return z.real * z.real + z.imag * z.imag
 
 
-def wpe_online(spec, params=None, dtype=np.float64, state=None, first_frame=0, with_state=False, with_lam=False):
+ARITHMETICS = ("plain", "fma")
+
+
+def fma(a, b, c):
+    """fmaf(a, b, c) of float32 arrays as float32(float64(a) * float64(b) + float64(c)): the product is exact in float64, the sum
+    rounds once there and once to float32 (the device of tests/baseline_ref.py for fmaf(re, re, im * im))."""
+    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
+
+
+def cx(re, im):
+    """complex64 from its two float32 components, neither touched by an arithmetic operation."""
+    out = np.empty(np.broadcast(re, im).shape, np.complex64)
+    out.real, out.imag = re, im
+    return out
+
+
+def cfma(a, b, acc):
+    """acc + a b as the header pairs it: two fmaf per component, the real-part product first."""
+    return cx(fma(-a.imag, b.imag, fma(a.real, b.real, acc.real)), fma(a.imag, b.real, fma(a.real, b.imag, acc.imag)))
+
+
+def cfma_conj(a, b, acc):
+    """acc + a conj(b), likewise."""
+    return cx(fma(a.imag, b.imag, fma(a.real, b.real, acc.real)), fma(a.imag, b.real, fma(-a.real, b.imag, acc.imag)))
+
+
+def wpe_online(spec, params=None, dtype=np.float64, state=None, first_frame=0, with_state=False, with_lam=False, arithmetic="plain"):
     """spec (T, F) complex, the frames first_frame ... first_frame + T - 1 of every row -> d (T, F) complex in `dtype`'s precision.
     `state` is what an earlier call returned (with_state=True) for the frames before first_frame; first_frame = 0 starts fresh
     whatever `state` holds.  with_state: also the state after the last frame, a dict g (F, K), P (F, K, K), s (F,), past
-    (F, D + K - 1) = the last raw frames, oldest first.  with_lam: also lam (T, F)."""
+    (F, D + K - 1) = the last raw frames, oldest first.  with_lam: also lam (T, F).
+    arithmetic (float32 only): "plain" rounds every product and every sum (numpy's complex64 arithmetic, what FLOOR was measured
+    with); "fma" follows the header's "Arithmetic" paragraph statement for statement: every complex multiply-add as two fmaf per
+    component in its pairing and order, the divisions by den and by alpha componentwise and correctly rounded."""
     p = dict(DEFAULTS)
     p.update(params or {})
     check_params(p)
     dt = np.dtype(dtype).type
+    assert arithmetic in ARITHMETICS and (arithmetic == "plain" or dt is np.float32)
+    fused = arithmetic == "fma"
     ct = np.complex64 if dt is np.float32 else np.complex128
     K, D = int(p["taps"]), int(p["delay"])
     alpha, delta, rho, beta = (dt(np.float32(p[name])) for name in ("forget", "loading", "power_floor", "smooth"))
@@ -86,7 +119,18 @@ def wpe_online(spec, params=None, dtype=np.float64, state=None, first_frame=0, w
             s = pw if first_frame + t == 0 else (beta * s + one_minus_beta * pw).astype(dt)
             phi = _max(rho * s, tiny)
             xt = full[:, H + t - D - K + 1:H + t - D + 1][:, ::-1]  # (F, K): column j = X_{t-D-j}
-            if dt is np.float32:                                 # term by term, in the header's order
+            if fused:                                            # term by term, in the header's order and pairing
+                pred = np.zeros(F, ct)
+                for j in range(K):
+                    pred = cfma_conj(xt[:, j], g[:, j], pred)
+                e = cx(x.real - pred.real, x.imag - pred.imag)
+                u = np.zeros((F, K), ct)
+                for k in range(K):
+                    u = cfma(P[:, :, k], xt[:, k, None], u)
+                q = np.zeros(F, dt)
+                for j in range(K):
+                    q = fma(xt[:, j].imag, u[:, j].imag, fma(xt[:, j].real, u[:, j].real, q))
+            elif dt is np.float32:                               # term by term, in the header's order
                 pred = np.zeros(F, ct)
                 for j in range(K):
                     pred = pred + np.conj(g[:, j]) * xt[:, j]
@@ -104,13 +148,18 @@ def wpe_online(spec, params=None, dtype=np.float64, state=None, first_frame=0, w
             e = e.astype(ct)
             lam = _max(_power(e, dt), phi)
             den = (alpha * lam + q).astype(dt)
-            kk = (u / den[:, None]).astype(ct)
-            Pn = ((P - kk[:, :, None] * np.conj(u)[:, None, :]) / alpha).astype(ct)
+            if fused:
+                kk = cx(u.real / den[:, None], u.imag / den[:, None])
+                Pn = cfma_conj(-kk[:, :, None], u[:, None, :], P)
+                Pn = cx(Pn.real / alpha, Pn.imag / alpha)
+            else:
+                kk = (u / den[:, None]).astype(ct)
+                Pn = ((P - kk[:, :, None] * np.conj(u)[:, None, :]) / alpha).astype(ct)
             Pn = np.where(low, Pn, np.conj(np.swapaxes(Pn, 1, 2)))           # the upper triangle is the lower one's conjugate
             idx = np.arange(K)
             Pn[:, idx, idx] = Pn[:, idx, idx].real
             P = Pn
-            g = (g + kk * np.conj(e)[:, None]).astype(ct)
+            g = cfma_conj(kk, e[:, None], g) if fused else (g + kk * np.conj(e)[:, None]).astype(ct)
             d[t] = e
             lams[t] = lam
     out = [d]

@@ -6,6 +6,13 @@ Bounds (derived, not tuned):
   statements run in float32 on the host over these very shapes (python tests/baseline_cases.py), never a device figure; the factor
   4 is the project's convention from the quality metrics.  The restatement is applied to the DOWNLOADED device spectrogram, so the
   STFT's own error does not enter.
+* adn_spectral_gain, per (clip, bin): E = max_t |M_dev - M_64| / max_t M_64 <= 4 floor for every bin of every clip, beside the bound
+  above (tests/recursive_bounds.py), and every entry of the state (clip, row of P / Pmin / S, bin) likewise against its own float64
+  value.  The floor is the case's own: the largest E of the float32 restatement on the same downloaded spectrogram over every bin of
+  the case's three clips, measured when the test runs, never below 2^-23, never from the device, and asserted under the cap of 1e-4.
+  The operator has one arithmetic (contraction off, one step), so both floor columns of the printed line hold the same figure.  The
+  same bound holds the tilted cases (an 80 dB slope over the bins, built on the host and uploaded), and a power of two per bin,
+  2^-((5 b) mod 13), has to come back bit for bit: M scaled by the factor, the state by its square.
 * Chunk, batch and isolation tests: exact equality, as include/adn.h pins them.
 * End to end, in two links: the device's audio against the restatement's resynthesis fed the device's own magnitudes within the
   tree's inverse-STFT tolerance TOL = 1e-4 of max |ref| (tests/test_gpu_denoise.py::test_resynth); and against the whole float64
@@ -15,6 +22,9 @@ Bounds (derived, not tuned):
 * Quality: a cap, not parity -- the device's SI-SDR gain on the 8 dB white mix is at least half the restatement's.
 Measured on the MI355X: parity uses at most 0.47 of a floor (bound 4), typically 0.05; the resynthesis link 2.3e-7 of the maximum;
 the whole chain 5.4e-8 absolute at worst; SI-SDR 7.98 -> 13.70 dB, the restatement's gain to the printed digits.
+Per bin (profiles/recursive_bins.md): M at most 1.00 of the case's floor (bound 4), at least 0.71 (T = 1, where the floor is 2^-23);
+the state 1.00 in every one of the 39 cases, the tilted and the power-of-two case included -- the device's worst E is the float32
+restatement's own to the printed digits.  Every parity case takes under 0.2 s with its floor.
 """
 import ctypes
 import os
@@ -29,6 +39,8 @@ import baseline_cases as bc  # noqa: E402
 import baseline_ref as br  # noqa: E402
 import denoise_ref  # noqa: E402
 import footprint as fp  # noqa: E402
+import recursive_bounds as rb  # noqa: E402
+import solver_bounds as sb  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -64,16 +76,29 @@ def _raw(spec, out, col0=0, params=None, state_in=None, state_out=None, n_frames
     return rc
 
 
+def _check(label, got, state, bounds):
+    """The per-bin bound on the first clips of a case: M (n, 1, F, T) and the state (n, 3, F) of the device against the case's
+    float64 restatement, each within 4 floors of the case's own float32 floor, the floors under the cap."""
+    n = got.shape[0]
+    rb.assert_cap(label, bounds)
+    rb.assert_cap(label + " state", bounds.state)
+    sb.check(f"{label} [clips {n}]", got.cpu().numpy()[:, 0].transpose(0, 2, 1), bounds.ref[:n], bounds)
+    sb.check(f"{label} state [clips {n}]", rb.state_rows(state.cpu().numpy()), bounds.state.ref[:3 * n], bounds.state)
+
+
 # ---- 1. parity -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n_frames", bc.PARITY_FRAMES)
 @pytest.mark.parametrize("n_fft", bc.PARITY_N_FFT)
 def test_parity_with_the_float64_restatement(dev, n_fft, n_frames):
     from audiodenoiser_amd.baseline import spectral_gain
+    spec3, spec3_h = _spec(dev, n_fft, n_frames, 3)
+    bounds = rb.spectral_bounds(spec3.cpu().numpy())               # the floor of the case: on the downloaded device spectrogram
     for n_clips in bc.PARITY_CLIPS:
-        spec, spec_h = _spec(dev, n_fft, n_frames, n_clips)
+        spec, spec_h = spec3[:n_clips].contiguous(), spec3_h[:n_clips]
         got, state = spectral_gain(spec)
         assert got.shape == (n_clips, 1, n_fft // 2 + 1, n_frames) and got.dtype == torch.float32
         assert state.shape == (n_clips, 3, n_fft // 2 + 1)
+        _check(rb.gain_label(n_fft, n_frames), got, state, bounds)
         got_h, state_h = got.cpu().numpy().astype(np.float64)[:, 0], state.cpu().numpy().astype(np.float64)
         for c in range(n_clips):
             want, want_state = br.spectral_gain(spec_h[c])
@@ -84,6 +109,45 @@ def test_parity_with_the_float64_restatement(dev, n_fft, n_frames):
             # the state is the same recurrence: P, Pmin and S against their own largest value
             for row in range(3):
                 assert np.abs(state_h[c, row] - want_state[row]).max() <= 4.0 * br.FLOOR * np.abs(want_state[row]).max(), (c, row)
+
+
+def _upload(dev, a):
+    return torch.from_numpy(np.array(a, order="C")).to(dev)                # a writable copy: the cases are read-only
+
+
+def _same_bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+@pytest.mark.parametrize("n_fft", rb.TILTED_GAIN)
+def test_a_tilted_spectrum_is_held_bin_by_bin(dev, n_fft):
+    """80 dB from the first bin to the last, built on the host and uploaded: the clip-wide bound allows the quiet bins an error of
+    their own size, and a wrong gain_floor, gamma or alpha in the last bin alone passes it (tests/test_recursive_bounds_host.py)."""
+    from audiodenoiser_amd.baseline import spectral_gain
+    spec_h = sb.scale_spec(rb.gain_spec(n_fft, rb.TILTED_FRAMES), sb.tilt(n_fft // 2 + 1))
+    bounds = rb.spectral_bounds(spec_h)
+    for n_clips in bc.PARITY_CLIPS:
+        got, state = spectral_gain(_upload(dev, spec_h[:n_clips]))
+        _check(rb.gain_label(n_fft, rb.TILTED_FRAMES, "tilted"), got, state, bounds)
+
+
+def test_a_power_of_two_per_bin_comes_back_bit_for_bit(dev):
+    """Every rule of the operator is a ratio or is homogeneous in p_t, and the 1e-30 under N_t is far below every power here, so
+    2^-k times a bin's input is 2^-k times its magnitudes and 2^-2k times its state, exactly
+    (tests/test_recursive_bounds_host.py checks that the float32 restatement has the property; here no square leaves the normal
+    range).  There is no such case for adn_wpe_online and adn_wpe_mc_online: P_0 = 1 / delta and the 1e-30 in phi_t are absolute,
+    so those two operators are not scale invariant."""
+    from audiodenoiser_amd.baseline import spectral_gain
+    base, f = rb.gain_spec(rb.POW2_GAIN, rb.TILTED_FRAMES), sb.pow2(rb.POW2_GAIN // 2 + 1)
+    scaled = sb.scale_spec(base, f)
+    sb.assert_squares_stay_normal(base, scaled)
+    ft = _upload(dev, f.astype(np.float32))
+    plain, plain_state = spectral_gain(_upload(dev, base))
+    got, state = spectral_gain(_upload(dev, scaled))
+    sb.assert_squares_stay_normal(plain.cpu().numpy(), got.cpu().numpy(), plain_state.cpu().numpy(), state.cpu().numpy())
+    assert _same_bits(got, plain * ft[None, None, :, None])
+    assert _same_bits(state, plain_state * (ft * ft)[None, None, :])
+    _check(rb.gain_label(rb.POW2_GAIN, rb.TILTED_FRAMES, "pow2"), got, state, rb.spectral_bounds(scaled))
 
 
 # ---- 2. footprint ----------------------------------------------------------------------------------------------------------------

@@ -6,6 +6,15 @@ Bounds (derived, not tuned):
   statements run in float32 on the host over these very cases (python tests/dereverb_stream_cases.py), never a device figure; the
   factor 4 is the project's standing margin.  The restatement is applied to the DOWNLOADED device spectrogram, so the STFT's own
   error does not enter.  mag_out likewise against |d_64|, on the same scale.
+* adn_wpe_online, per (row, bin): E = max_t |d_dev - d_64| / max_t |d_64| <= 4 floor for every bin of every row, beside the bound
+  above (tests/recursive_bounds.py).  The floor is the case's own: the largest E of the float32 restatement on the same downloaded
+  spectrogram over every bin of the case's three rows and over two float32 arithmetics -- "plain" (every product rounded, what FLOOR
+  was measured with; the "pairwise" column of the printed line) and "fma" (the header's pairing and order of every multiply-add; the
+  "sequential" column) -- measured when the test runs, never below 2^-23 (which is what the cases with T <= D get, whose reference is
+  the input bit for bit), never from the device, and asserted under the cap of 1e-4.  The same bound holds the tilted cases (an 80 dB
+  slope over the bins, built on the host and uploaded) at the defaults and at the largest parameter set.  There is no power-of-two
+  case: P_0 = 1 / delta and the 1e-30 in phi_t are absolute, the operator is not scale invariant.
+* mag_out, bit for bit: sqrtf(fmaf(re, re, im * im)) of the device's own spec_out, evaluated in float32 on the host.
 * StreamDereverberator, per stream: max |audio_dev - audio_64| <= 4 FLOOR_AUDIO max |audio_64|, FLOOR_AUDIO the error of the
   end-to-end form with every statement in float32 on the host, the two transforms included.
 * Repeat, cut, batch, bin-subset, poisoned-state, pass-through, isolation, pool and reset tests: exact equality, as include/adn.h
@@ -14,6 +23,11 @@ Measured on the MI355X: parity uses at most 0.67 of a floor (bound 4): n_fft 64,
 1.94e-6 of max |d|; at the defaults at most 0.15, the median over all 192 comparisons 0.01; mag_out at most 0.52 floors.  The
 streams against the float64 end-to-end form: 1.8e-7 - 4.1e-7 of the maximum, 0.08 - 0.19 of the audio floor (bound 4).  The whole
 file: 69 cases in 7.9 s, the command-line case 2.2 s, every other one under 0.5 s.  The rest: profiles/bench_dereverb_stream.md.
+Per bin (profiles/recursive_bins.md): at most 1.00 of the case's floor (bound 4), reached at the largest parameter set at T = 97
+(n_fft 64: row 2, bin 1, E 1.9e-6), where the fma arithmetic sets the floor and the device's worst E is that restatement's own to
+the printed digits; at the defaults at most 0.52, the tilted cases 0.15 - 1.00, the median over the 48 parity cases 0.43.  With the floors
+the file is 73 cases in 17 s: the n_fft 512 cases at the largest parameter set 2.2 s each (three host runs of K = 32 over 771 bins),
+every other parity case under 1 s.
 """
 import ctypes
 import os
@@ -28,6 +42,8 @@ import dereverb_cases as dc  # noqa: E402
 import dereverb_stream_cases as sc  # noqa: E402
 import dereverb_stream_ref as ds  # noqa: E402
 import footprint as fp  # noqa: E402
+import recursive_bounds as rb  # noqa: E402
+import solver_bounds as sb  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -61,6 +77,17 @@ def _params(kw):
     return None if kw is None else WpeStreamParams(**kw)
 
 
+def _upload(dev, a):
+    return torch.from_numpy(np.array(a, order="C")).to(dev)                # a writable copy: the cases are read-only
+
+
+def _mag_is_of_spec_out(got_h, mag_h):
+    """mag_out (n, F, T) is, bit for bit, sqrtf(fmaf(re, re, im * im)) of the device's own spec_out (n, T, F), evaluated in float32
+    on the host: the header defines M_t as that function of e_t, and the kernel computes it from the value it stores."""
+    assert mag_h.dtype == np.float32 and got_h.dtype == np.complex64
+    assert np.array_equal(mag_h.view(np.int32), np.sqrt(ds._power(got_h, np.float32)).transpose(0, 2, 1).view(np.int32))
+
+
 # ---- 1. parity -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("kw", sc.PARITY_PARAMS, ids=sc.PARAM_IDS)
 @pytest.mark.parametrize("n_frames", sc.PARITY_FRAMES)
@@ -69,14 +96,17 @@ def test_parity_with_the_float64_restatement(dev, n_fft, n_frames, kw):
     from audiodenoiser_amd.dereverb import wpe_online
     f = n_fft // 2 + 1
     spec = _spec(dev, n_fft, n_frames, 3)
-    spec_h = spec.cpu().numpy().astype(np.complex128)
-    want = [ds.wpe_online(spec_h[c], kw) for c in range(3)]
+    bounds = rb.wpe_online_bounds(spec.cpu().numpy(), kw)        # the floor of the case: on the downloaded device spectrogram
+    rb.assert_cap(rb.online_label(n_fft, n_frames, kw), bounds)
+    want = list(bounds.ref)                                      # ds.wpe_online(row, kw) in float64, row by row
     col0, width = 5, n_frames + 9
     for n_rows in sc.PARITY_ROWS:
         mag = torch.full((n_rows, 1, f, width), float("nan"), device=dev)
         got, mag_out, state = wpe_online(spec[:n_rows].contiguous(), params=_params(kw), mag_out=mag, col0=col0)
         assert got.shape == (n_rows, n_frames, f) and got.dtype == torch.complex64 and mag_out is mag and state.dtype == torch.uint8
         got_h, mag_h = got.cpu().numpy(), mag.cpu().numpy()[:, 0]
+        sb.check(f"{rb.online_label(n_fft, n_frames, kw)} [rows {n_rows}]", got_h, bounds.ref[:n_rows], bounds)
+        _mag_is_of_spec_out(got_h, mag_h[:, :, col0:col0 + n_frames])
         # the poisoned columns outside [col0, col0 + T) are untouched
         assert bool((_bits(mag[..., :col0]) == _bits(torch.full((1,), float("nan"), device=dev))).all())
         assert bool((_bits(mag[..., col0 + n_frames:]) == _bits(torch.full((1,), float("nan"), device=dev))).all())
@@ -88,6 +118,24 @@ def test_parity_with_the_float64_restatement(dev, n_fft, n_frames, kw):
                   f"({err / scale / ds.FLOOR:.2f} floors), M {err_m / scale / ds.FLOOR:.2f} floors; bound 4")
             assert err <= 4.0 * ds.FLOOR * scale, (n_rows, c, err / scale)
             assert err_m <= 4.0 * ds.FLOOR * scale, (n_rows, c, err_m / scale)
+
+
+@pytest.mark.parametrize("kw", rb.TILTED_ONLINE_PARAMS, ids=("defaults", "largest"))
+@pytest.mark.parametrize("n_fft", rb.TILTED_ONLINE)
+def test_a_tilted_spectrum_is_held_bin_by_bin(dev, n_fft, kw):
+    """80 dB from the first bin to the last, built on the host and uploaded: the row-wide bound allows the quiet bins an error of
+    their own size -- a last bin that returns its input passes it (tests/test_recursive_bounds_host.py).  There is no power-of-two
+    case beside it: P_0 = 1 / delta and the 1e-30 in phi_t are absolute, so the operator is not scale invariant."""
+    from audiodenoiser_amd.dereverb import wpe_online
+    spec_h = sb.scale_spec(rb.online_spec(n_fft, rb.TILTED_FRAMES), sb.tilt(n_fft // 2 + 1))
+    bounds = rb.wpe_online_bounds(spec_h, kw)
+    label = rb.online_label(n_fft, rb.TILTED_FRAMES, kw, "tilted")
+    rb.assert_cap(label, bounds)
+    for n_rows in sc.PARITY_ROWS:
+        got, mag, _ = wpe_online(_upload(dev, spec_h[:n_rows]), params=_params(kw))
+        got_h = got.cpu().numpy()
+        sb.check(f"{label} [rows {n_rows}]", got_h, bounds.ref[:n_rows], bounds)
+        _mag_is_of_spec_out(got_h, mag.cpu().numpy()[:, 0])
 
 
 # ---- 2. exact pins ---------------------------------------------------------------------------------------------------------------
