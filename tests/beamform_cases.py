@@ -35,6 +35,12 @@ WIDE_CASE = (512, 97, 4, dict())
 LOADING_CASE = (64, 97, 4, dict(loading=1e-6))
 PITCH_CASE = (64, 23, 3, dict(mag_extra=9))
 UNIFORM_CASE = (64, 65, 5, dict(uniform_mask=True))
+# The instantiations the grid above does not reach (tests/variant_cover.py): C = 4 is the edge of the 4-lane layout (C == LPB, all 64
+# lanes stage a cell, 10 entries over 4 lanes), 6 and 7 are 21 and 28 entries over 8 lanes (3 and 4 per lane, a partial last
+# round).  Over PARITY_FRAMES at both ends of the reference channel, and C = 6 once at an interior column of G.  Judged per bin
+# only (tests/solver_bounds.py): the FLOOR constants are measured over parity_cases() and do not see these.
+VARIANT_CHANNELS = (4, 6, 7)
+VARIANT_REF_CASE = (64, 65, 6, (3,))
 
 
 def parity_cases():
@@ -50,6 +56,14 @@ def parity_cases():
 
 def refs_of(channels):
     return (0,) if channels == 1 else (0, channels - 1)
+
+
+def variant_cases():
+    """(n_fft, n_frames, C, reference channels) of every variant case."""
+    for n_frames in PARITY_FRAMES:
+        for channels in VARIANT_CHANNELS:
+            yield PARITY_N_FFT, n_frames, channels, refs_of(channels)
+    yield VARIANT_REF_CASE
 
 
 def params_of(extra, ref):

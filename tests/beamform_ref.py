@@ -67,9 +67,11 @@ def mask(specs, mags, rho, dtype=np.float64):
     return m
 
 
-def mvdr(specs, mags, params=None, dtype=np.float64, with_filter=False, order="pairwise"):
+def mvdr(specs, mags, params=None, dtype=np.float64, with_filter=False, order="pairwise", slip=None):
     """specs (C, T, F) complex, mags (C, F, width >= T) real -> Y (T, F) complex in `dtype`'s precision; with_filter: also w (F, C).
-    order: how the sums over t of both covariances are formed, as in dereverb_ref.wpe."""
+    order: how the sums over t of both covariances are formed, as in dereverb_ref.wpe.  slip: None, or
+    `slip(phi_s, phi_n) -> (phi_s, phi_n)` applied to the covariances before the solve -- the mutations of
+    tests/test_solver_bounds_host.py, never a reference."""
     specs = np.asarray(specs)
     C = specs.shape[0]
     p = dict(DEFAULTS)
@@ -95,7 +97,7 @@ def mvdr(specs, mags, params=None, dtype=np.float64, with_filter=False, order="p
                     P[:, k, r] = np.conj(P[:, r, k])
                 P[:, r, r] = P[:, r, r].real                                      # the diagonal's imaginary part is dropped
             phi.append(P)
-        phi_s, phi_n = phi
+        phi_s, phi_n = phi if slip is None else slip(*phi)
         idx = np.arange(C)
         tr = np.zeros(F, dt)
         for r in range(C):

@@ -38,6 +38,13 @@ ADDED = ((23, 3, dict(ref_channel=2), dict()),
          (23, 5, dict(refresh=4, forget=0.9, ref_channel=4), dict()),
          (65, 5, dict(loading=1e-6), dict()),
          (23, 3, dict(), dict(mag_extra=9, mag_col0=4)))
+# The instantiations the grid above does not reach (tests/variant_cover.py): mvdr_stream_kernel<4>, <6> and <7>, over PARITY_FRAMES,
+# C = 4 once at refresh 4 and forget 0.9, C = 7 once at its last reference channel.  A floor above VARIANT_CAP bounds nothing: such
+# a case may not be here (tests/test_variant_cover_host.py).
+VARIANT_CHANNELS = (4, 6, 7)
+VARIANT_ADDED = ((65, 4, dict(refresh=4, forget=0.9), dict()),
+                 (23, 7, dict(ref_channel=6), dict()))
+VARIANT_CAP = 5e-4
 
 
 def parity_cases():
@@ -45,6 +52,13 @@ def parity_cases():
         for channels in PARITY_CHANNELS:
             yield n_frames, channels, dict(), dict()
     yield from ADDED
+
+
+def variant_cases():
+    for n_frames in PARITY_FRAMES:
+        for channels in VARIANT_CHANNELS:
+            yield n_frames, channels, dict(), dict()
+    yield from VARIANT_ADDED
 
 
 def label(n_frames, channels, params, extra, kind="parity"):
@@ -118,6 +132,10 @@ def main():
         n_frames, channels, params, extra = case
         b = bounds(*host_inputs(n_frames, channels), channels, params)
         print(f"{label(*case)}: float32 floor {b.floors['sequential']:.3g}", flush=True)
+    for case in variant_cases():
+        n_frames, channels, params, extra = case
+        b = bounds(*host_inputs(n_frames, channels), channels, params)
+        print(f"{label(*case, kind='variant')}: float32 floor {b.floors['sequential']:.3g}", flush=True)
 
 
 if __name__ == "__main__":

@@ -31,6 +31,11 @@ CHUNK = 64                                  # frames per staged chunk of csrc/de
 # ... and three more parameter sets at T = 97: the smallest, the largest, and the weakest loading
 EXTRA_FRAMES = 97
 EXTRA_PARAMS = (dict(taps=1, delay=1, iterations=1), dict(taps=32, delay=8, iterations=2), dict(loading=1e-6))
+# The kernel layouts the cases above do not reach (tests/variant_cover.py): K = 19 is 16 lanes per bin with a partial fifth block
+# row, 21 the first K of 32 lanes (partial), 28 the last (all 28 blocks), 29 the first of 64 lanes (partial).  n_fft 64, judged per
+# bin only (tests/solver_bounds.py): FLOOR above is measured over parity_cases() and does not see these.
+VARIANT_TAPS = (19, 21, 28, 29)
+VARIANT_FRAMES = (23, 97)
 
 
 @functools.lru_cache(maxsize=None)
@@ -49,6 +54,13 @@ def parity_cases():
             yield n_fft, n_frames, None
         for params in EXTRA_PARAMS:
             yield n_fft, EXTRA_FRAMES, params
+
+
+def variant_cases():
+    """(n_fft, n_frames, params) of every variant case."""
+    for taps in VARIANT_TAPS:
+        for n_frames in VARIANT_FRAMES:
+            yield 64, n_frames, dict(taps=taps)
 
 
 def floor_of(spec, params=None):

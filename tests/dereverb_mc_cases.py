@@ -36,6 +36,13 @@ PARITY_GROUPS = (1, 3)
 # ... n_fft 512 (F = 257) once, and the weakest loading once
 WIDE_CASE = (512, 97, (2, 10), None)
 LOADING_CASE = (64, 97, (2, 16), dict(loading=1e-6))
+# The kernel layouts PARITY_CK does not reach (tests/variant_cover.py): one pair per key (lanes per bin, WINDOW, P block columns,
+# partial last row block, partial last P block, lanes doubled), the defaults taps = 32 // C where a key holds one -- (3, 10),
+# (5, 6), (7, 4) --, and beside them (6, 5), the remaining default, and (7, 1), the smallest N at the largest pitch of 28 cells.
+# n_fft 64, judged per bin only (tests/solver_bounds.py): the FLOOR constants are measured over parity_cases() and do not see these.
+VARIANT_CK = ((2, 6), (2, 8), (4, 5), (4, 2), (3, 2), (4, 4), (3, 4), (4, 7), (2, 14), (3, 10), (8, 3), (8, 1), (6, 2), (5, 6),
+              (5, 2), (7, 4), (5, 4), (6, 5), (7, 1))
+VARIANT_FRAMES = (23, 97)
 
 
 def parity_cases():
@@ -45,6 +52,13 @@ def parity_cases():
             yield PARITY_N_FFT, n_frames, ck, None
     yield WIDE_CASE
     yield LOADING_CASE
+
+
+def variant_cases():
+    """(n_fft, n_frames, (C, K), None) of every variant case."""
+    for ck in VARIANT_CK:
+        for n_frames in VARIANT_FRAMES:
+            yield PARITY_N_FFT, n_frames, ck, None
 
 
 def params_of(ck, extra=None):

@@ -34,9 +34,10 @@ def check_params(p, channels):
         raise ValueError("channels * taps")
 
 
-def wpe_mc(specs, params=None, dtype=np.float64, with_taps=False, order="pairwise"):
+def wpe_mc(specs, params=None, dtype=np.float64, with_taps=False, order="pairwise", slip=None):
     """specs (C, T, F) complex -> d (C, T, F) complex in `dtype`'s precision; with_taps: also G (F, N, C).  order: how every sum
-    over t is formed, as in dereverb_ref.wpe."""
+    over t is formed, as in dereverb_ref.wpe.  slip: None, or `slip(R, P) -> (R, P)` applied to every iteration's correlations
+    before the solve -- the mutations of tests/test_solver_bounds_host.py, never a reference."""
     specs = np.asarray(specs)
     C = specs.shape[0]
     p = defaults(C) if 1 <= C <= MAX_CHANNELS else dict(dr.DEFAULTS)
@@ -78,6 +79,8 @@ def wpe_mc(specs, params=None, dtype=np.float64, with_taps=False, order="pairwis
                     R[:, q, r] = np.conj(R[:, r, q])
                 for c in range(C):
                     P[:, r, c] = dr._sum_t(u[r] * np.conj(X[c]), ct, order)
+            if slip is not None:
+                R, P = slip(R, P)
             tr = np.zeros(F, dt)
             for r in range(N):
                 tr = tr + R[:, r, r].real

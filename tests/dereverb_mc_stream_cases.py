@@ -36,6 +36,12 @@ PARITY_GROUPS = (1, 3)
 WIDE_CASE = (512, 97, (2, 10), None)
 FORGET_CASE = (64, 97, (2, 16), dict(forget=ms.lowest_forget(32)))
 DELAY_CASE = (64, 97, (8, 4), dict(delay=8))
+# The channel counts PARITY_CK does not reach (tests/variant_cover.py): C is a run-time value of the kernel, and at 5, 6 and 7 the
+# defaults taps = 32 // C give N = 30, 30, 28 (rows of P idle), record sizes that are multiples of nothing and rings at c H with
+# odd H; (5, 2) and (7, 1) are short rings.  At T = 4 only frame 3 is filtered.  Judged per bin only (tests/recursive_bounds.py):
+# FLOOR below is measured over parity_cases() and does not see these.
+VARIANT_CK = ((5, 6), (6, 5), (7, 4), (5, 2), (7, 1))
+VARIANT_FRAMES = (4, 23, 97)
 # end to end: C = 2 at the defaults (taps 16), three recordings, with and without the gain
 E2E_FRAMES = 97
 E2E_CHANNELS = 2
@@ -55,6 +61,13 @@ def parity_cases():
     yield WIDE_CASE
     yield FORGET_CASE
     yield DELAY_CASE
+
+
+def variant_cases():
+    """(n_fft, n_frames, (C, K), None) of every variant case."""
+    for ck in VARIANT_CK:
+        for n_frames in VARIANT_FRAMES:
+            yield PARITY_N_FFT, n_frames, ck, None
 
 
 def case_id(case):

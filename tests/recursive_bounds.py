@@ -177,9 +177,17 @@ def _gain_rows(n_fft, n_frames, kind, factor=None):
     yield gain_label(n_fft, n_frames, kind) + " state", lambda: thunk().state
 
 
+def variant_cases():
+    """(label, thunk -> Bounds) of every variant case of adn_wpe_mc_online (the channel counts of tests/variant_cover.py that the
+    parity grid does not reach) on the host's own inputs."""
+    for n_fft, n_frames, ck, extra in msc.variant_cases():
+        yield (mc_label(n_fft, n_frames, ck, extra, "variant"),
+               lambda a=(n_fft, n_frames, ck[0]), p=msc.params_of(ck, extra): wpe_mc_online_bounds(mc_spec(*a), a[2], p))
+
+
 def host_cases():
-    """(label, thunk -> Bounds) of every parity, tilted and power-of-two case on the host's own inputs; nothing is computed before
-    a thunk is called.  A spectral-gain case has two rows: M, and the state."""
+    """(label, thunk -> Bounds) of every parity, tilted, power-of-two and variant case on the host's own inputs; nothing is
+    computed before a thunk is called.  A spectral-gain case has two rows: M, and the state."""
     for n_fft in bc.PARITY_N_FFT:
         for n_frames in bc.PARITY_FRAMES:
             yield from _gain_rows(n_fft, n_frames, "parity")
@@ -198,6 +206,7 @@ def host_cases():
         yield (mc_label(64, TILTED_FRAMES, ck, None, "tilted"),
                lambda ck=ck: wpe_mc_online_bounds(_scaled(mc_spec(64, TILTED_FRAMES, ck[0]), sb.tilt), ck[0], msc.params_of(ck)))
     yield from _gain_rows(POW2_GAIN, TILTED_FRAMES, "pow2", sb.pow2)
+    yield from variant_cases()
 
 
 LINE = re.compile(r"per bin: (.*?): floor pairwise (\S+) sequential (\S+); worst E (\S+) = (\S+) floors \(bound 4\) at row (\d+) bin (\d+)")
@@ -229,12 +238,13 @@ def main(logs):
         print(rows[-1], flush=True)
         if d is not None:
             op = label.split()[0] + (" state" if label.endswith(" state") else "")
-            if op not in largest or d[0] > largest[op][0]:
-                largest[op] = (d[0], label)
+            for name in (op, op + ", variant cases") if " variant " in label else (op,):
+                if name not in largest or d[0] > largest[name][0]:
+                    largest[name] = (d[0], label)
     top = "".join(f"* `{op}`: {v:.2f} floors ({label})\n" for op, (v, label) in largest.items()) or "* no device log was given\n"
     text = ("# Per-bin float32 floors of the recursions\n\n"
-            "Written by `python tests/recursive_bounds.py <logs of the GPU tests>`.  One row per parity, tilted and power-of-two "
-            "case of `adn_spectral_gain` (two rows: the magnitudes, and the state, every entry against its own reference value), "
+            "Written by `python tests/recursive_bounds.py <logs of the GPU tests>`.  One row per parity, tilted, power-of-two "
+            "and variant (`tests/variant_cover.py`) case of `adn_spectral_gain` (two rows: the magnitudes, and the state, every entry against its own reference value), "
             "`adn_wpe_online` and `adn_wpe_mc_online`.  `E` is the largest error of a (row, bin) relative to that bin's own maximum "
             "over the frames, against the float64 restatement (`tests/recursive_bounds.py`).  The two floor columns are the float32 "
             "restatement's largest `E` in its two arithmetics, \"plain\" (every product rounded: numpy's complex64) and \"fma\" (the "

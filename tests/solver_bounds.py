@@ -240,9 +240,30 @@ def _scaled(spec, factor):
     return spec if factor is None else scale_spec(spec, factor(spec.shape[-1]))
 
 
+VARIANT_CAP = 5e-4                           # a variant case whose floor exceeds this bounds nothing and may not be in a table
+
+
+def mvdr_variant_extra(channels, refs):
+    """What a variant case's label carries: nothing at both ends of the reference channel, the channel where it names one."""
+    return None if tuple(refs) == bc.refs_of(channels) else dict(ref_channel=refs[0])
+
+
+def variant_cases():
+    """(label, thunk -> Bounds) of every variant case (the kernel layouts of tests/variant_cover.py that the parity grids do not
+    reach) on the host's own inputs."""
+    for n_fft, n_frames, kw in dc.variant_cases():
+        yield wpe_label(n_fft, n_frames, kw, "variant"), lambda a=(n_fft, n_frames), kw=kw: wpe_bounds(wpe_spec(*a), kw)
+    for n_fft, n_frames, ck, extra in mc.variant_cases():
+        yield (mc_label(n_fft, n_frames, ck, extra, "variant"),
+               lambda a=(n_fft, n_frames, ck[0]), p=mc.params_of(ck, extra): wpe_mc_bounds(mc_spec(*a), a[2], p))
+    for n_fft, n_frames, channels, refs in bc.variant_cases():
+        yield (mvdr_label(n_fft, n_frames, channels, mvdr_variant_extra(channels, refs), "variant"),
+               lambda a=(n_fft, n_frames, channels), r=refs: mvdr_bounds(*mvdr_inputs(*a), a[2], None, r))
+
+
 def host_cases():
-    """(label, thunk -> Bounds) of every parity, tilted and power-of-two case on the host's own inputs; nothing is computed before
-    a thunk is called."""
+    """(label, thunk -> Bounds) of every parity, tilted, power-of-two and variant case on the host's own inputs; nothing is
+    computed before a thunk is called."""
     for n_fft, n_frames, kw in dc.parity_cases():
         yield wpe_label(n_fft, n_frames, kw), lambda a=(n_fft, n_frames), kw=kw: wpe_bounds(wpe_spec(*a), kw)
     for n_fft, n_frames, ck, extra in mc.parity_cases():
@@ -260,6 +281,7 @@ def host_cases():
         for channels in TILTED_MVDR:
             yield (mvdr_label(64, TILTED_FRAMES, channels, None, kind),
                    lambda c=channels, f=factor: _mvdr_case(64, TILTED_FRAMES, c, dict(), f))
+    yield from variant_cases()
 
 
 def main(logs):
@@ -271,7 +293,7 @@ def main(logs):
             base = re.sub(r" \[[^\]]*\]$", "", label)                      # the run within a case: [clips 3], [ref 7 groups 1]
             if base not in device or ratio > device[base][0]:
                 device[base] = (ratio, m.group(4), label[len(base):].strip(" []"), m.group(6), m.group(7), floor)
-    rows = []
+    rows, largest = [], {}
     for label, thunk in host_cases():
         b = thunk()
         d = device.get(label)
@@ -279,8 +301,14 @@ def main(logs):
         spread = f"{b.floors['sequential'] / b.floors['pairwise']:.2f}" if b.floors["pairwise"] > 0 else "–"
         rows.append(f"| {label} | {b.floors['pairwise']:.2e} | {b.floors['sequential']:.2e} | {spread} | {there} |")
         print(rows[-1], flush=True)
+        if d is not None:
+            for op in (label.split()[0], label.split()[0] + ", variant cases") if " variant " in label else (label.split()[0],):
+                if op not in largest or d[0] > largest[op][0]:
+                    largest[op] = (d[0], label)
+    top = "".join(f"* `{op}`: {v:.2f} floors ({label})\n" for op, (v, label) in sorted(largest.items())) or "* no device log was given\n"
     text = ("# Per-bin float32 floors of the batch solvers\n\n"
-            "Written by `python tests/solver_bounds.py <logs of the GPU tests>`.  One row per parity, tilted and power-of-two case of "
+            "Written by `python tests/solver_bounds.py <logs of the GPU tests>`.  One row per parity, tilted, power-of-two and variant "
+            "case (the kernel layouts of `tests/variant_cover.py` that the parity grids do not reach) of "
             "`adn_wpe`, `adn_wpe_mc` and `adn_mvdr`.  `E` is the largest error of a (row, bin) relative to that bin's own maximum over "
             "the frames, against the float64 restatement (`tests/solver_bounds.py`).  The two floor columns are the float32 "
             "restatement's largest `E` with numpy's pairwise sums over t and with sequential sums, **measured on the host** from the "
@@ -289,6 +317,7 @@ def main(logs):
             "(for the parity cases on the downloaded device spectrogram, whose last bits are not the host's: where T is a few "
             "frames the solve is conditioned by the loading alone and the two floors differ by up to 3 x, which is why a floor is "
             "measured on the very input the device ran on), over every run of the case (1 and 3 clips / groups, both reference channels), with the place it sits.\n\n"
+            "Largest device `E` in floors per operator (bound 4):\n\n" + top + "\n"
             "| case | floor, pairwise | floor, sequential | sequential / pairwise | device: worst E in floors of its run's floor, where |\n"
             "|---|---|---|---|---|\n" + "\n".join(rows) + "\n")
     open(os.path.join(ROOT, "profiles", "solver_bins.md"), "w").write(text)

@@ -23,6 +23,9 @@ Measured on the MI355X: parity uses at most 0.69 of a floor among the full-rank 
 restatement's, to the printed digits.
 Per bin (profiles/solver_bins.md): at most 2.34 of the case's floor (bound 4): n_fft 64, T = 23, C = 2, ref 0, group 1, bin 15,
 E 4.4e-6; the tilted cases at most 2.04, the power-of-two cases 1.75 and bit for bit; the median over the 118 runs 0.90.
+The instantiations that grid does not reach (tests/variant_cover.py: C = 4, 6, 7 over the parity frames, C = 6 at reference
+channel 3, per bin only): at most 3.03 floors (C = 7, T = 97, ref 0, group 2, bin 1, E 7.6e-6 on a floor of 2.5e-6), 3.00 at ref 6;
+the median over the 62 runs 0.89.
 """
 import ctypes
 import os
@@ -40,7 +43,7 @@ import solver_bounds as sb  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-PIN_CHANNELS = (2, 3, 5, 8)                                # 4 and 8 lanes per bin; 1, 2, 2 and 5 triangle entries per lane
+PIN_CHANNELS = (2, 3, 4, 5, 7, 8)                          # 4 and 8 lanes per bin; 1, 2, 3, 2, 4 and 5 triangle entries per lane
 
 
 @pytest.fixture(scope="module")
@@ -137,6 +140,28 @@ def test_parity_with_the_float64_restatement(dev, n_frames, channels):
                          ids=("n_fft512", "loading1e-6", "wide_mag", "uniform_mask"))
 def test_parity_at_the_wide_transform_the_weakest_loading_a_wide_pitch_and_another_mask(dev, case):
     _parity(dev, *case)
+
+
+@pytest.mark.parametrize("n_fft,n_frames,channels,refs", tuple(bc.variant_cases()),
+                         ids=[f"T{t}-C{c}" + ("" if r == bc.refs_of(c) else f"-ref{r[0]}") for _, t, c, r in bc.variant_cases()])
+def test_parity_at_the_instantiations_the_grid_does_not_reach(dev, n_fft, n_frames, channels, refs):
+    """mvdr_kernel<4> (the edge of the 4-lane layout), <6> and <7> (21 and 28 triangle entries over 8 lanes, a partial last round)
+    over the parity frames at both ends of the reference channel, and C = 6 once at an interior column of G
+    (tests/variant_cover.py).  Per bin only: the FLOOR constants of beamform_ref are measured over the parity grid."""
+    from audiodenoiser_amd.beamform import mvdr
+    f = n_fft // 2 + 1
+    spec, mag = _inputs(dev, n_fft, n_frames, channels)
+    bounds = sb.mvdr_bounds(spec.cpu().numpy(), mag.cpu().numpy()[:, 0], channels, None, refs)
+    assert bounds.floor <= sb.VARIANT_CAP, bounds.floor
+    label = sb.mvdr_label(n_fft, n_frames, channels, sb.mvdr_variant_extra(channels, refs), "variant")
+    for ref in refs:
+        for n_groups in bc.PARITY_GROUPS:
+            got, out_mag = mvdr(spec[:n_groups * channels].contiguous(), mag[:n_groups * channels].contiguous(), channels,
+                                _params(dict(ref_channel=ref)))
+            assert got.shape == (n_groups, n_frames, f) and got.dtype == torch.complex64
+            got_h = got.cpu().numpy()
+            assert np.array_equal(out_mag.cpu().numpy()[:, 0].view(np.int32), _mag_of(got_h).transpose(0, 2, 1).view(np.int32))
+            sb.check(f"{label} [ref {ref} groups {n_groups}]", got_h, bounds.ref[ref][:n_groups], bounds)
 
 
 def _upload(dev, a):
@@ -250,8 +275,8 @@ def test_a_non_finite_value_stays_in_its_own_group_and_bin(dev, channels, bad):
 
 
 # ---- 4. footprint ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n_fft,n_frames,channels", ((64, 65, 2), (64, 5, 3), (64, 23, 8), (512, 23, 4)),
-                         ids=("C2", "C3short", "C8", "n_fft512"))
+@pytest.mark.parametrize("n_fft,n_frames,channels", ((64, 65, 2), (64, 5, 3), (64, 23, 8), (512, 23, 4), (64, 23, 7)),
+                         ids=("C2", "C3short", "C8", "n_fft512", "C7"))
 def test_footprint_only_what_the_call_owns(dev, n_fft, n_frames, channels):
     from audiodenoiser_amd import _lib
     from audiodenoiser_amd.beamform import mvdr

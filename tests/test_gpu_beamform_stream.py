@@ -14,6 +14,8 @@ Measured on the MI355X (profiles/bench_beamform_stream.md): parity uses at most 
 forget 0.9, bin 24, E 2.4e-4; the median over the 58 runs 0.73.  The stream's audio 0.68 ... 1.09 floors per group.  At loading
 1e-6 the floor is 0.26 (frame 0 solves a rank-one system that only the loading conditions), so that case's bound holds nothing
 beyond finiteness; it stays in the grid.  C = 1 against the untouched windows: bit for bit.
+The instantiations that grid does not reach (tests/variant_cover.py: C = 4, 6, 7, floors capped at 5e-4): at most 1.19 floors
+(C = 7, T = 23, group 0, bin 8, E 2.7e-4), the median over the 28 runs 0.75.
 """
 import ctypes
 import os
@@ -33,7 +35,7 @@ import solver_bounds as sb  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-PIN_CHANNELS = (2, 3, 5, 8)                                # 4 and 8 lanes per bin; 1, 2, 2 and 5 triangle entries per lane
+PIN_CHANNELS = (2, 3, 4, 5, 7, 8)                          # 4 and 8 lanes per bin; 1, 2, 3, 2, 4 and 5 triangle entries per lane
 F = bsc.N_BINS
 
 
@@ -100,6 +102,22 @@ def test_parity_with_the_float64_restatement(dev, case):
         got_h = got.cpu().numpy()
         assert np.array_equal(out_mag.cpu().numpy()[:, 0].view(np.int32), _mag_of(got_h).transpose(0, 2, 1).view(np.int32))
         sb.check(f"{bsc.label(*case)} [groups {n_groups}]", got_h, bounds.ref[:n_groups], bounds)
+
+
+@pytest.mark.parametrize("case", tuple(bsc.variant_cases()), ids=lambda c: f"T{c[0]}-C{c[1]}-" + "-".join(f"{k}{v}" for k, v in {**c[2], **c[3]}.items()))
+def test_parity_at_the_instantiations_the_grid_does_not_reach(dev, case):
+    """mvdr_stream_kernel<4>, <6> and <7> (tests/variant_cover.py): the same bound, the floor the case's own and under the cap."""
+    n_frames, channels, kw, extra = case
+    spec, mag, col0 = _inputs(dev, n_frames, channels, extra)
+    bounds = bsc.bounds(spec.cpu().numpy(), mag.cpu().numpy()[:, 0, :, col0:col0 + n_frames], channels, kw)
+    assert bounds.floor <= bsc.VARIANT_CAP, bounds.floor
+    for n_groups in bsc.PARITY_GROUPS:
+        n = n_groups * channels
+        got, out_mag, state = _online(spec[:n], mag[:n], channels, kw, mag_col0=col0)
+        assert got.shape == (n_groups, n_frames, F) and got.dtype == torch.complex64
+        got_h = got.cpu().numpy()
+        assert np.array_equal(out_mag.cpu().numpy()[:, 0].view(np.int32), _mag_of(got_h).transpose(0, 2, 1).view(np.int32))
+        sb.check(f"{bsc.label(*case, kind='variant')} [groups {n_groups}]", got_h, bounds.ref[:n_groups], bounds)
 
 
 # ---- 2. exact pins ---------------------------------------------------------------------------------------------------------------
@@ -256,7 +274,7 @@ def _traced(dev, channels, carved):
     return sd, Traced, ()
 
 
-@pytest.mark.parametrize("channels", (2, 5), ids=lambda c: f"C{c}")
+@pytest.mark.parametrize("channels", (2, 5, 7), ids=lambda c: f"C{c}")
 def test_stream_is_online_bit_for_bit_writes_nothing_else_and_meets_the_float64_chain(dev, channels):
     c = channels
     x = bc.parity_audio(bsc.N_FFT, STREAM_FRAMES, c)[:2 * c, :STREAM_LENGTH]
@@ -391,7 +409,7 @@ def test_command_line_live(dev, tmp_path):
 
 
 # ---- 5. footprint and refusals -------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n_frames,channels", ((23, 2), (5, 3), (23, 8)), ids=("C2", "C3short", "C8"))
+@pytest.mark.parametrize("n_frames,channels", ((23, 2), (5, 3), (23, 8), (23, 7)), ids=("C2", "C3short", "C8", "C7"))
 def test_online_writes_only_what_the_call_owns_and_refused_calls_write_nothing(dev, n_frames, channels):
     from audiodenoiser_amd import _lib
     from audiodenoiser_amd.beamform import mvdr_stream_state_bytes

@@ -21,6 +21,8 @@ at the defaults at most 0.34 (n_fft 64, T = 22, clip 1), the median over all cas
 the maximum; SI-SDR 3.33 -> 6.54 dB, the cascade 8.79 dB against 6.49 dB for the gain alone: the restatement's, to the printed digits.
 Per bin (profiles/solver_bins.md): at most 2.85 of the case's floor (bound 4): n_fft 64, T = 5, clip 0, bin 14, E 6.3e-5; the tilted
 cases at most 1.35, the power-of-two case 0.83 and bit for bit; the median over the 57 runs 1.05.
+The lane layouts that grid does not reach (tests/variant_cover.py: K = 19, 21, 28, 29 at T = 23 and 97, per bin only): at most
+1.88 floors (K = 21, T = 23, clip 1, bin 16, E 1.8e-4), the median over the 16 runs 1.02.
 """
 import ctypes
 import os
@@ -131,6 +133,22 @@ def _mag_within_2_ulp(got_h, mag_h):
     ref = np.sqrt(got_h.real.astype(np.float64) ** 2 + got_h.imag.astype(np.float64) ** 2).transpose(0, 2, 1)   # (n, F, T)
     ulps = np.abs(mag_h.astype(np.float64) - ref) / np.spacing(np.maximum(ref, np.finfo(np.float32).tiny).astype(np.float32))
     assert ulps.max() <= 2.0, float(ulps.max())
+
+
+@pytest.mark.parametrize("n_fft,n_frames,kw", tuple(dc.variant_cases()), ids=lambda v: f"K{v['taps']}" if isinstance(v, dict) else str(v))
+def test_parity_at_the_lane_layouts_the_grid_does_not_reach(dev, n_fft, n_frames, kw):
+    """K = 19, 21, 28, 29 (tests/variant_cover.py): wpe_kernel<32>, and a partial last block row at every lane grouping.  Per bin
+    only: dereverb_ref.FLOOR is measured over the parity grid and does not speak for these."""
+    from audiodenoiser_amd.dereverb import wpe
+    spec = _spec(dev, n_fft, n_frames, 3)
+    bounds = sb.wpe_bounds(spec.cpu().numpy(), kw)             # the float64 restatement and the case's own float32 floor
+    assert bounds.floor <= sb.VARIANT_CAP, bounds.floor
+    for n_clips in dc.PARITY_CLIPS:
+        got, mag = wpe(spec[:n_clips].contiguous(), _params(kw))
+        assert got.shape == (n_clips, n_frames, n_fft // 2 + 1) and got.dtype == torch.complex64
+        got_h = got.cpu().numpy()
+        _mag_within_2_ulp(got_h, mag.cpu().numpy()[:, 0])
+        sb.check(f"{sb.wpe_label(n_fft, n_frames, kw, 'variant')} [clips {n_clips}]", got_h, bounds.ref[:n_clips], bounds)
 
 
 @pytest.mark.parametrize("n_fft", sb.TILTED_WPE)

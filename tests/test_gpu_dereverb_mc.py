@@ -23,6 +23,8 @@ SI-SDR of the joint class 3.33 -> 9.95 and 3.36 -> 10.52 dB: the restatement's, 
 Per bin (profiles/solver_bins.md): at most 3.62 of the case's floor (bound 4): the power-of-two case at (2, 10), T = 97, group 0,
 channel 0, bin 1, E 3.2e-4 -- the bin of the group-wide figure above; 3.18 there unscaled, 2.59 tilted; both power-of-two cases bit
 for bit; the median over the 94 runs 0.85.
+The 17 layouts PARITY_CK does not reach (tests/variant_cover.py: 19 pairs at T = 23 and 97, per bin only): at most 1.96 floors
+((5, 2), T = 23, group 1, channel 4, bin 10, E 1.1e-4), next 1.94 at (6, 5); the median over the 76 runs 1.19.
 """
 import ctypes
 import os
@@ -40,7 +42,9 @@ import solver_bounds as sb  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-PIN_CK = ((2, 5), (3, 7), (3, 8), (2, 16))                 # 16, 32, 32 and 64 lanes per bin; K % 4 != 0 twice, == 0 twice
+# 16, 32, 32 and 64 lanes per bin; K % 4 != 0 twice, == 0 twice; (5, 6): two P block columns, the second with a repeated last channel;
+# (3, 2): lanes doubled beyond what the blocks need
+PIN_CK = ((2, 5), (3, 7), (3, 8), (2, 16), (5, 6), (3, 2))
 
 
 @pytest.fixture(scope="module")
@@ -119,6 +123,26 @@ def test_parity_with_the_float64_restatement(dev, n_frames, ck):
 @pytest.mark.parametrize("case", (mc.WIDE_CASE, mc.LOADING_CASE), ids=("n_fft512", "loading1e-6"))
 def test_parity_at_the_wide_transform_and_the_weakest_loading(dev, case):
     _parity(dev, *case)
+
+
+@pytest.mark.parametrize("n_frames", mc.VARIANT_FRAMES)
+@pytest.mark.parametrize("ck", mc.VARIANT_CK, ids=lambda ck: f"C{ck[0]}K{ck[1]}")
+def test_parity_at_the_lane_layouts_the_grid_does_not_reach(dev, ck, n_frames):
+    """One (C, K) per key of tests/variant_cover.py that PARITY_CK leaves out: the doubled lane groups, two P block columns with a
+    repeated last channel (C = 5, 6, 7), the defaults taps = 32 // C of 3, 5, 6 and 7 microphones.  Per bin only: the FLOOR constants
+    of dereverb_mc_ref are measured over the parity grid and do not speak for these."""
+    from audiodenoiser_amd.dereverb import wpe_joint
+    n_fft, channels, kw = mc.PARITY_N_FFT, ck[0], mc.params_of(ck)
+    spec = _spec(dev, n_fft, n_frames, channels)
+    bounds = sb.wpe_mc_bounds(spec.cpu().numpy(), channels, kw)     # the float64 restatement and the case's own float32 floor
+    assert bounds.floor <= sb.VARIANT_CAP, bounds.floor
+    for n_groups in mc.PARITY_GROUPS:
+        got, mag = wpe_joint(spec[:n_groups * channels].contiguous(), channels, _params(kw))
+        assert got.shape == (n_groups * channels, n_frames, n_fft // 2 + 1) and got.dtype == torch.complex64
+        got_h = got.cpu().numpy()
+        assert np.array_equal(mag.cpu().numpy()[:, 0].view(np.int32), _mag_of(got_h).transpose(0, 2, 1).view(np.int32))
+        sb.check(f"{sb.mc_label(n_fft, n_frames, ck, None, 'variant')} [groups {n_groups}]", got_h,
+                 bounds.ref[:n_groups * channels], bounds)
 
 
 def _upload(dev, a):
@@ -230,8 +254,8 @@ def test_a_non_finite_value_stays_in_its_own_group_and_bin(dev, ck, bad):
 
 
 # ---- 4. footprint ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n_fft,n_frames,ck", ((64, 65, (2, 10)), (64, 5, (3, 7)), (64, 70, (8, 4)), (512, 23, (2, 16))),
-                         ids=("C2K10", "C3K7short", "C8K4", "n_fft512"))
+@pytest.mark.parametrize("n_fft,n_frames,ck", ((64, 65, (2, 10)), (64, 5, (3, 7)), (64, 70, (8, 4)), (512, 23, (2, 16)), (64, 23, (7, 4))),
+                         ids=("C2K10", "C3K7short", "C8K4", "n_fft512", "C7K4"))
 def test_footprint_only_what_the_call_owns(dev, n_fft, n_frames, ck):
     from audiodenoiser_amd import _lib
     from audiodenoiser_amd.dereverb import wpe_joint
@@ -325,6 +349,28 @@ def test_joint_end_to_end_and_quality(dev):
     with pytest.raises(ValueError, match="channels"):
         dn.denoise(torch.zeros((9, 600), device=dev))
     assert tight.denoise(short[0]).shape == (6000,)
+
+
+@pytest.mark.parametrize("channels", (5, 6, 7), ids=lambda c: f"C{c}")
+def test_no_parameters_is_the_library_s_null_at_five_six_and_seven_channels(dev, channels):
+    """taps = 32 // C is stated twice, by joint_default_taps of the library and by the Python classes: a 5-, 6- or 7-channel
+    recording through the class with no parameters is, bit for bit, adn_wpe_mc with params = NULL."""
+    from audiodenoiser_amd.dereverb import Dereverberator, WpeParams, wpe_joint
+    from audiodenoiser_amd.griffin_lim import stft_complex
+    c = channels
+    xd = torch.from_numpy(mc.parity_audio(64, 97, c)[:c].copy()).to(dev)
+    length = xd.shape[1]
+    spec = stft_complex(xd, 512, 128)
+    t = spec.shape[1]
+    out = torch.empty((c, t, 257, 2), device=dev)
+    y = torch.zeros((c, 1, 257, max(t, 16)), device=dev)
+    assert _raw(spec, c, out, y, None) == 0                                         # params = NULL
+    d = torch.view_as_complex(out)
+    got, got_mag = wpe_joint(spec, c)                                               # Python's default
+    assert _same(got, d) and _same(got_mag, y[..., :t]) and not _same(d, spec)
+    assert _same(wpe_joint(spec, c, WpeParams(taps=32 // c))[0], d)
+    assert not _same(wpe_joint(spec, c, WpeParams(taps=32 // c - 1))[0], d)
+    assert torch.equal(Dereverberator(dev, channels="joint").denoise(xd), _resynth_by_hand(dev, y, d, length))
 
 
 def test_separate_and_mono_are_today_s_bits(dev):

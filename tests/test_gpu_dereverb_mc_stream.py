@@ -29,6 +29,8 @@ Per bin (profiles/recursive_bins.md): at most 0.74 of the case's floor (bound 4)
 E 1.9e-7; at T = 97 0.06 - 0.44, where the plain arithmetic sets the floor and the device follows the fma one; the tilted cases
 0.21 and 0.32, the device's worst E there the fma restatement's own to the printed digits.  With the floors the file is 54 cases
 in 14 s, the n_fft 512 parity case 1.1 s, every other parity case under 0.5 s.
+The channel counts that grid does not reach (tests/variant_cover.py: C = 5, 6, 7 at T = 4, 23, 97, per bin only): at most 0.94
+floors ((6, 5), T = 23, group 2, channel 2, bin 6, E 1.7e-7), the median over the 30 runs 0.24.
 """
 import ctypes
 import os
@@ -127,6 +129,33 @@ def test_parity_with_the_float64_restatement(dev, case):
                   f"M {err_m / scale / ms.FLOOR:.2f} floors; bound 4")
             assert err <= 4.0 * ms.FLOOR * scale, (n_groups, g, err / scale)
             assert err_m <= 4.0 * ms.FLOOR * scale, (n_groups, g, err_m / scale)
+
+
+@pytest.mark.parametrize("case", tuple(msc.variant_cases()), ids=msc.case_id)
+def test_parity_at_the_channel_counts_the_grid_does_not_reach(dev, case):
+    """C = 5, 6, 7 (tests/variant_cover.py): N = 30, 30, 28 at the defaults taps = 32 // C, rows of P idle, records and rings of no
+    round size; (5, 2) and (7, 1) the short rings.  Per bin only: dereverb_mc_stream_ref.FLOOR is measured over the parity grid.
+    At T = 4 <= D + 1 the floor is 2^-23 or close to it: the pass-through of the first D frames is held exactly."""
+    from audiodenoiser_amd.dereverb import wpe_online_joint
+    n_fft, n_frames, ck, extra = case
+    channels, f = ck[0], n_fft // 2 + 1
+    spec = _spec(dev, n_fft, n_frames, channels)
+    label = rb.mc_label(n_fft, n_frames, ck, extra, "variant")
+    bounds = rb.wpe_mc_online_bounds(spec.cpu().numpy(), channels, msc.params_of(ck, extra))   # on the downloaded device spectrogram
+    rb.assert_cap(label, bounds)
+    col0, width = 5, n_frames + 9
+    nan = _bits(torch.full((1,), float("nan"), device=dev))
+    for n_groups in msc.PARITY_GROUPS:
+        n = n_groups * channels
+        mag = torch.full((n, 1, f, width), float("nan"), device=dev)
+        got, mag_out, state = wpe_online_joint(spec[:n].contiguous(), channels, params=_params(ck, extra), mag_out=mag, col0=col0)
+        assert got.shape == (n, n_frames, f) and got.dtype == torch.complex64 and mag_out is mag
+        got_h, mag_h = got.cpu().numpy(), mag.cpu().numpy()[:, 0]
+        delay = 3
+        assert _same(got[:, :delay], spec[:n, :delay])                             # the first D frames: X itself
+        sb.check(f"{label} [groups {n_groups}]", got_h, bounds.ref[:n], bounds)
+        _mag_is_of_spec_out(got_h, mag_h[:, :, col0:col0 + n_frames])
+        assert bool((_bits(mag[..., :col0]) == nan).all()) and bool((_bits(mag[..., col0 + n_frames:]) == nan).all())
 
 
 @pytest.mark.parametrize("ck", rb.TILTED_MC, ids=lambda ck: f"C{ck[0]}K{ck[1]}")
@@ -341,7 +370,8 @@ def test_quality_on_the_two_microphone_recording(dev):
 
 
 # ---- 6. footprint ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n_fft,n_frames,ck,extra", ((512, 23, (2, 16), None), (64, 4, (3, 7), None), (64, 23, (8, 4), dict(delay=8))))
+@pytest.mark.parametrize("n_fft,n_frames,ck,extra", ((512, 23, (2, 16), None), (64, 4, (3, 7), None), (64, 23, (8, 4), dict(delay=8)),
+                                                    (64, 23, (7, 4), None)))
 def test_online_writes_only_what_the_call_owns(dev, n_fft, n_frames, ck, extra):
     from audiodenoiser_amd import _lib
     from audiodenoiser_amd.dereverb import wpe_online_joint, wpe_stream_state_bytes_joint
@@ -449,7 +479,102 @@ def test_stream_writes_only_its_columns_and_its_states(dev, gain):
     assert fp.keeps_fill(h_s, 0xFF) and fp.keeps_fill(h_y, 0xFF) and fp.keeps_fill(h_w, 0xFF)
 
 
-# ---- 7. command line -------------------------------------------------------------------------------------------------------------
+# ---- 7. seven channels: the lockstep stream against the online form, and no parameters against the library's NULL --------------------
+def test_stream_is_online_bit_for_bit_and_writes_nothing_else_at_seven_channels(dev):
+    """adn_wpe_mc_stream at (C, K) = (7, 4), the least round record: every step of a StreamDereverberator over two recordings is
+    compared, call by call, with adn_wpe_mc_online on the ring's own spectrogram -- the ring cells, the kept columns of the windows
+    and the WPE state bit for bit, and not one byte else.  The ring is the first section of the stream state: [stream][RX][F]
+    float2, frame t at t mod RX, RX = max_steps * block (csrc/stream_kernels.hip)."""
+    from audiodenoiser_amd.dereverb import StreamDereverberator, wpe_online_joint
+    c, f, hop, block, n_frames = 7, 33, 16, 4, 23
+    length = (n_frames - 1) * hop + 5                            # 23 frames: five whole blocks and one of three frames
+
+    class Traced(StreamDereverberator):
+        online_state, calls = None, 0
+
+        def ring(self):
+            n, rx = self.n_streams, self.max_steps * self.block_frames
+            return torch.view_as_complex(self._state.view(torch.float32)[:n * rx * f * 2].view(n, rx, f, 2))
+
+        def _net(self, x, first_step, n_steps, final_length=-1):
+            n, w, b = self.n_streams, self.window_frames, self.block_frames
+            rx = self.max_steps * b
+            end = (first_step + n_steps) * b
+            if final_length >= 0:
+                end = min(end, 1 + final_length // self.hop_length)
+            frames = list(range(first_step * b, end))
+            idx = [t % rx for t in frames]
+            ring = self.ring()
+            spec = ring[:, idx].clone()
+            x_before, ring_before = x.clone(), ring.clone()
+            d, m, self.online_state = wpe_online_joint(spec, c, state=self.online_state, first_frame=frames[0], params=self.params)
+            super()._net(x, first_step, n_steps, final_length)
+            kept = x.view(n, n_steps, f, w)[..., w - b:].permute(0, 2, 1, 3).reshape(n, 1, f, n_steps * b)
+            assert _same(ring[:, idx], d) and _same(kept[..., :len(frames)], m), (first_step, n_steps)
+            assert torch.equal(self._wpe_state, self.online_state), (first_step, n_steps)
+            x_want, ring_want = x_before.clone(), ring_before.clone()
+            want_kept = x_want.view(n, n_steps, f, w)[..., w - b:].permute(0, 2, 1, 3).reshape(n, 1, f, n_steps * b).clone()
+            want_kept[..., :len(frames)] = m
+            x_want.view(n, n_steps, f, w)[..., w - b:] = want_kept.view(n, f, n_steps, b).permute(0, 2, 1, 3)
+            ring_want[:, idx] = d
+            assert _same(x, x_want) and _same(ring, ring_want) and not _same(x, x_before), (first_step, n_steps)
+            Traced.calls += 1
+            return x
+
+    xd = torch.from_numpy(msc.parity_audio(64, n_frames, c)[:2 * c, :length].copy()).to(dev)
+    sd = Traced(dev, n_streams=2 * c, channels=c, n_fft=64, hop_length=hop, block_frames=block, params=_params((c, 4)))
+    got = _push_all(sd, xd, [200, length - 200])
+    torch.cuda.synchronize(dev)
+    assert Traced.calls >= 2 and got.shape == (2 * c, length) and bool(torch.isfinite(got).all())
+    plain = _sd(dev, n_streams=2 * c, channels=c, n_fft=64, hop_length=hop, block_frames=block)       # no parameters: taps = 32 // 7
+    assert torch.equal(_push_all(plain, xd, [length]), got)
+
+
+@pytest.mark.parametrize("channels", (5, 6, 7), ids=lambda c: f"C{c}")
+def test_no_parameters_is_the_library_s_null_at_five_six_and_seven_channels(dev, channels):
+    """taps = 32 // C is stated twice, by joint_default_taps of the library and by the Python classes: with no parameters the
+    online call and the stream class give, bit for bit, what the ABI gives for params = NULL."""
+    from audiodenoiser_amd import _lib
+    from audiodenoiser_amd.dereverb import WpeStreamParams, wpe_online_joint, wpe_stream_state_bytes_joint
+    c, f, n_frames = channels, 33, 23
+    L = _lib.load()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    spec = _spec(dev, 64, n_frames, c)[:c].contiguous()
+    want, want_mag, want_state = wpe_online_joint(spec, c)                          # Python's default
+    need = ctypes.c_size_t(0)
+    assert L.adn_wpe_mc_stream_state_bytes(1, c, f, None, ctypes.byref(need)) == 0
+    assert need.value == want_state.numel() == wpe_stream_state_bytes_joint(1, c, f, WpeStreamParams(taps=32 // c))
+    out = torch.empty((c, n_frames, f, 2), device=dev)
+    mag = torch.empty((c, 1, f, n_frames), device=dev)
+    state = torch.full((need.value,), 0xFF, dtype=torch.uint8, device=dev)
+    assert L.adn_wpe_mc_online(torch.view_as_real(spec).data_ptr(), 1, c, n_frames, f, 0, None, state.data_ptr(), need.value, 1,
+                               out.data_ptr(), mag.data_ptr(), n_frames, 0, stream) == 0
+    torch.cuda.synchronize(dev)
+    assert _same(torch.view_as_complex(out), want) and _same(mag, want_mag) and torch.equal(state, want_state)
+    assert not _same(wpe_online_joint(spec, c, params=WpeStreamParams(taps=32 // c - 1))[0], want)
+    # the class: its own step, adn_wpe_mc_stream with its parameters, and adn_wpe_mc_stream with NULL
+    sd = _sd(dev, n_streams=c, channels=c, n_fft=64, hop_length=16)
+    assert sd.params == WpeStreamParams(taps=32 // c) and sd._wpe_state.numel() == need.value
+    xd = torch.from_numpy(msc.parity_audio(64, n_frames, c)[:c].copy()).to(dev)
+    results = []
+    for p in ("class", ctypes.byref(sd.params.to_struct()), None):
+        sd.reset()
+        sd._wpe_state.fill_(0xFF)
+        win = sd.analyze(xd.contiguous(), xd.shape[1], 0, 2)
+        if p == "class":
+            sd._net(win, 0, 2)
+        else:
+            assert L.adn_wpe_mc_stream(sd._state.data_ptr(), sd._state.numel(), win.data_ptr(), c, c, 0, 2, -1, *sd._plan, sd.max_steps, p,
+                                       sd._wpe_state.data_ptr(), sd._wpe_state.numel(), stream) == 0
+        torch.cuda.synchronize(dev)
+        results.append((win.clone(), sd._state.clone(), sd._wpe_state.clone()))
+    for other in results[1:]:
+        for a, b_ in zip(results[0], other):
+            assert _same(a, b_) if a.dtype != torch.uint8 else torch.equal(a, b_)
+    sd.reset()
+
+
+# ---- 8. command line -------------------------------------------------------------------------------------------------------------
 def test_command_line_live_joint(dev, tmp_path):
     import json
     import subprocess

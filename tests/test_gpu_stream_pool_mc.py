@@ -124,7 +124,7 @@ def _against_lockstep(dev, channels, pool_call, lock_call, pool_need, lock_need)
         fp.assert_guards_intact(h_y, "windows of the pool")
 
 
-@pytest.mark.parametrize("channels", (2, 5, 8), ids=lambda c: f"C{c}")         # 4 lanes per bin, and 8
+@pytest.mark.parametrize("channels", (2, 5, 7, 8), ids=lambda c: f"C{c}")      # 4 lanes per bin, and 8; 7: the least round record
 def test_mvdr_pool_call_leaves_what_the_lockstep_call_leaves(dev, channels):
     lib, c = _lib(), channels
     L = lib.load()
@@ -145,7 +145,7 @@ def test_mvdr_pool_call_leaves_what_the_lockstep_call_leaves(dev, channels):
                           _size(L.adn_mvdr_stream_state_bytes, len(NAMED), c, F, ctypes.byref(p)))
 
 
-@pytest.mark.parametrize("channels,taps", ((2, 16), (4, 8)), ids=("C2K16", "C4K8"))
+@pytest.mark.parametrize("channels,taps", ((2, 16), (4, 8), (7, 4)), ids=("C2K16", "C4K8", "C7K4"))
 def test_wpe_pool_call_leaves_what_the_lockstep_call_leaves(dev, channels, taps):
     lib, c = _lib(), channels
     L = lib.load()
@@ -262,8 +262,8 @@ def _signals(audio, channels):
     return [np.ascontiguousarray(audio[g * c:(g + 1) * c, at:at + n]) for (g, at), n in zip(starts, _LENGTHS)]
 
 
-@pytest.mark.parametrize("channels,wpe,gain", ((2, False, False), (3, True, True), (5, False, True), (4, True, False)),
-                         ids=("C2", "C3-wpe-gain", "C5-gain", "C4-wpe"))
+@pytest.mark.parametrize("channels,wpe,gain", ((2, False, False), (3, True, True), (5, False, True), (4, True, False), (7, True, False)),
+                         ids=("C2", "C3-wpe-gain", "C5-gain", "C4-wpe", "C7-wpe"))
 def test_every_recording_of_the_beamformer_pool_equals_its_solo_run(dev, channels, wpe, gain):
     from audiodenoiser_amd.beamform import BeamformStreamPool, MvdrStreamParams, StreamBeamformer
     c = channels
@@ -283,7 +283,7 @@ def test_every_recording_of_the_beamformer_pool_equals_its_solo_run(dev, channel
         pool.push(pool.open(), np.zeros(10, np.float32))                                           # (C, m), not (m,)
 
 
-@pytest.mark.parametrize("channels,gain", ((2, False), (4, True)), ids=("C2", "C4-gain"))
+@pytest.mark.parametrize("channels,gain", ((2, False), (4, True), (7, False)), ids=("C2", "C4-gain", "C7"))
 def test_every_recording_of_the_dereverb_pool_equals_its_solo_run(dev, channels, gain):
     from audiodenoiser_amd.dereverb import DereverbStreamPool, StreamDereverberator
     c = channels

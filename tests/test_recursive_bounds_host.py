@@ -26,7 +26,10 @@ and test_gpu_dereverb_mc_stream.py hold the device to, applied to the restatemen
     1e-5 of the last bin's own scale added to one frame of that bin, untilted, defaults:
       wpe_online n_fft 64, T 23:              20.6 x              wpe_mc_online (2, 16), n_fft 64, T 23:  15.2 x
       wpe_online n_fft 512, T 40:              8.1 x  (asserted as "fails the bound": 1e-5 against 4 x a floor of 3.1e-7)
-  A separation of 10 x is asserted for every line but the last.  Not caught, and not claimed: the same 1e-5 on a T = 97 case, whose
+    wpe_mc_online, the variant case (C, K) = (7, 4), n_fft 64, T 97 (tests/variant_cover.py), the last channel's column of G never
+    updated, so that the channel returns its input -- what the offline kernel's dropped last column of P becomes here:
+                                   E 0.14, 15300 x in the bin that shows it the least
+  A separation of 10 x is asserted for every line but the one at n_fft 512, T 40.  Not caught, and not claimed: the same 1e-5 on a T = 97 case, whose
   floor of 3e-6 puts the bound at 1.2e-5.
 """
 import os
@@ -210,6 +213,35 @@ def test_a_last_bin_that_returns_its_input_is_caught_wpe_mc_online():
 
     _judge(f"wpe_mc_online {ck} last bin returned as the input", bounds, _online_todays(bounds, ck[0], ms.FLOOR), mutate,
            [(r, -1) for r in range(3 * ck[0])])
+
+
+def test_a_last_channel_whose_taps_are_never_updated_is_caught_wpe_mc_online():
+    """(C, K) = (7, 4), a variant case (tests/variant_cover.py): N = 28, the last four rows of the 32-row layout idle.  The slip
+    the offline kernel's "last column of P dropped" becomes here: the last channel's column of G stays what frame 0 made it, zero,
+    so that channel returns its input.  Run frame by frame through the state, in both arithmetics."""
+    ck = (7, 4)
+    c, kw = ck[0], msc.params_of(ck)
+    spec = rb.mc_spec(64, T, c)
+    bounds = rb.wpe_mc_online_bounds(spec, c, kw)
+    label = rb.mc_label(64, T, ck, None, "variant")
+    assert label in [name for name, _ in rb.variant_cases()]
+    rb.assert_cap(label, bounds)
+    for a in rb.ARITHMETICS:
+        got = bounds.f32[a]
+        assert sb.worst(got, bounds.ref)[0] <= bounds.floor
+        state, frames = None, []
+        for t in range(T):
+            d, state = ms.wpe_mc_online(spec[:c, t:t + 1], kw, dtype=np.float32, state=state, first_frame=t, with_state=True, arithmetic=a)
+            state["G"][:, c - 1] = 0
+            frames.append(d)
+        bad = got.copy()
+        bad[:c] = np.concatenate(frames, axis=1)
+        e = sb.per_bin(bad, bounds.ref)[c - 1]                                     # the last channel of group 0, every bin
+        over = float(e.min()) / (sb.MARGIN * bounds.floor)
+        print(f"wpe_mc_online {ck} T {T}, the last channel's taps never updated [{a}]: the bin that shows it the least has E {float(e.min()):.3g} "
+              f"= {over:.3g} x the per-bin bound (floor {bounds.floor:.3g})")
+        assert over >= SEPARATION, (a, over)
+        assert np.array_equal(bad[c - 1, 3:], spec[c - 1, 3:])                     # that channel is its input
 
 
 def _added(bounds, row):

@@ -13,6 +13,12 @@ test_gpu_beamform.py hold the device to, applied to the restatements themselves.
   WPE at one tap and one iteration (5e-7) and for joint WPE at two channels, one tap and one iteration (1.2e-5), which is where
   (b) is held to 10 x; at the defaults of WPE and joint WPE (floors 4e-5 and 1.1e-4 to 1.6e-4: the Cholesky solve of 20 to 32
   unknowns) it is still caught, by 6 x and by 1.6 x to 2.3 x, which is asserted as "fails the bound".
+* The slips the layouts of tests/variant_cover.py could make, on one variant case per operator (untilted, T 97, group / clip 0
+  recomputed with the slip in the float32 sequential restatement); each lands outside the bound, by the printed multiple:
+    wpe_mc (5, 6), the last channel's column of P dropped (G's last column zero):            E 4.6,    7800 x
+    wpe_mc (5, 6), a repeated last channel kept (bin b's column C is bin b + 1's column 0):  E 4.5e6,  7.6e9 x
+    wpe K 29, the last tap of the partial eighth block row dropped (the filter of 28 taps):  E 0.30,   1600 x
+    mvdr C 7, Phi_n[6, 6] (the last triangle entry) misses the last frame's term:            E 0.086,  3100 x at both reference channels
 """
 import os
 import sys
@@ -24,6 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import beamform_cases as bc  # noqa: E402
 import beamform_ref as bf  # noqa: E402
 import dereverb_mc_cases as mc  # noqa: E402
+import dereverb_mc_ref as mr  # noqa: E402
 import dereverb_ref as dr  # noqa: E402
 import solver_bounds as sb  # noqa: E402
 
@@ -191,6 +198,91 @@ def test_the_per_bin_bound_catches_what_the_clip_wide_bound_passes(op, arg):
     else:                                                  # the floor of the defaults is above 2.5e-5: caught, but not by 10 x
         case.judge("(b) 1e-3 of its own scale in bin F - 1", _last_bin, separation=1.0)
         _Tilted(op, arg if op == "wpe" else (2, 1), ONE_TAP).judge("(b) 1e-3 of its own scale in bin F - 1, one tap", _last_bin)
+
+
+# ---- the slips the variant layouts could make (tests/variant_cover.py) land outside the bound ---------------------------------------
+def _slipped(what, bounds, rows, run):
+    """The float32 sequential restatement of a variant case stands in for the device; `run()` recomputes `rows` of it with the
+    slip.  -> by how many bounds the slipped result misses, asserted > 1; the unslipped one passes."""
+    got = bounds.f32["sequential"]
+    assert sb.worst(got, bounds.ref)[0] <= bounds.floor
+    bad = got.copy()
+    bad[rows] = run()
+    assert not np.array_equal(bad, got)
+    e, r, b = sb.worst(bad, bounds.ref)
+    over = e / (sb.MARGIN * bounds.floor)
+    print(f"{what}: E {e:.3g} at row {r} bin {b} = {over:.3g} x the per-bin bound (floor {bounds.floor:.3g})")
+    assert over > 1.0, (what, over)
+    return over
+
+
+def test_a_dropped_or_a_kept_column_of_p_is_caught_at_two_p_block_columns():
+    """(C, K) = (5, 6): the second P block column holds channel 4 and three repeats of it.  (1) The last channel's column of P is
+    dropped: G's last column is zero.  (2) A repeat is kept and not discarded: column `C` of a bin is the next bin's column 0 in
+    the kernel's LDS, so bin b + 1 solves channel 0 with bin b's last column of P."""
+    ck = (5, 6)
+    c, kw = ck[0], mc.params_of(ck)
+    spec = sb.mc_spec(64, T, c)
+    bounds = sb.wpe_mc_bounds(spec, c, kw)
+    assert sb.mc_label(64, T, ck, None, "variant") in [label for label, _ in sb.variant_cases()]
+
+    def dropped(R, P):
+        P = P.copy()
+        P[:, :, c - 1] = 0
+        return R, P
+
+    def kept(R, P):
+        P = P.copy()
+        P[1:, :, 0] = P[:-1, :, c - 1]
+        return R, P
+
+    for what, slip in (("the last channel's column of P dropped", dropped), ("a repeated last channel kept", kept)):
+        _slipped(f"wpe_mc {ck} T {T}, {what}", bounds, slice(0, c),
+                 lambda slip=slip: mr.wpe_mc(spec[:c], kw, dtype=np.float32, order="sequential", slip=slip))
+
+
+def test_a_dropped_last_tap_of_a_partial_block_row_is_caught():
+    """adn_wpe at K = 29: the eighth block row holds tap 28 alone.  Dropped, the filter is the one of 28 taps."""
+    kw = dict(taps=29)
+    spec = sb.wpe_spec(64, T)
+    bounds = sb.wpe_bounds(spec, kw)
+    assert sb.wpe_label(64, T, kw, "variant") in [label for label, _ in sb.variant_cases()]
+    _slipped(f"wpe K 29 T {T}, the last tap dropped", bounds, slice(0, 1),
+             lambda: dr.wpe(spec[0], dict(taps=28), dtype=np.float32, order="sequential")[None])
+
+
+def test_a_last_triangle_entry_of_phi_n_that_is_not_updated_is_caught():
+    """adn_mvdr at C = 7: 28 triangle entries over 8 lanes, four rounds, the last one partial: entry 27 is Phi_n[6, 6].  The
+    smallest form of the slip: that one entry misses the last frame's term (left at zero instead, the factorisation has no real
+    root and the result is NaN, which the bound refuses outright)."""
+    c = 7
+    spec, mags = sb.mvdr_inputs(64, T, c)
+    bounds = sb.mvdr_bounds(spec, mags, c)
+    assert sb.mvdr_label(64, T, c, None, "variant") in [label for label, _ in sb.variant_cases()]
+    seen = {}
+
+    def record(phi_s, phi_n):
+        seen["entry"] = phi_n[:, c - 1, c - 1].copy()
+        return phi_s, phi_n
+
+    bf.mvdr(spec[:c, :T - 1], mags[:c, :, :T - 1], None, dtype=np.float32, order="sequential", slip=record)      # the sums over T - 1 frames
+
+    def stale(phi_s, phi_n):
+        phi_n = phi_n.copy()
+        assert not np.array_equal(phi_n[:, c - 1, c - 1], seen["entry"])
+        phi_n[:, c - 1, c - 1] = seen["entry"]
+        return phi_s, phi_n
+
+    for ref in bc.refs_of(c):
+        got, want = bounds.f32["sequential"][ref], bounds.ref[ref]
+        assert sb.worst(got, want)[0] <= bounds.floor
+        bad = got.copy()
+        bad[0] = bf.mvdr(spec[:c], mags[:c], dict(ref_channel=ref), dtype=np.float32, order="sequential", slip=stale)
+        e, r, b = sb.worst(bad, want)
+        over = e / (sb.MARGIN * bounds.floor)
+        print(f"mvdr C {c} T {T} ref {ref}, Phi_n[{c - 1}, {c - 1}] not updated: E {e:.3g} at row {r} bin {b} = {over:.3g} x the per-bin "
+              f"bound (floor {bounds.floor:.3g})")
+        assert over > 1.0, (ref, over)
 
 
 @pytest.mark.parametrize("channels", sb.TILTED_MVDR, ids=lambda c: f"C{c}")
