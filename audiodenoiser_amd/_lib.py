@@ -148,6 +148,42 @@ def load() -> ctypes.CDLL:
         return L
 
 
+_echo = None
+
+
+def load_echo() -> ctypes.CDLL:
+    """Load libadn_echo.so (include/adn_echo.h; built with libadn.so, which is loaded first: the stream state the echo canceller
+    works on is that library's).  Its failed calls leave their message in ``adn_aec_last_error``: ``check_echo``."""
+    global _echo
+    load()
+    with _lock:
+        if _echo is not None:
+            return _echo
+        path = _build.ECHO_LIB
+        if not os.path.exists(path):
+            raise AdnError(f"{path} is missing: python -m audiodenoiser_amd.build")
+        try:
+            L = ctypes.CDLL(path)
+        except OSError as exc:
+            raise AdnError(f"cannot load {path}: {exc}") from exc
+        vp, sz, ci, cl = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_long
+        asp = ctypes.POINTER(AecParamsStruct)
+        L.adn_aec_last_error.restype = ctypes.c_char_p
+        L.adn_aec_stream_state_bytes.argtypes = [ci, ci, asp, ctypes.POINTER(sz)]
+        L.adn_aec_online.argtypes = [vp, vp, ci, ci, ci, cl, asp, vp, sz, ci, vp, vp, ci, ci, vp]
+        L.adn_aec_stream.argtypes = [vp, sz, vp, ci, cl, ci, cl, ci, ci, ci, ci, ci, ci, asp, vp, sz, vp]
+        for name in ECHO_EXPORTED_SYMBOLS[1:]:
+            getattr(L, name).restype = ci
+        _echo = L
+        return L
+
+
+def check_echo(rc: int, what: str) -> None:
+    if rc != 0:
+        msg = load_echo().adn_aec_last_error()
+        raise AdnError(f"{what} failed (status {rc}): {msg.decode() if msg else ''}")
+
+
 class SpectralParamsStruct(ctypes.Structure):
     """``adn_spectral_params`` of include/adn.h (the Python face is ``audiodenoiser_amd.baseline.SpectralParams``)."""
     _fields_ = [(name, ctypes.c_float) for name in ("smooth", "beta", "gamma", "alpha", "gain_floor", "bias")]
@@ -174,6 +210,12 @@ class MvdrStreamParamsStruct(ctypes.Structure):
     """``adn_mvdr_stream_params`` of include/adn.h (the Python face is ``audiodenoiser_amd.beamform.MvdrStreamParams``)."""
     _fields_ = [("ref_channel", ctypes.c_int), ("refresh", ctypes.c_int), ("forget", ctypes.c_float), ("loading", ctypes.c_float),
                 ("mask_floor", ctypes.c_float)]
+
+
+class AecParamsStruct(ctypes.Structure):
+    """``adn_aec_params`` of include/adn_echo.h (the Python face is ``audiodenoiser_amd.echo.AecParams``)."""
+    _fields_ = [("taps", ctypes.c_int), ("delay", ctypes.c_int), ("forget", ctypes.c_float), ("loading", ctypes.c_float),
+                ("quiet", ctypes.c_float)]
 
 
 class SpectralRow(ctypes.Structure):
@@ -230,3 +272,6 @@ EXPORTED_SYMBOLS = (
     "adn_mvdr_workspace_bytes", "adn_mvdr",
     "adn_mvdr_stream_state_bytes", "adn_mvdr_online", "adn_mvdr_stream", "adn_mvdr_stream_pool",
 )
+
+# libadn_echo.so (include/adn_echo.h): a library of its own, so that the table above stays libadn.so's whole symbol table
+ECHO_EXPORTED_SYMBOLS = ("adn_aec_last_error", "adn_aec_stream_state_bytes", "adn_aec_online", "adn_aec_stream")

@@ -1,7 +1,9 @@
-"""Build libadn.so (hand-written HIP for gfx950) in-tree: ``python -m audiodenoiser_amd.build``.
+"""Build libadn.so and libadn_echo.so (hand-written HIP for gfx950) in-tree: ``python -m audiodenoiser_amd.build``.
 
 Every ``csrc/*.hip`` is compiled to an object (in parallel, per-file flags in ``FILE_FLAGS``) and the objects are
-linked into ``audiodenoiser_amd/_lib/libadn.so`` (git-ignored, shipped to the GPU box with the working tree).  A
+linked into ``audiodenoiser_amd/_lib/libadn.so`` (git-ignored, shipped to the GPU box with the working tree).  The same
+objects, ``csrc/echo_stream_kernels.hip`` and ``csrc/echo/*.hip`` (the C ABI of ``include/adn_echo.h``) are linked into ``_lib/libadn_echo.so``
+under a version script of its own: libadn.so's symbol table is the one ``include/adn.h`` declares, and stays so.  A
 content hash of the sources and flags is stored next to the library so that a copied tree with fresh mtimes does
 not trigger a rebuild (stamp = two lines: the code digest that identifies the build in bench.py / profiles, and the
 raw-bytes digest that decides about rebuilding).
@@ -23,6 +25,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIBDIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(LIBDIR, "libadn.so")
+ECHO_LIB = os.path.join(LIBDIR, "libadn_echo.so")
 STAMP = os.path.join(LIBDIR, "libadn.sha256")
 LOCK = os.path.join(LIBDIR, ".build.lock")
 ARCH = "gfx950"
@@ -30,6 +33,8 @@ COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "
 # only the C ABI of include/adn.h leaves the library (ADN_API there + this version script: `adn_*` global, the rest local)
 VERSION_SCRIPT = os.path.join(CSRC, "libadn.map")
 LINK_FLAGS = ["-fPIC", "-shared", f"-Wl,--version-script={VERSION_SCRIPT}"]
+ECHO_VERSION_SCRIPT = os.path.join(CSRC, "libadn_echo.map")
+ECHO_LINK_FLAGS = ["-fPIC", "-shared", f"-Wl,--version-script={ECHO_VERSION_SCRIPT}"]
 # wino4_kernels.hip: the SLP vectoriser pairs unrelated scalars of the 6x6 transform into v_pk_* operations and pays
 # for it with ~140 v_mov per K-chunk (the transform is scalar by design: one channel per lane and pass)
 FILE_FLAGS = {"wino4_kernels.hip": ["-fno-slp-vectorize"]}
@@ -41,8 +46,18 @@ def _extra_flags():
     return os.environ.get("ADN_BUILD_DEFINES", "").split()
 
 
+# csrc/*.hip that belong to libadn_echo.so alone: libadn.so holds nothing of the echo canceller
+ECHO_ONLY = ("echo_stream_kernels.hip",)
+
+
 def _sources():
-    return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+    return sorted(p for p in glob.glob(os.path.join(CSRC, "*.hip")) if os.path.basename(p) not in ECHO_ONLY)
+
+
+def _echo_sources():
+    """What libadn_echo.so is linked from beside the objects of libadn.so: the kernel file and the C ABI of include/adn_echo.h."""
+    return [os.path.join(CSRC, name) for name in ECHO_ONLY if os.path.exists(os.path.join(CSRC, name))] \
+        + sorted(glob.glob(os.path.join(CSRC, "echo", "*.hip")))
 
 
 def _strip_comments(text: str) -> str:
@@ -90,7 +105,9 @@ def _strip_comments(text: str) -> str:
 
 
 def _digest_files():
-    return _sources() + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(INCLUDE, "adn.h"), VERSION_SCRIPT]
+    return (_sources() + _echo_sources() + sorted(glob.glob(os.path.join(CSRC, "*.h")))
+            + [os.path.join(INCLUDE, "adn.h")] + sorted(glob.glob(os.path.join(INCLUDE, "adn_*.h")))
+            + [VERSION_SCRIPT, ECHO_VERSION_SCRIPT])
 
 
 def _flags_tag() -> bytes:
@@ -133,7 +150,7 @@ def hipcc_path():
 
 
 def up_to_date() -> bool:
-    if not (os.path.exists(LIB) and os.path.exists(STAMP)):
+    if not (os.path.exists(LIB) and os.path.exists(ECHO_LIB) and os.path.exists(STAMP)):
         return False
     with open(STAMP) as f:
         lines = f.read().split()
@@ -165,18 +182,20 @@ def build(force: bool = False, verbose: bool = False) -> str:
                         print(" ".join(cmd), file=sys.stderr)
                     subprocess.run(cmd, check=True)
                     return obj
-                workers = max(1, min(len(_sources()), (os.cpu_count() or 2) // 2))
+                n_own = len(_sources())
+                workers = max(1, min(n_own, (os.cpu_count() or 2) // 2))
                 with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
-                    objs = list(pool.map(compile_one, _sources()))
-                cmd = [hipcc, f"--offload-arch={ARCH}"] + LINK_FLAGS + ["-o", tmp] + objs
-                if verbose:
-                    print(" ".join(cmd), file=sys.stderr)
-                try:
-                    subprocess.run(cmd, check=True)
-                    os.replace(tmp, LIB)
-                finally:
-                    if os.path.exists(tmp):
-                        os.remove(tmp)
+                    objs = list(pool.map(compile_one, _sources() + _echo_sources()))
+                for flags, members, dst in ((LINK_FLAGS, objs[:n_own], LIB), (ECHO_LINK_FLAGS, objs, ECHO_LIB)):
+                    cmd = [hipcc, f"--offload-arch={ARCH}"] + flags + ["-o", tmp] + members
+                    if verbose:
+                        print(" ".join(cmd), file=sys.stderr)
+                    try:
+                        subprocess.run(cmd, check=True)
+                        os.replace(tmp, dst)
+                    finally:
+                        if os.path.exists(tmp):
+                            os.remove(tmp)
             with open(STAMP + ".tmp", "w") as f:
                 f.write(_digest() + "\n" + _raw_digest() + "\n")
             os.replace(STAMP + ".tmp", STAMP)

@@ -742,7 +742,8 @@ static const char *stream_plan_text = ": need a power-of-two n_fft in [64, 4096]
                                       "lookahead >= 0, block + lookahead <= window, n_streams >= 1 and 1 <= max_steps <= 65536";
 
 // The limits of a call of n_steps steps from `first`, then what it covers (adn_internal.h, stream_call_of).
-static int stream_call(const char *who, const adn::StreamGeom &g, long first, int n_steps, long final_length, adn::StreamCall *c)
+// (not static: csrc/echo/echo_api.hip, the C ABI of libadn_echo.so, puts the same two checks in front of adn_aec_stream; adn_host.h)
+int stream_call(const char *who, const adn::StreamGeom &g, long first, int n_steps, long final_length, adn::StreamCall *c)
 {
     const std::string w(who);
     if (first < 0 || n_steps < 1) return fail(ADN_ERR_INVALID, w + ": need first_step >= 0 and n_steps >= 1");
@@ -788,7 +789,7 @@ int adn_stream_state_bytes(int n_streams, int n_fft, int hop, int window, int bl
     return ADN_OK;
 }
 
-static int stream_state(const char *who, void *state, size_t state_bytes, int n_streams, int n_fft, int hop, int window, int block,
+int stream_state(const char *who, void *state, size_t state_bytes, int n_streams, int n_fft, int hop, int window, int block,
                         int lookahead, int max_steps, adn::StreamGeom *g)
 {
     const std::string w(who);

@@ -70,3 +70,11 @@ struct DeviceGuard {
 inline bool aligned_to(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 }  // namespace adn
+
+// The two checks that stand in front of every entry point working on an adn_stream_* state (adn_api.hip): the state against its
+// plan, and the steps of a call.  Declared for csrc/echo/echo_api.hip, which puts them in front of adn_aec_stream.
+extern "C" {
+int stream_state(const char *who, void *state, size_t state_bytes, int n_streams, int n_fft, int hop, int window, int block,
+                 int lookahead, int max_steps, adn::StreamGeom *g);
+int stream_call(const char *who, const adn::StreamGeom &g, long first, int n_steps, long final_length, adn::StreamCall *c);
+}

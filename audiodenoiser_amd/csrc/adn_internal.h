@@ -625,6 +625,24 @@ hipError_t launch_mvdr_stream(float *sstate, float *y, int n_streams, int C, con
 // the same for a pool's recordings, as launch_wpe_mc_stream_pool: Y_t and |Y_t| over the first row of each group
 hipError_t launch_mvdr_stream_pool(float *sstate, float *y, int C, const StreamGeom &g, const StreamPoolRows &rows,
                                    const MvdrStreamConsts &k, float *state, hipStream_t st);
+// Acoustic echo cancellation (echo_stream_kernels.hip; adn_echo.h, "echo stream"): one RLS update per frame from the K delayed far-end
+// frames to the microphone, per (pair, bin).  AecConsts: the parameters and p0 = 1 / loading, derived once per call on the host in
+// fp32.  astate: aec_record_floats(K, D) = 2 K^2 + 4 K + 2 D floats per (slot, bin) -- P, h and the last D + K far-end frames --
+// [slot][bin] consecutive, pair i = slot i; a pair that starts at frame 0 reads none of it.  The launches differ in where the frames
+// are: frame-major spectrograms mic / far / spec_out [row][frame][F] (frames first_frame .. first_frame + T - 1); or the X rings of a
+// lockstep stream state whose streams 2 g and 2 g + 1 are the microphone and the far end of pair g (frames f_first .. f_last of
+// `call`; e_t over stream 2 g's ring cells, M_t into columns [W - B, W) of its windows of y, nothing of stream 2 g + 1 written).
+// aec_stream_grid: the workgroups of a launch over n_pairs pairs.
+struct AecConsts {
+    int K, D;
+    float alpha, p0, quiet;
+};
+long aec_record_floats(int K, int D);
+long aec_stream_grid(long n_pairs, int F, int K);
+hipError_t launch_aec_online(const void *mic, const void *far, int n_rows, int T, int F, int first_frame, const AecConsts &c, float *astate,
+                             void *spec_out, float *mag_out, int width, int col0, hipStream_t st);
+hipError_t launch_aec_stream(float *state, float *y, int n_streams, const StreamGeom &g, const StreamCall &call, const AecConsts &c,
+                             float *astate, hipStream_t st);
 hipError_t launch_quantize_pad(const float *in, int n, int h, int w, float *out, int H, int W, hipStream_t st);
 hipError_t launch_per_clip_l1(const float *a, const float *b, int n_clips, long elems, float *out, hipStream_t st);
 // Polyphase resampler and SNR mixer (resample_kernels.hip).  resample_ratio: up / down of a rate pair, false outside the limits

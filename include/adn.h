@@ -1125,6 +1125,9 @@ ADN_API int adn_mvdr_stream_pool(void *pool_state, size_t pool_state_bytes, int 
                                  int block, int lookahead, long ring_samples, const adn_stream_pool_row *rows, int n_rows, float *y,
                                  const adn_mvdr_stream_params *params, void *mvdr_state, size_t mvdr_state_bytes, void *stream);
 
+/* ---- echo stream: acoustic echo cancellation lives in a header and a library of its own: adn_echo.h and libadn_echo.so.  The symbol
+ * table of libadn.so is this header's, name for name, and stays so. */
+
 /* ---- environment switches -------------------------------------------------------------------------------------------------
  * Read ONCE, when a U-Net handle is created (never per call).  None is needed in production: the defaults are the measured best
  * and every family below is covered by the parity tests (tests/test_gpu_variants.py::MODES).  They select between kernel
