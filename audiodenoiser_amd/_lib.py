@@ -184,6 +184,39 @@ def check_echo(rc: int, what: str) -> None:
         raise AdnError(f"{what} failed (status {rc}): {msg.decode() if msg else ''}")
 
 
+_call = None
+
+
+def load_call() -> ctypes.CDLL:
+    """Load libadn_call.so (include/adn_call.h; built with the other two, which are loaded first: the pool state and the echo state
+    it works on are theirs).  Its failed calls leave their message in ``adn_call_last_error``: ``check_call``."""
+    global _call
+    load_echo()
+    with _lock:
+        if _call is not None:
+            return _call
+        path = _build.CALL_LIB
+        if not os.path.exists(path):
+            raise AdnError(f"{path} is missing: python -m audiodenoiser_amd.build")
+        try:
+            L = ctypes.CDLL(path)
+        except OSError as exc:
+            raise AdnError(f"cannot load {path}: {exc}") from exc
+        vp, sz, ci, cl = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_long
+        L.adn_call_last_error.restype = ctypes.c_char_p
+        L.adn_aec_stream_pool.argtypes = [vp, sz, ci, ci, ci, ci, ci, ci, ci, cl, vp, ci, vp, ctypes.POINTER(AecParamsStruct), vp, sz, vp]
+        for name in CALL_EXPORTED_SYMBOLS[1:]:
+            getattr(L, name).restype = ci
+        _call = L
+        return L
+
+
+def check_call(rc: int, what: str) -> None:
+    if rc != 0:
+        msg = load_call().adn_call_last_error()
+        raise AdnError(f"{what} failed (status {rc}): {msg.decode() if msg else ''}")
+
+
 class SpectralParamsStruct(ctypes.Structure):
     """``adn_spectral_params`` of include/adn.h (the Python face is ``audiodenoiser_amd.baseline.SpectralParams``)."""
     _fields_ = [(name, ctypes.c_float) for name in ("smooth", "beta", "gamma", "alpha", "gain_floor", "bias")]
@@ -275,3 +308,7 @@ EXPORTED_SYMBOLS = (
 
 # libadn_echo.so (include/adn_echo.h): a library of its own, so that the table above stays libadn.so's whole symbol table
 ECHO_EXPORTED_SYMBOLS = ("adn_aec_last_error", "adn_aec_stream_state_bytes", "adn_aec_online", "adn_aec_stream")
+
+# libadn_call.so (include/adn_call.h): operators of a two-way call that the two closed tables above cannot take.  This table is
+# open: the next call operator is added here, in the header and in csrc/libadn_call.map
+CALL_EXPORTED_SYMBOLS = ("adn_call_last_error", "adn_aec_stream_pool")

@@ -1,9 +1,11 @@
-"""Build libadn.so and libadn_echo.so (hand-written HIP for gfx950) in-tree: ``python -m audiodenoiser_amd.build``.
+"""Build libadn.so, libadn_echo.so and libadn_call.so (hand-written HIP for gfx950) in-tree: ``python -m audiodenoiser_amd.build``.
 
 Every ``csrc/*.hip`` is compiled to an object (in parallel, per-file flags in ``FILE_FLAGS``) and the objects are
 linked into ``audiodenoiser_amd/_lib/libadn.so`` (git-ignored, shipped to the GPU box with the working tree).  The same
 objects, ``csrc/echo_stream_kernels.hip`` and ``csrc/echo/*.hip`` (the C ABI of ``include/adn_echo.h``) are linked into ``_lib/libadn_echo.so``
-under a version script of its own: libadn.so's symbol table is the one ``include/adn.h`` declares, and stays so.  A
+under a version script of its own: libadn.so's symbol table is the one ``include/adn.h`` declares, and stays so.  Those
+objects and ``csrc/call/*.hip`` (the C ABI of ``include/adn_call.h``) are linked into ``_lib/libadn_call.so`` under a third version
+script, which names that header's functions one by one: the four of ``adn_echo.h`` are in the library and stay local.  A
 content hash of the sources and flags is stored next to the library so that a copied tree with fresh mtimes does
 not trigger a rebuild (stamp = two lines: the code digest that identifies the build in bench.py / profiles, and the
 raw-bytes digest that decides about rebuilding).
@@ -26,6 +28,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIBDIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(LIBDIR, "libadn.so")
 ECHO_LIB = os.path.join(LIBDIR, "libadn_echo.so")
+CALL_LIB = os.path.join(LIBDIR, "libadn_call.so")
 STAMP = os.path.join(LIBDIR, "libadn.sha256")
 LOCK = os.path.join(LIBDIR, ".build.lock")
 ARCH = "gfx950"
@@ -35,6 +38,8 @@ VERSION_SCRIPT = os.path.join(CSRC, "libadn.map")
 LINK_FLAGS = ["-fPIC", "-shared", f"-Wl,--version-script={VERSION_SCRIPT}"]
 ECHO_VERSION_SCRIPT = os.path.join(CSRC, "libadn_echo.map")
 ECHO_LINK_FLAGS = ["-fPIC", "-shared", f"-Wl,--version-script={ECHO_VERSION_SCRIPT}"]
+CALL_VERSION_SCRIPT = os.path.join(CSRC, "libadn_call.map")
+CALL_LINK_FLAGS = ["-fPIC", "-shared", f"-Wl,--version-script={CALL_VERSION_SCRIPT}"]
 # wino4_kernels.hip: the SLP vectoriser pairs unrelated scalars of the 6x6 transform into v_pk_* operations and pays
 # for it with ~140 v_mov per K-chunk (the transform is scalar by design: one channel per lane and pass)
 FILE_FLAGS = {"wino4_kernels.hip": ["-fno-slp-vectorize"]}
@@ -58,6 +63,11 @@ def _echo_sources():
     """What libadn_echo.so is linked from beside the objects of libadn.so: the kernel file and the C ABI of include/adn_echo.h."""
     return [os.path.join(CSRC, name) for name in ECHO_ONLY if os.path.exists(os.path.join(CSRC, name))] \
         + sorted(glob.glob(os.path.join(CSRC, "echo", "*.hip")))
+
+
+def _call_sources():
+    """What libadn_call.so is linked from beside everything libadn_echo.so is linked from: the C ABI of include/adn_call.h."""
+    return sorted(glob.glob(os.path.join(CSRC, "call", "*.hip")))
 
 
 def _strip_comments(text: str) -> str:
@@ -105,9 +115,10 @@ def _strip_comments(text: str) -> str:
 
 
 def _digest_files():
-    return (_sources() + _echo_sources() + sorted(glob.glob(os.path.join(CSRC, "*.h")))
+    return (_sources() + _echo_sources() + _call_sources() + sorted(glob.glob(os.path.join(CSRC, "*.h")))
+            + sorted(glob.glob(os.path.join(CSRC, "echo", "*.h"))) + sorted(glob.glob(os.path.join(CSRC, "call", "*.h")))
             + [os.path.join(INCLUDE, "adn.h")] + sorted(glob.glob(os.path.join(INCLUDE, "adn_*.h")))
-            + [VERSION_SCRIPT, ECHO_VERSION_SCRIPT])
+            + [VERSION_SCRIPT, ECHO_VERSION_SCRIPT, CALL_VERSION_SCRIPT])
 
 
 def _flags_tag() -> bytes:
@@ -150,7 +161,7 @@ def hipcc_path():
 
 
 def up_to_date() -> bool:
-    if not (os.path.exists(LIB) and os.path.exists(ECHO_LIB) and os.path.exists(STAMP)):
+    if not (os.path.exists(LIB) and os.path.exists(ECHO_LIB) and os.path.exists(CALL_LIB) and os.path.exists(STAMP)):
         return False
     with open(STAMP) as f:
         lines = f.read().split()
@@ -183,10 +194,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
                     subprocess.run(cmd, check=True)
                     return obj
                 n_own = len(_sources())
+                n_echo = n_own + len(_echo_sources())
                 workers = max(1, min(n_own, (os.cpu_count() or 2) // 2))
                 with concurrent.futures.ThreadPoolExecutor(max_workers=workers) as pool:
-                    objs = list(pool.map(compile_one, _sources() + _echo_sources()))
-                for flags, members, dst in ((LINK_FLAGS, objs[:n_own], LIB), (ECHO_LINK_FLAGS, objs, ECHO_LIB)):
+                    objs = list(pool.map(compile_one, _sources() + _echo_sources() + _call_sources()))
+                for flags, members, dst in ((LINK_FLAGS, objs[:n_own], LIB), (ECHO_LINK_FLAGS, objs[:n_echo], ECHO_LIB),
+                                            (CALL_LINK_FLAGS, objs, CALL_LIB)):
                     cmd = [hipcc, f"--offload-arch={ARCH}"] + flags + ["-o", tmp] + members
                     if verbose:
                         print(" ".join(cmd), file=sys.stderr)

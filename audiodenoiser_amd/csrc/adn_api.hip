@@ -865,12 +865,9 @@ static const char *stream_pool_text = ": need the plan of the stream section (po
                                       "window >= 16, block >= 1, lookahead >= 0, block + lookahead <= window), 1 <= n_slots <= 2^20 and "
                                       "n_fft - hop + (block + lookahead - 1) hop + n_fft / 2 + block hop <= ring_samples <= 2^28";
 
-struct PoolState {
-    adn::StreamGeom g;
-    long ring_off, total, R;
-};
-
-static int pool_state(const char *who, void *state, size_t state_bytes, int n_slots, int n_fft, int hop, int window, int block,
+// (pool_state, pool_rows and pool_recordings are not static: csrc/call/call_api.hip, the C ABI of libadn_call.so, puts the same
+// checks in front of its pool operators; PoolState and their declarations are adn_host.h's)
+int pool_state(const char *who, void *state, size_t state_bytes, int n_slots, int n_fft, int hop, int window, int block,
                       int lookahead, long ring, PoolState *p)
 {
     const std::string w(who);
@@ -885,8 +882,8 @@ static int pool_state(const char *who, void *state, size_t state_bytes, int n_sl
 
 // The row table of a call, every row inside the stream section's limits; max_new / max_span: the most frames a row transforms and
 // the most positions a row's emit covers (the grids are sized for them); max_out: the most samples a row writes out.
-static int pool_rows(const char *who, const PoolState &p, int n_slots, const adn_stream_pool_row *rows, int n_rows,
-                     adn::StreamPoolRows *t, int *max_new, int *max_span, long *max_out)
+int pool_rows(const char *who, const PoolState &p, int n_slots, const adn_stream_pool_row *rows, int n_rows,
+              adn::StreamPoolRows *t, int *max_new, int *max_span, long *max_out)
 {
     const std::string w(who);
     if (!rows) return fail(ADN_ERR_INVALID, w + ": null pointer");
@@ -917,7 +914,7 @@ static int pool_rows(const char *who, const PoolState &p, int n_slots, const adn
 
 // The rows of a call on RECORDINGS of `channels` streams (adn.h, adn_wpe_mc_stream_pool), pool_rows passed: recording r owns
 // the slots r C ... r C + C - 1, a group is C consecutive rows that name them in channel order and agree in step and final_length.
-static int pool_recordings(const char *who, int n_slots, int channels, const adn_stream_pool_row *rows, int n_rows)
+int pool_recordings(const char *who, int n_slots, int channels, const adn_stream_pool_row *rows, int n_rows)
 {
     const std::string w(who);
     if (n_slots % channels) return fail(ADN_ERR_INVALID, w + ": n_slots must be a multiple of channels");

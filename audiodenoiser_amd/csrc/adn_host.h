@@ -78,3 +78,17 @@ int stream_state(const char *who, void *state, size_t state_bytes, int n_streams
                  int lookahead, int max_steps, adn::StreamGeom *g);
 int stream_call(const char *who, const adn::StreamGeom &g, long first, int n_steps, long final_length, adn::StreamCall *c);
 }
+
+// The same for a pool state (adn_api.hip): the state against its plan, the row table of a call, and the rows of a call on recordings
+// of `channels` streams.  Declared for csrc/call/call_api.hip, which puts them in front of the pool operators of libadn_call.so.
+struct PoolState {
+    adn::StreamGeom g;
+    long ring_off, total, R;
+};
+extern "C" {
+int pool_state(const char *who, void *state, size_t state_bytes, int n_slots, int n_fft, int hop, int window, int block,
+               int lookahead, long ring, PoolState *p);
+int pool_rows(const char *who, const PoolState &p, int n_slots, const adn_stream_pool_row *rows, int n_rows,
+              adn::StreamPoolRows *t, int *max_new, int *max_span, long *max_out);
+int pool_recordings(const char *who, int n_slots, int channels, const adn_stream_pool_row *rows, int n_rows);
+}

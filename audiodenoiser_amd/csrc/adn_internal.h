@@ -643,6 +643,10 @@ hipError_t launch_aec_online(const void *mic, const void *far, int n_rows, int T
                              void *spec_out, float *mag_out, int width, int col0, hipStream_t st);
 hipError_t launch_aec_stream(float *state, float *y, int n_streams, const StreamGeom &g, const StreamCall &call, const AecConsts &c,
                              float *astate, hipStream_t st);
+// the same for a pool's CALLS of `mics` microphones that share one far end (adn_call.h): rows = mics + 1 per call, the microphones
+// first; pair (call, m) uses operator-state slot (first slot of the call / (mics + 1)) mics + m
+hipError_t launch_aec_stream_pool(float *state, float *y, int mics, const StreamGeom &g, const StreamPoolRows &rows, const AecConsts &c,
+                                  float *astate, hipStream_t st);
 hipError_t launch_quantize_pad(const float *in, int n, int h, int w, float *out, int H, int W, hipStream_t st);
 hipError_t launch_per_clip_l1(const float *a, const float *b, int n_clips, long elems, float *out, hipStream_t st);
 // Polyphase resampler and SNR mixer (resample_kernels.hip).  resample_ratio: up / down of a rate pair, false outside the limits

@@ -4,6 +4,7 @@
 // the stream state and of the steps are adn_api.hip's own (stream_state, stream_call), the ones in front of adn_wpe_stream.
 #include "../adn_host.h"
 #include "../../../include/adn_echo.h"
+#include "echo_checks.h"
 
 #include <string>
 
@@ -16,8 +17,9 @@ extern "C" {
 
 const char *adn_aec_last_error(void) { return adn::g_err.c_str(); }
 
-// The parameters of a call (NULL = the defaults), refused outside their legal ranges.
-static int aec_consts(const char *who, const adn_aec_params *params, adn::AecConsts *k)
+// The parameters of a call (NULL = the defaults), refused outside their legal ranges.  (Not static, nor aec_state_check below:
+// echo_checks.h, for csrc/call/call_api.hip.)
+int aec_consts(const char *who, const adn_aec_params *params, adn::AecConsts *k)
 {
     const std::string w(who);
     const adn_aec_params defaults = {8, 0, 0.995f, 10.f, 1e-8f};
@@ -44,7 +46,7 @@ static size_t aec_bytes(int n_slots, int n_bins, const adn::AecConsts &k)
     return (size_t)n_slots * (size_t)n_bins * (size_t)adn::aec_record_floats(k.K, k.D) * sizeof(float);
 }
 
-static int aec_state_check(const std::string &w, const void *state, size_t state_bytes, int n_slots, int n_bins, const adn::AecConsts &k)
+int aec_state_check(const std::string &w, const void *state, size_t state_bytes, int n_slots, int n_bins, const adn::AecConsts &k)
 {
     if (!state) return fail(ADN_ERR_INVALID, w + ": null pointer (the echo state)");
     if (n_slots < 1 || n_slots > (1 << 20) || n_bins < 1 || n_bins > (1 << 20))

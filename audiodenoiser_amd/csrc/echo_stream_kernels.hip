@@ -33,6 +33,13 @@
 //   InRing<StreamCall>    pair g is streams 2 g (microphone) and 2 g + 1 (far end) of an adn_stream_* state: both X rings are read
 //                         for frames f_first .. f_last, e_t goes into stream 2 g's ring cells, M_t into columns [W - B, W) of window
 //                         row 2 g of y; nothing of stream 2 g + 1 is written.  Operator-state slot g.
+//   EchoPoolCalls         InRing<StreamPoolRows> and M: the row table holds CALLS of M microphones and one far end, M + 1 rows each,
+//                         the microphones first (include/adn_call.h).  Pair g is microphone m = g % M of call i = g / M: its frames,
+//                         its step and its ring slot are table row i (M + 1) + m's, its far-end ring slot table row i (M + 1) + M's,
+//                         its window row in y the microphone's table row, its operator-state slot
+//                         (slot of the call's first row / (M + 1)) M + m.  Nothing of a far-end slot is written.  Every row
+//                         derives its own frames [t0, t1] from its step, so they differ BETWEEN workgroups; a workgroup is still one
+//                         pair, so its groups walk the same frames and the barriers stay uniform.
 // The step itself is one function, compiled with fp contraction off, every multiply-add an explicit fmaf.
 //
 // Cost (derived): per row-frame 8 K^2 + 12 K fp32 FMAs -- 4 K^2 for u, 4 K^2 for the update (a lane evaluates all K entries of its
@@ -58,6 +65,11 @@ struct EchoFrameMajor {
     const float2 *far;
 };
 
+struct EchoPoolCalls {
+    InRing<StreamPoolRows> r;
+    int M;                                            // microphones per call
+};
+
 // ---- where a pair's frames are: the microphone row / slot, the far-end row / slot, the operator-state slot
 struct PairRows {
     RowFrames mic, far;                               // .slot: the ring slot (InRing) or the row (frame-major)
@@ -73,6 +85,12 @@ __device__ __forceinline__ PairRows pair_of(const InRing<StreamCall> &s, long g,
     const RowFrames m = frames_of(s, 2 * g, F, c);
     return PairRows{m, RowFrames{2 * g + 1, m.t0, m.t1}, 2 * g, g};
 }
+__device__ __forceinline__ PairRows pair_of(const EchoPoolCalls &s, long g, int F, StreamCall &c)
+{
+    const long i = g / s.M, first = i * (s.M + 1), row = first + (g - i * s.M);
+    const RowFrames m = frames_of(s.r, row, F, c);
+    return PairRows{m, RowFrames{slot_of(s.r.rows, first + s.M), m.t0, m.t1}, row, group_slot_of(s.r, i, s.M + 1) * s.M + (g - i * s.M)};
+}
 __device__ __forceinline__ float2 load_far(const EchoFrameMajor &s, const PairRows &p, const StreamCall &, int F, int bin, int t)
 {
     return s.far[(p.far.slot * s.f.T + (t - s.f.first_frame)) * (long)F + bin];
@@ -81,6 +99,10 @@ __device__ __forceinline__ float2 load_far(const InRing<StreamCall> &s, const Pa
 {
     return load_frame(s, p.far, c, p.far.slot, F, bin, t);
 }
+__device__ __forceinline__ float2 load_far(const EchoPoolCalls &s, const PairRows &p, const StreamCall &c, int F, int bin, int t)
+{
+    return load_frame(s.r, p.far, c, p.far.slot, F, bin, t);
+}
 __device__ __forceinline__ float2 load_mic(const EchoFrameMajor &s, const PairRows &p, const StreamCall &c, int F, int bin, int t)
 {
     return load_frame(s.f, p.mic, c, p.out_row, F, bin, t);
@@ -88,6 +110,10 @@ __device__ __forceinline__ float2 load_mic(const EchoFrameMajor &s, const PairRo
 __device__ __forceinline__ float2 load_mic(const InRing<StreamCall> &s, const PairRows &p, const StreamCall &c, int F, int bin, int t)
 {
     return load_frame(s, p.mic, c, p.out_row, F, bin, t);
+}
+__device__ __forceinline__ float2 load_mic(const EchoPoolCalls &s, const PairRows &p, const StreamCall &c, int F, int bin, int t)
+{
+    return load_frame(s.r, p.mic, c, p.out_row, F, bin, t);
 }
 __device__ __forceinline__ void store_out(const EchoFrameMajor &s, const PairRows &p, const StreamCall &c, int F, int bin, int t, float2 e,
                                           float m)
@@ -98,6 +124,12 @@ __device__ __forceinline__ void store_out(const InRing<StreamCall> &s, const Pai
                                           float2 e, float m)
 {
     store_frame(s, p.mic, c, p.out_row, F, bin, t, e, m);
+}
+
+__device__ __forceinline__ void store_out(const EchoPoolCalls &s, const PairRows &p, const StreamCall &c, int F, int bin, int t,
+                                          float2 e, float m)
+{
+    store_frame(s.r, p.mic, c, p.out_row, F, bin, t, e, m);
 }
 
 // One frame of one row, as lane j of its group sees it.  y, r_t: the microphone and the far-end value; Pr: row j of P; pos = t mod H.
@@ -262,6 +294,15 @@ hipError_t launch_aec_stream(float *state, float *y, int n_streams, const Stream
     if (call.f_last < call.f_first) return hipSuccess;
     InRing<StreamCall> src{state, y, g, call};
     return launch(src, n_streams / 2, g.n_fft / 2 + 1, c, astate, st);
+}
+
+// rows: whole calls of `mics` microphones and a far end, mics + 1 rows each (the entry point has checked the table)
+hipError_t launch_aec_stream_pool(float *state, float *y, int mics, const StreamGeom &g, const StreamPoolRows &rows, const AecConsts &c,
+                                  float *astate, hipStream_t st)
+{
+    if (mics < 1 || rows.n < mics + 1 || rows.n % (mics + 1)) return hipErrorInvalidValue;
+    EchoPoolCalls src{InRing<StreamPoolRows>{state, y, g, rows}, mics};
+    return launch(src, (long)(rows.n / (mics + 1)) * mics, g.n_fft / 2 + 1, c, astate, st);
 }
 
 }  // namespace adn

@@ -11,7 +11,8 @@
     python -m audiodenoiser_amd.echo MIC.wav FAR.wav OUT.wav --live [--chunk N] [--block B] [--taps K] [--delay D] [--forget A] [--gain]
 
 The operator is DEFINED in ``include/adn_echo.h`` ("echo stream"; float64 restatement: ``tests/echo_ref.py``;
-``csrc/echo_stream_kernels.hip``; its three entry points are ``libadn_echo.so``'s, a library beside ``libadn.so`` built with it) and is
+``csrc/echo_stream_kernels.hip``; its three entry points are ``libadn_echo.so``'s, a library beside ``libadn.so`` built with it, and
+the pool form's is ``libadn_call.so``'s, ``include/adn_call.h``) and is
 unpinned against any package: per (pair, bin) an exponentially forgetting RLS filter of
 ``taps`` STFT frames from the far-end reference ``R`` to the microphone ``Y``, ``e_t = Y_t - sum_j conj(h_j) R_{t-D-j}``, updated
 once per frame -- except on a frame whose far-end power is at most ``quiet``, which leaves the filter untouched: a silent far end is
@@ -34,10 +35,21 @@ The live form is ``StreamEchoCanceller``: ``StreamDenoiser`` over ``n_streams = 
     near = se.push(block)                              # (2, m): microphone, far end -> (k,): what has become final
     tail = se.flush()
 
+The pool form is ``EchoStreamPool``: ``StreamPool`` over CALLS of ``mics`` microphones that share one far end, calls that open,
+stall and hang up on their own clocks, the ready ones batched into one ``adn_aec_stream_pool`` launch per tick; only the
+microphone rows are resynthesised.  With ``mics=1`` a call is the pair above, bit for bit.
+
+    pool = EchoStreamPool(max_calls=64, mics=1)        # or mics=4: a speakerphone, one loudspeaker
+    cid = pool.open()                                  # or open(input_rate=48000) with input_rates=(48000,)
+    pool.push(cid, block)                              # (mics + 1, m): the microphones first, the far end last
+    for cid, near, finished in pool.step(): ...        # (k,), or (mics, k) for mics > 1
+    pool.close(cid)
+
 The defaults (8 taps, no delay, forget 0.995, loading 10, quiet 1e-8) are the values of the host prototype
 (``profiles/bench_echo.md``); they were not tuned by ear.
 
-What is NOT here: a pool form with pairs of independent timing; more than one reference channel; partitioned time-domain filters;
+What is NOT here: pools that mix ``mics``; a lockstep object with several microphones per far end; echo cancellation chained into
+``BeamformStreamPool``; more than one reference channel; partitioned time-domain filters;
 double-talk detectors; non-linear echo; any tuning by ear.  There is no CPU path.
 """
 from __future__ import annotations
@@ -55,10 +67,11 @@ from .denoise import Denoiser
 from .dereverb import _mag_buffer, _need_cells, _spec_dims
 from .griffin_lim import stft_complex
 from .resample import _resample_device
-from .stream import StreamDenoiser, _check_stream_args, causal_carrier
+from .stream import POOL_MAX_ROWS, RecordingBook, StreamDenoiser, StreamPool, _check_stream_args, causal_carrier
 from .wav import read_wav, write_wav
 
-__all__ = ["AecParams", "aec_stream_state_bytes", "aec_online", "EchoCanceller", "StreamEchoCanceller"]
+__all__ = ["AecParams", "aec_stream_state_bytes", "aec_pool_state_bytes", "aec_online", "EchoCanceller", "StreamEchoCanceller",
+           "EchoStreamPool"]
 
 
 @dataclasses.dataclass(frozen=True)
@@ -102,6 +115,20 @@ def aec_stream_state_bytes(n_slots: int, n_bins: int, params: AecParams = None) 
     _lib.check_echo(_lib.load_echo().adn_aec_stream_state_bytes(n_slots, n_bins, _aec_params("aec_stream_state_bytes", params), ctypes.byref(need)),
                "adn_aec_stream_state_bytes")
     return int(need.value)
+
+
+def _check_mics(who, mics):
+    if isinstance(mics, bool) or not isinstance(mics, int) or not 1 <= mics <= 7:
+        raise ValueError(f"{who}: need an integer 1 <= mics <= 7 (a call is mics + 1 <= 8 streams)")
+
+
+def aec_pool_state_bytes(max_calls: int, mics: int, n_bins: int, params: AecParams = None) -> int:
+    """The bytes of the echo state of an ``adn_aec_stream_pool`` over ``max_calls`` calls of ``mics`` microphones: a slot per
+    microphone, ``aec_stream_state_bytes(max_calls * mics, n_bins, params)`` (no device needed)."""
+    _check_mics("aec_pool_state_bytes", mics)
+    if isinstance(max_calls, bool) or not isinstance(max_calls, int) or max_calls < 1:
+        raise ValueError("aec_pool_state_bytes: need an integer max_calls >= 1")
+    return aec_stream_state_bytes(max_calls * mics, n_bins, params)
 
 
 def aec_online(mic_spec: torch.Tensor, far_spec: torch.Tensor, state: torch.Tensor = None, first_frame: int = 0,
@@ -289,6 +316,87 @@ class StreamEchoCanceller(StreamDenoiser):
         out = self._cat(outs)[::2]
         out = out[0] if out.shape[0] == 1 else out.contiguous()
         return out.cpu().numpy() if self._numpy else out
+
+
+class EchoStreamPool(StreamPool):
+    """``StreamPool`` over CALLS with the echo canceller in the network's place: a call is ``mics`` microphones and the ONE far end
+    they share, ``mics + 1`` streams; calls open, stall, close and run at their own rates, and a tick batches whatever is ready
+    into one launch per kernel.
+
+        pool = EchoStreamPool(max_calls=64, mics=4)
+        cid = pool.open()                                  # or open(input_rate=48000) with input_rates=(48000,)
+        pool.push(cid, block)                              # (5, m): the next samples of the four microphones, then of the far end
+        for cid, near, finished in pool.step(): ...        # (4, k): what has become final of every microphone; (k,) for mics = 1
+
+    Call ``c`` owns the stream slots ``c (mics + 1) ... c (mics + 1) + mics`` of the pool state, the far end the last one, and the
+    slots ``c mics ... c mics + mics - 1`` of the echo state (``stream.RecordingBook`` with ``mics + 1`` channels;
+    ``include/adn_call.h``, ``adn_aec_stream_pool``, a function of ``libadn_call.so``).  A tick analyses the ``mics + 1`` rows of
+    every ready call, runs ``adn_aec_stream_pool`` in place on the windows, ``256 // (mics + 1)`` calls a library call, and drops
+    the far-end windows; with ``gain=True`` then ``adn_spectral_gain_windows`` on the kept columns of the microphone rows
+    (``gain_params``, a state per microphone, ``cid * mics + m``).  ``adn_stream_pool_emit`` -- and ``adn_stream_pool_emit_rate``
+    for a call at an ``input_rate`` -- run on the microphone rows alone: the far end is pushed, ring-buffered and analysed once
+    per call and never resynthesised, which is safe because an emit writes nothing but its own slot's overlap-add tail and only
+    that slot's later emits read it.  The echo state needs no reset: a call's step 0 starts its pairs afresh.
+
+    Claimed: every microphone of every call is, bit for bit, what a solo ``StreamEchoCanceller(pairs=1, input_rate=...)`` with the
+    same parameters returns for that microphone and the call's far end, whatever its neighbours do; a call returns as many samples
+    as came in; a call's slots are reusable without a reset.  Not claimed: pools that mix ``mics``; more than one step per call
+    and tick; graph capture of a tick; anything ``StreamEchoCanceller`` does not claim."""
+
+    def __init__(self, device=None, max_calls: int = 16, mics: int = 1, backlog_steps: int = 4, sample_rate: int = 8000,
+                 n_fft: int = 512, hop_length: int = 128, block_frames: int = 4, params: AecParams = None, gain: bool = False,
+                 gain_params: SpectralParams = None, input_rates=None):
+        who = "EchoStreamPool"
+        _check_mics(who, mics)
+        if isinstance(max_calls, bool) or not isinstance(max_calls, int) or max_calls < 1:
+            raise ValueError(f"{who}: need an integer max_calls >= 1")
+        window, ahead, _ = causal_carrier(block_frames)
+        _aec_params(who, params)
+        self.book = RecordingBook(max_calls, mics + 1, backlog_steps, n_fft, hop_length, window, block_frames, ahead, input_rates,
+                                  sample_rate)
+        self.params, self.mics, self.max_calls, self.gain = params, mics, max_calls, bool(gain)
+        self.gain_params = _spectral_params(who, gain_params, "gain_params")
+        dev = rocm_device(who, device)
+        self.model = None
+        self.batch_windows = POOL_MAX_ROWS
+        f = n_fft // 2 + 1
+        self._aec_state = torch.empty((aec_pool_state_bytes(max_calls, mics, f, params),), dtype=torch.uint8, device=dev)
+        self._gain_state = torch.empty((max_calls * mics, 3, f), dtype=torch.float32, device=dev)
+        self._setup(dev)
+
+    def reset(self):
+        """Forget every call, the gain's noise estimates included: all slots are free."""
+        super().reset()
+        self._gain_state.fill_(-1.0)
+
+    def network(self, x):
+        raise RuntimeError("EchoStreamPool: there is no network; the canceller runs between analyze and emit (adn_aec_stream_pool)")
+
+    def _mic_rows(self, rows):
+        C = self.channels
+        return [r for i, r in enumerate(rows) if i % C != C - 1]
+
+    def _emit_rows(self, rows):
+        """The microphone rows: the far end of a call is never resynthesised."""
+        return self._mic_rows(rows)
+
+    def _net(self, x: torch.Tensor, rows) -> torch.Tensor:
+        """The tick's stream rows ``rows`` (``mics + 1`` per call) and their windows ``x`` -> the microphone windows, compacted,
+        holding ``|e|`` (or the gain's result) in the kept columns."""
+        L, C, M, plan = _lib.load_call(), self.channels, self.mics, self.book.plan
+        lead = (self._state.data_ptr(), self._state.numel(), self._args[0], M) + self._args[1:]
+        p = ctypes.byref(self.params.to_struct()) if self.params is not None else None
+        per = POOL_MAX_ROWS // C * C                         # whole calls
+        for i in range(0, len(rows), per):
+            part, group = x[i:i + per], rows[i:i + per]
+            with torch.cuda.device(self.device):
+                _lib.check_call(L.adn_aec_stream_pool(*lead, self._rows(group), len(group), part.data_ptr(), p, self._aec_state.data_ptr(),
+                                                      self._aec_state.numel(), current_stream(self.device)), "adn_aec_stream_pool")
+        y = x.reshape(len(rows) // C, C, *x.shape[1:])[:, :M].reshape(-1, *x.shape[1:]).contiguous()
+        if self.gain:                                        # a state per microphone: cid mics + m
+            _gain_kept_columns(y, [(slot // C * M + slot % C, k, final) for slot, k, final in self._mic_rows(rows)], 1,
+                               self._gain_state, plan, self.gain_params)
+        return y
 
 
 class _FilePair:

@@ -638,7 +638,8 @@ class StreamPool:
     Recordings.  A subclass whose ``book`` is a ``RecordingBook`` (``DereverbStreamPool(channels=C)``, ``BeamformStreamPool``) serves
     RECORDINGS of ``C`` microphones: ``open`` returns a recording id, ``push`` takes ``(C, m)``, recording ``r`` lives in the device
     slots ``r C ... r C + C - 1``, a tick's rows are its recordings' ``C`` stream rows in channel order, ``256 // C`` recordings a
-    call, and ``step`` returns ``(C, k)`` per recording -- or ``(k,)`` where ``_emit_rows`` keeps the first row of each.  This class
+    call, and ``step`` returns ``(C, k)`` per recording -- or ``(E, k)`` where ``_emit_rows`` keeps ``E`` rows of each, ``(k,)`` for
+    ``E = 1``.  This class
     itself, and every pool with ``channels = 1``, is the pool of single streams above."""
 
     def __init__(self, model, max_streams: int = 64, backlog_steps: int = 4, n_fft: int = 512, hop_length: int = 128,
@@ -818,7 +819,10 @@ class StreamPool:
 
     def _emit_rows(self, rows):
         """The stream rows of a tick that ``emit`` takes back to audio, ``_net``'s result holding one window for each: all of them
-        here; a class whose operator leaves a recording's result in its first row keeps that one (``BeamformStreamPool``)."""
+        here; a class whose operator leaves a recording's result in its first row keeps that one (``BeamformStreamPool``), and one
+        whose recordings carry rows that are only read keeps the others (``EchoStreamPool``: the microphones, not the far end).
+        Any rows of each recording may be kept, the same channels of every one, in channel order: ``step`` reads the channels off
+        the first recording's kept rows."""
         return rows
 
     def analyze(self, rows) -> torch.Tensor:
@@ -868,8 +872,9 @@ class StreamPool:
         outs = [self.emit(y[i * POOL_MAX_ROWS:i * POOL_MAX_ROWS + len(g)], g) for i, g in enumerate(groups)]
         out = torch.cat(outs) if len(outs) > 1 else outs[0]
         calls, rated = book.rate_calls(rows)             # the rows of streams at a rate of their own go back to it
-        if C > 1:                                        # a call per emitted channel: slot sid C + e, row i E + e of `out`
-            calls = [(i * E + e, (c[0] * C + e,) + c[1:]) for i, c in calls for e in range(E)]
+        if C > 1:                                        # a call per emitted channel: slot sid C + its channel, row i E + e of `out`
+            kept = [r[0] - rows[0][0] * C for r in erows[:E]]            # the channels `_emit_rows` keeps of a recording
+            calls = [(i * E + e, (c[0] * C + kept[e],) + c[1:]) for i, c in calls for e in range(E)]
             rated = {i: (None if j is None else j * E, n) for i, (j, n) in rated.items()}
         rout = self.emit_rate(out, calls) if calls else None
         plain = any(self._numpy[r[0]] and i not in rated for i, r in enumerate(rows))

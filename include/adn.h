@@ -1126,7 +1126,8 @@ ADN_API int adn_mvdr_stream_pool(void *pool_state, size_t pool_state_bytes, int 
                                  const adn_mvdr_stream_params *params, void *mvdr_state, size_t mvdr_state_bytes, void *stream);
 
 /* ---- echo stream: acoustic echo cancellation lives in a header and a library of its own: adn_echo.h and libadn_echo.so.  The symbol
- * table of libadn.so is this header's, name for name, and stays so. */
+ * table of libadn.so is this header's, name for name, and stays so.  Operators of a two-way call that neither closed table can take
+ * -- the pool form of the echo canceller first -- are declared in adn_call.h and exported by libadn_call.so, whose table is open. */
 
 /* ---- environment switches -------------------------------------------------------------------------------------------------
  * Read ONCE, when a U-Net handle is created (never per call).  None is needed in production: the defaults are the measured best

@@ -86,7 +86,10 @@ extern "C" {
  * 2^31; col0 >= 0 and col0 + n_frames <= width when a mag_out is given; spec_out overlapping an input; a grid of 2^31 workgroups or
  * more; for adn_aec_stream what adn_wpe_stream refuses about the stream state and the steps, and an odd n_streams.
  * ADN_ERR_WORKSPACE: a state below adn_aec_stream_state_bytes.  Element offsets are 64-bit.
- * Not here: a pool form with pairs of independent timing; more than one reference channel; partitioned time-domain filters;
+ * The pool form -- calls of one or several microphones that share a far end, each on its own clock, the same recursion on a pool
+ * state -- is declared in adn_call.h and exported by libadn_call.so: this library's table is closed at the four functions below.  It
+ * sizes its state with adn_aec_stream_state_bytes, which stays here.
+ * Not here: more than one reference channel; partitioned time-domain filters;
  * double-talk detectors; non-linear echo; any tuning by ear. */
 typedef struct adn_aec_params { int taps, delay; float forget, loading, quiet; } adn_aec_params;
 ADN_API const char *adn_aec_last_error(void);   /* the message of this thread's last failed adn_aec_* call; "" before any */

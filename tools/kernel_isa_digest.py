@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel digest of the gfx950 ISA hipcc generates for csrc/*.hip (no GPU needed): a refactoring that must not change the
+"""Per-kernel digest of the gfx950 ISA hipcc generates for csrc/*.hip and the echo library's own files (no GPU needed): a refactoring that must not change the
 generated code (deleting a closed experiment switch, renaming) is checked by comparing two runs.
 
     python tools/kernel_isa_digest.py > /tmp/before.json ; ...edit... ; python tools/kernel_isa_digest.py --compare /tmp/before.json
@@ -43,10 +43,11 @@ def digests(text):
 
 
 def main():
+    sources = B._sources() + B._echo_sources()               # libadn.so's kernels and the ones libadn_echo.so adds
     with concurrent.futures.ThreadPoolExecutor(max_workers=4) as pool:
-        texts = list(pool.map(asm_of, B._sources()))
+        texts = list(pool.map(asm_of, sources))
     cur = {}
-    for src, t in zip(B._sources(), texts):
+    for src, t in zip(sources, texts):
         for k, v in digests(t).items():
             cur[os.path.basename(src) + ":" + k] = v
     if "--compare" in sys.argv:
