@@ -13,7 +13,7 @@ __all__ = ["UNet", "SpectrogramDataset", "WavToSpecDataset", "audio_to_magnitude
            "WpeStreamParams", "wpe_online", "StreamDereverberator", "DereverbStreamPool", "Beamformer", "MvdrParams", "mvdr",
            "MvdrStreamParams", "mvdr_online", "mvdr_stream_state_bytes", "StreamBeamformer",
            "BeamformStreamPool", "EchoCanceller", "AecParams", "aec_online", "aec_stream_state_bytes", "StreamEchoCanceller",
-           "EchoStreamPool", "aec_pool_state_bytes"]
+           "EchoStreamPool", "aec_pool_state_bytes", "aec_mr_online", "aec_mr_state_bytes"]
 # (resample / reverb themselves: audiodenoiser_amd.resample.resample, audiodenoiser_amd.reverb.reverb -- the modules own the names)
 
 
@@ -47,7 +47,7 @@ def __getattr__(name):
         import importlib
         return getattr(importlib.import_module(".beamform", __name__), name)
     if name in ("EchoCanceller", "AecParams", "aec_online", "aec_stream_state_bytes", "StreamEchoCanceller", "EchoStreamPool",
-                "aec_pool_state_bytes"):
+                "aec_pool_state_bytes", "aec_mr_online", "aec_mr_state_bytes"):
         import importlib
         return getattr(importlib.import_module(".echo", __name__), name)
     if name in ("StreamDenoiser", "StreamPool"):

@@ -204,7 +204,11 @@ def load_call() -> ctypes.CDLL:
             raise AdnError(f"cannot load {path}: {exc}") from exc
         vp, sz, ci, cl = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_long
         L.adn_call_last_error.restype = ctypes.c_char_p
-        L.adn_aec_stream_pool.argtypes = [vp, sz, ci, ci, ci, ci, ci, ci, ci, cl, vp, ci, vp, ctypes.POINTER(AecParamsStruct), vp, sz, vp]
+        asp = ctypes.POINTER(AecParamsStruct)
+        L.adn_aec_stream_pool.argtypes = [vp, sz, ci, ci, ci, ci, ci, ci, ci, cl, vp, ci, vp, asp, vp, sz, vp]
+        L.adn_aec_mr_state_bytes.argtypes = [ci, ci, ci, asp, ctypes.POINTER(sz)]
+        L.adn_aec_mr_online.argtypes = [vp, vp, ci, ci, ci, ci, cl, asp, vp, sz, ci, vp, vp, ci, ci, vp]
+        L.adn_aec_mr_stream.argtypes = [vp, sz, vp, ci, ci, cl, ci, cl, ci, ci, ci, ci, ci, ci, asp, vp, sz, vp]
         for name in CALL_EXPORTED_SYMBOLS[1:]:
             getattr(L, name).restype = ci
         _call = L
@@ -311,4 +315,4 @@ ECHO_EXPORTED_SYMBOLS = ("adn_aec_last_error", "adn_aec_stream_state_bytes", "ad
 
 # libadn_call.so (include/adn_call.h): operators of a two-way call that the two closed tables above cannot take.  This table is
 # open: the next call operator is added here, in the header and in csrc/libadn_call.map
-CALL_EXPORTED_SYMBOLS = ("adn_call_last_error", "adn_aec_stream_pool")
+CALL_EXPORTED_SYMBOLS = ("adn_call_last_error", "adn_aec_stream_pool", "adn_aec_mr_state_bytes", "adn_aec_mr_online", "adn_aec_mr_stream")

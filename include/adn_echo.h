@@ -89,7 +89,8 @@ extern "C" {
  * The pool form -- calls of one or several microphones that share a far end, each on its own clock, the same recursion on a pool
  * state -- is declared in adn_call.h and exported by libadn_call.so: this library's table is closed at the four functions below.  It
  * sizes its state with adn_aec_stream_state_bytes, which stays here.
- * Not here: more than one reference channel; partitioned time-domain filters;
+ * Not here: more than one reference channel (stereo and surround far ends are "echo stream multireference" of adn_call.h, the
+ * same recursion on the stacked references, exported by libadn_call.so); partitioned time-domain filters;
  * double-talk detectors; non-linear echo; any tuning by ear. */
 typedef struct adn_aec_params { int taps, delay; float forget, loading, quiet; } adn_aec_params;
 ADN_API const char *adn_aec_last_error(void);   /* the message of this thread's last failed adn_aec_* call; "" before any */

@@ -43,7 +43,7 @@ def digests(text):
 
 
 def main():
-    sources = B._sources() + B._echo_sources()               # libadn.so's kernels and the ones libadn_echo.so adds
+    sources = B._sources() + B._echo_sources() + B._call_sources()   # libadn.so's kernels and the ones libadn_echo.so and libadn_call.so add
     with concurrent.futures.ThreadPoolExecutor(max_workers=4) as pool:
         texts = list(pool.map(asm_of, sources))
     cur = {}
@@ -53,13 +53,16 @@ def main():
     if "--compare" in sys.argv:
         old = json.load(open(sys.argv[sys.argv.index("--compare") + 1]))
         names = subprocess.run(["c++filt"] + [k.split(":", 1)[1] for k in sorted(set(old) | set(cur))], capture_output=True, text=True).stdout.splitlines()
-        diff = 0
+        diff = new = 0
         for k, dn in zip(sorted(set(old) | set(cur)), names):
             a, b = old.get(k), cur.get(k)
-            if a != b:
+            if a is None:                                        # a kernel the earlier run did not have changes no existing code
+                new += 1
+                print(f"NEW  {k.split(':')[0]} {dn[:110]}: {b}")
+            elif a != b:
                 diff += 1
                 print(f"DIFF {k.split(':')[0]} {dn[:110]}: {a} -> {b}")
-        print(f"{len(cur)} kernels, {diff} differ")
+        print(f"{len(cur)} kernels, {new} new, {diff} differ")
         sys.exit(1 if diff else 0)
     json.dump(cur, sys.stdout, indent=0, sort_keys=True)
 
